@@ -9,6 +9,9 @@ blocks over RCCL/xGMI so every rank holds the full C (north_star's exchange step
 GFLOP/s over all ranks, 2*nnz*n flops per rank-step, max-over-ranks time, all-gather included.
 
 Prints ONE JSON line on rank 0; see DESIGN.md §Measurement for how roofline / cpu_baseline are defined.
+`--steps` is the number of timed steps and `ms_per_step` the wall time of one of them.  Inputs are seeded, so
+`--dump-outputs DIR` (rows of the C of the last timed step, see dump_outputs) lets two builds be compared output
+for output.
 """
 from __future__ import annotations
 
@@ -47,7 +50,39 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget for the CPU baseline sample")
     ap.add_argument("--extras", action="store_true", help="also time SpMV / gather / merge (configs 3, 4 scaled)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the C of the last timed step to DIR/C.npy (rows of C, in its dtype; a fixed seeded "
+                         "sample of rows when the whole C exceeds 32 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_BYTES = 32 << 20          # --dump-outputs budget
+SEED_DUMP = 5
+
+
+def dump_rows(rows_total, n, itemsize):
+    """Row indices of C that --dump-outputs writes: all of them when C fits in DUMP_BYTES, else a sorted sample
+    drawn with a fixed seed (the same rows for the same arguments)."""
+    keep = max(1, DUMP_BYTES // max(1, n * itemsize))
+    if keep >= rows_total:
+        return np.arange(rows_total, dtype=np.int64)
+    return np.sort(np.random.default_rng(np.random.PCG64(SEED_DUMP)).choice(rows_total, size=keep, replace=False))
+
+
+def dump_outputs(dirname, C, colmajor):
+    """DIR/C.npy: rows dump_rows(...) of the result C = A @ B as an (rows, n) array, C's dtype (float64 / float32).
+    C is the tensor the timed step wrote: (n, rows) when colmajor, else (rows, n)."""
+    import torch
+    rows_total, n = (C.shape[1], C.shape[0]) if colmajor else (C.shape[0], C.shape[1])
+    idx = torch.from_numpy(dump_rows(rows_total, n, C.element_size())).to(C.device)
+    sample = C.index_select(1, idx).t() if colmajor else C.index_select(0, idx)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "C.npy"), np.ascontiguousarray(sample.cpu().numpy()))
 
 
 def cpu_baseline(args, p, j, x, B_host):
@@ -185,6 +220,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # before anything below runs the SpMM again into the same buffer
+        dump_outputs(args.dump_outputs, C_full if world > 1 else C_loc, colmajor)
 
     step_ms = np.array([a.elapsed_time(b) for a, b in ev])          # whole SpMM call (plan build + repack + kernel)
     kt = (ctypes.c_float * 256)()
