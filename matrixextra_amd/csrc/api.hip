@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <memory>
 #include <new>
 
 namespace mx {
@@ -21,12 +22,6 @@ int set_error(const char *fmt, ...)
     va_end(ap);
     return 1;
 }
-
-int spmv_launch(int m, int64_t nnz, const int32_t *indptr, const int32_t *indices, const double *values,
-                const void *v, int v_dtype, void *y, hipStream_t st);
-// xfer.hip: synchronous host <-> device copies, pipelined through pinned slots + a host copy pool when large
-int xfer_h2d(void *dst_dev, const void *src_host, size_t bytes);
-int xfer_d2h(void *dst_host, const void *src_dev, size_t bytes);
 
 // MXGPU_TRACE=1: wall-clock phases of an export-level call on stderr
 struct Trace {
@@ -155,9 +150,32 @@ static int spmv_host(int m, const int32_t *indptr, const int32_t *indices, const
 struct mx_result {
     mx::DevBuf indptr, indices, values;
     mx_result_info info;
+    void set_sizes(int64_t indptr_len, int64_t nnz, int64_t values_len)
+    {
+        info.indptr_len = indptr_len;
+        info.nnz = nnz;
+        info.values_len = values_len;
+    }
 };
 
 using namespace mx;
+
+// The one owner of an mx_result under construction: `body` fills it and returns 0, or fails and the result is
+// freed.  Every success ends with the null stream synchronised, which mx_result_finish's transfers rely on
+// (device buffers the body frees on its way out are safe: hipFree synchronises the device).
+template <typename Body>
+static int begin_result(mx_result **res_out, mx_result_info *info, int values_dtype, Body &&body)
+{
+    std::unique_ptr<mx_result> res(new (std::nothrow) mx_result());
+    MX_REQUIRE(res, "out of host memory");
+    res->info.values_dtype = values_dtype;
+    res->info.alias_structure = 0;
+    if (const int rc = body(*res)) return rc;
+    MX_HIP(hipStreamSynchronize(nullptr));
+    *info = res->info;
+    *res_out = res.release();
+    return 0;
+}
 
 extern "C" {
 
@@ -293,62 +311,43 @@ int mx_csr_elemwise_begin(int op, int nrows, const int32_t *indptr1, const int32
     *res_out = nullptr;
     const bool lgl = op == MX_OP_OR || op == MX_OP_XOR || op == MX_OP_AND;
     const size_t vb = lgl ? 4 : 8;
-    mx_result *res = new (std::nothrow) mx_result();
-    MX_REQUIRE(res, "out of host memory");
-    res->info.values_dtype = lgl ? MX_LGL : MX_F64;
-    res->info.alias_structure = 0;
-    int rc = 0;
-    do {
+    return begin_result(res_out, info, lgl ? MX_LGL : MX_F64, [&](mx_result &res) {
         // identical-structure fast paths: pointer identity, as operators.cpp:104-108 / :343-346 test it
         if (nnz1 == nnz2 && indptr1 == indptr2 && indices1 == indices2) {
             if (op == MX_OP_SUB && values1 == values2) {
                 // operators.cpp:348-355: IntegerVector(indptr.size()) zeros, empty indices / values
-                res->info.indptr_len = (int64_t)nrows + 1;
-                res->info.nnz = 0;
-                res->info.values_len = 0;
-                if ((rc = res->indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1)))) break;
-                if (hipMemset(res->indptr.p, 0, sizeof(int32_t) * ((size_t)nrows + 1)) != hipSuccess) {
-                    rc = set_error("hipMemset failed"); break;
-                }
-                break;
+                res.set_sizes((int64_t)nrows + 1, 0, 0);
+                if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+                MX_HIP(hipMemset(res.indptr.p, 0, sizeof(int32_t) * ((size_t)nrows + 1)));
+                return 0;
             }
-            res->info.alias_structure = 1;
-            res->info.indptr_len = (int64_t)nrows + 1;
-            res->info.nnz = nnz1;
-            res->info.values_len = nnz1;
+            res.info.alias_structure = 1;
+            res.set_sizes((int64_t)nrows + 1, nnz1, nnz1);
             DevBuf a, b;
-            if ((rc = a.upload(values1, vb * (size_t)nnz1))) break;
-            if ((rc = b.upload(values2, vb * (size_t)nnz2))) break;
-            if ((rc = res->values.alloc(vb * (size_t)nnz1))) break;
-            if ((rc = mxd_values_elemwise(op, nnz1, a.p, b.p, res->values.p, nullptr))) break;
-            if (hipStreamSynchronize(nullptr) != hipSuccess) { rc = set_error("stream sync failed"); break; }
-            break;
+            if (a.upload(values1, vb * (size_t)nnz1)) return 1;
+            if (b.upload(values2, vb * (size_t)nnz2)) return 1;
+            if (res.values.alloc(vb * (size_t)nnz1)) return 1;
+            return mxd_values_elemwise(op, nnz1, a.p, b.p, res.values.p, nullptr);
         }
         Csr A, B;
-        if ((rc = A.upload(indptr1, indices1, values1, nrows, vb))) break;
-        if ((rc = B.upload(indptr2, indices2, values2, nrows, vb))) break;
+        if (A.upload(indptr1, indices1, values1, nrows, vb)) return 1;
+        if (B.upload(indptr2, indices2, values2, nrows, vb)) return 1;
         DevBuf ws;
-        if ((rc = ws.alloc(mxd_merge_workspace_bytes(nrows)))) break;
-        if ((rc = res->indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1)))) break;
+        if (ws.alloc(mxd_merge_workspace_bytes(nrows))) return 1;
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
         int64_t nnz_out = 0;
-        if ((rc = mxd_csr_merge_count(op, nrows, A.p.as<int32_t>(), A.j.as<int32_t>(), A.nnz, B.p.as<int32_t>(),
-                                      B.j.as<int32_t>(), B.nnz, res->indptr.as<int32_t>(), ws.p, &nnz_out, nullptr)))
-            break;
-        if ((rc = res->indices.alloc(sizeof(int32_t) * (size_t)nnz_out))) break;
-        if ((rc = res->values.alloc(vb * (size_t)nnz_out))) break;
-        if ((rc = mxd_csr_merge_fill(op, nrows, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, A.nnz, B.p.as<int32_t>(),
-                                     B.j.as<int32_t>(), B.x.p, B.nnz, res->indptr.as<int32_t>(),
-                                     res->indices.as<int32_t>(), res->values.p, nullptr)))
-            break;
-        if (hipStreamSynchronize(nullptr) != hipSuccess) { rc = set_error("stream sync failed"); break; }
-        res->info.indptr_len = (int64_t)nrows + 1;
-        res->info.nnz = nnz_out;
-        res->info.values_len = nnz_out;
-    } while (0);
-    if (rc) { delete res; return rc; }
-    *info = res->info;
-    *res_out = res;
-    return 0;
+        if (mxd_csr_merge_count(op, nrows, A.p.as<int32_t>(), A.j.as<int32_t>(), A.nnz, B.p.as<int32_t>(),
+                                B.j.as<int32_t>(), B.nnz, res.indptr.as<int32_t>(), ws.p, &nnz_out, nullptr))
+            return 1;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
+        if (res.values.alloc(vb * (size_t)nnz_out)) return 1;
+        if (mxd_csr_merge_fill(op, nrows, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, A.nnz, B.p.as<int32_t>(),
+                               B.j.as<int32_t>(), B.x.p, B.nnz, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
+                               res.values.p, nullptr))
+            return 1;
+        res.set_sizes((int64_t)nrows + 1, nnz_out, nnz_out);
+        return 0;
+    });
 }
 
 // ---- row gather --------------------------------------------------------------------------------
@@ -363,44 +362,31 @@ int mx_copy_csr_rows_begin(const int32_t *indptr, int nrows, const int32_t *indi
     *res_out = nullptr;
     const bool has_values = value_dtype != MX_NONE && n_values > 0;   // slice.cpp:246,257
     const size_t vb = has_values ? dtype_bytes(value_dtype) : 0;
-    mx_result *res = new (std::nothrow) mx_result();
-    MX_REQUIRE(res, "out of host memory");
-    res->info.values_dtype = value_dtype;
-    res->info.alias_structure = 0;
-    int rc = 0;
-    do {
+    return begin_result(res_out, info, value_dtype, [&](mx_result &res) {
         Csr A;
-        if ((rc = A.upload(indptr, indices, values, nrows, vb))) break;
+        if (A.upload(indptr, indices, values, nrows, vb)) return 1;
         DevBuf rows, ws;
-        if ((rc = rows.upload(rows_take, sizeof(int32_t) * (size_t)n_take))) break;
-        if ((rc = ws.alloc(mxd_gather_workspace_bytes((int)n_take)))) break;
-        if ((rc = res->indptr.alloc(sizeof(int32_t) * ((size_t)n_take + 1)))) break;
+        if (rows.upload(rows_take, sizeof(int32_t) * (size_t)n_take)) return 1;
+        if (ws.alloc(mxd_gather_workspace_bytes((int)n_take))) return 1;
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)n_take + 1))) return 1;
         int64_t nnz_out = 0;
-        if ((rc = mxd_csr_gather_count((int)n_take, A.p.as<int32_t>(), rows.as<int32_t>(), res->indptr.as<int32_t>(),
-                                       ws.p, &nnz_out, nullptr)))
-            break;
+        if (mxd_csr_gather_count((int)n_take, A.p.as<int32_t>(), rows.as<int32_t>(), res.indptr.as<int32_t>(), ws.p,
+                                 &nnz_out, nullptr))
+            return 1;
         if (nnz_out == 0) {          // slice.cpp:236-240: three EMPTY vectors (even the indptr)
-            res->info.indptr_len = 0;
-            res->info.nnz = 0;
-            res->info.values_len = 0;
-            break;
+            res.set_sizes(0, 0, 0);
+            return 0;
         }
-        if ((rc = res->indices.alloc(sizeof(int32_t) * (size_t)nnz_out))) break;
-        if (has_values && (rc = res->values.alloc(vb * (size_t)nnz_out))) break;
-        if ((rc = mxd_csr_gather_fill((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, rows.as<int32_t>(),
-                                      res->indptr.as<int32_t>(), res->indices.as<int32_t>(), res->values.p,
-                                      has_values ? value_dtype : MX_NONE, nnz_out, nullptr)))
-            break;
-        if (hipStreamSynchronize(nullptr) != hipSuccess) { rc = set_error("stream sync failed"); break; }
-        res->info.indptr_len = n_take + 1;
-        res->info.nnz = nnz_out;
-        res->info.values_len = has_values ? nnz_out : 0;
-        if (!has_values) res->info.values_dtype = MX_NONE;
-    } while (0);
-    if (rc) { delete res; return rc; }
-    *info = res->info;
-    *res_out = res;
-    return 0;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
+        if (has_values && res.values.alloc(vb * (size_t)nnz_out)) return 1;
+        if (mxd_csr_gather_fill((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, rows.as<int32_t>(),
+                                res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.p,
+                                has_values ? value_dtype : MX_NONE, nnz_out, nullptr))
+            return 1;
+        res.set_sizes(n_take + 1, nnz_out, has_values ? nnz_out : 0);
+        if (!has_values) res.info.values_dtype = MX_NONE;
+        return 0;
+    });
 }
 
 // ---- column-filtering slices (§8f rank 2) ----------------------------------------------------------------
@@ -418,38 +404,26 @@ int mx_copy_csr_rows_col_seq_begin(const int32_t *indptr, int nrows, const int32
     for (int64_t c = 1; c < n_cols_take; c++) { if (cols_take[c] < min_col) min_col = cols_take[c]; if (cols_take[c] > max_col) max_col = cols_take[c]; }
     min_col -= index1 ? 1 : 0; max_col -= index1 ? 1 : 0;
     const bool has_values = value_dtype != MX_NONE && n_values > 0;
-    mx_result *res = new (std::nothrow) mx_result();
-    MX_REQUIRE(res, "out of host memory");
-    res->info.values_dtype = MX_F64;                                         // always a NumericVector (slice.cpp:363)
-    res->info.alias_structure = 0;
-    int rc = 0;
-    do {
+    return begin_result(res_out, info, MX_F64, [&](mx_result &res) {   // always a NumericVector (slice.cpp:363)
         Csr A;
-        if ((rc = A.upload(indptr, indices, values, nrows, has_values ? dtype_bytes(value_dtype) : 0))) break;
+        if (A.upload(indptr, indices, values, nrows, has_values ? dtype_bytes(value_dtype) : 0)) return 1;
         DevBuf rows, ws;
-        if ((rc = rows.upload(rows_take, sizeof(int32_t) * (size_t)n_take))) break;
-        if ((rc = ws.alloc(mxd_gather_workspace_bytes((int)n_take)))) break;
-        if ((rc = res->indptr.alloc(sizeof(int32_t) * ((size_t)n_take + 1)))) break;
+        if (rows.upload(rows_take, sizeof(int32_t) * (size_t)n_take)) return 1;
+        if (ws.alloc(mxd_gather_workspace_bytes((int)n_take))) return 1;
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)n_take + 1))) return 1;
         const double avg = nrows > 0 ? (double)A.nnz / nrows : 0.0;
         int64_t nnz_out = 0;
-        if ((rc = mxd_csr_colrange_count((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), rows.as<int32_t>(), min_col,
-                                         max_col, avg, res->indptr.as<int32_t>(), ws.p, &nnz_out, nullptr))) break;
-        res->info.indptr_len = n_take + 1;
-        res->info.nnz = nnz_out;
-        res->info.values_len = has_values ? nnz_out : 0;
-        if (nnz_out == 0) { res->info.values_len = 0; break; }                 // slice.cpp:355-359
-        if ((rc = res->indices.alloc(sizeof(int32_t) * (size_t)nnz_out))) break;
-        if (has_values && (rc = res->values.alloc(sizeof(double) * (size_t)nnz_out))) break;
-        if ((rc = mxd_csr_colrange_fill((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p,
-                                        has_values ? value_dtype : MX_NONE, rows.as<int32_t>(), min_col, max_col, avg,
-                                        res->indptr.as<int32_t>(), res->indices.as<int32_t>(), res->values.as<double>(),
-                                        nullptr))) break;
-        if (hipStreamSynchronize(nullptr) != hipSuccess) { rc = set_error("stream sync failed"); break; }
-    } while (0);
-    if (rc) { delete res; return rc; }
-    *info = res->info;
-    *res_out = res;
-    return 0;
+        if (mxd_csr_colrange_count((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), rows.as<int32_t>(), min_col,
+                                   max_col, avg, res.indptr.as<int32_t>(), ws.p, &nnz_out, nullptr)) return 1;
+        res.set_sizes(n_take + 1, nnz_out, has_values ? nnz_out : 0);       // full-length indptr even when empty
+        if (nnz_out == 0) return 0;                                           // slice.cpp:355-359
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
+        if (has_values && res.values.alloc(sizeof(double) * (size_t)nnz_out)) return 1;
+        return mxd_csr_colrange_fill((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p,
+                                     has_values ? value_dtype : MX_NONE, rows.as<int32_t>(), min_col, max_col, avg,
+                                     res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.as<double>(),
+                                     nullptr);
+    });
 }
 
 int mx_copy_csr_arbitrary_begin(const int32_t *indptr, int nrows, const int32_t *indices, const void *values,
@@ -473,52 +447,38 @@ int mx_copy_csr_arbitrary_begin(const int32_t *indptr, int nrows, const int32_t 
         if (c && cols_take[c] < cols_take[c - 1]) cols_sorted = false;
     }
     const int ncol_map = max_j + 1;
-    mx_result *res = new (std::nothrow) mx_result();
-    MX_REQUIRE(res, "out of host memory");
-    res->info.values_dtype = has_values ? value_dtype : MX_NONE;
-    res->info.alias_structure = 0;
-    int rc = 0;
-    do {
+    return begin_result(res_out, info, has_values ? value_dtype : MX_NONE, [&](mx_result &res) {
         Csr A;
-        if ((rc = A.upload(indptr, indices, values, nrows, vb))) break;
+        if (A.upload(indptr, indices, values, nrows, vb)) return 1;
         DevBuf rows, cols, start, pos, ws, mws;
-        if ((rc = rows.upload(rows_take, sizeof(int32_t) * (size_t)n_take))) break;
-        if ((rc = cols.upload(cols_take, sizeof(int32_t) * (size_t)n_cols_take))) break;
-        if ((rc = start.alloc(sizeof(int32_t) * ((size_t)ncol_map + 1)))) break;
-        if ((rc = pos.alloc(sizeof(int32_t) * (size_t)n_cols_take))) break;
-        if ((rc = mws.alloc(mxd_colmap_workspace_bytes(ncol_map)))) break;
-        if ((rc = ws.alloc(mxd_gather_workspace_bytes((int)n_take)))) break;
-        if ((rc = res->indptr.alloc(sizeof(int32_t) * ((size_t)n_take + 1)))) break;
-        if ((rc = mxd_colmap_build(cols.as<int32_t>(), n_cols_take, ncol_map, start.as<int32_t>(), pos.as<int32_t>(),
-                                   mws.p, nullptr))) break;
+        if (rows.upload(rows_take, sizeof(int32_t) * (size_t)n_take)) return 1;
+        if (cols.upload(cols_take, sizeof(int32_t) * (size_t)n_cols_take)) return 1;
+        if (start.alloc(sizeof(int32_t) * ((size_t)ncol_map + 1))) return 1;
+        if (pos.alloc(sizeof(int32_t) * (size_t)n_cols_take)) return 1;
+        if (mws.alloc(mxd_colmap_workspace_bytes(ncol_map))) return 1;
+        if (ws.alloc(mxd_gather_workspace_bytes((int)n_take))) return 1;
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)n_take + 1))) return 1;
+        if (mxd_colmap_build(cols.as<int32_t>(), n_cols_take, ncol_map, start.as<int32_t>(), pos.as<int32_t>(), mws.p,
+                             nullptr)) return 1;
         const double avg = nrows > 0 ? (double)A.nnz / nrows : 0.0;
         int64_t nnz_out = 0;
-        if ((rc = mxd_csr_colmap_count((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), rows.as<int32_t>(), ncol_map,
-                                       start.as<int32_t>(), avg, res->indptr.as<int32_t>(), ws.p, &nnz_out, nullptr))) break;
-        res->info.indptr_len = n_take + 1;
-        res->info.nnz = nnz_out;
-        res->info.values_len = has_values ? nnz_out : 0;
-        if (nnz_out == 0) break;
-        if ((rc = res->indices.alloc(sizeof(int32_t) * (size_t)nnz_out))) break;
-        if (has_values && (rc = res->values.alloc(vb * (size_t)nnz_out))) break;
-        if ((rc = mxd_csr_colmap_fill((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p,
-                                      has_values ? value_dtype : MX_NONE, rows.as<int32_t>(), ncol_map,
-                                      start.as<int32_t>(), pos.as<int32_t>(), avg, res->indptr.as<int32_t>(),
-                                      res->indices.as<int32_t>(), res->values.p, nullptr))) break;
-        if (!cols_sorted) {                                                   // slice.cpp:540-560
-            DevBuf tj, tx;
-            if ((rc = tj.alloc(sizeof(int32_t) * (size_t)nnz_out))) break;
-            if (has_values && (rc = tx.alloc(vb * (size_t)nnz_out))) break;
-            if ((rc = mxd_csr_sort_rows((int)n_take, nnz_out, res->indptr.as<int32_t>(), res->indices.as<int32_t>(),
-                                        res->values.p, has_values ? value_dtype : MX_NONE, tj.as<int32_t>(), tx.p, nullptr))) break;
-            if (hipStreamSynchronize(nullptr) != hipSuccess) { rc = set_error("stream sync failed"); break; }
-        }
-        if (hipStreamSynchronize(nullptr) != hipSuccess) { rc = set_error("stream sync failed"); break; }
-    } while (0);
-    if (rc) { delete res; return rc; }
-    *info = res->info;
-    *res_out = res;
-    return 0;
+        if (mxd_csr_colmap_count((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), rows.as<int32_t>(), ncol_map,
+                                 start.as<int32_t>(), avg, res.indptr.as<int32_t>(), ws.p, &nnz_out, nullptr)) return 1;
+        res.set_sizes(n_take + 1, nnz_out, has_values ? nnz_out : 0);
+        if (nnz_out == 0) return 0;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
+        if (has_values && res.values.alloc(vb * (size_t)nnz_out)) return 1;
+        if (mxd_csr_colmap_fill((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p,
+                                has_values ? value_dtype : MX_NONE, rows.as<int32_t>(), ncol_map, start.as<int32_t>(),
+                                pos.as<int32_t>(), avg, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
+                                res.values.p, nullptr)) return 1;
+        if (cols_sorted) return 0;
+        DevBuf tj, tx;                                                        // slice.cpp:540-560
+        if (tj.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
+        if (has_values && tx.alloc(vb * (size_t)nnz_out)) return 1;
+        return mxd_csr_sort_rows((int)n_take, nnz_out, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
+                                 res.values.p, has_values ? value_dtype : MX_NONE, tj.as<int32_t>(), tx.p, nullptr);
+    });
 }
 
 int mx_reverse_rows_begin(const int32_t *indptr, int nrows, const int32_t *indices, const void *values,
@@ -529,37 +489,25 @@ int mx_reverse_rows_begin(const int32_t *indptr, int nrows, const int32_t *indic
     *res_out = nullptr;
     const bool has_values = value_dtype != MX_NONE && n_values > 0;           // slice.cpp:66
     const size_t vb = has_values ? dtype_bytes(value_dtype) : 0;
-    mx_result *res = new (std::nothrow) mx_result();
-    MX_REQUIRE(res, "out of host memory");
-    res->info.values_dtype = has_values ? value_dtype : MX_NONE;
-    res->info.alias_structure = 0;
-    int rc = 0;
-    do {
+    return begin_result(res_out, info, has_values ? value_dtype : MX_NONE, [&](mx_result &res) {
         Csr A;
-        if ((rc = A.upload(indptr, indices, values, nrows, vb))) break;
+        if (A.upload(indptr, indices, values, nrows, vb)) return 1;
         DevBuf rows, ws;
-        if ((rc = rows.alloc(sizeof(int32_t) * (size_t)nrows))) break;
-        if ((rc = ws.alloc(mxd_gather_workspace_bytes(nrows)))) break;
-        if ((rc = res->indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1)))) break;
-        if ((rc = mxd_reversed_iota(nrows, rows.as<int32_t>(), nullptr))) break;
+        if (rows.alloc(sizeof(int32_t) * (size_t)nrows)) return 1;
+        if (ws.alloc(mxd_gather_workspace_bytes(nrows))) return 1;
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        if (mxd_reversed_iota(nrows, rows.as<int32_t>(), nullptr)) return 1;
         int64_t nnz_out = 0;
-        if ((rc = mxd_csr_gather_count(nrows, A.p.as<int32_t>(), rows.as<int32_t>(), res->indptr.as<int32_t>(), ws.p,
-                                       &nnz_out, nullptr))) break;
-        res->info.indptr_len = (int64_t)nrows + 1;                            // always full length (slice.cpp:57)
-        res->info.nnz = nnz_out;
-        res->info.values_len = has_values ? nnz_out : 0;
-        if (nnz_out == 0) break;
-        if ((rc = res->indices.alloc(sizeof(int32_t) * (size_t)nnz_out))) break;
-        if (has_values && (rc = res->values.alloc(vb * (size_t)nnz_out))) break;
-        if ((rc = mxd_csr_gather_fill(nrows, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, rows.as<int32_t>(),
-                                      res->indptr.as<int32_t>(), res->indices.as<int32_t>(), res->values.p,
-                                      has_values ? value_dtype : MX_NONE, nnz_out, nullptr))) break;
-        if (hipStreamSynchronize(nullptr) != hipSuccess) { rc = set_error("stream sync failed"); break; }
-    } while (0);
-    if (rc) { delete res; return rc; }
-    *info = res->info;
-    *res_out = res;
-    return 0;
+        if (mxd_csr_gather_count(nrows, A.p.as<int32_t>(), rows.as<int32_t>(), res.indptr.as<int32_t>(), ws.p,
+                                 &nnz_out, nullptr)) return 1;
+        res.set_sizes((int64_t)nrows + 1, nnz_out, has_values ? nnz_out : 0);   // always full length (slice.cpp:57)
+        if (nnz_out == 0) return 0;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
+        if (has_values && res.values.alloc(vb * (size_t)nnz_out)) return 1;
+        return mxd_csr_gather_fill(nrows, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, rows.as<int32_t>(),
+                                   res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.p,
+                                   has_values ? value_dtype : MX_NONE, nnz_out, nullptr);
+    });
 }
 
 int mx_reverse_columns_inplace(const int32_t *indptr, int nrows, int32_t *indices, void *values, int value_dtype,
@@ -668,37 +616,26 @@ int mx_cbind_csr_begin(const int32_t *Xp, int nX, const int32_t *Xj, const void 
     *res_out = nullptr;
     const bool has_values = value_dtype != MX_NONE && (nvX > 0 || nvY > 0);           // cbind.cpp:19-20
     const size_t vb = has_values ? dtype_bytes(value_dtype) : 0;
-    mx_result *res = new (std::nothrow) mx_result();
-    MX_REQUIRE(res, "out of host memory");
-    res->info.values_dtype = value_dtype == MX_NONE ? MX_F64 : value_dtype;           // binary: empty NumericVector
-    res->info.alias_structure = 0;
-    int rc = 0;
-    do {
+    // binary: an empty NumericVector
+    return begin_result(res_out, info, value_dtype == MX_NONE ? MX_F64 : value_dtype, [&](mx_result &res) {
         Csr X, Y;
-        if ((rc = X.upload(Xp, Xj, Xx, nX, vb))) break;
-        if ((rc = Y.upload(Yp, Yj, Yx, nY, vb))) break;
+        if (X.upload(Xp, Xj, Xx, nX, vb)) return 1;
+        if (Y.upload(Yp, Yj, Yx, nY, vb)) return 1;
         const int nrows = nX > nY ? nX : nY;
         const int64_t nnz = X.nnz + Y.nnz;
-        if (nnz > INT_MAX) { rc = set_error("cbind result exceeds R's int32 index range"); break; }
-        res->info.indptr_len = (int64_t)nrows + 1;
-        res->info.nnz = nnz;
-        res->info.values_len = has_values ? nnz : 0;
-        if ((rc = res->indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1)))) break;
+        MX_REQUIRE(nnz <= INT_MAX, "cbind result exceeds R's int32 index range");
+        res.set_sizes((int64_t)nrows + 1, nnz, has_values ? nnz : 0);
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
         if (nnz == 0) {                                                               // cbind.cpp:22-29: zeros
-            if (hipMemset(res->indptr.p, 0, sizeof(int32_t) * ((size_t)nrows + 1)) != hipSuccess) rc = set_error("hipMemset failed");
-            break;
+            MX_HIP(hipMemset(res.indptr.p, 0, sizeof(int32_t) * ((size_t)nrows + 1)));
+            return 0;
         }
-        if ((rc = res->indices.alloc(sizeof(int32_t) * (size_t)nnz))) break;
-        if (has_values && (rc = res->values.alloc(vb * (size_t)nnz))) break;
-        if ((rc = mxd_csr_cbind(nX, nY, X.p.as<int32_t>(), X.j.as<int32_t>(), X.x.p, Y.p.as<int32_t>(), Y.j.as<int32_t>(),
-                                Y.x.p, has_values ? value_dtype : MX_NONE, nnz, res->indptr.as<int32_t>(),
-                                res->indices.as<int32_t>(), res->values.p, nullptr))) break;
-        if (hipStreamSynchronize(nullptr) != hipSuccess) { rc = set_error("stream sync failed"); break; }
-    } while (0);
-    if (rc) { delete res; return rc; }
-    *info = res->info;
-    *res_out = res;
-    return 0;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz)) return 1;
+        if (has_values && res.values.alloc(vb * (size_t)nnz)) return 1;
+        return mxd_csr_cbind(nX, nY, X.p.as<int32_t>(), X.j.as<int32_t>(), X.x.p, Y.p.as<int32_t>(), Y.j.as<int32_t>(),
+                             Y.x.p, has_values ? value_dtype : MX_NONE, nnz, res.indptr.as<int32_t>(),
+                             res.indices.as<int32_t>(), res.values.p, nullptr);
+    });
 }
 
 int mx_concat_csr_batch_begin(const mx_rbind_input *objs, int n_inputs, int out_kind, mx_result **res_out,
@@ -714,67 +651,51 @@ int mx_concat_csr_batch_begin(const mx_rbind_input *objs, int n_inputs, int out_
     }
     MX_REQUIRE(nrows <= INT_MAX - 1 && nnz <= INT_MAX, "rbind result exceeds R's int32 index range");
     const size_t vb = out_kind == 0 ? 8 : out_kind == 1 ? 4 : 0;
-    mx_result *res = new (std::nothrow) mx_result();
-    MX_REQUIRE(res, "out of host memory");
-    res->info.values_dtype = out_kind == 0 ? MX_F64 : out_kind == 1 ? MX_LGL : MX_NONE;
-    res->info.alias_structure = 0;
-    res->info.indptr_len = nrows + 1;
-    res->info.nnz = nnz;
-    res->info.values_len = vb ? nnz : 0;
-    int rc = 0;
-    do {
-        if ((rc = res->indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1)))) break;
-        if ((rc = res->indices.alloc(sizeof(int32_t) * (size_t)nnz))) break;
-        if (vb && (rc = res->values.alloc(vb * (size_t)nnz))) break;
-        if (hipMemset(res->indptr.p, 0, sizeof(int32_t)) != hipSuccess) { rc = set_error("hipMemset failed"); break; }
+    return begin_result(res_out, info, out_kind == 0 ? MX_F64 : out_kind == 1 ? MX_LGL : MX_NONE, [&](mx_result &res) {
+        res.set_sizes(nrows + 1, nnz, vb ? nnz : 0);
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz)) return 1;
+        if (vb && res.values.alloc(vb * (size_t)nnz)) return 1;
+        MX_HIP(hipMemset(res.indptr.p, 0, sizeof(int32_t)));
         int row = 0;
         int64_t pos = 0;
-        for (int k = 0; k < n_inputs && !rc; k++) {
+        for (int k = 0; k < n_inputs; k++) {
             const mx_rbind_input &o = objs[k];
             const bool vec = o.kind >= 3;
             const size_t ivb = (o.kind == 0 || o.kind == 3) ? 8 : (o.kind == 2 || o.kind == 6) ? 0 : 4;
             DevBuf p, j, x;
-            if (!vec && (rc = p.upload(o.indptr, sizeof(int32_t) * ((size_t)o.nrows + 1)))) break;
-            if ((rc = j.upload(o.indices, sizeof(int32_t) * (size_t)o.nnz))) break;
-            if (ivb && (rc = x.upload(o.values, ivb * (size_t)o.nnz))) break;
-            if ((rc = mxd_csr_rbind_append(o.kind, p.as<int32_t>(), j.as<int32_t>(), ivb ? x.p : nullptr, vec ? 1 : o.nrows,
-                                           o.nnz, out_kind, row, pos, res->indptr.as<int32_t>(), res->indices.as<int32_t>(),
-                                           res->values.p, nullptr))) break;
-            if (hipStreamSynchronize(nullptr) != hipSuccess) { rc = set_error("stream sync failed"); break; }
+            if (!vec && p.upload(o.indptr, sizeof(int32_t) * ((size_t)o.nrows + 1))) return 1;
+            if (j.upload(o.indices, sizeof(int32_t) * (size_t)o.nnz)) return 1;
+            if (ivb && x.upload(o.values, ivb * (size_t)o.nnz)) return 1;
+            if (mxd_csr_rbind_append(o.kind, p.as<int32_t>(), j.as<int32_t>(), ivb ? x.p : nullptr, vec ? 1 : o.nrows,
+                                     o.nnz, out_kind, row, pos, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
+                                     res.values.p, nullptr)) return 1;
+            MX_HIP(hipStreamSynchronize(nullptr));
             row += vec ? 1 : o.nrows;
             pos += o.nnz;
         }
-    } while (0);
-    if (rc) { delete res; return rc; }
-    *info = res->info;
-    *res_out = res;
-    return 0;
+        return 0;
+    });
 }
 
 int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, void *out_values)
 {
     MX_REQUIRE(res, "mx_result_finish: null handle");
-    int rc = 0;
-    do {
-        const mx_result_info &inf = res->info;
-        if (!inf.alias_structure) {
-            if (inf.indptr_len > 0 && out_indptr &&
-                mx::xfer_d2h(out_indptr, res->indptr.p, sizeof(int32_t) * (size_t)inf.indptr_len) != 0) {
-                rc = set_error("D2H copy of indptr failed"); break;
-            }
-            if (inf.nnz > 0 && out_indices &&
-                mx::xfer_d2h(out_indices, res->indices.p, sizeof(int32_t) * (size_t)inf.nnz) != 0) {
-                rc = set_error("D2H copy of indices failed"); break;
-            }
-        }
-        const size_t vb = dtype_bytes(inf.values_dtype);
-        if (vb && inf.values_len > 0 && out_values && res->values.p &&
-            mx::xfer_d2h(out_values, res->values.p, vb * (size_t)inf.values_len) != 0) {
-            rc = set_error("D2H copy of values failed"); break;
-        }
-    } while (0);
-    delete res;
-    return rc;
+    const std::unique_ptr<mx_result> owned(res);
+    const mx_result_info &inf = res->info;
+    if (!inf.alias_structure) {
+        if (inf.indptr_len > 0 && out_indptr &&
+            mx::xfer_d2h(out_indptr, res->indptr.p, sizeof(int32_t) * (size_t)inf.indptr_len) != 0)
+            return set_error("D2H copy of indptr failed");
+        if (inf.nnz > 0 && out_indices &&
+            mx::xfer_d2h(out_indices, res->indices.p, sizeof(int32_t) * (size_t)inf.nnz) != 0)
+            return set_error("D2H copy of indices failed");
+    }
+    const size_t vb = dtype_bytes(inf.values_dtype);
+    if (vb && inf.values_len > 0 && out_values && res->values.p &&
+        mx::xfer_d2h(out_values, res->values.p, vb * (size_t)inf.values_len) != 0)
+        return set_error("D2H copy of values failed");
+    return 0;
 }
 
 int mx_result_discard(mx_result *res) { delete res; return 0; }

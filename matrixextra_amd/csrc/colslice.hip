@@ -16,10 +16,6 @@
 
 namespace mx {
 
-int exclusive_scan_i32(const int32_t *counts, int64_t n, int32_t *out, int64_t *total_dev, void *workspace,
-                       hipStream_t st);
-size_t scan_workspace_bytes(int64_t n);
-
 constexpr int CS_BLOCK = 256;
 
 template <int G>
@@ -199,8 +195,6 @@ void reversed_iota_kernel(int n, int32_t *__restrict__ out)
     if (i < n) out[i] = n - 1 - i;
 }
 
-static inline size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 }  // namespace mx
 
 #define MX_GROUP_SWITCH(G, ...)                                                              \
@@ -213,20 +207,6 @@ static inline size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
         default: return mx::set_error("bad lane-group size %d", G);                          \
     }
 
-static int finish_count(int r, int32_t *lens, int32_t *new_indptr, void *scan_ws, int64_t *nnz_out_host, hipStream_t st)
-{
-    int64_t *total_dev = (int64_t *)scan_ws;
-    const int rc = mx::exclusive_scan_i32(lens, r, new_indptr, total_dev, scan_ws, st);
-    if (rc) return rc;
-    if (nnz_out_host) {
-        MX_HIP(hipMemcpyAsync(nnz_out_host, total_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        MX_HIP(hipStreamSynchronize(st));
-        MX_REQUIRE(*nnz_out_host <= (int64_t)INT_MAX, "result has %lld entries: exceeds R's int32 index range",
-                   (long long)*nnz_out_host);
-    }
-    return 0;
-}
-
 // lanes per picked row: the source rows' mean length is what matters (nnz_src / nrows_src)
 static int group_for(double avg) { return mx::pick_group(avg); }
 
@@ -237,14 +217,13 @@ extern "C" int mxd_csr_colrange_count(int r, const int32_t *indptr, const int32_
     MX_REQUIRE(r >= 0 && new_indptr && workspace, "mxd_csr_colrange_count: bad arguments");
     hipStream_t st = mx::as_stream(stream);
     int32_t *lens = (int32_t *)workspace;
-    void *scan_ws = (char *)workspace + mx::pad16((size_t)(r > 0 ? r : 1) * sizeof(int32_t));
     if (r > 0) {
         const int G = group_for(avg_row_len);
         MX_GROUP_SWITCH(G, hipLaunchKernelGGL((mx::colrange_count_kernel<GG>), dim3((unsigned)mx::ceil_div(r, mx::CS_BLOCK / GG)),
                                               dim3(mx::CS_BLOCK), 0, st, r, indptr, indices, rows_take, min_col, max_col, lens));
         MX_LAUNCH_CHECK();
     }
-    return finish_count(r, lens, new_indptr, scan_ws, nnz_out_host, st);
+    return mx::finish_count(r, workspace, new_indptr, nnz_out_host, st);
 }
 
 extern "C" int mxd_csr_colrange_fill(int r, const int32_t *indptr, const int32_t *indices, const void *values,
@@ -274,7 +253,7 @@ extern "C" int mxd_csr_colrange_fill(int r, const int32_t *indptr, const int32_t
 extern "C" size_t mxd_colmap_workspace_bytes(int ncol_map)
 {
     // [cursor int32[ncol_map]][counts int32[ncol_map]][scan workspace]
-    return 2 * mx::pad16((size_t)(ncol_map > 0 ? ncol_map : 1) * sizeof(int32_t)) + mx::scan_workspace_bytes(ncol_map);
+    return 2 * mx::padded_i32_bytes(ncol_map) + mx::scan_workspace_bytes(ncol_map);
 }
 
 extern "C" int mxd_colmap_build(const int32_t *cols_take, int64_t n, int ncol_map, int32_t *start, int32_t *pos,
@@ -282,7 +261,7 @@ extern "C" int mxd_colmap_build(const int32_t *cols_take, int64_t n, int ncol_ma
 {
     MX_REQUIRE(n >= 0 && ncol_map >= 0 && start && workspace, "mxd_colmap_build: bad arguments");
     hipStream_t st = mx::as_stream(stream);
-    const size_t seg = mx::pad16((size_t)(ncol_map > 0 ? ncol_map : 1) * sizeof(int32_t));
+    const size_t seg = mx::padded_i32_bytes(ncol_map);
     int32_t *cursor = (int32_t *)workspace;
     int32_t *cnt = (int32_t *)((char *)workspace + seg);
     void *scan_ws = (char *)workspace + 2 * seg;
@@ -311,14 +290,13 @@ extern "C" int mxd_csr_colmap_count(int r, const int32_t *indptr, const int32_t 
     MX_REQUIRE(r >= 0 && new_indptr && workspace, "mxd_csr_colmap_count: bad arguments");
     hipStream_t st = mx::as_stream(stream);
     int32_t *lens = (int32_t *)workspace;
-    void *scan_ws = (char *)workspace + mx::pad16((size_t)(r > 0 ? r : 1) * sizeof(int32_t));
     if (r > 0) {
         const int G = group_for(avg_row_len);
         MX_GROUP_SWITCH(G, hipLaunchKernelGGL((mx::colmap_rows_count_kernel<GG>), dim3((unsigned)mx::ceil_div(r, mx::CS_BLOCK / GG)),
                                               dim3(mx::CS_BLOCK), 0, st, r, indptr, indices, rows_take, ncol_map, start, lens));
         MX_LAUNCH_CHECK();
     }
-    return finish_count(r, lens, new_indptr, scan_ws, nnz_out_host, st);
+    return mx::finish_count(r, workspace, new_indptr, nnz_out_host, st);
 }
 
 extern "C" int mxd_csr_colmap_fill(int r, const int32_t *indptr, const int32_t *indices, const void *values,

@@ -13,10 +13,6 @@
 
 namespace mx {
 
-int exclusive_scan_i32(const int32_t *counts, int64_t n, int32_t *out, int64_t *total_dev, void *workspace,
-                       hipStream_t st);
-size_t scan_workspace_bytes(int64_t n);
-
 constexpr int GATHER_BLOCK = 256;
 
 __global__ __launch_bounds__(GATHER_BLOCK)
@@ -142,11 +138,7 @@ static int launch_sort_rows(int G, int m, const int32_t *indptr, const int32_t *
 
 }  // namespace mx
 
-extern "C" size_t mxd_gather_workspace_bytes(int r)
-{
-    const size_t lens = ((size_t)(r > 0 ? r : 1) * sizeof(int32_t) + 15) & ~(size_t)15;
-    return lens + mx::scan_workspace_bytes(r);
-}
+extern "C" size_t mxd_gather_workspace_bytes(int r) { return mx::count_workspace_bytes(r); }
 
 extern "C" int mxd_csr_gather_count(int r, const int32_t *indptr, const int32_t *rows_take, int32_t *new_indptr,
                                     void *workspace, int64_t *nnz_out_host, void *stream)
@@ -154,24 +146,12 @@ extern "C" int mxd_csr_gather_count(int r, const int32_t *indptr, const int32_t 
     MX_REQUIRE(r >= 0, "mxd_csr_gather_count: negative r");
     MX_REQUIRE(new_indptr && workspace, "mxd_csr_gather_count: null pointer");
     hipStream_t st = mx::as_stream(stream);
-    int32_t *lens = (int32_t *)workspace;
-    const size_t lens_bytes = ((size_t)(r > 0 ? r : 1) * sizeof(int32_t) + 15) & ~(size_t)15;
-    void *scan_ws = (char *)workspace + lens_bytes;
     if (r > 0) {
         hipLaunchKernelGGL(mx::gather_lengths_kernel, dim3((unsigned)mx::ceil_div(r, mx::GATHER_BLOCK)),
-                           dim3(mx::GATHER_BLOCK), 0, st, r, indptr, rows_take, lens);
+                           dim3(mx::GATHER_BLOCK), 0, st, r, indptr, rows_take, (int32_t *)workspace);
         MX_LAUNCH_CHECK();
     }
-    int64_t *total_dev = (int64_t *)scan_ws;
-    const int rc = mx::exclusive_scan_i32(lens, r, new_indptr, total_dev, scan_ws, st);
-    if (rc) return rc;
-    if (nnz_out_host) {
-        MX_HIP(hipMemcpyAsync(nnz_out_host, total_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        MX_HIP(hipStreamSynchronize(st));
-        MX_REQUIRE(*nnz_out_host <= (int64_t)INT_MAX, "result has %lld entries: exceeds R's int32 index range",
-                   (long long)*nnz_out_host);
-    }
-    return 0;
+    return mx::finish_count(r, workspace, new_indptr, nnz_out_host, st);
 }
 
 extern "C" int mxd_csr_gather_fill(int r, const int32_t *indptr, const int32_t *indices, const void *values,

@@ -30,10 +30,6 @@
 
 namespace mx {
 
-int exclusive_scan_i32(const int32_t *counts, int64_t n, int32_t *out, int64_t *total_dev, void *workspace,
-                       hipStream_t st);
-size_t scan_workspace_bytes(int64_t n);
-
 constexpr int MERGE_BLOCK = 256;
 
 // ballot restricted to this lane's G-wide group
@@ -305,12 +301,7 @@ int merge_fill_launch(int op, int G, int m, const int32_t *p1, const int32_t *j1
 
 }  // namespace mx
 
-extern "C" size_t mxd_merge_workspace_bytes(int m)
-{
-    // [counts int32[m] padded to 16 B][scan workspace]
-    const size_t counts = ((size_t)(m > 0 ? m : 1) * sizeof(int32_t) + 15) & ~(size_t)15;
-    return counts + mx::scan_workspace_bytes(m);
-}
+extern "C" size_t mxd_merge_workspace_bytes(int m) { return mx::count_workspace_bytes(m); }
 
 extern "C" int mxd_csr_merge_count(int op, int m, const int32_t *indptr1, const int32_t *indices1, int64_t nnz1,
                                    const int32_t *indptr2, const int32_t *indices2, int64_t nnz2,
@@ -319,23 +310,12 @@ extern "C" int mxd_csr_merge_count(int op, int m, const int32_t *indptr1, const 
     MX_REQUIRE(m >= 0, "mxd_csr_merge_count: negative m");
     MX_REQUIRE(out_indptr && workspace, "mxd_csr_merge_count: null pointer");
     hipStream_t st = mx::as_stream(stream);
-    int32_t *counts = (int32_t *)workspace;
-    const size_t counts_bytes = ((size_t)(m > 0 ? m : 1) * sizeof(int32_t) + 15) & ~(size_t)15;
-    void *scan_ws = (char *)workspace + counts_bytes;
     if (m > 0) {
-        const int rc = mx::merge_count_launch(op, mx::merge_group(m, nnz1, nnz2), m, indptr1, indices1, indptr2, indices2, counts, st);
+        const int rc = mx::merge_count_launch(op, mx::merge_group(m, nnz1, nnz2), m, indptr1, indices1, indptr2, indices2,
+                                              (int32_t *)workspace, st);
         if (rc) return rc;
     }
-    int64_t *total_dev = (int64_t *)scan_ws;   // first word of the scan workspace
-    const int rc = mx::exclusive_scan_i32(counts, m, out_indptr, total_dev, scan_ws, st);
-    if (rc) return rc;
-    if (nnz_out_host) {
-        MX_HIP(hipMemcpyAsync(nnz_out_host, total_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        MX_HIP(hipStreamSynchronize(st));
-        MX_REQUIRE(*nnz_out_host <= (int64_t)INT_MAX, "result has %lld entries: exceeds R's int32 index range",
-                   (long long)*nnz_out_host);
-    }
-    return 0;
+    return mx::finish_count(m, workspace, out_indptr, nnz_out_host, st);
 }
 
 extern "C" int mxd_csr_merge_fill(int op, int m, const int32_t *indptr1, const int32_t *indices1, const void *values1,

@@ -38,6 +38,30 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// scan.hip: exclusive scan of counts[0..n) into out[0..n]; the int64 total goes to *total_dev (the workspace's
+// first word when null)
+size_t scan_workspace_bytes(int64_t n);
+int exclusive_scan_i32(const int32_t *counts, int64_t n, int32_t *out, int64_t *total_dev, void *workspace,
+                       hipStream_t st);
+// (hidden: internal to libmxgpu, kept out of its dynamic symbol table)
+#pragma GCC visibility push(hidden)
+// bytes of an int32 array of max(n, 1) entries, padded to 16 B
+size_t padded_i32_bytes(int64_t n);
+// count -> scan -> read-back: workspace is [int32 counts[n], padded_i32_bytes(n)][scan workspace]; counts are
+// scanned into indptr[0..n], and the total is read back into *nnz_out_host (when non-null) and checked against R's
+// int32 index range
+size_t count_workspace_bytes(int64_t n);
+int finish_count(int64_t n, void *workspace, int32_t *indptr, int64_t *nnz_out_host, hipStream_t st);
+#pragma GCC visibility pop
+
+// xfer.hip: synchronous host <-> device copies, pipelined through pinned slots + a host copy pool when large
+int xfer_h2d(void *dst_dev, const void *src_host, size_t bytes);
+int xfer_d2h(void *dst_host, const void *src_dev, size_t bytes);
+
+// spmv.hip
+int spmv_launch(int m, int64_t nnz, const int32_t *indptr, const int32_t *indices, const double *values,
+                const void *v, int v_dtype, void *y, hipStream_t st);
+
 // lanes-per-row for the sub-wave ("group") kernels: smallest power of two
 // >= avg row length, clamped to [lo, 64]
 inline int pick_group(double avg_len, int lo = 4)

@@ -174,6 +174,24 @@ int exclusive_scan_i32(const int32_t *counts, int64_t n, int32_t *out, int64_t *
     return 0;
 }
 
+size_t padded_i32_bytes(int64_t n) { return ((size_t)(n > 0 ? n : 1) * sizeof(int32_t) + 15) & ~(size_t)15; }
+
+size_t count_workspace_bytes(int64_t n) { return padded_i32_bytes(n) + scan_workspace_bytes(n); }
+
+int finish_count(int64_t n, void *workspace, int32_t *indptr, int64_t *nnz_out_host, hipStream_t st)
+{
+    void *scan_ws = (char *)workspace + padded_i32_bytes(n);
+    int64_t *total_dev = (int64_t *)scan_ws;
+    if (exclusive_scan_i32((const int32_t *)workspace, n, indptr, total_dev, scan_ws, st)) return 1;
+    if (nnz_out_host) {
+        MX_HIP(hipMemcpyAsync(nnz_out_host, total_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        MX_HIP(hipStreamSynchronize(st));
+        MX_REQUIRE(*nnz_out_host <= (int64_t)INT_MAX, "result has %lld entries: exceeds R's int32 index range",
+                   (long long)*nnz_out_host);
+    }
+    return 0;
+}
+
 }  // namespace mx
 
 extern "C" size_t mxd_scan_workspace_bytes(int64_t n) { return mx::scan_workspace_bytes(n); }

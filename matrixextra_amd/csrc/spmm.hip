@@ -1017,10 +1017,6 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
     }
 }
 
-int exclusive_scan_i32(const int32_t *counts, int64_t n, int32_t *out, int64_t *total_dev, void *workspace,
-                       hipStream_t st);
-size_t scan_workspace_bytes(int64_t n);
-
 }  // namespace mx
 
 // device-resident plan of one CSR matrix (see the v3 comment above)
