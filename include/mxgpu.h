@@ -118,7 +118,9 @@ int mxd_spmm_csr_dense_ex(int m, int n, int K,
  * stream sync (the padded size comes back to the host).  npanels <= 0 picks K*128 B / 2.5 MB.
  * mxd_spmm_plan_run: sync_mode 0 = free running, 1 = the waves of a CU's workgroup meet at every panel boundary,
  * 2 = 1 + one timing barrier per generation among the workgroups of an XCD group; -1 = default (1).
- * Needs 16-B aligned rows of B; wg_per_cu is ignored (one 1024-thread workgroup per CU). */
+ * Needs 16-B aligned rows of B (and of C when C is row-major).  wg_per_cu 1 / 2 / 4 = that many workgroups of
+ * 16 / 8 / 4 wavefronts per CU (1024 / 512 / 256 rows per generation); any other value picks the default (1).
+ * mxd_spmm_csr_dense_ex runs its plans with the defaults (wg_per_cu and sync_mode). */
 typedef struct mx_spmm_plan mx_spmm_plan;
 int mxd_spmm_plan_create(int m, int K, const int32_t *indptr, const int32_t *indices, const double *values,
                          int npanels, void *stream, mx_spmm_plan **plan);

@@ -128,7 +128,7 @@ __device__ __forceinline__ void spmm_chunk(int cnt, int jv, double av,
 
 // TR rows per workgroup.  COLMAJOR: stage the tile in LDS and write transposed.
 // VSTORE (COLMAJOR only): two consecutive rows per lane -> wider stores; needs
-// even ldc and 2*sizeof(real_t)-aligned C.
+// even m, even ldc and 2*sizeof(real_t)-aligned C.
 template <typename real_t, int VEC, bool COLMAJOR, bool VSTORE, int TR>
 __global__ __launch_bounds__(SPMM_WAVES * MX_WAVE)
 void spmm_rowwave_kernel(int m, int n,
@@ -237,7 +237,9 @@ static int dispatch_spmm(int m, int n, const int32_t *indptr, const int32_t *ind
     // widest per-lane access the operands allow (16 B when rows of B are 16-B aligned)
     const bool b_vec = (n % VECMAX == 0) && (ldb % VECMAX == 0) && ((uintptr_t)B % (VECMAX * sizeof(real_t)) == 0);
     if (colmajor) {
-        const bool vs = (ldc % 2 == 0) && ((uintptr_t)C % (2 * sizeof(real_t)) == 0);
+        // paired stores write rows grow and grow+1 (grow even): with m odd the last pair would write row m, which
+        // is the column's ldc padding when ldc > m
+        const bool vs = (m % 2 == 0) && (ldc % 2 == 0) && ((uintptr_t)C % (2 * sizeof(real_t)) == 0);
         if (b_vec) return vs ? launch_spmm<real_t, VECMAX, true, true>(m, n, indptr, indices, values, B, ldb, C, ldc, stream)
                              : launch_spmm<real_t, VECMAX, true, false>(m, n, indptr, indices, values, B, ldb, C, ldc, stream);
         return vs ? launch_spmm<real_t, 1, true, true>(m, n, indptr, indices, values, B, ldb, C, ldc, stream)

@@ -84,27 +84,35 @@ class DeviceCSR:
                 None if self.values is None else self.values.cpu().numpy())
 
 
+def _spmm_out(A: DeviceCSR, B: torch.Tensor, out: torch.Tensor | None, colmajor: bool):
+    """Checks B and `out` of an SpMM launch (the kernels write m x n elements at ldc = n, or n x m at ldc = m, and
+    nothing checks that on the device side); allocates `out` when it is None.  Returns (out, ldc)."""
+    if B.dim() != 2 or B.stride(1) != 1 or B.shape[0] != A.K or B.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"B must be a {A.K} x n float64 / float32 tensor with unit column stride, "
+                         f"got {tuple(B.shape)} {B.dtype} with strides {B.stride()}")
+    n = int(B.shape[1])
+    shape = (n, A.m) if colmajor else (A.m, n)
+    if out is not None and (tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != B.dtype
+                            or out.device != B.device):
+        raise ValueError(f"out must be a contiguous {shape} {B.dtype} tensor on {B.device}, "
+                         f"got {tuple(out.shape)} {out.dtype} on {out.device} (contiguous: {out.is_contiguous()})")
+    if not B.is_cuda:
+        raise ValueError("B must be a device tensor")
+    if out is None:
+        out = torch.empty(shape, dtype=B.dtype, device=B.device)
+    return out, shape[1]
+
+
 def spmm(A: DeviceCSR, B: torch.Tensor, out: torch.Tensor | None = None, colmajor: bool = False,
          algo: int = 0, npanels: int = 0, wg_per_cu: int = 0):
     """C = A @ B with B (K x n) row-major in HBM.  colmajor=False: C row-major (m x n) —
     gemm_csr_drm_as_drm layout; colmajor=True: C column-major (what tcrossprod_csr_dense returns to R),
     stored as a row-major (n x m) tensor and returned as its transposed view.
     algo: 0 auto, 1 row-wave kernel, 2 slab/panel kernel (include/mxgpu.h mx_spmm_algo)."""
+    out, ldc = _spmm_out(A, B, out, colmajor)
     lib = _lib.load()
-    assert B.is_cuda and B.dim() == 2 and B.stride(1) == 1 and B.shape[0] == A.K
     n = int(B.shape[1])
     dt = MX_F64 if B.dtype == torch.float64 else MX_F32
-    assert B.dtype in (torch.float64, torch.float32)
-    if colmajor:
-        if out is None:
-            out = torch.empty((n, A.m), dtype=B.dtype, device=B.device)
-        assert out.shape == (n, A.m) and out.is_contiguous()
-        ldc = A.m
-    else:
-        if out is None:
-            out = torch.empty((A.m, n), dtype=B.dtype, device=B.device)
-        assert out.shape == (A.m, n) and out.is_contiguous()
-        ldc = n
     if A.nnz == 0:                       # reference early-out (matmul.cpp:128-129,160-161): all zeros
         out.zero_()
         return out.t() if colmajor else out
@@ -120,18 +128,10 @@ def spmm_planned(A: DeviceCSR, B: torch.Tensor, out: torch.Tensor | None = None,
                  npanels: int = 0, wg_per_cu: int = 0, sync_mode: int = -1, rebuild_plan: bool = False):
     """C = A @ B through the planned panel-sweep kernel (v3).  The plan is built on first use (or every call with
     rebuild_plan=True, which is what a one-shot product from plain CSR costs) and cached on the DeviceCSR."""
+    out, ldc = _spmm_out(A, B, out, colmajor)
     lib = _lib.load()
-    assert B.is_cuda and B.dim() == 2 and B.stride(1) == 1 and B.shape[0] == A.K
     n = int(B.shape[1])
     dt = MX_F64 if B.dtype == torch.float64 else MX_F32
-    if colmajor:
-        if out is None:
-            out = torch.empty((n, A.m), dtype=B.dtype, device=B.device)
-        ldc = A.m
-    else:
-        if out is None:
-            out = torch.empty((A.m, n), dtype=B.dtype, device=B.device)
-        ldc = n
     if A.nnz == 0:
         out.zero_()
         return out.t() if colmajor else out

@@ -74,3 +74,24 @@ def test_ngRMatrix_identity_shortcuts():
     assert isinstance(x, mx.lgRMatrix) and x.p.tolist() == [0, 0, 0] and x.j.size == 0
     s = operators.add_csr_matrices(A, B, True)
     assert isinstance(s, mx.dgRMatrix) and s.x.tolist() == [2.0, 2.0]
+
+
+def test_device_spmm_rejects_mismatched_out():
+    """device.spmm / spmm_planned check `out` before anything is launched (a wrong one used to be written out of
+    bounds by spmm_planned); host tensors suffice, the checks run before the device-tensor check."""
+    import torch
+    from matrixextra_amd import device as D
+    A = D.DeviceCSR(torch.zeros(6, dtype=torch.int32), torch.zeros(0, dtype=torch.int32),
+                    torch.zeros(0, dtype=torch.float64), 5, 7, 0)
+    B = torch.zeros(7, 3, dtype=torch.float64)
+    for fn in (D.spmm, D.spmm_planned):
+        for colmajor, bad in ((False, torch.zeros(3, 5, dtype=torch.float64)),      # the col-major shape
+                              (True, torch.zeros(5, 3, dtype=torch.float64)),       # the row-major shape
+                              (False, torch.zeros(5, 6, dtype=torch.float64)[:, :3]),  # right shape, not contiguous
+                              (False, torch.zeros(5, 3, dtype=torch.float32))):     # wrong dtype
+            with pytest.raises(ValueError, match="out must be a contiguous"):
+                fn(A, B, out=bad, colmajor=colmajor)
+        with pytest.raises(ValueError, match="B must be"):
+            fn(A, torch.zeros(6, 3, dtype=torch.float64))
+        with pytest.raises(ValueError, match="B must be a device tensor"):
+            fn(A, B, out=torch.zeros(5, 3, dtype=torch.float64))
