@@ -270,6 +270,23 @@ int mxd_csr_rows_sorted(int m, const int32_t *indptr, const int32_t *indices,
 int mxd_csr_sort_rows(int m, int64_t nnz, const int32_t *indptr, int32_t *indices, void *values,
                       int value_dtype, int32_t *tmp_indices, void *tmp_values, void *stream);
 
+/* Device transpose of a CSR structure (transpose.hip), replacing t_deep_internal's coercion chain
+ * (R/trans.R:46-56: as(x, "TsparseMatrix") -> t_shallow -> as(x, "RsparseMatrix" / "CsparseMatrix")) and the
+ * Matrix coercions that as.csr.matrix / as.csc.matrix call for a CSC / CSR input (R/conversions.R).  The CSC
+ * arrays of a matrix are the CSR arrays of its transpose, so this serves CSR -> CSR of X^T, CSR -> CSC and
+ * CSC -> CSR alike.  Input: m x n CSR with nnz = indptr[m] entries (nnz passed by the caller); value_dtype
+ * MX_F64 / MX_LGL / MX_NONE.  Output: out_indptr[n+1]; output row c lists, in strictly ascending order, the
+ * source rows of the entries in column c (stable over the input's row order, whatever the order inside a
+ * row); values are copied bit for bit.  Repeated (row, col) pairs inside one input row are merged as Matrix's
+ * triplet coercion does: f64 summed in source order, logical by R's `|`, pattern kept once.  out_indices /
+ * out_values hold nnz entries; *nnz_out_host (after an internal stream sync) is the count after merging.
+ * A column index outside [0, n) fails the call; nothing is written out of bounds.
+ * workspace: mxd_csr_transpose_workspace_bytes(nnz). */
+size_t mxd_csr_transpose_workspace_bytes(int64_t nnz);
+int mxd_csr_transpose(int m, int n, const int32_t *indptr, const int32_t *indices, const void *values,
+                      int value_dtype, int64_t nnz, int32_t *out_indptr, int32_t *out_indices,
+                      void *out_values, void *workspace, int64_t *nnz_out_host, void *stream);
+
 /* ========================================================================== */
 /* (1) export level — host pointers, names follow the Rcpp exports            */
 /* ========================================================================== */
@@ -408,6 +425,13 @@ typedef struct {
 } mx_rbind_input;
 int mx_concat_csr_batch_begin(const mx_rbind_input *objects, int n_inputs, int out_kind,
                               mx_result **res, mx_result_info *info);
+/* t_deep / as.csc.matrix / as.csr.matrix(dgCMatrix): replaces t_deep_internal (R/trans.R:46-56) and the Matrix
+ * coercions that R/conversions.R's as.csr.matrix / as.csc.matrix call, through mxd_csr_transpose.  indptr has
+ * nrows + 1 entries starting at 0; value_dtype MX_F64 / MX_LGL / MX_NONE; n_values = length of the values vector
+ * (0 => pattern).  info.indptr_len = ncols + 1; info.nnz = entries after duplicates are merged. */
+int mx_csr_transpose_begin(const int32_t *indptr, int nrows, int ncols, const int32_t *indices,
+                           const void *values, int value_dtype, int64_t n_values,
+                           mx_result **res, mx_result_info *info);
 int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, void *out_values);
 int mx_result_discard(mx_result *res);
 

@@ -7,6 +7,7 @@
 ### This overlay rebinds those 19 wrappers inside the MatrixExtra namespace so that they `.Call` the routines of
 ### the same names registered by mxgpu_r.so (matrixextra_amd/csrc/r_shim.cpp), which forward to libmxgpu.so.
 ### Every other native routine (~140 of them) keeps pointing at MatrixExtra's own CPU code.
+### It also rebinds t_deep_internal (R/trans.R:46-56) to the device transpose for general d/l/n R/C classes.
 ###
 ### Usage:
 ###   library(MatrixExtra)
@@ -62,11 +63,44 @@ mxgpu_enable <- function(shim_path, min_nnz = 0L) {
         assign(fn, gpu_fun, envir = ns)
         lockBinding(fn, ns)
     }
+    ## t_deep_internal (R/trans.R:46-56), which t(), t_deep() and the deep transposes behind it call: general
+    ## d/l/n R/C classes go through the device transpose; any other class (symmetric, triangular, ...) keeps the
+    ## saved CPU function.
+    cpu_t <- get("t_deep_internal", envir = ns)
+    .mxgpu_state$saved_t_deep <- cpu_t
+    native_t <- getNativeSymbolInfo("mxgpu_csr_transpose", dll)
+    gpu_t <- function(x) {
+        cls <- class(x)[1L]
+        if (!(cls %in% c("dgRMatrix", "lgRMatrix", "ngRMatrix", "dgCMatrix", "lgCMatrix", "ngCMatrix")))
+            return(cpu_t(x))
+        check_valid_matrix(x)
+        csr <- inherits(x, "RsparseMatrix")
+        vals <- if (startsWith(cls, "n")) NULL else x@x
+        r <- .Call(native_t, x@p, if (csr) x@j else x@i, vals, if (csr) ncol(x) else nrow(x))
+        out <- new(cls)
+        out@Dim <- rev(x@Dim)
+        out@Dimnames <- rev(x@Dimnames)
+        out@p <- r$indptr
+        if (csr) out@j <- r$indices else out@i <- r$indices
+        if (!is.null(vals)) out@x <- r$values
+        out
+    }
+    ## check_valid_matrix and the rest of MatrixExtra's internals resolve in its namespace
+    environment(gpu_t) <- list2env(list(native_t = native_t, cpu_t = cpu_t), parent = ns)
+    unlockBinding("t_deep_internal", ns)
+    assign("t_deep_internal", gpu_t, envir = ns)
+    lockBinding("t_deep_internal", ns)
     invisible(TRUE)
 }
 
 mxgpu_disable <- function() {
     ns <- asNamespace("MatrixExtra")
+    if (!is.null(.mxgpu_state$saved_t_deep)) {
+        unlockBinding("t_deep_internal", ns)
+        assign("t_deep_internal", .mxgpu_state$saved_t_deep, envir = ns)
+        lockBinding("t_deep_internal", ns)
+        .mxgpu_state$saved_t_deep <- NULL
+    }
     for (fn in names(.mxgpu_state$saved)) {
         unlockBinding(fn, ns)
         assign(fn, .mxgpu_state$saved[[fn]], envir = ns)

@@ -14,6 +14,7 @@ from . import _lib  # noqa: F401
 from .matrices import (DenseMatrix, MatrixExtraError, NA_INTEGER, NA_LOGICAL, NA_REAL, RsparseMatrix,  # noqa: F401
                        as_csr_matrix, check_valid_matrix, dgCMatrix, dgRMatrix, float32, from_scipy,
                        lgRMatrix, ngRMatrix, options, sort_sparse_indices)
+from .matrices import as_csc_matrix, t_deep, t_shallow  # noqa: F401
 from .matmul import RLogical, crossprod, tcrossprod  # noqa: F401  (`%*%` is the @ operator)
 from .operators import (add_csr_matrices, logicalor_csr_matrices, multiply_csr_by_csr,  # noqa: F401
                         xor_csr_matrices)

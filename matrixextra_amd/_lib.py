@@ -64,6 +64,8 @@ def load() -> C.CDLL:
     lib.mxd_scan_workspace_bytes.argtypes = [C.c_int64]
     lib.mxd_colmap_workspace_bytes.restype = C.c_size_t
     lib.mxd_colmap_workspace_bytes.argtypes = [C.c_int]
+    lib.mxd_csr_transpose_workspace_bytes.restype = C.c_size_t
+    lib.mxd_csr_transpose_workspace_bytes.argtypes = [C.c_int64]
     if lib.mx_abi_version() != 1:
         raise MxError("libmxgpu.so ABI version mismatch")
     _lib = lib

@@ -678,6 +678,36 @@ int mx_concat_csr_batch_begin(const mx_rbind_input *objs, int n_inputs, int out_
     });
 }
 
+// ---- transpose: t_deep / CSR <-> CSC -------------------------------------------------------------------
+int mx_csr_transpose_begin(const int32_t *indptr, int nrows, int ncols, const int32_t *indices, const void *values,
+                           int value_dtype, int64_t n_values, mx_result **res_out, mx_result_info *info)
+{
+    MX_REQUIRE(res_out && info && indptr, "mx_csr_transpose_begin: null pointer");
+    MX_REQUIRE(nrows >= 0 && ncols >= 0, "mx_csr_transpose_begin: negative dimension");
+    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
+               "mx_csr_transpose_begin: unsupported value dtype %d", value_dtype);
+    MX_REQUIRE(indptr[0] == 0 && indptr[nrows] >= 0, "mx_csr_transpose_begin: bad index pointer");
+    *res_out = nullptr;
+    const bool has_values = value_dtype != MX_NONE && n_values > 0;
+    MX_REQUIRE(!has_values || n_values == indptr[nrows], "mx_csr_transpose_begin: lengths of indices and values differ");
+    const size_t vb = has_values ? dtype_bytes(value_dtype) : 0;
+    return begin_result(res_out, info, has_values ? value_dtype : MX_NONE, [&](mx_result &res) {
+        Csr A;
+        if (A.upload(indptr, indices, values, nrows, vb)) return 1;
+        DevBuf ws;
+        if (ws.alloc(mxd_csr_transpose_workspace_bytes(A.nnz))) return 1;
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)ncols + 1))) return 1;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)A.nnz)) return 1;
+        if (has_values && res.values.alloc(vb * (size_t)A.nnz)) return 1;
+        int64_t nnz_out = 0;
+        if (mxd_csr_transpose(nrows, ncols, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p,
+                              has_values ? value_dtype : MX_NONE, A.nnz, res.indptr.as<int32_t>(),
+                              res.indices.as<int32_t>(), res.values.p, ws.p, &nnz_out, nullptr)) return 1;
+        res.set_sizes((int64_t)ncols + 1, nnz_out, has_values ? nnz_out : 0);
+        return 0;
+    });
+}
+
 int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, void *out_values)
 {
     MX_REQUIRE(res, "mx_result_finish: null handle");

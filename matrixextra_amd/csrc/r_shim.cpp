@@ -3,7 +3,8 @@
 // Exports, for the 19 hot-path routines (+ 12 column-slice / reversal routines of SURVEY §8f rank 2), exactly the native-routine names and arities that the
 // reference registers in CallEntries[] (src/RcppExports.cpp:2233-2242, 2290-2291, 2297-2298, 2333-2334,
 // 2341-2343), so R code written as `.Call("_MatrixExtra_<fn>", ...)` (R/RcppExports.R) dispatches
-// unchanged, plus mxgpu_register() to add them to a DllInfo.  Written against the plain R C API
+// unchanged, plus mxgpu_register() to add them to a DllInfo.  It also exports mxgpu_csr_transpose, the device
+// transpose behind the overlay's t_deep_internal.  Written against the plain R C API
 // (no Rcpp): INTEGER()/REAL(), Rf_allocMatrix, Rf_error.
 //
 // This file is NOT part of libmxgpu.so and cannot be compiled in the development image (no R headers):
@@ -383,6 +384,28 @@ SEXP _MatrixExtra_logicaland_csr_by_dvec_internal(SEXP p_, SEXP j_, SEXP x_, SEX
     return out;
 }
 
+// Device transpose behind the overlay's t_deep_internal (R/trans.R:46-56): the CSR (or CSC) slots of x^T.
+// values: a double vector (dg*), a logical vector (lg*) or NULL (ng*); ncol: columns of the CSR view (ncol(x) for
+// an RsparseMatrix, nrow(x) for a CsparseMatrix).  Returns list(indptr=, indices=, values=).
+SEXP mxgpu_csr_transpose(SEXP p_, SEXP idx, SEXP x_, SEXP ncol)
+{
+    Protect p;
+    p_ = as_type(p_, INTSXP, p); idx = as_type(idx, INTSXP, p);
+    int dtype = MX_NONE;
+    const void *v = nullptr;
+    int64_t nv = 0;
+    if (TYPEOF(x_) == REALSXP) { dtype = MX_F64; v = REAL(x_); nv = XLENGTH(x_); }
+    else if (TYPEOF(x_) == LGLSXP) { dtype = MX_LGL; v = LOGICAL(x_); nv = XLENGTH(x_); }
+    else if (x_ != R_NilValue) Rf_error("mxgpu_csr_transpose: values must be double, logical or NULL");
+    mx_result *res = nullptr;
+    mx_result_info info;
+    if (mx_csr_transpose_begin(INTEGER(p_), (int)XLENGTH(p_) - 1, Rf_asInteger(ncol), INTEGER(idx), v, dtype, nv,
+                               &res, &info))
+        fail();
+    if (dtype != MX_NONE) info.values_dtype = dtype;     // an empty result keeps the values' R type
+    return finish_guarded(res, info, R_NilValue, R_NilValue);
+}
+
 #define MX_ENTRY(name, n) {"_MatrixExtra_" #name, (DL_FUNC)&_MatrixExtra_##name, n}
 static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(matmul_dense_csc_numeric, 5), MX_ENTRY(matmul_dense_csc_float32, 5),
@@ -401,6 +424,7 @@ static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(reverse_columns_inplace_numeric, 4), MX_ENTRY(reverse_columns_inplace_logical, 4),
     MX_ENTRY(reverse_columns_inplace_binary, 4),
     MX_ENTRY(multiply_csr_by_dvec_no_NAs_numeric, 11), MX_ENTRY(logicaland_csr_by_dvec_internal, 5),
+    {"mxgpu_csr_transpose", (DL_FUNC)&mxgpu_csr_transpose, 4},
     {NULL, NULL, 0}
 };
 

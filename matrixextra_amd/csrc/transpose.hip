@@ -1,0 +1,466 @@
+// transpose.hip — stable device transpose of a CSR structure (t_deep, CSR <-> CSC).
+//
+// The CSC arrays of a matrix are the CSR arrays of its transpose, so one routine serves CSR -> CSR of X^T
+// (t_deep_internal, R/trans.R:46-56), CSR -> CSC (as.csc.matrix) and CSC -> CSR (as.csr.matrix of a dgCMatrix).
+//
+// Output row c of the transpose holds the source rows of every input entry in column c, in strictly ascending
+// source-row order whatever the order inside the input rows.  The transpose is a stable sort of the row-major
+// entries by column, done as an LSD radix sort with 8-bit digits (one pass when n <= 256, else
+// ceil(bits(n-1) / 8)), carrying the entry index k and the source row as payloads:
+//
+//   per pass    count:   per-tile digit counts -> table[digit][tile]          (no global atomics: a hot column,
+//               scan:    exclusive scan of the table (exclusive_scan_i32)      such as cbind(1, X)'s intercept,
+//               scatter: stable in-tile rank from wave64 ballots + a            costs what any column costs)
+//                        per-wave count table in LDS, tile staged in LDS in digit order, then plain stores of
+//                        each digit's contiguous run; pass 0 finds source rows by a binary search of indptr
+//                        over the rows its tile spans
+//   gather      out_indices[q] = carried row, out_values[q] = values[perm[q]] (bit copies), duplicate flag
+//   indptr      out_indptr[c] = first q with sorted key >= c (binary search, one thread per column)
+//
+// Column indices are checked where they are first read (pass 0's count and scatter): an index outside [0, n)
+// raises the error flag and is replaced by 0 before it is used, so bad input is reported, never written out of
+// bounds.  Later passes read only the clamped keys.
+//
+// Duplicates, (row, col) pairs that occur more than once in one input row, end up adjacent after the sort.  The
+// gather pass flags them for the cost of one compare per entry; only when the flag is set does a compaction
+// run: heads -> scan -> merge each run in source order -> remap indptr.  The merge rule is what Matrix's
+// TsparseMatrix coercion (which t_deep_internal goes through) does to repeated triplets: f64 values are summed
+// in source order, R logicals are combined with R's `|`, pattern entries collapse to one.  The logical rule is
+// Matrix's documented behaviour for l-sparse triplets; it was not re-checked against a running R (none was
+// available when this was written).
+// Each run is merged by one thread, sequentially, because an f64 sum in source order is sequential.
+#include "mx_common.h"
+
+namespace mx {
+
+constexpr int TP_BLOCK = 256;
+constexpr int TP_ITEMS = 16;
+constexpr int TP_WAVES = TP_BLOCK / MX_WAVE;
+constexpr int TP_TILE = TP_BLOCK * TP_ITEMS;            // 4096 entries per tile
+constexpr int TP_WAVE_SPAN = MX_WAVE * TP_ITEMS;        // each wave owns 1024 consecutive entries of its tile
+constexpr int TP_RADIX = 256;
+static_assert(TP_BLOCK == TP_RADIX, "the per-digit prefix step uses one thread per digit");
+
+// flags in the workspace: [0] a column index outside [0, n), [1] duplicates present
+constexpr size_t TP_FLAG_BYTES = 256;
+
+// last row r in [lo, m) with indptr[r] <= k (indptr[lo] <= k holds for every caller)
+__device__ __forceinline__ int tp_row_of(const int32_t *__restrict__ indptr, int lo, int m, int64_t k)
+{
+    int hi = m;
+    while (hi - lo > 1) {
+        const int mid = (int)(((int64_t)lo + hi) >> 1);
+        if (indptr[mid] <= k) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// lanes of the wave holding the same digit (nbits significant low bits) as this lane, among the valid lanes
+__device__ __forceinline__ uint64_t tp_peers(int d, bool valid, int nbits)
+{
+    uint64_t peers = __ballot(valid);
+    for (int b = 0; b < nbits; b++) {
+        const bool bit = (d >> b) & 1;
+        const uint64_t bal = __ballot(bit);
+        peers &= bit ? bal : ~bal;
+    }
+    return peers;
+}
+
+// pass 0 reads the caller's indices: check before the key is used anywhere
+template <bool FIRST>
+__device__ __forceinline__ int tp_load_key(const int32_t *__restrict__ keys, int64_t k, int n, bool &bad)
+{
+    int key = keys[k];
+    if (FIRST && (unsigned)key >= (unsigned)n) { bad = true; key = 0; }
+    return key;
+}
+
+// per-tile digit counts -> table[d * ntiles + tile]
+template <bool FIRST>
+__global__ __launch_bounds__(TP_BLOCK)
+void tp_count_kernel(const int32_t *__restrict__ keys, int64_t nnz, int n, int shift, int nbits, int ntiles,
+                     int32_t *__restrict__ table, int32_t *__restrict__ flags)
+{
+    __shared__ int32_t hist[TP_WAVES][TP_RADIX];
+    for (int i = threadIdx.x; i < TP_WAVES * TP_RADIX; i += TP_BLOCK) (&hist[0][0])[i] = 0;
+    __syncthreads();
+    const int wave = threadIdx.x / MX_WAVE, lane = lane_id();
+    const int64_t base = (int64_t)blockIdx.x * TP_TILE + wave * TP_WAVE_SPAN;
+    bool bad = false;
+    for (int it = 0; it < TP_ITEMS; it++) {
+        const int64_t k = base + it * MX_WAVE + lane;
+        const bool valid = k < nnz;
+        const int key = valid ? tp_load_key<FIRST>(keys, k, n, bad) : 0;
+        const int d = (key >> shift) & (TP_RADIX - 1);
+        const uint64_t peers = tp_peers(d, valid, nbits);
+        // one add per (wave, digit) group, by the group's lowest lane; the table is private to the wave
+        if (valid && lane == __builtin_ctzll(peers)) hist[wave][d] += __popcll(peers);
+    }
+    if (FIRST && bad) flags[0] = 1;
+    __syncthreads();
+    const int d = threadIdx.x;
+    int sum = 0;
+#pragma unroll
+    for (int w = 0; w < TP_WAVES; w++) sum += hist[w][d];
+    table[(int64_t)d * ntiles + blockIdx.x] = sum;
+}
+
+// Stable scatter of one tile.  Each entry's slot in the tile's digit-sorted order is the tile-local start of its
+// digit + the counts of earlier waves + its rank inside the wave; the tile is staged in LDS in that order and
+// written out slot by slot, so consecutive lanes store consecutive positions of one digit's run (global position =
+// offset of (digit, tile) + slot - tile-local start of the digit).
+// Payloads: the entry index k (for the values, gathered once at the end) and the source row.  Pass 0 finds the
+// rows of its tile's consecutive entries by a binary search of indptr over the rows the tile spans, staged in LDS
+// when there are at most TP_SPAN_CAP of them.
+constexpr int TP_SPAN_CAP = 1024;
+
+template <bool FIRST>
+__global__ __launch_bounds__(TP_BLOCK)
+void tp_scatter_kernel(const int32_t *__restrict__ keys_in, const int32_t *__restrict__ perm_in,
+                       const int32_t *__restrict__ rows_in, const int32_t *__restrict__ indptr, int m, int64_t nnz,
+                       int n, int shift, int nbits, int ntiles, const int32_t *__restrict__ offsets,
+                       int32_t *__restrict__ keys_out, int32_t *__restrict__ perm_out, int32_t *__restrict__ rows_out)
+{
+    __shared__ int32_t cnt[TP_WAVES][TP_RADIX];
+    __shared__ int32_t delta[TP_RADIX];
+    __shared__ int32_t stage[3][TP_TILE];              // keys, entry index, row in slot order (48 KiB)
+    __shared__ int32_t span_ptr[FIRST ? TP_SPAN_CAP : 1];
+    __shared__ int32_t row_span[2];
+    __shared__ int32_t wave_tot[TP_WAVES];
+    const int64_t t0 = (int64_t)blockIdx.x * TP_TILE;
+    for (int i = threadIdx.x; i < TP_WAVES * TP_RADIX; i += TP_BLOCK) (&cnt[0][0])[i] = 0;
+    if (FIRST && threadIdx.x < 2) {
+        const int64_t k = threadIdx.x == 0 ? t0 : (t0 + TP_TILE - 1 < nnz ? t0 + TP_TILE - 1 : nnz - 1);
+        row_span[threadIdx.x] = tp_row_of(indptr, 0, m, k);
+    }
+    __syncthreads();
+    int r0 = 0, nspan = 0;
+    if (FIRST) {
+        r0 = row_span[0];
+        nspan = row_span[1] - r0 + 1;
+        if (nspan <= TP_SPAN_CAP)
+            for (int i = threadIdx.x; i < nspan; i += TP_BLOCK) span_ptr[i] = indptr[r0 + i];
+        __syncthreads();
+    }
+    const int wave = threadIdx.x / MX_WAVE, lane = lane_id();
+    const uint64_t lt_mask = (1ULL << lane) - 1;
+    const int64_t base = t0 + wave * TP_WAVE_SPAN;
+    int key[TP_ITEMS], rank[TP_ITEMS], pay[TP_ITEMS], row[TP_ITEMS];
+    bool bad = false;
+#pragma unroll
+    for (int it = 0; it < TP_ITEMS; it++) {
+        const int64_t k = base + it * MX_WAVE + lane;
+        const bool valid = k < nnz;
+        key[it] = valid ? tp_load_key<FIRST>(keys_in, k, n, bad) : 0;
+        pay[it] = valid ? (FIRST ? (int)k : perm_in[k]) : 0;
+        if (!FIRST) {
+            row[it] = valid ? rows_in[k] : 0;
+        } else if (!valid) {
+            row[it] = 0;
+        } else if (nspan <= TP_SPAN_CAP) {          // last r in the span with indptr[r] <= k
+            int lo = 0, hi = nspan;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (span_ptr[mid] <= k) lo = mid; else hi = mid;
+            }
+            row[it] = r0 + lo;
+        } else {
+            row[it] = tp_row_of(indptr, r0, row_span[1] + 1, k);
+        }
+        const int d = (key[it] >> shift) & (TP_RADIX - 1);
+        const uint64_t peers = tp_peers(d, valid, nbits);
+        const int before = valid ? cnt[wave][d] : 0;
+        rank[it] = before + __popcll(peers & lt_mask);
+        if (valid && lane == __builtin_ctzll(peers)) cnt[wave][d] = before + __popcll(peers);
+    }
+    __syncthreads();
+    {   // one thread per digit: tile-local start of the digit (block exclusive scan of the digit totals), then
+        // cnt[w][d] -> first slot of wave w's digit-d entries, delta[d] -> global position of slot 0
+        const int d = threadIdx.x;
+        int total = 0;
+#pragma unroll
+        for (int w = 0; w < TP_WAVES; w++) total += cnt[w][d];
+        int incl = total;
+#pragma unroll
+        for (int off = 1; off < MX_WAVE; off <<= 1) {
+            const int o = __shfl_up(incl, off, MX_WAVE);
+            if (lane >= off) incl += o;
+        }
+        if (lane == MX_WAVE - 1) wave_tot[wave] = incl;
+        __syncthreads();
+        int start = incl - total;
+        for (int w = 0; w < wave; w++) start += wave_tot[w];
+        delta[d] = offsets[(int64_t)d * ntiles + blockIdx.x] - start;
+        int run = start;
+#pragma unroll
+        for (int w = 0; w < TP_WAVES; w++) { const int c = cnt[w][d]; cnt[w][d] = run; run += c; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < TP_ITEMS; it++) {
+        if (base + it * MX_WAVE + lane >= nnz) break;
+        const int slot = cnt[wave][(key[it] >> shift) & (TP_RADIX - 1)] + rank[it];
+        stage[0][slot] = key[it];
+        stage[1][slot] = pay[it];
+        stage[2][slot] = row[it];
+    }
+    __syncthreads();
+    const int tile_n = nnz - t0 < TP_TILE ? (int)(nnz - t0) : TP_TILE;
+    for (int i = threadIdx.x; i < tile_n; i += TP_BLOCK) {
+        const int kk = stage[0][i];
+        const int pos = delta[(kk >> shift) & (TP_RADIX - 1)] + i;
+        keys_out[pos] = kk;
+        perm_out[pos] = stage[1][i];
+        rows_out[pos] = stage[2][i];
+    }
+}
+
+// out_rows[q] / out_values[q] from the sorted permutation; flags[1] = 1 when two neighbours are the same (col, row)
+template <typename VT, bool HAS_VALUES>
+__global__ __launch_bounds__(256)
+void tp_gather_kernel(const int32_t *__restrict__ keys, const int32_t *__restrict__ perm, int64_t nnz,
+                      const int32_t *__restrict__ rows, const VT *__restrict__ values, int32_t *__restrict__ out_rows,
+                      VT *__restrict__ out_values, int32_t *__restrict__ flags)
+{
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = lane_id();
+    const bool valid = q < nnz;
+    int key = -1, row = -1;
+    if (valid) {
+        row = rows[q];
+        key = keys[q];
+        out_rows[q] = row;
+        if (HAS_VALUES) out_values[q] = values[perm[q]];
+    }
+    int pkey = __shfl_up(key, 1, MX_WAVE), prow = __shfl_up(row, 1, MX_WAVE);
+    if (lane == 0 && valid && q > 0) { pkey = keys[q - 1]; prow = rows[q - 1]; }
+    const bool dup = valid && q > 0 && pkey == key && prow == row;
+    if (__ballot(dup) != 0ULL && lane == 0) flags[1] = 1;
+}
+
+// out_indptr[c] = number of sorted keys < c, for c in [0, n]
+__global__ __launch_bounds__(256)
+void tp_indptr_kernel(const int32_t *__restrict__ keys, int64_t nnz, int64_t n, int32_t *__restrict__ out_indptr)
+{
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c <= n; c += (int64_t)gridDim.x * blockDim.x) {
+        int64_t lo = 0, count = nnz;
+        while (count > 0) {
+            const int64_t step = count >> 1;
+            if (keys[lo + step] < c) { lo += step + 1; count -= step + 1; }
+            else count = step;
+        }
+        out_indptr[c] = (int32_t)lo;
+    }
+}
+
+// ---- duplicate compaction (runs only when the gather pass saw duplicates) --------------------------------
+__device__ __forceinline__ bool tp_is_head(const int32_t *__restrict__ keys, const int32_t *__restrict__ rows,
+                                           int64_t q)
+{
+    return q == 0 || keys[q] != keys[q - 1] || rows[q] != rows[q - 1];
+}
+
+__global__ __launch_bounds__(256)
+void tp_heads_kernel(const int32_t *__restrict__ keys, const int32_t *__restrict__ rows, int64_t nnz,
+                     int32_t *__restrict__ heads)
+{
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nnz) heads[q] = tp_is_head(keys, rows, q) ? 1 : 0;
+}
+
+// VK: 0 f64 (sum in source order), 1 R logical (R's `|`), 2 pattern (one entry)
+template <int VK>
+__global__ __launch_bounds__(256)
+void tp_merge_kernel(const int32_t *__restrict__ keys, const int32_t *__restrict__ rows, const void *__restrict__ vals,
+                     int64_t nnz, const int32_t *__restrict__ newpos, int32_t *__restrict__ merged_rows,
+                     void *__restrict__ merged_vals)
+{
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nnz || !tp_is_head(keys, rows, q)) return;
+    const int64_t dest = newpos[q];
+    merged_rows[dest] = rows[q];
+    int64_t e = q + 1;
+    if (VK == 0) {
+        const double *v = (const double *)vals;
+        double acc = v[q];
+        for (; e < nnz && !tp_is_head(keys, rows, e); e++) acc += v[e];
+        ((double *)merged_vals)[dest] = acc;
+    } else if (VK == 1) {
+        const int32_t *v = (const int32_t *)vals;
+        int acc = v[q];
+        for (; e < nnz && !tp_is_head(keys, rows, e); e++) acc = r_logical_or(acc, v[e]);
+        ((int32_t *)merged_vals)[dest] = acc;
+    }
+}
+
+__global__ __launch_bounds__(256)
+void tp_remap_indptr_kernel(int64_t n, const int32_t *__restrict__ newpos, int32_t *__restrict__ indptr)
+{
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c <= n; c += (int64_t)gridDim.x * blockDim.x)
+        indptr[c] = newpos[indptr[c]];
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------
+static int64_t tp_ntiles(int64_t nnz) { return ceil_div(nnz > 0 ? nnz : 1, TP_TILE); }
+
+static size_t tp_scan_ws_bytes(int64_t nnz)
+{
+    const size_t a = scan_workspace_bytes(TP_RADIX * tp_ntiles(nnz)), b = scan_workspace_bytes(nnz);
+    return ((a > b ? a : b) + 15) & ~(size_t)15;
+}
+
+// workspace: [flags][keys0 nnz+1][perm0 nnz][keys1 nnz+1][perm1 nnz][rows0 nnz+1][rows1 nnz+1][table T]
+// [offsets T+1][scan].  Each keys/perm pair is contiguous, so a free pair also holds nnz doubles during compaction.
+struct TpLayout {
+    int32_t *flags, *keys[2], *perm[2], *rows[2], *table, *offsets;
+    void *scan_ws;
+    size_t bytes;
+    TpLayout(void *ws, int64_t nnz)
+    {
+        char *p = (char *)ws;
+        const int64_t T = TP_RADIX * tp_ntiles(nnz);
+        flags = (int32_t *)p;            p += TP_FLAG_BYTES;
+        for (int b = 0; b < 2; b++) {
+            keys[b] = (int32_t *)p;      p += padded_i32_bytes(nnz + 1);
+            perm[b] = (int32_t *)p;      p += padded_i32_bytes(nnz);
+        }
+        for (int b = 0; b < 2; b++) {
+            rows[b] = (int32_t *)p;      p += padded_i32_bytes(nnz + 1);
+        }
+        table = (int32_t *)p;            p += padded_i32_bytes(T);
+        offsets = (int32_t *)p;          p += padded_i32_bytes(T + 1);
+        scan_ws = p;                     p += tp_scan_ws_bytes(nnz);
+        bytes = (size_t)(p - (char *)ws);
+    }
+};
+
+static int bits_of(int64_t v)   // bits needed to hold v >= 0
+{
+    int b = 0;
+    while (v > 0) { b++; v >>= 1; }
+    return b;
+}
+
+static unsigned grid_for(int64_t n, int block, int64_t cap = (int64_t)1 << 20)
+{
+    int64_t g = ceil_div(n > 0 ? n : 1, block);
+    return (unsigned)(g < cap ? g : cap);
+}
+
+static int csr_transpose(int m, int n, const int32_t *indptr, const int32_t *indices, const void *values,
+                         int value_dtype, int64_t nnz, int32_t *out_indptr, int32_t *out_indices, void *out_values,
+                         void *workspace, int64_t *nnz_out_host, hipStream_t st)
+{
+    MX_REQUIRE(m >= 0 && n >= 0 && nnz >= 0 && nnz <= INT_MAX, "mxd_csr_transpose: bad size");
+    MX_REQUIRE(m > 0 || nnz == 0, "mxd_csr_transpose: entries without rows");
+    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
+               "mxd_csr_transpose: unsupported value dtype %d", value_dtype);
+    MX_REQUIRE(nnz_out_host && out_indptr && (nnz == 0 || (indptr && indices && out_indices && workspace)),
+               "mxd_csr_transpose: null pointer");
+    const bool has_values = value_dtype != MX_NONE;
+    MX_REQUIRE(!has_values || nnz == 0 || (values && out_values), "mxd_csr_transpose: null values pointer");
+    if (nnz == 0) {
+        MX_HIP(hipMemsetAsync(out_indptr, 0, sizeof(int32_t) * ((size_t)n + 1), st));
+        *nnz_out_host = 0;
+        return 0;
+    }
+    TpLayout L(workspace, nnz);
+    MX_HIP(hipMemsetAsync(L.flags, 0, 2 * sizeof(int32_t), st));
+
+    const int key_bits = bits_of(n > 0 ? n - 1 : 0);
+    const int npasses = n <= TP_RADIX ? 1 : (key_bits + 7) / 8;
+    const int ntiles = (int)tp_ntiles(nnz);
+    const int64_t T = (int64_t)TP_RADIX * ntiles;
+    for (int pass = 0; pass < npasses; pass++) {
+        const int shift = 8 * pass;
+        const int nbits = key_bits - shift < 8 ? (key_bits - shift > 0 ? key_bits - shift : 0) : 8;
+        const int32_t *kin = pass == 0 ? indices : L.keys[(pass - 1) & 1];
+        const int32_t *pin = pass == 0 ? nullptr : L.perm[(pass - 1) & 1];
+        const int32_t *rin = pass == 0 ? nullptr : L.rows[(pass - 1) & 1];
+        int32_t *kout = L.keys[pass & 1], *pout = L.perm[pass & 1], *rout = L.rows[pass & 1];
+        if (pass == 0)
+            hipLaunchKernelGGL(tp_count_kernel<true>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, nnz, n, shift, nbits,
+                               ntiles, L.table, L.flags);
+        else
+            hipLaunchKernelGGL(tp_count_kernel<false>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, nnz, n, shift, nbits,
+                               ntiles, L.table, L.flags);
+        MX_LAUNCH_CHECK();
+        if (exclusive_scan_i32(L.table, T, L.offsets, nullptr, L.scan_ws, st)) return 1;
+        if (pass == 0)
+            hipLaunchKernelGGL(tp_scatter_kernel<true>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, pin, rin, indptr, m,
+                               nnz, n, shift, nbits, ntiles, L.offsets, kout, pout, rout);
+        else
+            hipLaunchKernelGGL(tp_scatter_kernel<false>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, pin, rin, indptr, m,
+                               nnz, n, shift, nbits, ntiles, L.offsets, kout, pout, rout);
+        MX_LAUNCH_CHECK();
+    }
+    const int fin = (npasses - 1) & 1;
+    const int32_t *skeys = L.keys[fin], *sperm = L.perm[fin], *srows = L.rows[fin];
+    const unsigned gq = (unsigned)ceil_div(nnz, 256);
+    if (value_dtype == MX_F64)
+        hipLaunchKernelGGL((tp_gather_kernel<double, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz, srows,
+                           (const double *)values, out_indices, (double *)out_values, L.flags);
+    else if (value_dtype == MX_LGL)
+        hipLaunchKernelGGL((tp_gather_kernel<int32_t, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz, srows,
+                           (const int32_t *)values, out_indices, (int32_t *)out_values, L.flags);
+    else
+        hipLaunchKernelGGL((tp_gather_kernel<int32_t, false>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz,
+                           srows, nullptr, out_indices, nullptr, L.flags);
+    MX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tp_indptr_kernel, dim3(grid_for((int64_t)n + 1, 256)), dim3(256), 0, st, skeys, nnz, (int64_t)n,
+                       out_indptr);
+    MX_LAUNCH_CHECK();
+
+    int32_t flags[2] = {0, 0};
+    MX_HIP(hipMemcpyAsync(flags, L.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipStreamSynchronize(st));
+    MX_REQUIRE(!flags[0], "mxd_csr_transpose: column index outside [0, %d)", n);
+    if (!flags[1]) { *nnz_out_host = nnz; return 0; }
+
+    // duplicates: the other keys/perm pair and the other rows buffer are free now; perm[fin] takes the head flags
+    int32_t *heads = L.perm[fin], *newpos = L.rows[fin ^ 1];
+    int32_t *merged_rows = L.perm[fin];                          // heads are consumed by the scan before the merge
+    void *merged_vals = L.keys[fin ^ 1];                         // keys + perm of the free pair: >= 8 * nnz bytes
+    hipLaunchKernelGGL(tp_heads_kernel, dim3(gq), dim3(256), 0, st, skeys, out_indices, nnz, heads);
+    MX_LAUNCH_CHECK();
+    int64_t *total_dev = (int64_t *)L.scan_ws;
+    if (exclusive_scan_i32(heads, nnz, newpos, total_dev, L.scan_ws, st)) return 1;
+    if (value_dtype == MX_F64)
+        hipLaunchKernelGGL(tp_merge_kernel<0>, dim3(gq), dim3(256), 0, st, skeys, out_indices, out_values, nnz, newpos,
+                           merged_rows, merged_vals);
+    else if (value_dtype == MX_LGL)
+        hipLaunchKernelGGL(tp_merge_kernel<1>, dim3(gq), dim3(256), 0, st, skeys, out_indices, out_values, nnz, newpos,
+                           merged_rows, merged_vals);
+    else
+        hipLaunchKernelGGL(tp_merge_kernel<2>, dim3(gq), dim3(256), 0, st, skeys, out_indices, out_values, nnz, newpos,
+                           merged_rows, merged_vals);
+    MX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tp_remap_indptr_kernel, dim3(grid_for((int64_t)n + 1, 256)), dim3(256), 0, st, (int64_t)n,
+                       newpos, out_indptr);
+    MX_LAUNCH_CHECK();
+    int64_t total = 0;
+    MX_HIP(hipMemcpyAsync(&total, total_dev, sizeof(total), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipStreamSynchronize(st));
+    MX_HIP(hipMemcpyAsync(out_indices, merged_rows, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToDevice, st));
+    if (has_values)
+        MX_HIP(hipMemcpyAsync(out_values, merged_vals, (value_dtype == MX_F64 ? 8 : 4) * (size_t)total,
+                              hipMemcpyDeviceToDevice, st));
+    *nnz_out_host = total;
+    return 0;
+}
+
+}  // namespace mx
+
+extern "C" size_t mxd_csr_transpose_workspace_bytes(int64_t nnz)
+{
+    return mx::TpLayout(nullptr, nnz > 0 ? nnz : 0).bytes;
+}
+
+extern "C" int mxd_csr_transpose(int m, int n, const int32_t *indptr, const int32_t *indices, const void *values,
+                                 int value_dtype, int64_t nnz, int32_t *out_indptr, int32_t *out_indices,
+                                 void *out_values, void *workspace, int64_t *nnz_out_host, void *stream)
+{
+    return mx::csr_transpose(m, n, indptr, indices, values, value_dtype, nnz, out_indptr, out_indices, out_values,
+                             workspace, nnz_out_host, mx::as_stream(stream));
+}

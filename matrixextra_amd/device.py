@@ -194,3 +194,28 @@ def csr_gather_rows(A: DeviceCSR, rows: torch.Tensor):
     check(lib.mxd_csr_gather_fill(C.c_int(r), _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(rows), _dp(new_p),
                                   _dp(new_j), _dp(new_x), C.c_int(vd), C.c_int64(nnz_out.value), _stream()))
     return DeviceCSR(new_p, new_j, new_x, r, A.K, int(nnz_out.value))
+
+
+def csr_transpose(A: DeviceCSR) -> DeviceCSR:
+    """CSR of A^T (equivalently: CSR <-> CSC) on device-resident operands through mxd_csr_transpose: rows of the
+    result in ascending source-row order, values copied bit for bit, repeated (row, col) pairs merged."""
+    lib = _lib.load()
+    dev = A.indptr.device
+    if A.values is None:
+        vd = MX_NONE
+    elif A.values.dtype == torch.float64:
+        vd = MX_F64
+    elif A.values.dtype == torch.int32:
+        vd = MX_LGL
+    else:
+        raise ValueError(f"values must be float64 or int32 (R logical), got {A.values.dtype}")
+    ws = torch.empty(max(lib.mxd_csr_transpose_workspace_bytes(A.nnz), 16), dtype=torch.uint8, device=dev)
+    out_p = torch.empty(A.K + 1, dtype=torch.int32, device=dev)
+    out_j = torch.empty(max(A.nnz, 1), dtype=torch.int32, device=dev)
+    out_x = None if A.values is None else torch.empty(max(A.nnz, 1), dtype=A.values.dtype, device=dev)
+    nnz_out = C.c_int64(0)
+    check(lib.mxd_csr_transpose(C.c_int(A.m), C.c_int(A.K), _dp(A.indptr), _dp(A.indices), _dp(A.values),
+                                C.c_int(vd), C.c_int64(A.nnz), _dp(out_p), _dp(out_j), _dp(out_x), _dp(ws),
+                                C.byref(nnz_out), _stream()))
+    nnz = int(nnz_out.value)
+    return DeviceCSR(out_p, out_j[:nnz], None if out_x is None else out_x[:nnz], A.K, A.m, nnz)

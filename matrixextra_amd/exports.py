@@ -534,3 +534,36 @@ def logicaland_csr_by_dvec_internal(indptr, indices, values, dvec, ncols):
     check(_lib.load().mx_logicaland_csr_by_dvec_internal(ptr(p), ptr(j), ptr(xv), C.c_int(p.size - 1), ptr(dv),
                                                          C.c_int64(dv.size), C.c_int(int(ncols)), ptr(out)))
     return out
+
+
+# ----------------------------------------------------------------------------- transpose (t_deep, CSR <-> CSC)
+def csr_transpose(indptr, indices, values, ncol):
+    """CSR arrays of the transpose of an (len(indptr)-1) x ncol CSR; CSC input is the CSR of its transpose, so this
+    is also CSR -> CSC and CSC -> CSR.  Replaces t_deep_internal (R/trans.R:46-56) and the Matrix coercions of
+    as.csr.matrix / as.csc.matrix (R/conversions.R).  values: float64, int32 R logicals, or None (pattern; the
+    result's `values` is then None).  Output rows are in ascending source-row order; repeated (row, col) pairs are
+    merged (f64 summed in source order, logicals by R's `|`, pattern once)."""
+    lib = _lib.load()
+    p, j = _i32(indptr), _i32(indices)
+    if values is None:
+        v, vdt = None, MX_NONE
+    else:
+        v = np.asarray(values)
+        if v.dtype == np.int32:
+            vdt = MX_LGL
+        elif v.dtype == np.float64:
+            vdt = MX_F64
+        else:
+            raise TypeError(f"values must be float64 or int32 (R logical), got {v.dtype}")
+        v = np.ascontiguousarray(v)
+    res = C.c_void_p()
+    info = ResultInfo()
+    check(lib.mx_csr_transpose_begin(ptr(p), C.c_int(p.size - 1), C.c_int(int(ncol)), ptr(j), ptr(v), C.c_int(vdt),
+                                     C.c_int64(0 if v is None else v.size), C.byref(res), C.byref(info)))
+    if v is None:
+        out = _finish(res, info)
+        out["values"] = None
+        return out
+    out = _finish(res, info, empty_values_dtype=v.dtype)
+    out["values"] = out["values"].astype(v.dtype, copy=False)     # no entries: an empty vector of the input's type
+    return out

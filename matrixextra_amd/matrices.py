@@ -25,6 +25,7 @@ options = {
     "MatrixExtra.nthreads": 1,          # accepted and forwarded; the GPU path ignores it
     "MatrixExtra.inplace_sort": False,
     "MatrixExtra.drop_sparse": False,
+    "MatrixExtra.fast_transpose": False,   # t(): False -> t_deep (a real transpose), True -> t_shallow (R/trans.R:58-72)
 }
 
 
@@ -94,6 +95,9 @@ class RsparseMatrix:
         return type(self)(self.p.copy(), self.j.copy(), None if self.x is None else self.x.copy(),
                           self.Dim, list(self.Dimnames))
 
+    def t(self):                                      # R/trans.R:66-72 (t_masked_csr)
+        return _t_masked(self)
+
     # ---- operator wiring (setMethod registrations of the reference)
     def __matmul__(self, other):                      # `%*%`  R/matmul.R:469, :755-767
         from . import matmul
@@ -113,7 +117,7 @@ class RsparseMatrix:
 
     def __mul__(self, other):                         # R/operators.R:147 (CSR), :1217-1260 (vector)
         from . import operators
-        if not isinstance(other, RsparseMatrix):
+        if not isinstance(other, (RsparseMatrix, dgCMatrix)):
             return operators.csr_op_vector(self, other, "*")
         return operators.multiply_csr_by_csr(self, other, logical=False)
 
@@ -191,7 +195,7 @@ class ngRMatrix(RsparseMatrix):
 
 
 class dgCMatrix:
-    """Compressed sparse column, numeric (only what `matrix %*% CsparseMatrix` needs)."""
+    """Compressed sparse column, numeric: `matrix %*% CsparseMatrix`, t(), and +, -, * with an RsparseMatrix."""
     r_class = "dgCMatrix"
     __array_ufunc__ = None
 
@@ -217,6 +221,29 @@ class dgCMatrix:
     def __rmatmul__(self, other):                     # matrix %*% CsparseMatrix, R/matmul.R:200
         from . import matmul
         return matmul.matmul(other, self)
+
+    def t(self):                                      # R/trans.R:58-64 (t_masked_csc)
+        return _t_masked(self)
+
+    # sparseMatrix (op) RsparseMatrix, R/operators.R:147-179, :810-870: the CSC side goes through as.csr.matrix and
+    # the result is a dgRMatrix
+    def __add__(self, other):
+        from . import operators
+        if not isinstance(other, RsparseMatrix):
+            return NotImplemented
+        return operators.add_csr_matrices(self, other, False)
+
+    def __sub__(self, other):
+        from . import operators
+        if not isinstance(other, RsparseMatrix):
+            return NotImplemented
+        return operators.add_csr_matrices(self, other, True)
+
+    def __mul__(self, other):
+        from . import operators
+        if not isinstance(other, RsparseMatrix):
+            return NotImplemented
+        return operators.multiply_csr_by_csr(self, other, logical=False)
 
 
 class float32:
@@ -275,7 +302,11 @@ def from_scipy(A, logical=False, binary=False):
 def as_csr_matrix(x, logical=False, binary=False):
     """as.csr.matrix (R/conversions.R:180-295), reduced to the classes that exist here:
     dgRMatrix passes through; lgRMatrix/ngRMatrix are expanded to numeric (or kept/converted
-    to logical when `logical=TRUE`); scipy matrices and dense arrays are converted."""
+    to logical when `logical=TRUE`); a dgCMatrix goes through the device transpose; scipy matrices and dense
+    arrays are converted."""
+    if isinstance(x, dgCMatrix):
+        check_valid_matrix(x)
+        x = _csc_to_csr(x, binary=binary)
     if isinstance(x, RsparseMatrix):
         if binary:
             return x if isinstance(x, ngRMatrix) else ngRMatrix(x.p, x.j, None, x.Dim, x.Dimnames)
@@ -298,6 +329,72 @@ def as_csr_matrix(x, logical=False, binary=False):
         out.Dimnames = list(dimnames_of(x))
         return out
     return from_scipy(x, logical=logical, binary=binary)
+
+
+def _csc_to_csr(x, binary=False):
+    """CSR arrays of a dgCMatrix through the device transpose (its CSC arrays are the CSR of x^T)."""
+    from . import exports
+    res = exports.csr_transpose(x.p, x.i, None if binary else x.x, x.Dim[0])
+    if binary:
+        return ngRMatrix(res["indptr"], res["indices"], None, x.Dim, x.Dimnames)
+    return dgRMatrix(res["indptr"], res["indices"], res["values"], x.Dim, x.Dimnames)
+
+
+def as_csc_matrix(x):
+    """as.csc.matrix (R/conversions.R) -> dgCMatrix.  Values become f64 by as_csr_matrix's rules (NA_LOGICAL ->
+    NA_real_, pattern -> 1.0); the CSR -> CSC step is the device transpose."""
+    from . import exports
+    if isinstance(x, dgCMatrix):
+        return x
+    x = as_csr_matrix(x)
+    check_valid_matrix(x)
+    res = exports.csr_transpose(x.p, x.j, x.x, x.Dim[1])
+    return dgCMatrix(res["indptr"], res["indices"], res["values"], x.Dim, x.Dimnames)
+
+
+_SHALLOW = {"dgRMatrix": "dgCMatrix", "dgCMatrix": "dgRMatrix", "lgRMatrix": "lgCMatrix", "ngRMatrix": "ngCMatrix"}
+
+
+def t_shallow(x):
+    """t_shallow (R/trans.R:1-30, :128-150): relabels CSR as the CSC of the transpose (and back) without copying:
+    the result shares x's `p` and index arrays; Dim and Dimnames are swapped.  Only dgRMatrix <-> dgCMatrix exist
+    here."""
+    Dim = (x.Dim[1], x.Dim[0])
+    Dimnames = list(reversed(dimnames_of(x)))
+    if type(x) is dgRMatrix:
+        out = dgCMatrix.__new__(dgCMatrix)
+        out.p, out.i, out.x = x.p, x.j, x.x
+    elif type(x) is dgCMatrix:
+        out = dgRMatrix.__new__(dgRMatrix)
+        out.p, out.j, out.x = x.p, x.i, x.x
+    else:
+        target = _SHALLOW.get(getattr(x, "r_class", None))
+        if target is None:
+            stop(f"t_shallow: unsupported class {type(x).__name__}.")
+        stop(f"t_shallow: {x.r_class} would become a {target}, which this package does not provide.")
+    out.Dim, out.Dimnames = Dim, Dimnames
+    return out
+
+
+def t_deep(x):
+    """t_deep (R/trans.R:46-56, :153-162): a real transpose on the device that keeps the class: the CSR (or CSC)
+    arrays of x^T, rows in ascending order, Dim and Dimnames swapped."""
+    from . import exports
+    if not isinstance(x, (RsparseMatrix, dgCMatrix)):
+        stop(f"t_deep: unsupported class {type(x).__name__}.")
+    check_valid_matrix(x)
+    if isinstance(x, dgCMatrix):
+        res = exports.csr_transpose(x.p, x.i, x.x, x.Dim[0])
+        return dgCMatrix(res["indptr"], res["indices"], res["values"], (x.Dim[1], x.Dim[0]),
+                         list(reversed(dimnames_of(x))))
+    res = exports.csr_transpose(x.p, x.j, x.x, x.Dim[1])
+    return type(x)(res["indptr"], res["indices"], res["values"], (x.Dim[1], x.Dim[0]),
+                   list(reversed(dimnames_of(x))))
+
+
+def _t_masked(x):
+    """t_masked_csr / t_masked_csc (R/trans.R:58-72)."""
+    return t_shallow(x) if options.get("MatrixExtra.fast_transpose", False) else t_deep(x)
 
 
 def check_valid_matrix(X):
