@@ -287,6 +287,44 @@ int mxd_csr_transpose(int m, int n, const int32_t *indptr, const int32_t *indice
                       int value_dtype, int64_t nnz, int32_t *out_indptr, int32_t *out_indices,
                       void *out_values, void *workspace, int64_t *nnz_out_host, void *stream);
 
+/* COO -> CSR (coo.hip / transpose.hip), replacing Matrix's TsparseMatrix -> RsparseMatrix coercion that
+ * as.csr.matrix calls (R/conversions.R:180-295) and the route of t_deep_internal (R/trans.R:46-56).  Input: nnz
+ * triplets (rows[k], cols[k], values[k]) of an m x n matrix, 0-based, any order, duplicates allowed; value_dtype
+ * MX_F64 / MX_LGL / MX_NONE.  Output: canonical CSR, out_indptr[m+1], each row's columns strictly ascending,
+ * values copied bit for bit.  Repeated (row, col) pairs are merged as mxd_csr_transpose merges them (f64 summed
+ * in input order, logical by R's `|`, pattern kept once); explicit zeros stay.  out_indices / out_values hold nnz
+ * entries; *nnz_out_host (after an internal stream sync) is the count after merging.  A row outside [0, m) or a
+ * column outside [0, n) fails the call and is never used to write; nnz > INT32_MAX is refused up front.
+ * COO -> CSC is the same call with the roles swapped: (n, m, cols, rows) gives the CSC arrays.
+ * workspace: mxd_coo_to_csr_workspace_bytes(nnz, n) with n the column count passed to the call. */
+size_t mxd_coo_to_csr_workspace_bytes(int64_t nnz, int n);
+int mxd_coo_to_csr(int m, int n, const int32_t *rows, const int32_t *cols, const void *values, int value_dtype,
+                   int64_t nnz, int32_t *out_indptr, int32_t *out_indices, void *out_values, void *workspace,
+                   int64_t *nnz_out_host, void *stream);
+/* CSR / CSC -> COO: out_rows[k] = the row of entry k (the column, for a CSC), storage order kept; the COO's
+ * other index vector and its values are the input's indices and values as they are.  nnz = indptr[m]. */
+int mxd_csr_to_coo(int m, int64_t nnz, const int32_t *indptr, int32_t *out_rows, void *stream);
+/* CSR (.) COO (multiply_csr_by_coo_elemwise / logicaland_csr_by_coo_elemwise, src/operators.cpp:572-720):
+ * X is m x ncol with rows sorted ascending and unique (f64 values, or int32 R logicals when logical != 0); the
+ * COO Y is given as nnz_y triplets.  Entry k of Y is kept when y_k is non-zero or NaN (logical: non-zero, NA
+ * included), its row is in [0, m) and its column in [0, ncol), and X[row, col] is non-zero or NaN; its value is
+ * x * y (logical: R's 3-valued AND).  Kept entries come out in Y's input order, one per occurrence.
+ * pass 1 counts and scans (one host read-back of the count into *nnz_out_host); pass 2 fills out_rows / out_cols
+ * / out_values with that many entries.  workspace: mxd_csr_by_coo_workspace_bytes(nnz_y), shared by both passes. */
+size_t mxd_csr_by_coo_workspace_bytes(int64_t nnz_y);
+int mxd_csr_by_coo_count(int logical, int m, int ncol, const int32_t *indptr, const int32_t *indices,
+                         const void *x_values, const int32_t *y_rows, const int32_t *y_cols, const void *y_values,
+                         int64_t nnz_y, void *workspace, int64_t *nnz_out_host, void *stream);
+int mxd_csr_by_coo_fill(int logical, int m, int ncol, const int32_t *indptr, const int32_t *indices,
+                        const void *x_values, const int32_t *y_rows, const int32_t *y_cols, const void *y_values,
+                        int64_t nnz_y, const void *workspace, int32_t *out_rows, int32_t *out_cols,
+                        void *out_values, void *stream);
+/* COO (op) dense vector, the COO twin of mxd_csr_by_dvec (multiply_coo_by_dense_ignore_NAs_template,
+ * src/operators.cpp:2856-3425): out[k] = values[k] op dvec[(rows[k] + cols[k]*m) mod dvec_len], same ops and
+ * arithmetic as mxd_csr_by_dvec. */
+int mxd_coo_by_dvec(int m, int ncols, int64_t nnz, const int32_t *rows, const int32_t *cols, const void *values,
+                    const void *dvec, int64_t dvec_len, int op, int x_is_lhs, void *values_out, void *stream);
+
 /* ========================================================================== */
 /* (1) export level — host pointers, names follow the Rcpp exports            */
 /* ========================================================================== */
@@ -432,6 +470,32 @@ int mx_concat_csr_batch_begin(const mx_rbind_input *objects, int n_inputs, int o
 int mx_csr_transpose_begin(const int32_t *indptr, int nrows, int ncols, const int32_t *indices,
                            const void *values, int value_dtype, int64_t n_values,
                            mx_result **res, mx_result_info *info);
+/* as.csr.matrix / as.csc.matrix of a TsparseMatrix (Matrix's T -> R / T -> C coercion, R/conversions.R:180-295)
+ * through mxd_coo_to_csr: nrows x ncols COO with n_entries triplets; value_dtype MX_F64 / MX_LGL / MX_NONE.
+ * Pass (ncols, nrows, cols, rows) for the CSC.  info.indptr_len = nrows + 1; info.nnz = entries after merging. */
+int mx_coo_to_csr_begin(const int32_t *rows, const int32_t *cols, const void *values, int value_dtype,
+                        int64_t n_entries, int nrows, int ncols, mx_result **res, mx_result_info *info);
+/* as.coo.matrix of a CSR / CSC (R/conversions.R:515-590): out_rows[indptr[nrows]] receives the row (CSC: column)
+ * of every entry in storage order. */
+int mx_csr_to_coo(const int32_t *indptr, int nrows, int32_t *out_rows);
+/* multiply_csr_by_coo_elemwise / logicaland_csr_by_coo_elemwise  src/operators.cpp:572-720 (RcppExports.cpp:1319,
+ * 1336): logical = 0 f64, 1 R logicals.  X_indptr has max_row_X + 1 entries.  The result is a COO held in the
+ * mx_result: the indptr vector holds the row ids (info.indptr_len = info.nnz), indices the column ids, values
+ * the values. */
+int mx_multiply_csr_by_coo_begin(int logical, const int32_t *X_indptr, const int32_t *X_indices,
+                                 const void *X_values, const int32_t *Y_rows, const int32_t *Y_cols,
+                                 const void *Y_values, int64_t nnz_Y, int max_row_X, int max_col_X,
+                                 mx_result **res, mx_result_info *info);
+/* multiply_coo_by_dense_ignore_NAs_numeric  src/operators.cpp:3363-3394: flags as for
+ * mx_multiply_csr_by_dvec_no_NAs_numeric; values_out f64[nnz]. */
+int mx_multiply_coo_by_dense_ignore_NAs_numeric(const int32_t *ii, const int32_t *jj, const double *xx, int64_t nnz,
+                                                const double *dvec, int64_t dvec_len, int nrows, int ncols,
+                                                int multiply, int powerto, int divide, int divrest, int intdiv,
+                                                int X_is_LHS, double *values_out);
+/* multiply_coo_by_dense_ignore_NAs_logical  src/operators.cpp:3396-3418: R logicals, values_out int32[nnz] */
+int mx_multiply_coo_by_dense_ignore_NAs_logical(const int32_t *ii, const int32_t *jj, const int32_t *xx, int64_t nnz,
+                                                const int32_t *dvec, int64_t dvec_len, int nrows, int ncols,
+                                                int32_t *values_out);
 int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, void *out_values);
 int mx_result_discard(mx_result *res);
 

@@ -7,7 +7,8 @@
 ### This overlay rebinds those 19 wrappers inside the MatrixExtra namespace so that they `.Call` the routines of
 ### the same names registered by mxgpu_r.so (matrixextra_amd/csrc/r_shim.cpp), which forward to libmxgpu.so.
 ### Every other native routine (~140 of them) keeps pointing at MatrixExtra's own CPU code.
-### It also rebinds t_deep_internal (R/trans.R:46-56) to the device transpose for general d/l/n R/C classes.
+### It also rebinds t_deep_internal (R/trans.R:46-56) to the device transpose for general d/l/n R/C classes, and
+### as.csr.matrix / as.csc.matrix to the device COO sort for general d/l/n TsparseMatrix inputs.
 ###
 ### Usage:
 ###   library(MatrixExtra)
@@ -34,7 +35,10 @@
     "reverse_rows_numeric", "reverse_rows_logical", "reverse_rows_binary",
     "reverse_columns_inplace_numeric", "reverse_columns_inplace_logical", "reverse_columns_inplace_binary",
     ## rank 4: values-only CSR (op) vector
-    "multiply_csr_by_dvec_no_NAs_numeric", "logicaland_csr_by_dvec_internal"
+    "multiply_csr_by_dvec_no_NAs_numeric", "logicaland_csr_by_dvec_internal",
+    ## COO (TsparseMatrix) operands
+    "multiply_csr_by_coo_elemwise", "logicaland_csr_by_coo_elemwise",
+    "multiply_coo_by_dense_ignore_NAs_numeric", "multiply_coo_by_dense_ignore_NAs_logical"
 )
 
 mxgpu_enable <- function(shim_path, min_nnz = 0L) {
@@ -90,6 +94,38 @@ mxgpu_enable <- function(shim_path, min_nnz = 0L) {
     unlockBinding("t_deep_internal", ns)
     assign("t_deep_internal", gpu_t, envir = ns)
     lockBinding("t_deep_internal", ns)
+    ## as.csr.matrix / as.csc.matrix (R/conversions.R): a general d/l/n TsparseMatrix is sorted into CSR / CSC
+    ## order on the device (repeated triplets merged as Matrix merges them), then handed to the saved function,
+    ## which applies the binary / logical flags and the value type to the CSR / CSC it receives.  Any other class
+    ## goes to the saved CPU function unchanged.
+    native_coo <- getNativeSymbolInfo("mxgpu_coo_to_csr", dll)
+    .mxgpu_state$saved_conv <- list()
+    for (conv in c("as.csr.matrix", "as.csc.matrix")) {
+        cpu_conv <- get(conv, envir = ns)
+        .mxgpu_state$saved_conv[[conv]] <- cpu_conv
+        to_csr <- conv == "as.csr.matrix"
+        gpu_conv <- function(x, ...) {
+            cls <- class(x)[1L]
+            if (!(cls %in% c("dgTMatrix", "lgTMatrix", "ngTMatrix")))
+                return(cpu_conv(x, ...))
+            check_valid_matrix(x)
+            vals <- if (cls == "ngTMatrix") NULL else x@x
+            r <- if (to_csr) .Call(native_coo, x@i, x@j, vals, nrow(x), ncol(x))
+                 else .Call(native_coo, x@j, x@i, vals, ncol(x), nrow(x))
+            out <- new(paste0(substr(cls, 1L, 2L), if (to_csr) "RMatrix" else "CMatrix"))
+            out@Dim <- x@Dim
+            out@Dimnames <- x@Dimnames
+            out@p <- r$indptr
+            if (to_csr) out@j <- r$indices else out@i <- r$indices
+            if (!is.null(vals)) out@x <- r$values
+            cpu_conv(out, ...)
+        }
+        environment(gpu_conv) <- list2env(list(native_coo = native_coo, cpu_conv = cpu_conv, to_csr = to_csr),
+                                          parent = ns)
+        unlockBinding(conv, ns)
+        assign(conv, gpu_conv, envir = ns)
+        lockBinding(conv, ns)
+    }
     invisible(TRUE)
 }
 
@@ -101,6 +137,12 @@ mxgpu_disable <- function() {
         lockBinding("t_deep_internal", ns)
         .mxgpu_state$saved_t_deep <- NULL
     }
+    for (conv in names(.mxgpu_state$saved_conv)) {
+        unlockBinding(conv, ns)
+        assign(conv, .mxgpu_state$saved_conv[[conv]], envir = ns)
+        lockBinding(conv, ns)
+    }
+    .mxgpu_state$saved_conv <- list()
     for (fn in names(.mxgpu_state$saved)) {
         unlockBinding(fn, ns)
         assign(fn, .mxgpu_state$saved[[fn]], envir = ns)

@@ -3,7 +3,7 @@
 Layers (SURVEY.md §1 / DESIGN.md):
   csrc/*.hip + include/mxgpu.h   hand-written HIP kernels behind a C-ABI (libmxgpu.so)
   exports.py                     twins of R/RcppExports.R wrappers (ctypes -> C-ABI)
-  matrices.py                    dgRMatrix / lgRMatrix / ngRMatrix / dgCMatrix / float32 stand-ins
+  matrices.py                    dgRMatrix / lgRMatrix / ngRMatrix / dgCMatrix / d/l/ngTMatrix / float32 stand-ins
   matmul.py operators.py slice.py   mirrors of the R glue (checks, messages, dimnames, classes)
   device.py                      device-resident CSR + mxd_* launches on torch tensors (bench, multi-GPU)
   distributed.py                 row-block sharding + RCCL all-gather of C
@@ -15,9 +15,10 @@ from .matrices import (DenseMatrix, MatrixExtraError, NA_INTEGER, NA_LOGICAL, NA
                        as_csr_matrix, check_valid_matrix, dgCMatrix, dgRMatrix, float32, from_scipy,
                        lgRMatrix, ngRMatrix, options, sort_sparse_indices)
 from .matrices import as_csc_matrix, t_deep, t_shallow  # noqa: F401
+from .matrices import TsparseMatrix, as_coo_matrix, dgTMatrix, lgTMatrix, ngTMatrix  # noqa: F401
 from .matmul import RLogical, crossprod, tcrossprod  # noqa: F401  (`%*%` is the @ operator)
-from .operators import (add_csr_matrices, logicalor_csr_matrices, multiply_csr_by_csr,  # noqa: F401
-                        xor_csr_matrices)
+from .operators import (add_csr_matrices, logicalor_csr_matrices, multiply_csr_by_coo,  # noqa: F401
+                        multiply_csr_by_csr, xor_csr_matrices)
 from .slice import subset_csr  # noqa: F401
 
 __version__ = "0.1.0"

@@ -708,6 +708,125 @@ int mx_csr_transpose_begin(const int32_t *indptr, int nrows, int ncols, const in
     });
 }
 
+// ---- COO: as.csr.matrix / as.csc.matrix of a TsparseMatrix, as.coo.matrix, CSR (.) COO, COO (op) vector ----
+int mx_coo_to_csr_begin(const int32_t *rows, const int32_t *cols, const void *values, int value_dtype,
+                        int64_t n_entries, int nrows, int ncols, mx_result **res_out, mx_result_info *info)
+{
+    MX_REQUIRE(res_out && info, "mx_coo_to_csr_begin: null output pointer");
+    MX_REQUIRE(nrows >= 0 && ncols >= 0 && n_entries >= 0, "mx_coo_to_csr_begin: negative size");
+    MX_REQUIRE(n_entries <= INT_MAX, "mx_coo_to_csr_begin: %lld entries exceed R's int32 index range",
+               (long long)n_entries);
+    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
+               "mx_coo_to_csr_begin: unsupported value dtype %d", value_dtype);
+    *res_out = nullptr;
+    const bool has_values = value_dtype != MX_NONE;
+    const size_t vb = dtype_bytes(value_dtype);
+    return begin_result(res_out, info, value_dtype, [&](mx_result &res) {
+        DevBuf r, c, x, ws;
+        if (r.upload(rows, sizeof(int32_t) * (size_t)n_entries)) return 1;
+        if (c.upload(cols, sizeof(int32_t) * (size_t)n_entries)) return 1;
+        if (has_values && x.upload(values, vb * (size_t)n_entries)) return 1;
+        if (ws.alloc(mxd_coo_to_csr_workspace_bytes(n_entries, ncols))) return 1;
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)n_entries)) return 1;
+        if (has_values && res.values.alloc(vb * (size_t)n_entries)) return 1;
+        int64_t nnz_out = 0;
+        if (mxd_coo_to_csr(nrows, ncols, r.as<int32_t>(), c.as<int32_t>(), x.p, value_dtype, n_entries,
+                           res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.p, ws.p, &nnz_out,
+                           nullptr)) return 1;
+        res.set_sizes((int64_t)nrows + 1, nnz_out, has_values ? nnz_out : 0);
+        return 0;
+    });
+}
+
+int mx_csr_to_coo(const int32_t *indptr, int nrows, int32_t *out_rows)
+{
+    MX_REQUIRE(indptr && nrows >= 0, "mx_csr_to_coo: bad arguments");
+    MX_REQUIRE(indptr[0] == 0 && indptr[nrows] >= 0, "mx_csr_to_coo: bad index pointer");
+    const int64_t nnz = indptr[nrows];
+    if (nnz == 0) return 0;
+    MX_REQUIRE(out_rows, "mx_csr_to_coo: null pointer");
+    DevBuf p, o;
+    if (p.upload(indptr, sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+    if (o.alloc(sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (mxd_csr_to_coo(nrows, nnz, p.as<int32_t>(), o.as<int32_t>(), nullptr)) return 1;
+    return mx::xfer_d2h(out_rows, o.p, sizeof(int32_t) * (size_t)nnz);
+}
+
+int mx_multiply_csr_by_coo_begin(int logical, const int32_t *X_indptr, const int32_t *X_indices,
+                                 const void *X_values, const int32_t *Y_rows, const int32_t *Y_cols,
+                                 const void *Y_values, int64_t nnz_Y, int max_row_X, int max_col_X,
+                                 mx_result **res_out, mx_result_info *info)
+{
+    MX_REQUIRE(res_out && info && X_indptr, "mx_multiply_csr_by_coo_begin: null pointer");
+    MX_REQUIRE(max_row_X >= 0 && max_col_X >= 0 && nnz_Y >= 0, "mx_multiply_csr_by_coo_begin: negative size");
+    MX_REQUIRE(nnz_Y <= INT_MAX, "mx_multiply_csr_by_coo_begin: %lld entries exceed R's int32 index range",
+               (long long)nnz_Y);
+    *res_out = nullptr;
+    const size_t vb = logical ? 4 : 8;
+    return begin_result(res_out, info, logical ? MX_LGL : MX_F64, [&](mx_result &res) {
+        Csr X;
+        if (X.upload(X_indptr, X_indices, X_values, max_row_X, vb)) return 1;
+        DevBuf r, c, y, ws;
+        if (r.upload(Y_rows, sizeof(int32_t) * (size_t)nnz_Y)) return 1;
+        if (c.upload(Y_cols, sizeof(int32_t) * (size_t)nnz_Y)) return 1;
+        if (y.upload(Y_values, vb * (size_t)nnz_Y)) return 1;
+        if (ws.alloc(mxd_csr_by_coo_workspace_bytes(nnz_Y))) return 1;
+        int64_t nnz_out = 0;
+        if (mxd_csr_by_coo_count(logical, max_row_X, max_col_X, X.p.as<int32_t>(), X.j.as<int32_t>(), X.x.p,
+                                 r.as<int32_t>(), c.as<int32_t>(), y.p, nnz_Y, ws.p, &nnz_out, nullptr)) return 1;
+        res.set_sizes(nnz_out, nnz_out, nnz_out);                  // row ids travel in the indptr vector
+        if (res.indptr.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
+        if (res.values.alloc(vb * (size_t)nnz_out)) return 1;
+        if (nnz_out == 0) return 0;
+        return mxd_csr_by_coo_fill(logical, max_row_X, max_col_X, X.p.as<int32_t>(), X.j.as<int32_t>(), X.x.p,
+                                   r.as<int32_t>(), c.as<int32_t>(), y.p, nnz_Y, ws.p, res.indptr.as<int32_t>(),
+                                   res.indices.as<int32_t>(), res.values.p, nullptr);
+    });
+}
+
+static int coo_by_dvec_export(const int32_t *ii, const int32_t *jj, const void *xx, int64_t nnz, const void *dvec,
+                              int64_t dvec_len, int nrows, int ncols, int op, int lhs, void *values_out)
+{
+    MX_REQUIRE(nrows >= 0 && ncols >= 0 && nnz >= 0 && dvec_len >= 0, "coo (op) vector: negative size");
+    if (nnz == 0) return 0;
+    MX_REQUIRE(dvec_len > 0, "coo (op) vector: empty vector");
+    const size_t eb = op == MX_DV_LOGICAL_AND ? 4 : 8;
+    DevBuf i, j, x, D, o;
+    if (i.upload(ii, sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (j.upload(jj, sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (x.upload(xx, eb * (size_t)nnz)) return 1;
+    if (D.upload(dvec, eb * (size_t)dvec_len)) return 1;
+    if (o.alloc(eb * (size_t)nnz)) return 1;
+    if (mxd_coo_by_dvec(nrows, ncols, nnz, i.as<int32_t>(), j.as<int32_t>(), x.p, D.p, dvec_len, op, lhs, o.p, nullptr))
+        return 1;
+    return mx::xfer_d2h(values_out, o.p, eb * (size_t)nnz);
+}
+
+int mx_multiply_coo_by_dense_ignore_NAs_numeric(const int32_t *ii, const int32_t *jj, const double *xx, int64_t nnz,
+                                                const double *dvec, int64_t dvec_len, int nrows, int ncols,
+                                                int multiply, int powerto, int divide, int divrest, int intdiv,
+                                                int X_is_LHS, double *values_out)
+{
+    // same precedence as the reference's if/else chain (operators.cpp:2872-2883)
+    int op;
+    if (multiply) op = MX_DV_MULTIPLY;
+    else if (powerto) op = MX_DV_POWERTO;
+    else if (divide) op = MX_DV_DIVIDE;
+    else if (divrest) op = MX_DV_DIVREST;
+    else if (intdiv) op = MX_DV_INTDIV;
+    else return set_error("Internal error. Please file an issue in GitHub.");        // throw_internal_err()
+    return coo_by_dvec_export(ii, jj, xx, nnz, dvec, dvec_len, nrows, ncols, op, X_is_LHS, values_out);
+}
+
+int mx_multiply_coo_by_dense_ignore_NAs_logical(const int32_t *ii, const int32_t *jj, const int32_t *xx, int64_t nnz,
+                                                const int32_t *dvec, int64_t dvec_len, int nrows, int ncols,
+                                                int32_t *values_out)
+{
+    return coo_by_dvec_export(ii, jj, xx, nnz, dvec, dvec_len, nrows, ncols, MX_DV_LOGICAL_AND, 1, values_out);
+}
+
 int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, void *out_values)
 {
     MX_REQUIRE(res, "mx_result_finish: null handle");

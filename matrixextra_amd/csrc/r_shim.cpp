@@ -4,7 +4,8 @@
 // reference registers in CallEntries[] (src/RcppExports.cpp:2233-2242, 2290-2291, 2297-2298, 2333-2334,
 // 2341-2343), so R code written as `.Call("_MatrixExtra_<fn>", ...)` (R/RcppExports.R) dispatches
 // unchanged, plus mxgpu_register() to add them to a DllInfo.  It also exports mxgpu_csr_transpose, the device
-// transpose behind the overlay's t_deep_internal.  Written against the plain R C API
+// transpose behind the overlay's t_deep_internal, and mxgpu_coo_to_csr, the device COO sort behind its
+// as.csr.matrix / as.csc.matrix of a TsparseMatrix.  Written against the plain R C API
 // (no Rcpp): INTEGER()/REAL(), Rf_allocMatrix, Rf_error.
 //
 // This file is NOT part of libmxgpu.so and cannot be compiled in the development image (no R headers):
@@ -406,6 +407,92 @@ SEXP mxgpu_csr_transpose(SEXP p_, SEXP idx, SEXP x_, SEXP ncol)
     return finish_guarded(res, info, R_NilValue, R_NilValue);
 }
 
+// COO -> CSR behind the overlay's as.csr.matrix / as.csc.matrix of a general d/l/n TsparseMatrix: i, j 0-based
+// (the @i / @j slots), values as for mxgpu_csr_transpose.  Call with (j, i, x, ncol, nrow) for the CSC slots.
+// Returns list(indptr=, indices=, values=) with repeated (i, j) merged as Matrix's coercion merges them.
+SEXP mxgpu_coo_to_csr(SEXP i_, SEXP j_, SEXP x_, SEXP nrow, SEXP ncol)
+{
+    Protect p;
+    i_ = as_type(i_, INTSXP, p); j_ = as_type(j_, INTSXP, p);
+    if (XLENGTH(i_) != XLENGTH(j_)) Rf_error("mxgpu_coo_to_csr: row and column indices have different length");
+    int dtype = MX_NONE;
+    const void *v = nullptr;
+    if (TYPEOF(x_) == REALSXP) { dtype = MX_F64; v = REAL(x_); }
+    else if (TYPEOF(x_) == LGLSXP) { dtype = MX_LGL; v = LOGICAL(x_); }
+    else if (x_ != R_NilValue) Rf_error("mxgpu_coo_to_csr: values must be double, logical or NULL");
+    if (v && XLENGTH(x_) != XLENGTH(i_)) Rf_error("mxgpu_coo_to_csr: values and indices have different length");
+    mx_result *res = nullptr;
+    mx_result_info info;
+    if (mx_coo_to_csr_begin(INTEGER(i_), INTEGER(j_), v, dtype, (int64_t)XLENGTH(i_), Rf_asInteger(nrow),
+                            Rf_asInteger(ncol), &res, &info))
+        fail();
+    if (dtype != MX_NONE) info.values_dtype = dtype;
+    return finish_guarded(res, info, R_NilValue, R_NilValue);
+}
+
+// CSR (.) COO  (src/operators.cpp:673-720; glue src/RcppExports.cpp:1317-1350, 8 arguments): list(row, col, val)
+static SEXP csr_by_coo(int logical, SEXP p_, SEXP j_, SEXP x_, SEXP yi, SEXP yj, SEXP yx, SEXP max_row, SEXP max_col)
+{
+    Protect p;
+    const SEXPTYPE vt = logical ? LGLSXP : REALSXP;
+    p_ = as_type(p_, INTSXP, p); j_ = as_type(j_, INTSXP, p); x_ = as_type(x_, vt, p);
+    yi = as_type(yi, INTSXP, p); yj = as_type(yj, INTSXP, p); yx = as_type(yx, vt, p);
+    const int m = Rf_asInteger(max_row);
+    if (XLENGTH(p_) != (R_xlen_t)m + 1) Rf_error("multiply_csr_by_coo: indptr does not match max_row_X");
+    if (XLENGTH(yi) != XLENGTH(yj) || XLENGTH(yi) != XLENGTH(yx)) Rf_error("multiply_csr_by_coo: bad COO lengths");
+    const void *xv = logical ? (const void *)LOGICAL(x_) : (const void *)REAL(x_);
+    const void *yv = logical ? (const void *)LOGICAL(yx) : (const void *)REAL(yx);
+    mx_result *res = nullptr;
+    mx_result_info info;
+    if (mx_multiply_csr_by_coo_begin(logical, INTEGER(p_), INTEGER(j_), xv, INTEGER(yi), INTEGER(yj), yv,
+                                     (int64_t)XLENGTH(yi), m, Rf_asInteger(max_col), &res, &info))
+        fail();
+    SEXP out = PROTECT(finish_guarded(res, info, R_NilValue, R_NilValue));
+    SEXP nm = PROTECT(Rf_allocVector(STRSXP, 3));
+    SET_STRING_ELT(nm, 0, Rf_mkChar("row"));
+    SET_STRING_ELT(nm, 1, Rf_mkChar("col"));
+    SET_STRING_ELT(nm, 2, Rf_mkChar("val"));
+    Rf_setAttrib(out, R_NamesSymbol, nm);
+    UNPROTECT(2);
+    return out;
+}
+SEXP _MatrixExtra_multiply_csr_by_coo_elemwise(SEXP p_, SEXP j_, SEXP x_, SEXP yi, SEXP yj, SEXP yx, SEXP mr, SEXP mc)
+{ return csr_by_coo(0, p_, j_, x_, yi, yj, yx, mr, mc); }
+SEXP _MatrixExtra_logicaland_csr_by_coo_elemwise(SEXP p_, SEXP j_, SEXP x_, SEXP yi, SEXP yj, SEXP yx, SEXP mr, SEXP mc)
+{ return csr_by_coo(1, p_, j_, x_, yi, yj, yx, mr, mc); }
+
+// values-only COO (op) vector  (src/operators.cpp:3363-3418; 12 and 6 arguments)
+SEXP _MatrixExtra_multiply_coo_by_dense_ignore_NAs_numeric(SEXP ii, SEXP jj, SEXP xx, SEXP dvec, SEXP nrows,
+                                                           SEXP ncols, SEXP multiply, SEXP powerto, SEXP divide,
+                                                           SEXP divrest, SEXP intdiv, SEXP lhs)
+{
+    Protect p;
+    ii = as_type(ii, INTSXP, p); jj = as_type(jj, INTSXP, p); xx = as_type(xx, REALSXP, p);
+    dvec = as_type(dvec, REALSXP, p);
+    SEXP out = p(Rf_allocVector(REALSXP, XLENGTH(xx)));
+    if (mx_multiply_coo_by_dense_ignore_NAs_numeric(INTEGER(ii), INTEGER(jj), REAL(xx), (int64_t)XLENGTH(xx),
+                                                    REAL(dvec), (int64_t)XLENGTH(dvec), Rf_asInteger(nrows),
+                                                    Rf_asInteger(ncols), Rf_asLogical(multiply),
+                                                    Rf_asLogical(powerto), Rf_asLogical(divide),
+                                                    Rf_asLogical(divrest), Rf_asLogical(intdiv), Rf_asLogical(lhs),
+                                                    REAL(out)))
+        fail();
+    return out;
+}
+SEXP _MatrixExtra_multiply_coo_by_dense_ignore_NAs_logical(SEXP ii, SEXP jj, SEXP xx, SEXP dvec, SEXP nrows,
+                                                           SEXP ncols)
+{
+    Protect p;
+    ii = as_type(ii, INTSXP, p); jj = as_type(jj, INTSXP, p); xx = as_type(xx, LGLSXP, p);
+    dvec = as_type(dvec, LGLSXP, p);
+    SEXP out = p(Rf_allocVector(LGLSXP, XLENGTH(xx)));
+    if (mx_multiply_coo_by_dense_ignore_NAs_logical(INTEGER(ii), INTEGER(jj), LOGICAL(xx), (int64_t)XLENGTH(xx),
+                                                    LOGICAL(dvec), (int64_t)XLENGTH(dvec), Rf_asInteger(nrows),
+                                                    Rf_asInteger(ncols), LOGICAL(out)))
+        fail();
+    return out;
+}
+
 #define MX_ENTRY(name, n) {"_MatrixExtra_" #name, (DL_FUNC)&_MatrixExtra_##name, n}
 static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(matmul_dense_csc_numeric, 5), MX_ENTRY(matmul_dense_csc_float32, 5),
@@ -424,7 +511,10 @@ static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(reverse_columns_inplace_numeric, 4), MX_ENTRY(reverse_columns_inplace_logical, 4),
     MX_ENTRY(reverse_columns_inplace_binary, 4),
     MX_ENTRY(multiply_csr_by_dvec_no_NAs_numeric, 11), MX_ENTRY(logicaland_csr_by_dvec_internal, 5),
+    MX_ENTRY(multiply_csr_by_coo_elemwise, 8), MX_ENTRY(logicaland_csr_by_coo_elemwise, 8),
+    MX_ENTRY(multiply_coo_by_dense_ignore_NAs_numeric, 12), MX_ENTRY(multiply_coo_by_dense_ignore_NAs_logical, 6),
     {"mxgpu_csr_transpose", (DL_FUNC)&mxgpu_csr_transpose, 4},
+    {"mxgpu_coo_to_csr", (DL_FUNC)&mxgpu_coo_to_csr, 5},
     {NULL, NULL, 0}
 };
 

@@ -29,6 +29,9 @@
 // Matrix's documented behaviour for l-sparse triplets; it was not re-checked against a running R (none was
 // available when this was written).
 // Each run is merged by one thread, sequentially, because an f64 sum in source order is sequential.
+//
+// COO -> CSR (mxd_coo_to_csr, at the end of this file) runs the same passes twice: pass 0 can take the source
+// rows from the caller instead of an indptr search (TP_SRC_ROWS).
 #include "mx_common.h"
 
 namespace mx {
@@ -115,28 +118,36 @@ void tp_count_kernel(const int32_t *__restrict__ keys, int64_t nnz, int n, int s
 // when there are at most TP_SPAN_CAP of them.
 constexpr int TP_SPAN_CAP = 1024;
 
-template <bool FIRST>
+// SRC: where the pass reads its source rows.  TP_SRC_SORTED: a later pass (rows_in / perm_in of the previous
+// pass); TP_SRC_INDPTR: pass 0 of a CSR (binary search of indptr); TP_SRC_ROWS: pass 0 of a COO (the caller's
+// row ids in rows_in, checked against [0, m) where they are read: a bad one sets flags[2] and is replaced by 0).
+enum { TP_SRC_SORTED = 0, TP_SRC_INDPTR = 1, TP_SRC_ROWS = 2 };
+
+template <int SRC>
 __global__ __launch_bounds__(TP_BLOCK)
 void tp_scatter_kernel(const int32_t *__restrict__ keys_in, const int32_t *__restrict__ perm_in,
                        const int32_t *__restrict__ rows_in, const int32_t *__restrict__ indptr, int m, int64_t nnz,
                        int n, int shift, int nbits, int ntiles, const int32_t *__restrict__ offsets,
-                       int32_t *__restrict__ keys_out, int32_t *__restrict__ perm_out, int32_t *__restrict__ rows_out)
+                       int32_t *__restrict__ keys_out, int32_t *__restrict__ perm_out, int32_t *__restrict__ rows_out,
+                       int32_t *__restrict__ flags)
 {
+    constexpr bool FIRST = SRC != TP_SRC_SORTED;
+    constexpr bool SEARCH = SRC == TP_SRC_INDPTR;
     __shared__ int32_t cnt[TP_WAVES][TP_RADIX];
     __shared__ int32_t delta[TP_RADIX];
     __shared__ int32_t stage[3][TP_TILE];              // keys, entry index, row in slot order (48 KiB)
-    __shared__ int32_t span_ptr[FIRST ? TP_SPAN_CAP : 1];
+    __shared__ int32_t span_ptr[SEARCH ? TP_SPAN_CAP : 1];
     __shared__ int32_t row_span[2];
     __shared__ int32_t wave_tot[TP_WAVES];
     const int64_t t0 = (int64_t)blockIdx.x * TP_TILE;
     for (int i = threadIdx.x; i < TP_WAVES * TP_RADIX; i += TP_BLOCK) (&cnt[0][0])[i] = 0;
-    if (FIRST && threadIdx.x < 2) {
+    if (SEARCH && threadIdx.x < 2) {
         const int64_t k = threadIdx.x == 0 ? t0 : (t0 + TP_TILE - 1 < nnz ? t0 + TP_TILE - 1 : nnz - 1);
         row_span[threadIdx.x] = tp_row_of(indptr, 0, m, k);
     }
     __syncthreads();
     int r0 = 0, nspan = 0;
-    if (FIRST) {
+    if (SEARCH) {
         r0 = row_span[0];
         nspan = row_span[1] - r0 + 1;
         if (nspan <= TP_SPAN_CAP)
@@ -147,15 +158,16 @@ void tp_scatter_kernel(const int32_t *__restrict__ keys_in, const int32_t *__res
     const uint64_t lt_mask = (1ULL << lane) - 1;
     const int64_t base = t0 + wave * TP_WAVE_SPAN;
     int key[TP_ITEMS], rank[TP_ITEMS], pay[TP_ITEMS], row[TP_ITEMS];
-    bool bad = false;
+    bool bad = false, bad_row = false;
 #pragma unroll
     for (int it = 0; it < TP_ITEMS; it++) {
         const int64_t k = base + it * MX_WAVE + lane;
         const bool valid = k < nnz;
         key[it] = valid ? tp_load_key<FIRST>(keys_in, k, n, bad) : 0;
         pay[it] = valid ? (FIRST ? (int)k : perm_in[k]) : 0;
-        if (!FIRST) {
+        if (!SEARCH) {
             row[it] = valid ? rows_in[k] : 0;
+            if (SRC == TP_SRC_ROWS && (unsigned)row[it] >= (unsigned)m) { bad_row = true; row[it] = 0; }
         } else if (!valid) {
             row[it] = 0;
         } else if (nspan <= TP_SPAN_CAP) {          // last r in the span with indptr[r] <= k
@@ -174,6 +186,7 @@ void tp_scatter_kernel(const int32_t *__restrict__ keys_in, const int32_t *__res
         rank[it] = before + __popcll(peers & lt_mask);
         if (valid && lane == __builtin_ctzll(peers)) cnt[wave][d] = before + __popcll(peers);
     }
+    if (SRC == TP_SRC_ROWS && bad_row) flags[2] = 1;
     __syncthreads();
     {   // one thread per digit: tile-local start of the digit (block exclusive scan of the digit totals), then
         // cnt[w][d] -> first slot of wave w's digit-d entries, delta[d] -> global position of slot 0
@@ -348,6 +361,46 @@ static unsigned grid_for(int64_t n, int block, int64_t cap = (int64_t)1 << 20)
     return (unsigned)(g < cap ? g : cap);
 }
 
+// The LSD radix passes shared by the CSR transpose and the COO sort: a stable sort of nnz entries by key
+// (keys in [0, n), checked in pass 0), carrying the entry index and the source row (src0 says where pass 0 finds
+// it).  *fin receives the buffer index of the sorted keys / perm / rows in L.
+static int tp_sort_passes(int src0, const int32_t *keys0, const int32_t *rows0, const int32_t *indptr, int m, int n,
+                          int64_t nnz, const TpLayout &L, int32_t *flags, int *fin, hipStream_t st)
+{
+    const int key_bits = bits_of(n > 0 ? n - 1 : 0);
+    const int npasses = n <= TP_RADIX ? 1 : (key_bits + 7) / 8;
+    const int ntiles = (int)tp_ntiles(nnz);
+    const int64_t T = (int64_t)TP_RADIX * ntiles;
+    for (int pass = 0; pass < npasses; pass++) {
+        const int shift = 8 * pass;
+        const int nbits = key_bits - shift < 8 ? (key_bits - shift > 0 ? key_bits - shift : 0) : 8;
+        const int32_t *kin = pass == 0 ? keys0 : L.keys[(pass - 1) & 1];
+        const int32_t *pin = pass == 0 ? nullptr : L.perm[(pass - 1) & 1];
+        const int32_t *rin = pass == 0 ? rows0 : L.rows[(pass - 1) & 1];
+        int32_t *kout = L.keys[pass & 1], *pout = L.perm[pass & 1], *rout = L.rows[pass & 1];
+        if (pass == 0)
+            hipLaunchKernelGGL(tp_count_kernel<true>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, nnz, n, shift, nbits,
+                               ntiles, L.table, flags);
+        else
+            hipLaunchKernelGGL(tp_count_kernel<false>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, nnz, n, shift, nbits,
+                               ntiles, L.table, flags);
+        MX_LAUNCH_CHECK();
+        if (exclusive_scan_i32(L.table, T, L.offsets, nullptr, L.scan_ws, st)) return 1;
+        if (pass > 0)
+            hipLaunchKernelGGL(tp_scatter_kernel<TP_SRC_SORTED>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, pin, rin,
+                               indptr, m, nnz, n, shift, nbits, ntiles, L.offsets, kout, pout, rout, flags);
+        else if (src0 == TP_SRC_INDPTR)
+            hipLaunchKernelGGL(tp_scatter_kernel<TP_SRC_INDPTR>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, pin, rin,
+                               indptr, m, nnz, n, shift, nbits, ntiles, L.offsets, kout, pout, rout, flags);
+        else
+            hipLaunchKernelGGL(tp_scatter_kernel<TP_SRC_ROWS>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, pin, rin,
+                               indptr, m, nnz, n, shift, nbits, ntiles, L.offsets, kout, pout, rout, flags);
+        MX_LAUNCH_CHECK();
+    }
+    *fin = (npasses - 1) & 1;
+    return 0;
+}
+
 static int csr_transpose(int m, int n, const int32_t *indptr, const int32_t *indices, const void *values,
                          int value_dtype, int64_t nnz, int32_t *out_indptr, int32_t *out_indices, void *out_values,
                          void *workspace, int64_t *nnz_out_host, hipStream_t st)
@@ -368,34 +421,8 @@ static int csr_transpose(int m, int n, const int32_t *indptr, const int32_t *ind
     TpLayout L(workspace, nnz);
     MX_HIP(hipMemsetAsync(L.flags, 0, 2 * sizeof(int32_t), st));
 
-    const int key_bits = bits_of(n > 0 ? n - 1 : 0);
-    const int npasses = n <= TP_RADIX ? 1 : (key_bits + 7) / 8;
-    const int ntiles = (int)tp_ntiles(nnz);
-    const int64_t T = (int64_t)TP_RADIX * ntiles;
-    for (int pass = 0; pass < npasses; pass++) {
-        const int shift = 8 * pass;
-        const int nbits = key_bits - shift < 8 ? (key_bits - shift > 0 ? key_bits - shift : 0) : 8;
-        const int32_t *kin = pass == 0 ? indices : L.keys[(pass - 1) & 1];
-        const int32_t *pin = pass == 0 ? nullptr : L.perm[(pass - 1) & 1];
-        const int32_t *rin = pass == 0 ? nullptr : L.rows[(pass - 1) & 1];
-        int32_t *kout = L.keys[pass & 1], *pout = L.perm[pass & 1], *rout = L.rows[pass & 1];
-        if (pass == 0)
-            hipLaunchKernelGGL(tp_count_kernel<true>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, nnz, n, shift, nbits,
-                               ntiles, L.table, L.flags);
-        else
-            hipLaunchKernelGGL(tp_count_kernel<false>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, nnz, n, shift, nbits,
-                               ntiles, L.table, L.flags);
-        MX_LAUNCH_CHECK();
-        if (exclusive_scan_i32(L.table, T, L.offsets, nullptr, L.scan_ws, st)) return 1;
-        if (pass == 0)
-            hipLaunchKernelGGL(tp_scatter_kernel<true>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, pin, rin, indptr, m,
-                               nnz, n, shift, nbits, ntiles, L.offsets, kout, pout, rout);
-        else
-            hipLaunchKernelGGL(tp_scatter_kernel<false>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, pin, rin, indptr, m,
-                               nnz, n, shift, nbits, ntiles, L.offsets, kout, pout, rout);
-        MX_LAUNCH_CHECK();
-    }
-    const int fin = (npasses - 1) & 1;
+    int fin = 0;
+    if (tp_sort_passes(TP_SRC_INDPTR, indices, nullptr, indptr, m, n, nnz, L, L.flags, &fin, st)) return 1;
     const int32_t *skeys = L.keys[fin], *sperm = L.perm[fin], *srows = L.rows[fin];
     const unsigned gq = (unsigned)ceil_div(nnz, 256);
     if (value_dtype == MX_F64)
@@ -450,7 +477,112 @@ static int csr_transpose(int m, int n, const int32_t *indptr, const int32_t *ind
     return 0;
 }
 
+// ---- COO -> CSR: the transpose's passes run twice -----------------------------------------------------------
+// Stage 1 stably sorts the triplets by column, carrying the row id and the entry index: pass 0 reads the rows
+// from the caller (TP_SRC_ROWS) instead of searching an indptr.  The result is a CSC whose columns list their
+// rows in input order.  Stage 2 is csr_transpose of that CSC: its stable sort by row gives each CSR row its
+// columns in ascending order with repeated (row, col) pairs adjacent and in input order, and its compaction
+// merges them by Matrix's triplet rules.
+// workspace: [TpLayout(nnz)][csc indptr n+1][csc rows nnz][csc values 8 * nnz]; stage 2 re-uses the TpLayout part.
+// Stage 1's flags sit at L.flags[4..7] ([4] column out of range, [5] the gather's duplicate flag, unused,
+// [6] row out of range), out of the way of stage 2's flags[0..1].
+static size_t coo_ws_bytes(int64_t nnz, int n)
+{
+    return TpLayout(nullptr, nnz).bytes + padded_i32_bytes((int64_t)n + 1) + padded_i32_bytes(nnz) +
+           (((size_t)8 * (size_t)(nnz > 0 ? nnz : 1) + 15) & ~(size_t)15);
+}
+
+static int coo_to_csr(int m, int n, const int32_t *rows, const int32_t *cols, const void *values, int value_dtype,
+                      int64_t nnz, int32_t *out_indptr, int32_t *out_indices, void *out_values, void *workspace,
+                      int64_t *nnz_out_host, hipStream_t st)
+{
+    MX_REQUIRE(m >= 0 && n >= 0 && nnz >= 0, "mxd_coo_to_csr: negative size");
+    MX_REQUIRE(nnz <= INT_MAX, "mxd_coo_to_csr: %lld entries exceed R's int32 index range", (long long)nnz);
+    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
+               "mxd_coo_to_csr: unsupported value dtype %d", value_dtype);
+    MX_REQUIRE(nnz_out_host && out_indptr && (nnz == 0 || (rows && cols && out_indices && workspace)),
+               "mxd_coo_to_csr: null pointer");
+    const bool has_values = value_dtype != MX_NONE;
+    MX_REQUIRE(!has_values || nnz == 0 || (values && out_values), "mxd_coo_to_csr: null values pointer");
+    if (nnz == 0) {
+        MX_HIP(hipMemsetAsync(out_indptr, 0, sizeof(int32_t) * ((size_t)m + 1), st));
+        *nnz_out_host = 0;
+        return 0;
+    }
+    MX_REQUIRE(m > 0 && n > 0, "mxd_coo_to_csr: %lld entries in a %d x %d matrix: index outside the matrix",
+               (long long)nnz, m, n);
+    TpLayout L(workspace, nnz);
+    char *p = (char *)workspace + L.bytes;
+    int32_t *csc_indptr = (int32_t *)p;  p += padded_i32_bytes((int64_t)n + 1);
+    int32_t *csc_rows = (int32_t *)p;    p += padded_i32_bytes(nnz);
+    void *csc_values = p;
+    int32_t *F = L.flags + 4;
+    MX_HIP(hipMemsetAsync(F, 0, 4 * sizeof(int32_t), st));
+
+    int fin = 0;
+    if (tp_sort_passes(TP_SRC_ROWS, cols, rows, nullptr, m, n, nnz, L, F, &fin, st)) return 1;
+    const int32_t *skeys = L.keys[fin], *sperm = L.perm[fin], *srows = L.rows[fin];
+    const unsigned gq = (unsigned)ceil_div(nnz, 256);
+    if (value_dtype == MX_F64)
+        hipLaunchKernelGGL((tp_gather_kernel<double, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz, srows,
+                           (const double *)values, csc_rows, (double *)csc_values, F);
+    else if (value_dtype == MX_LGL)
+        hipLaunchKernelGGL((tp_gather_kernel<int32_t, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz, srows,
+                           (const int32_t *)values, csc_rows, (int32_t *)csc_values, F);
+    else
+        hipLaunchKernelGGL((tp_gather_kernel<int32_t, false>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz,
+                           srows, nullptr, csc_rows, nullptr, F);
+    MX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tp_indptr_kernel, dim3(grid_for((int64_t)n + 1, 256)), dim3(256), 0, st, skeys, nnz, (int64_t)n,
+                       csc_indptr);
+    MX_LAUNCH_CHECK();
+
+    // stage 2 ends with the stream synchronised; bad indices were clamped to 0, so it runs safely either way
+    if (csr_transpose(n, m, csc_indptr, csc_rows, has_values ? csc_values : nullptr, value_dtype, nnz, out_indptr,
+                      out_indices, out_values, workspace, nnz_out_host, st))
+        return 1;
+    int32_t flags[4] = {0, 0, 0, 0};
+    MX_HIP(hipMemcpyAsync(flags, F, sizeof(flags), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipStreamSynchronize(st));
+    MX_REQUIRE(!flags[0], "mxd_coo_to_csr: column index outside [0, %d)", n);
+    MX_REQUIRE(!flags[2], "mxd_coo_to_csr: row index outside [0, %d)", m);
+    return 0;
+}
+
+// ---- CSR -> COO: row id of every entry, storage order kept -------------------------------------------------
+__global__ __launch_bounds__(256)
+void csr_rows_of_entries_kernel(const int32_t *__restrict__ indptr, int m, int64_t nnz, int32_t *__restrict__ rows)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < nnz) rows[k] = tp_row_of(indptr, 0, m, k);
+}
+
 }  // namespace mx
+
+extern "C" size_t mxd_coo_to_csr_workspace_bytes(int64_t nnz, int n)
+{
+    return mx::coo_ws_bytes(nnz > 0 ? nnz : 0, n > 0 ? n : 0);
+}
+
+extern "C" int mxd_coo_to_csr(int m, int n, const int32_t *rows, const int32_t *cols, const void *values,
+                              int value_dtype, int64_t nnz, int32_t *out_indptr, int32_t *out_indices,
+                              void *out_values, void *workspace, int64_t *nnz_out_host, void *stream)
+{
+    return mx::coo_to_csr(m, n, rows, cols, values, value_dtype, nnz, out_indptr, out_indices, out_values, workspace,
+                          nnz_out_host, mx::as_stream(stream));
+}
+
+extern "C" int mxd_csr_to_coo(int m, int64_t nnz, const int32_t *indptr, int32_t *out_rows, void *stream)
+{
+    MX_REQUIRE(m >= 0 && nnz >= 0 && nnz <= INT_MAX, "mxd_csr_to_coo: bad size");
+    MX_REQUIRE(m > 0 || nnz == 0, "mxd_csr_to_coo: entries without rows");
+    if (nnz == 0) return 0;
+    MX_REQUIRE(indptr && out_rows, "mxd_csr_to_coo: null pointer");
+    hipLaunchKernelGGL(mx::csr_rows_of_entries_kernel, dim3((unsigned)mx::ceil_div(nnz, 256)), dim3(256), 0,
+                       mx::as_stream(stream), indptr, m, nnz, out_rows);
+    MX_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" size_t mxd_csr_transpose_workspace_bytes(int64_t nnz)
 {

@@ -219,3 +219,44 @@ def csr_transpose(A: DeviceCSR) -> DeviceCSR:
                                 C.byref(nnz_out), _stream()))
     nnz = int(nnz_out.value)
     return DeviceCSR(out_p, out_j[:nnz], None if out_x is None else out_x[:nnz], A.K, A.m, nnz)
+
+
+def _value_dtype(values) -> int:
+    if values is None:
+        return MX_NONE
+    if values.dtype == torch.float64:
+        return MX_F64
+    if values.dtype == torch.int32:
+        return MX_LGL
+    raise ValueError(f"values must be float64 or int32 (R logical), got {values.dtype}")
+
+
+def coo_to_csr(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor | None, m: int, n: int) -> DeviceCSR:
+    """Canonical CSR of an m x n COO held in HBM (int32 0-based triplets, any order) through mxd_coo_to_csr:
+    columns ascending and unique per row, repeated (i, j) merged by Matrix's triplet rules.  coo_to_csr(j, i, x,
+    n, m) gives the CSC arrays."""
+    lib = _lib.load()
+    dev = i.device
+    nnz = int(i.numel())
+    if int(j.numel()) != nnz or (x is not None and int(x.numel()) != nnz):
+        raise ValueError("i, j and x must have the same length")
+    if i.dtype != torch.int32 or j.dtype != torch.int32 or not (i.is_contiguous() and j.is_contiguous()):
+        raise ValueError("i and j must be contiguous int32 tensors")
+    vd = _value_dtype(x)
+    ws = torch.empty(max(lib.mxd_coo_to_csr_workspace_bytes(nnz, int(n)), 16), dtype=torch.uint8, device=dev)
+    out_p = torch.empty(int(m) + 1, dtype=torch.int32, device=dev)
+    out_j = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+    out_x = None if x is None else torch.empty(max(nnz, 1), dtype=x.dtype, device=dev)
+    nnz_out = C.c_int64(0)
+    check(lib.mxd_coo_to_csr(C.c_int(int(m)), C.c_int(int(n)), _dp(i), _dp(j), _dp(x), C.c_int(vd), C.c_int64(nnz),
+                             _dp(out_p), _dp(out_j), _dp(out_x), _dp(ws), C.byref(nnz_out), _stream()))
+    k = int(nnz_out.value)
+    return DeviceCSR(out_p, out_j[:k], None if out_x is None else out_x[:k], int(m), int(n), k)
+
+
+def csr_to_coo(A: DeviceCSR):
+    """(i, j, x) of a device CSR in storage order through mxd_csr_to_coo: i is new, j and x are A's own tensors."""
+    lib = _lib.load()
+    rows = torch.empty(max(A.nnz, 1), dtype=torch.int32, device=A.indptr.device)
+    check(lib.mxd_csr_to_coo(C.c_int(A.m), C.c_int64(A.nnz), _dp(A.indptr), _dp(rows), _stream()))
+    return rows[:A.nnz], A.indices, A.values

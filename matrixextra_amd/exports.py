@@ -567,3 +567,111 @@ def csr_transpose(indptr, indices, values, ncol):
     out = _finish(res, info, empty_values_dtype=v.dtype)
     out["values"] = out["values"].astype(v.dtype, copy=False)     # no entries: an empty vector of the input's type
     return out
+
+
+# ----------------------------------------------------------------------------- COO (TsparseMatrix)
+def _values_kind(values):
+    """(array, mx dtype) of a value vector: float64, int32 R logicals, or None (pattern)."""
+    if values is None:
+        return None, MX_NONE
+    v = np.asarray(values)
+    if v.dtype == np.int32:
+        return np.ascontiguousarray(v), MX_LGL
+    if v.dtype == np.float64:
+        return np.ascontiguousarray(v), MX_F64
+    raise TypeError(f"values must be float64 or int32 (R logical), got {v.dtype}")
+
+
+def coo_to_csr(i, j, values, nrow, ncol):
+    """CSR arrays of an nrow x ncol COO (0-based triplets, any order, duplicates allowed): Matrix's
+    TsparseMatrix -> RsparseMatrix coercion behind as.csr.matrix (R/conversions.R:180-295).  Rows come out with
+    ascending, unique columns; repeated (i, j) pairs are merged (f64 summed in input order, logicals by R's `|`,
+    pattern once).  coo_to_csr(j, i, x, ncol, nrow) gives the CSC arrays.  values None -> `values` is None."""
+    lib = _lib.load()
+    ri, cj = _i32(i), _i32(j)
+    if ri.size != cj.size:
+        raise ValueError("row and column indices have different length")
+    v, vdt = _values_kind(values)
+    if v is not None and v.size != ri.size:
+        raise ValueError("values and indices have different number of entries")
+    res = C.c_void_p()
+    info = ResultInfo()
+    check(lib.mx_coo_to_csr_begin(ptr(ri), ptr(cj), ptr(v), C.c_int(vdt), C.c_int64(ri.size), C.c_int(int(nrow)),
+                                  C.c_int(int(ncol)), C.byref(res), C.byref(info)))
+    if v is None:
+        out = _finish(res, info)
+        out["values"] = None
+        return out
+    out = _finish(res, info, empty_values_dtype=v.dtype)
+    out["values"] = out["values"].astype(v.dtype, copy=False)
+    return out
+
+
+def csr_to_coo(indptr):
+    """Row id of every entry of a CSR (column id, for a CSC), in storage order: the index vector as.coo.matrix
+    adds (R/conversions.R:515-590)."""
+    p = _i32(indptr)
+    out = np.empty(int(p[-1]) if p.size else 0, dtype=np.int32)
+    check(_lib.load().mx_csr_to_coo(ptr(p), C.c_int(p.size - 1), ptr(out)))
+    return out
+
+
+def _csr_by_coo(logical, X_csr_indptr, X_csr_indices, X_csr_values, Y_coo_row, Y_coo_col, Y_coo_val, max_row_X,
+                max_col_X):
+    lib = _lib.load()
+    vdt = np.int32 if logical else np.float64
+    p, xj = _i32(X_csr_indptr), _i32(X_csr_indices)
+    xv = np.ascontiguousarray(X_csr_values, dtype=vdt)
+    yi, yj = _i32(Y_coo_row), _i32(Y_coo_col)
+    yv = np.ascontiguousarray(Y_coo_val, dtype=vdt)
+    if not (yi.size == yj.size == yv.size):
+        raise ValueError("COO row, column and value vectors have different lengths")
+    if p.size != int(max_row_X) + 1:
+        raise ValueError("X_csr_indptr must have max_row_X + 1 entries")
+    res = C.c_void_p()
+    info = ResultInfo()
+    check(lib.mx_multiply_csr_by_coo_begin(C.c_int(int(bool(logical))), ptr(p), ptr(xj), ptr(xv), ptr(yi), ptr(yj),
+                                           ptr(yv), C.c_int64(yi.size), C.c_int(int(max_row_X)),
+                                           C.c_int(int(max_col_X)), C.byref(res), C.byref(info)))
+    out = _finish(res, info, empty_values_dtype=vdt)
+    return dict(row=out["indptr"], col=out["indices"], val=out["values"].astype(vdt, copy=False))
+
+
+def multiply_csr_by_coo_elemwise(X_csr_indptr, X_csr_indices, X_csr_values, Y_coo_row, Y_coo_col, Y_coo_val,
+                                 max_row_X, max_col_X):
+    """src/operators.cpp:673-696: dict(row, col, val) of the kept COO entries, in Y's input order."""
+    return _csr_by_coo(False, X_csr_indptr, X_csr_indices, X_csr_values, Y_coo_row, Y_coo_col, Y_coo_val,
+                       max_row_X, max_col_X)
+
+
+def logicaland_csr_by_coo_elemwise(X_csr_indptr, X_csr_indices, X_csr_values, Y_coo_row, Y_coo_col, Y_coo_val,
+                                   max_row_X, max_col_X):
+    """src/operators.cpp:698-720: R logicals in and out."""
+    return _csr_by_coo(True, X_csr_indptr, X_csr_indices, X_csr_values, Y_coo_row, Y_coo_col, Y_coo_val,
+                       max_row_X, max_col_X)
+
+
+def multiply_coo_by_dense_ignore_NAs_numeric(ii, jj, xx, dvec, nrows, ncols, multiply, powerto, divide, divrest,
+                                             intdiv, X_is_LHS):
+    """src/operators.cpp:3363-3394: values-only `X op v` / `v op X` of a COO with R's recycling."""
+    i, j = _i32(ii), _i32(jj)
+    xv = np.ascontiguousarray(xx, dtype=np.float64)
+    dv = np.ascontiguousarray(dvec, dtype=np.float64).reshape(-1)
+    out = np.empty(xv.size, dtype=np.float64)
+    check(_lib.load().mx_multiply_coo_by_dense_ignore_NAs_numeric(
+        ptr(i), ptr(j), ptr(xv), C.c_int64(xv.size), ptr(dv), C.c_int64(dv.size), C.c_int(int(nrows)),
+        C.c_int(int(ncols)), C.c_int(bool(multiply)), C.c_int(bool(powerto)), C.c_int(bool(divide)),
+        C.c_int(bool(divrest)), C.c_int(bool(intdiv)), C.c_int(bool(X_is_LHS)), ptr(out)))
+    return out
+
+
+def multiply_coo_by_dense_ignore_NAs_logical(ii, jj, xx, dvec, nrows, ncols):
+    """src/operators.cpp:3396-3418: R logicals in, R logicals out (3-valued AND)."""
+    i, j = _i32(ii), _i32(jj)
+    xv = np.ascontiguousarray(xx, dtype=np.int32)
+    dv = np.ascontiguousarray(dvec, dtype=np.int32).reshape(-1)
+    out = np.empty(xv.size, dtype=np.int32)
+    check(_lib.load().mx_multiply_coo_by_dense_ignore_NAs_logical(
+        ptr(i), ptr(j), ptr(xv), C.c_int64(xv.size), ptr(dv), C.c_int64(dv.size), C.c_int(int(nrows)),
+        C.c_int(int(ncols)), ptr(out)))
+    return out

@@ -5,6 +5,7 @@ R is not available in this image, so the S4 objects the reference dispatches on
 
     dgRMatrix / lgRMatrix / ngRMatrix   @p int32[nrow+1], @j int32[nnz] (0-based), @x, @Dim, @Dimnames
     dgCMatrix                           @p int32[ncol+1], @i int32[nnz], @x
+    dgTMatrix / lgTMatrix / ngTMatrix   @i, @j int32[nnz] (0-based triplets, any order, duplicates allowed), @x
     float32                             @Data  (numpy float32, column-major)
 
 R logicals are int32 {0, 1, NA_LOGICAL}.  The classes hold data only; all
@@ -117,6 +118,8 @@ class RsparseMatrix:
 
     def __mul__(self, other):                         # R/operators.R:147 (CSR), :1217-1260 (vector)
         from . import operators
+        if isinstance(other, TsparseMatrix):          # R/operators.R:81-135, :169-180
+            return operators.multiply_csr_by_coo(self, other, logical=False)
         if not isinstance(other, (RsparseMatrix, dgCMatrix)):
             return operators.csr_op_vector(self, other, "*")
         return operators.multiply_csr_by_csr(self, other, logical=False)
@@ -127,6 +130,8 @@ class RsparseMatrix:
 
     def __and__(self, other):                         # R/operators.R:183 (CSR), :1163-1169 (vector)
         from . import operators
+        if isinstance(other, TsparseMatrix):          # :194-206
+            return operators.multiply_csr_by_coo(self, other, logical=True)
         if not isinstance(other, RsparseMatrix):
             return operators.csr_op_vector(self, other, "&")
         return operators.multiply_csr_by_csr(self, other, logical=True)
@@ -194,6 +199,174 @@ class ngRMatrix(RsparseMatrix):
     r_class = "ngRMatrix"
 
 
+class TsparseMatrix:
+    """COO (triplets), as Matrix's TsparseMatrix: @i / @j 0-based row / column ids in any order, duplicates allowed
+    (they add up).  Subclasses fix the value type.  Operators follow the reference's registrations for
+    TsparseMatrix (R/operators.R:81-135, 169-215, 790-930, 1385-1500)."""
+    value_dtype = None
+    r_class = "TsparseMatrix"
+    __array_ufunc__ = None
+
+    def __init__(self, i, j, x=None, Dim=None, Dimnames=None):
+        self.i = np.ascontiguousarray(i, dtype=np.int32)
+        self.j = np.ascontiguousarray(j, dtype=np.int32)
+        if self.value_dtype is None:
+            self.x = None
+        else:
+            self.x = np.ascontiguousarray(x if x is not None else np.zeros(0), dtype=self.value_dtype)
+        if Dim is None:
+            Dim = (int(self.i.max()) + 1 if self.i.size else 0, int(self.j.max()) + 1 if self.j.size else 0)
+        self.Dim = (int(Dim[0]), int(Dim[1]))
+        self.Dimnames = list(Dimnames) if Dimnames is not None else [None, None]
+
+    def nrow(self):
+        return self.Dim[0]
+
+    def ncol(self):
+        return self.Dim[1]
+
+    @property
+    def shape(self):
+        return self.Dim
+
+    def rownames(self):
+        return self.Dimnames[0]
+
+    def colnames(self):
+        return self.Dimnames[1]
+
+    def has_x(self):
+        return self.x is not None
+
+    def toarray(self):
+        """as.matrix(): dense float64 with repeated triplets combined as Matrix does (numeric: summed; logical:
+        R's `|`, NA -> nan; pattern: 1)."""
+        out = np.zeros(self.Dim, dtype=np.float64)
+        if self.x is None:
+            out[self.i, self.j] = 1.0
+        elif self.value_dtype == np.int32:
+            true, na = np.zeros(self.Dim, dtype=bool), np.zeros(self.Dim, dtype=bool)
+            np.logical_or.at(true, (self.i, self.j), (self.x != 0) & (self.x != NA_LOGICAL))
+            np.logical_or.at(na, (self.i, self.j), self.x == NA_LOGICAL)
+            out[na] = np.nan
+            out[true] = 1.0
+        else:
+            np.add.at(out, (self.i, self.j), self.x)
+        return out
+
+    def copy(self):
+        return type(self)(self.i.copy(), self.j.copy(), None if self.x is None else self.x.copy(), self.Dim,
+                          list(self.Dimnames))
+
+    def t(self):                                      # t_masked_coo -> t_shallow (R/trans.R:74-76)
+        return t_shallow(self)
+
+    # ---- operator wiring
+    def __add__(self, other):                         # sparseMatrix + RsparseMatrix, R/operators.R:808-811
+        from . import operators
+        if isinstance(other, RsparseMatrix):
+            return operators.add_csr_matrices(other, self, False)
+        if isinstance(other, dgCMatrix):              # TsparseMatrix + CsparseMatrix, :832-835
+            return t_shallow(operators.add_csr_matrices(t_shallow(other), t_shallow(self), False))
+        return NotImplemented
+
+    def __sub__(self, other):                         # sparseMatrix - RsparseMatrix, :857-860
+        from . import operators
+        if isinstance(other, RsparseMatrix):
+            return operators.add_csr_matrices(self, other, True)
+        if isinstance(other, dgCMatrix):
+            # (the reference's TsparseMatrix - CsparseMatrix method, :884-888, passes its operands swapped and so
+            # returns e2 - e1; the difference here is e1 - e2 like every other `-`)
+            return t_shallow(operators.add_csr_matrices(t_shallow(self), t_shallow(other), True))
+        return NotImplemented
+
+    def __mul__(self, other):                         # :169-180 (CSR), :1388-1402 (vector)
+        from . import operators
+        if isinstance(other, RsparseMatrix):
+            return operators.multiply_csr_by_coo(other, self, logical=False)
+        if isinstance(other, dgCMatrix):              # :189-192
+            return t_shallow(operators.multiply_csr_by_coo(t_shallow(other), t_shallow(self), logical=False))
+        if isinstance(other, TsparseMatrix):
+            return NotImplemented
+        return operators.csr_op_vector(self, other, "*")
+
+    def __rmul__(self, other):
+        from . import operators
+        return operators.csr_op_vector(self, other, "*")
+
+    def __and__(self, other):                         # :194-215 (CSR), :1405-1430 (vector)
+        from . import operators
+        if isinstance(other, RsparseMatrix):
+            return operators.multiply_csr_by_coo(other, self, logical=True)
+        if isinstance(other, dgCMatrix):
+            return t_shallow(operators.multiply_csr_by_coo(t_shallow(other), t_shallow(self), logical=True))
+        if isinstance(other, TsparseMatrix):
+            return NotImplemented
+        return operators.csr_op_vector(self, other, "&")
+
+    def __rand__(self, other):
+        from . import operators
+        return operators.csr_op_vector(self, other, "&")
+
+    def __or__(self, other):                          # sparseMatrix | RsparseMatrix, :903-906
+        from . import operators
+        if isinstance(other, RsparseMatrix):
+            return operators.logicalor_csr_matrices(self, other)
+        if isinstance(other, dgCMatrix):              # :913-924: the result would be an lgCMatrix
+            stop("TsparseMatrix | CsparseMatrix would give an lgCMatrix, which this package does not provide.")
+        return NotImplemented
+
+    def __truediv__(self, other):
+        from . import operators
+        return operators.csr_op_vector(self, other, "/")
+
+    def __rtruediv__(self, other):
+        from . import operators
+        return operators.csr_op_vector(self, other, "/", X_is_LHS=False)
+
+    def __pow__(self, other):
+        from . import operators
+        return operators.csr_op_vector(self, other, "^")
+
+    def __rpow__(self, other):
+        from . import operators
+        return operators.csr_op_vector(self, other, "^", X_is_LHS=False)
+
+    def __mod__(self, other):
+        from . import operators
+        return operators.csr_op_vector(self, other, "%%")
+
+    def __rmod__(self, other):
+        from . import operators
+        return operators.csr_op_vector(self, other, "%%", X_is_LHS=False)
+
+    def __floordiv__(self, other):
+        from . import operators
+        return operators.csr_op_vector(self, other, "%/%")
+
+    def __rfloordiv__(self, other):
+        from . import operators
+        return operators.csr_op_vector(self, other, "%/%", X_is_LHS=False)
+
+    def __repr__(self):
+        return f"<{self.r_class} {self.Dim[0]}x{self.Dim[1]}, {self.i.size} entries>"
+
+
+class dgTMatrix(TsparseMatrix):
+    value_dtype = np.float64
+    r_class = "dgTMatrix"
+
+
+class lgTMatrix(TsparseMatrix):
+    value_dtype = np.int32
+    r_class = "lgTMatrix"
+
+
+class ngTMatrix(TsparseMatrix):
+    value_dtype = None
+    r_class = "ngTMatrix"
+
+
 class dgCMatrix:
     """Compressed sparse column, numeric: `matrix %*% CsparseMatrix`, t(), and +, -, * with an RsparseMatrix."""
     r_class = "dgCMatrix"
@@ -227,23 +400,36 @@ class dgCMatrix:
 
     # sparseMatrix (op) RsparseMatrix, R/operators.R:147-179, :810-870: the CSC side goes through as.csr.matrix and
     # the result is a dgRMatrix
+    # CsparseMatrix (op) TsparseMatrix goes through t_shallow, R/operators.R:183-186, :826-829, :877-880
     def __add__(self, other):
         from . import operators
+        if isinstance(other, TsparseMatrix):
+            return t_shallow(operators.add_csr_matrices(t_shallow(self), t_shallow(other), False))
         if not isinstance(other, RsparseMatrix):
             return NotImplemented
         return operators.add_csr_matrices(self, other, False)
 
     def __sub__(self, other):
         from . import operators
+        if isinstance(other, TsparseMatrix):
+            return t_shallow(operators.add_csr_matrices(t_shallow(self), t_shallow(other), True))
         if not isinstance(other, RsparseMatrix):
             return NotImplemented
         return operators.add_csr_matrices(self, other, True)
 
     def __mul__(self, other):
         from . import operators
+        if isinstance(other, TsparseMatrix):
+            return t_shallow(operators.multiply_csr_by_coo(t_shallow(self), t_shallow(other), logical=False))
         if not isinstance(other, RsparseMatrix):
             return NotImplemented
         return operators.multiply_csr_by_csr(self, other, logical=False)
+
+    def __and__(self, other):                         # :208-211
+        from . import operators
+        if isinstance(other, TsparseMatrix):
+            return t_shallow(operators.multiply_csr_by_coo(t_shallow(self), t_shallow(other), logical=True))
+        return NotImplemented
 
 
 class float32:
@@ -302,11 +488,16 @@ def from_scipy(A, logical=False, binary=False):
 def as_csr_matrix(x, logical=False, binary=False):
     """as.csr.matrix (R/conversions.R:180-295), reduced to the classes that exist here:
     dgRMatrix passes through; lgRMatrix/ngRMatrix are expanded to numeric (or kept/converted
-    to logical when `logical=TRUE`); a dgCMatrix goes through the device transpose; scipy matrices and dense
+    to logical when `logical=TRUE`); a dgCMatrix goes through the device transpose, a d/l/n TsparseMatrix through
+    the device COO sort (repeated triplets merged before the value type changes); scipy matrices and dense
     arrays are converted."""
     if isinstance(x, dgCMatrix):
         check_valid_matrix(x)
         x = _csc_to_csr(x, binary=binary)
+    if isinstance(x, TsparseMatrix):
+        # Matrix coerces T -> R first (merging repeated triplets in the triplets' own type), then the value type
+        check_valid_matrix(x)
+        x = _coo_to_compressed(x, binary=binary)
     if isinstance(x, RsparseMatrix):
         if binary:
             return x if isinstance(x, ngRMatrix) else ngRMatrix(x.p, x.j, None, x.Dim, x.Dimnames)
@@ -340,12 +531,78 @@ def _csc_to_csr(x, binary=False):
     return dgRMatrix(res["indptr"], res["indices"], res["values"], x.Dim, x.Dimnames)
 
 
+def _coo_to_compressed(x, binary=False, csc=False):
+    """CSR (csc=True: the CSC arrays, returned as the CSR of x^T) of a TsparseMatrix through the device COO sort,
+    in the triplets' own value type."""
+    from . import exports
+    vals = None if binary else x.x
+    if csc:
+        res = exports.coo_to_csr(x.j, x.i, vals, x.Dim[1], x.Dim[0])
+        Dim, Dimnames = (x.Dim[1], x.Dim[0]), list(reversed(dimnames_of(x)))
+    else:
+        res = exports.coo_to_csr(x.i, x.j, vals, x.Dim[0], x.Dim[1])
+        Dim, Dimnames = x.Dim, list(dimnames_of(x))
+    if vals is None:
+        return ngRMatrix(res["indptr"], res["indices"], None, Dim, Dimnames)
+    cls = lgRMatrix if x.value_dtype == np.int32 else dgRMatrix
+    return cls(res["indptr"], res["indices"], res["values"], Dim, Dimnames)
+
+
+def as_coo_matrix(x, binary=False, logical=False):
+    """as.coo.matrix (R/conversions.R:515-590): a TsparseMatrix of the requested kind passes through; another
+    TsparseMatrix changes its value type entry by entry (no merging, as the reference relabels the slots); a CSR or
+    CSC gains the expanded index vector from the device (storage order: row-major for a CSR, column-major for a
+    CSC); dense and scipy inputs go through as_csr_matrix first."""
+    from . import exports
+    if binary and logical:
+        stop("Can pass only one of 'binary' or 'logical'.")
+    if ((type(x) is dgTMatrix and not binary and not logical) or (type(x) is ngTMatrix and binary)
+            or (type(x) is lgTMatrix and logical)):
+        return x
+    if isinstance(x, TsparseMatrix):
+        i, j, xv, Dim, Dimnames = x.i, x.j, x.x, x.Dim, list(dimnames_of(x))
+        kind = x.value_dtype
+    else:
+        if isinstance(x, dgCMatrix):
+            check_valid_matrix(x)
+            i, j, xv = x.i, exports.csr_to_coo(x.p), x.x
+        else:
+            if not isinstance(x, RsparseMatrix):
+                x = as_csr_matrix(x)
+            check_valid_matrix(x)
+            i, j, xv = exports.csr_to_coo(x.p), x.j, x.x
+        Dim, Dimnames = x.Dim, list(dimnames_of(x))
+        kind = None if xv is None else xv.dtype.type
+    if binary:
+        return ngTMatrix(i, j, None, Dim, Dimnames)
+    if logical:
+        if xv is None:
+            lv = np.ones(i.size, dtype=np.int32)
+        elif kind == np.int32:
+            lv = xv
+        else:
+            lv = np.where(np.isnan(xv), NA_LOGICAL, (xv != 0).astype(np.int32)).astype(np.int32)
+        return lgTMatrix(i, j, lv, Dim, Dimnames)
+    if xv is None:
+        dv = np.ones(i.size)
+    elif kind == np.int32:
+        dv = np.where(xv == NA_LOGICAL, NA_REAL, xv.astype(np.float64))
+    else:
+        dv = xv
+    return dgTMatrix(i, j, dv, Dim, Dimnames)
+
+
 def as_csc_matrix(x):
     """as.csc.matrix (R/conversions.R) -> dgCMatrix.  Values become f64 by as_csr_matrix's rules (NA_LOGICAL ->
-    NA_real_, pattern -> 1.0); the CSR -> CSC step is the device transpose."""
+    NA_real_, pattern -> 1.0); the CSR -> CSC step is the device transpose, and a TsparseMatrix is sorted into
+    CSC order on the device directly (repeated triplets merged before the value type changes)."""
     from . import exports
     if isinstance(x, dgCMatrix):
         return x
+    if isinstance(x, TsparseMatrix):
+        check_valid_matrix(x)
+        T = as_csr_matrix(_coo_to_compressed(x, csc=True))            # CSR of x^T in f64 = the CSC of x
+        return dgCMatrix(T.p, T.j, T.x, x.Dim, list(dimnames_of(x)))
     x = as_csr_matrix(x)
     check_valid_matrix(x)
     res = exports.csr_transpose(x.p, x.j, x.x, x.Dim[1])
@@ -358,10 +615,13 @@ _SHALLOW = {"dgRMatrix": "dgCMatrix", "dgCMatrix": "dgRMatrix", "lgRMatrix": "lg
 def t_shallow(x):
     """t_shallow (R/trans.R:1-30, :128-150): relabels CSR as the CSC of the transpose (and back) without copying:
     the result shares x's `p` and index arrays; Dim and Dimnames are swapped.  Only dgRMatrix <-> dgCMatrix exist
-    here."""
+    here.  A TsparseMatrix stays one, with its `i` and `j` arrays swapped."""
     Dim = (x.Dim[1], x.Dim[0])
     Dimnames = list(reversed(dimnames_of(x)))
-    if type(x) is dgRMatrix:
+    if isinstance(x, TsparseMatrix):                  # t_coo_to_coo (R/trans.R:74-76): i and j swap roles
+        out = type(x).__new__(type(x))
+        out.i, out.j, out.x = x.j, x.i, x.x
+    elif type(x) is dgRMatrix:
         out = dgCMatrix.__new__(dgCMatrix)
         out.p, out.i, out.x = x.p, x.j, x.x
     elif type(x) is dgCMatrix:
@@ -398,7 +658,7 @@ def _t_masked(x):
 
 
 def check_valid_matrix(X):
-    """R/utils.R:349-410, RsparseMatrix / CsparseMatrix branches."""
+    """R/utils.R:349-410, TsparseMatrix / RsparseMatrix / CsparseMatrix branches."""
     nrows, ncols = X.Dim
     if nrows < 0:
         stop("Matrix has invalid number of rows.")
@@ -409,6 +669,12 @@ def check_valid_matrix(X):
         stop("Row names of matrix do not match with number of rows.")
     if dn[1] is not None and len(dn[1]) and len(dn[1]) != ncols:
         stop("Column names of matrix do not match with number of columns.")
+    if isinstance(X, TsparseMatrix):
+        if X.i.size != X.j.size:
+            stop("Matrix is invalid (row and column indices have different length).")
+        if X.x is not None and X.x.size != X.i.size:
+            stop("Matrix is invalid (values and indices have different number of entries).")
+        return
     if isinstance(X, RsparseMatrix):
         idx, dim = X.j, nrows
     elif isinstance(X, dgCMatrix):

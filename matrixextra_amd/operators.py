@@ -1,6 +1,7 @@
 """Host-side mirror of the CSR (+) CSR part of R/operators.R
-(multiply_csr_by_csr :43-79, add_csr_matrices_internal :713-776 and their registrations) and of
-`CSR op vector` (multiply_csr_by_dvec_elemwise_internal :950-1153)."""
+(multiply_csr_by_csr :43-79, add_csr_matrices_internal :713-776 and their registrations), of CSR (.) COO
+(multiply_csr_by_coo :81-110) and of `CSR op vector` / `COO op vector` (multiply_csr_by_dvec_elemwise_internal
+:950-1153)."""
 from __future__ import annotations
 
 import warnings
@@ -8,8 +9,8 @@ import warnings
 import numpy as np
 
 from . import exports
-from .matrices import (RsparseMatrix, as_csr_matrix, check_valid_matrix, dgRMatrix, lgRMatrix, ngRMatrix,
-                       options, sort_sparse_indices, stop)
+from .matrices import (RsparseMatrix, TsparseMatrix, as_coo_matrix, as_csr_matrix, check_valid_matrix, dgRMatrix,
+                       dgTMatrix, lgRMatrix, lgTMatrix, ngRMatrix, options, sort_sparse_indices, stop)
 
 
 def _is_same_ngRMatrix(e1, e2):
@@ -57,6 +58,20 @@ def multiply_csr_by_csr(e1, e2, logical=False):
         return _assemble(dgRMatrix, e1, res)
     res = exports.logicaland_csr_elemwise(e1.p, e2.p, e1.j, e2.j, e1.x, e2.x)
     return _assemble(lgRMatrix, e1, res)
+
+
+def multiply_csr_by_coo(e1, e2, logical=False):
+    """R/operators.R:81-110: CSR `e1` times (or AND) COO `e2`, one output triplet per kept COO entry, in e2's
+    order; Dim is the elementwise max of the two, no Dimnames."""
+    if e1.Dim[0] != e2.Dim[0] or e1.Dim[1] != e2.Dim[1]:
+        warnings.warn("Matrices to multiply have different dimensions.")
+    e1 = _prepare(e1, logical)
+    e2 = as_coo_matrix(e2, logical=logical)
+    check_valid_matrix(e2)
+    fn = exports.logicaland_csr_by_coo_elemwise if logical else exports.multiply_csr_by_coo_elemwise
+    res = fn(e1.p, e1.j, e1.x, e2.i, e2.j, e2.x, e1.Dim[0], e1.Dim[1])
+    cls = lgTMatrix if logical else dgTMatrix
+    return cls(res["row"], res["col"], res["val"], (max(e1.Dim[0], e2.Dim[0]), max(e1.Dim[1], e2.Dim[1])))
 
 
 def add_csr_matrices_internal(e1, e2, is_substraction=False, is_ampersand=False, is_xor=False):
@@ -112,7 +127,7 @@ def _as_logical(v):
 
 
 def multiply_csr_by_dvec_elemwise_internal(e1, e2, logical=False, X_is_LHS=True, op="*"):
-    """R/operators.R:950-1153 for RsparseMatrix `e1`: `e1 op e2` (or `e2 op e1` when X_is_LHS is false) with a dense
+    """R/operators.R:950-1153 for RsparseMatrix or TsparseMatrix `e1`: `e1 op e2` (or `e2 op e1` when X_is_LHS is false) with a dense
     vector (or a same-shape dense matrix read as a vector), R's recycling, values-only result.  The routes the
     reference sends through multiply_csr_by_dvec_with_NAs or through a CsparseMatrix (vector with NA, division by
     zero, multiplication by Inf, `v op X` for ^ / %% %/% while NAs are kept) raise: they stay on the CPU."""
@@ -139,15 +154,23 @@ def multiply_csr_by_dvec_elemwise_internal(e1, e2, logical=False, X_is_LHS=True,
     if take_route_NAs:
         stop(_NOT_ACCELERATED % "981-1131")
     e2 = _as_logical(e2) if logical else e2f
-    e1 = as_csr_matrix(e1, logical=logical)                                   # :1020-1029
+    is_coo = isinstance(e1, TsparseMatrix)                                    # :990
+    e1 = as_coo_matrix(e1, logical=logical) if is_coo else as_csr_matrix(e1, logical=logical)   # :1020-1029
     out = type(e1).__new__(type(e1))
-    out.p, out.j, out.Dim, out.Dimnames = e1.p, e1.j, e1.Dim, list(e1.Dimnames)
+    if is_coo:
+        out.i, out.j = e1.i, e1.j
+    else:
+        out.p, out.j = e1.p, e1.j
+    out.Dim, out.Dimnames = e1.Dim, list(e1.Dimnames)
     if e2.size == 1:                                                          # :1031-1108
         if logical:
             if e2[0] == np.int32(-2147483648):
                 out.x = np.where(e1.x == np.int32(-2147483648), np.int32(-2147483648), np.int32(0)).astype(np.int32)
                 return out
             if e2[0] == 0:
+                if is_coo:
+                    return lgTMatrix(np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32),
+                                     np.zeros(0, dtype=np.int32), e1.Dim, e1.Dimnames)
                 res = lgRMatrix(np.zeros(e1.Dim[0] + 1, dtype=np.int32), np.zeros(0, dtype=np.int32),
                                 np.zeros(0, dtype=np.int32), e1.Dim, e1.Dimnames)
                 return res
@@ -158,7 +181,14 @@ def multiply_csr_by_dvec_elemwise_internal(e1, e2, logical=False, X_is_LHS=True,
             stop(_NOT_ACCELERATED % "1091-1095")
     elif e1.Dim[0] % e2.size != 0:                                            # :1114-1115
         warnings.warn("Number of elements in vector is not a multiple of matrix dimension.")
-    if logical:
+    if is_coo:                                                                # :1139-1150
+        if logical:
+            out.x = exports.multiply_coo_by_dense_ignore_NAs_logical(e1.i, e1.j, e1.x, e2, e1.Dim[0], e1.Dim[1])
+        else:
+            out.x = exports.multiply_coo_by_dense_ignore_NAs_numeric(e1.i, e1.j, e1.x, e2, e1.Dim[0], e1.Dim[1],
+                                                                     op == "*", op == "^", op == "/", op == "%%",
+                                                                     op == "%/%", X_is_LHS)
+    elif logical:
         out.x = exports.logicaland_csr_by_dvec_internal(e1.p, e1.j, e1.x, e2, e1.Dim[1])
     else:
         out.x = exports.multiply_csr_by_dvec_no_NAs_numeric(e1.p, e1.j, e1.x, e2, e1.Dim[1], op == "*", op == "^",
