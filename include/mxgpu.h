@@ -324,6 +324,41 @@ int mxd_csr_by_coo_fill(int logical, int m, int ncol, const int32_t *indptr, con
  * arithmetic as mxd_csr_by_dvec. */
 int mxd_coo_by_dvec(int m, int ncols, int64_t nnz, const int32_t *rows, const int32_t *cols, const void *values,
                     const void *dvec, int64_t dvec_len, int op, int x_is_lhs, void *values_out, void *stream);
+/* X[i, j] of a COO (cooslice.hip), replacing slice_coo_arbitrary_template (src/slice_coo.cpp:123-706).  Each
+ * axis is described by an mx_coo_axis:
+ *   MX_AXIS_AFFINE  all / seq / rev-seq selector: index r in [lo, hi] has the one position r - lo (reversed = 0)
+ *                   or hi - r (reversed = 1); other indices are not selected.  0 <= lo <= hi < the axis length.
+ *   MX_AXIS_MAP     arbitrary selector, through the dense map that mxd_colmap_build makes of the 1-based
+ *                   selector (ncol_map = nmap = max + 1): index r's positions are pos[start[r+1] .. start[r+2]),
+ *                   ascending; r + 1 >= nmap is not selected.
+ * Triplet k = (rows[k], cols[k], values[k]) gives one output (a, b, values[k]) for every position a of rows[k]
+ * (outer loop, ascending) and every position b of cols[k] (inner loop, ascending), triplets in storage order;
+ * values are copied bit for bit and keep their type (MX_F64 / MX_LGL / MX_NONE); nothing is merged.
+ * count: one lane per triplet, multiplicities in 64 bits; the total (one host read-back into *nnz_out_host) and any
+ * single triplet above INT32_MAX fail the call, as does a row outside [0, nrow) or a column outside [0, ncol),
+ * which is never used to read a map.  fill writes out_rows / out_cols / out_values (that many entries).
+ * workspace: mxd_coo_slice_workspace_bytes(nnz), shared by both passes. */
+typedef enum { MX_AXIS_AFFINE = 0, MX_AXIS_MAP = 1 } mx_coo_axis_kind;
+typedef struct {
+    int kind;                  /* mx_coo_axis_kind */
+    int lo, hi, reversed;      /* MX_AXIS_AFFINE */
+    int nmap;                  /* MX_AXIS_MAP: start has nmap + 1 entries */
+    const int32_t *start;      /* device pointers */
+    const int32_t *pos;
+} mx_coo_axis;
+size_t mxd_coo_slice_workspace_bytes(int64_t nnz);
+int mxd_coo_slice_count(int nrow, int ncol, const int32_t *rows, const int32_t *cols, int64_t nnz,
+                        const mx_coo_axis *axis_i, const mx_coo_axis *axis_j, void *workspace,
+                        int64_t *nnz_out_host, void *stream);
+int mxd_coo_slice_fill(int nrow, int ncol, const int32_t *rows, const int32_t *cols, const void *values,
+                       int value_dtype, int64_t nnz, const mx_coo_axis *axis_i, const mx_coo_axis *axis_j,
+                       const void *workspace, int32_t *out_rows, int32_t *out_cols, void *out_values, void *stream);
+/* X[i, j] with scalar i, j of a COO (slice_coo_single_template, src/slice_coo.cpp:3-71): *k_host = the smallest k
+ * with (rows[k], cols[k]) == (r, c), or -1; on a hit value_host (when non-null) receives values[k] (8 bytes for
+ * MX_F64, 4 for MX_LGL, nothing for MX_NONE).  One host read-back.  workspace: mxd_coo_single_workspace_bytes(). */
+size_t mxd_coo_single_workspace_bytes(void);
+int mxd_coo_single(const int32_t *rows, const int32_t *cols, const void *values, int value_dtype, int64_t nnz,
+                   int r, int c, void *workspace, int64_t *k_host, void *value_host, void *stream);
 
 /* ========================================================================== */
 /* (1) export level — host pointers, names follow the Rcpp exports            */
@@ -496,6 +531,22 @@ int mx_multiply_coo_by_dense_ignore_NAs_numeric(const int32_t *ii, const int32_t
 int mx_multiply_coo_by_dense_ignore_NAs_logical(const int32_t *ii, const int32_t *jj, const int32_t *xx, int64_t nnz,
                                                 const int32_t *dvec, int64_t dvec_len, int nrows, int ncols,
                                                 int32_t *values_out);
+/* slice_coo_arbitrary_{numeric,logical,binary}  src/slice_coo.cpp:123-706 (RcppExports.cpp:2103-2167), through
+ * mxd_coo_slice_count / _fill: ii / jj / xx hold nnz 0-based triplets (value_dtype MX_F64 / MX_LGL / MX_NONE);
+ * rows_take_base1 / cols_take_base1 are the 1-based selectors and the six flags are get_ij_properties' (R/slice.R:
+ * 59-143).  The result is a COO held in the mx_result, as for mx_multiply_csr_by_coo_begin: the indptr vector
+ * holds the row ids (info.indptr_len = info.nnz), indices the column ids, values the values.  An empty selector
+ * or nnz = 0 gives an empty result. */
+int mx_slice_coo_arbitrary_begin(const int32_t *ii, const int32_t *jj, const void *xx, int value_dtype,
+                                 int64_t nnz, const int32_t *rows_take_base1, int64_t n_rows_take,
+                                 const int32_t *cols_take_base1, int64_t n_cols_take, int all_i, int all_j,
+                                 int i_is_seq, int j_is_seq, int i_is_rev_seq, int j_is_rev_seq, int nrows,
+                                 int ncols, mx_result **res, mx_result_info *info);
+/* slice_coo_single_{numeric,logical,binary}  src/slice_coo.cpp:3-71 (RcppExports.cpp:2061-2101): i, j 0-based;
+ * *found = 1 when some triplet matches, and value_out (when non-null; f64 for MX_F64, int32 for MX_LGL) receives
+ * the value of the first one in storage order. */
+int mx_slice_coo_single(const int32_t *ii, const int32_t *jj, const void *xx, int value_dtype, int64_t nnz, int i,
+                        int j, int *found, void *value_out);
 int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, void *out_values);
 int mx_result_discard(mx_result *res);
 

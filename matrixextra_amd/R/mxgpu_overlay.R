@@ -38,7 +38,10 @@
     "multiply_csr_by_dvec_no_NAs_numeric", "logicaland_csr_by_dvec_internal",
     ## COO (TsparseMatrix) operands
     "multiply_csr_by_coo_elemwise", "logicaland_csr_by_coo_elemwise",
-    "multiply_coo_by_dense_ignore_NAs_numeric", "multiply_coo_by_dense_ignore_NAs_logical"
+    "multiply_coo_by_dense_ignore_NAs_numeric", "multiply_coo_by_dense_ignore_NAs_logical",
+    ## COO slicing, X[i, j] of a TsparseMatrix (subset_coo, R/slice_coo.R)
+    "slice_coo_single_numeric", "slice_coo_single_logical", "slice_coo_single_binary",
+    "slice_coo_arbitrary_numeric", "slice_coo_arbitrary_logical", "slice_coo_arbitrary_binary"
 )
 
 mxgpu_enable <- function(shim_path, min_nnz = 0L) {

@@ -19,6 +19,6 @@ from .matrices import TsparseMatrix, as_coo_matrix, dgTMatrix, lgTMatrix, ngTMat
 from .matmul import RLogical, crossprod, tcrossprod  # noqa: F401  (`%*%` is the @ operator)
 from .operators import (add_csr_matrices, logicalor_csr_matrices, multiply_csr_by_coo,  # noqa: F401
                         multiply_csr_by_csr, xor_csr_matrices)
-from .slice import subset_csr  # noqa: F401
+from .slice import subset_coo, subset_csr  # noqa: F401
 
 __version__ = "0.1.0"

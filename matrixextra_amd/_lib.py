@@ -70,6 +70,10 @@ def load() -> C.CDLL:
     lib.mxd_coo_to_csr_workspace_bytes.argtypes = [C.c_int64, C.c_int]
     lib.mxd_csr_by_coo_workspace_bytes.restype = C.c_size_t
     lib.mxd_csr_by_coo_workspace_bytes.argtypes = [C.c_int64]
+    lib.mxd_coo_slice_workspace_bytes.restype = C.c_size_t
+    lib.mxd_coo_slice_workspace_bytes.argtypes = [C.c_int64]
+    lib.mxd_coo_single_workspace_bytes.restype = C.c_size_t
+    lib.mxd_coo_single_workspace_bytes.argtypes = []
     if lib.mx_abi_version() != 1:
         raise MxError("libmxgpu.so ABI version mismatch")
     _lib = lib

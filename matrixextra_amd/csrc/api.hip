@@ -827,6 +827,116 @@ int mx_multiply_coo_by_dense_ignore_NAs_logical(const int32_t *ii, const int32_t
     return coo_by_dvec_export(ii, jj, xx, nnz, dvec, dvec_len, nrows, ncols, MX_DV_LOGICAL_AND, 1, values_out);
 }
 
+// ---- X[i, j] of a COO: slice_coo_arbitrary_* / slice_coo_single_* (src/slice_coo.cpp) ----
+// One axis of a slice from get_ij_properties' flags (R/slice.R:59-143): all / seq / rev-seq are affine
+// (process_i_arbitrary, src/slice_coo.cpp:73-114, and post_process_seq, :120-150); anything else becomes the dense
+// map of the 1-based selector (the reference's robin_map + i_indices_rep), in mxd_colmap_build's layout.
+static int coo_axis_setup(const int32_t *take_base1, int64_t n_take, int all, int is_seq, int is_rev_seq, int n,
+                          const char *what, mx_coo_axis *ax, DevBuf &start, DevBuf &pos)
+{
+    *ax = mx_coo_axis{MX_AXIS_AFFINE, 0, n - 1, 0, 0, nullptr, nullptr};
+    if (all) return 0;
+    const int first = take_base1[0] - 1, last = take_base1[n_take - 1] - 1;
+    if (is_seq || is_rev_seq) {
+        MX_REQUIRE(first >= 0 && first < n && last >= 0 && last < n, "slice of a COO: %s index outside [1, %d]", what,
+                   n);
+        MX_REQUIRE(is_seq ? first <= last : first >= last, "slice of a COO: %s selector is not a %s sequence", what,
+                   is_seq ? "ascending" : "descending");
+        ax->lo = is_seq ? first : last;
+        ax->hi = is_seq ? last : first;
+        ax->reversed = is_seq ? 0 : 1;
+        return 0;
+    }
+    int max_v = 0;
+    for (int64_t t = 0; t < n_take; t++) {
+        MX_REQUIRE(take_base1[t] >= 1 && take_base1[t] <= n, "slice of a COO: %s index outside [1, %d]", what, n);
+        if (take_base1[t] > max_v) max_v = take_base1[t];
+    }
+    const int nmap = max_v + 1;
+    // mxd_colmap_build's layout, made here by a stable counting sort while the selector is checked anyway: its
+    // device build orders repeated positions by an insertion sort in one lane per index, which is quadratic in the
+    // repeats of one index (minutes for 50 000 repeats)
+    std::unique_ptr<int32_t[]> h_start(new (std::nothrow) int32_t[(size_t)nmap + 1]);
+    std::unique_ptr<int32_t[]> h_pos(new (std::nothrow) int32_t[(size_t)n_take]);
+    MX_REQUIRE(h_start && h_pos, "out of host memory");
+    memset(h_start.get(), 0, sizeof(int32_t) * ((size_t)nmap + 1));
+    for (int64_t t = 0; t < n_take; t++) h_start[take_base1[t] + 1]++;  // key v counted at v + 1 <= nmap
+    for (int v = 1; v <= nmap; v++) h_start[v] += h_start[v - 1];            // start[v] = entries with key < v
+    for (int64_t t = 0; t < n_take; t++) h_pos[h_start[take_base1[t]]++] = (int32_t)t;
+    for (int v = nmap; v > 0; v--) h_start[v] = h_start[v - 1];             // undo the cursor shift
+    h_start[0] = 0;
+    if (start.upload(h_start.get(), sizeof(int32_t) * ((size_t)nmap + 1))) return 1;
+    if (pos.upload(h_pos.get(), sizeof(int32_t) * (size_t)n_take)) return 1;
+    *ax = mx_coo_axis{MX_AXIS_MAP, 0, 0, 0, nmap, start.as<int32_t>(), pos.as<int32_t>()};
+    return 0;
+}
+
+int mx_slice_coo_arbitrary_begin(const int32_t *ii, const int32_t *jj, const void *xx, int value_dtype,
+                                 int64_t nnz, const int32_t *rows_take_base1, int64_t n_rows_take,
+                                 const int32_t *cols_take_base1, int64_t n_cols_take, int all_i, int all_j,
+                                 int i_is_seq, int j_is_seq, int i_is_rev_seq, int j_is_rev_seq, int nrows,
+                                 int ncols, mx_result **res_out, mx_result_info *info)
+{
+    MX_REQUIRE(res_out && info, "mx_slice_coo_arbitrary_begin: null output pointer");
+    MX_REQUIRE(nrows >= 0 && ncols >= 0 && nnz >= 0 && n_rows_take >= 0 && n_cols_take >= 0,
+               "mx_slice_coo_arbitrary_begin: negative size");
+    MX_REQUIRE(nnz <= INT_MAX, "mx_slice_coo_arbitrary_begin: %lld entries exceed R's int32 index range",
+               (long long)nnz);
+    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
+               "mx_slice_coo_arbitrary_begin: unsupported value dtype %d", value_dtype);
+    MX_REQUIRE((nnz == 0 || (ii && jj && (value_dtype == MX_NONE || xx))) && (n_rows_take == 0 || rows_take_base1) &&
+               (n_cols_take == 0 || cols_take_base1), "mx_slice_coo_arbitrary_begin: null pointer");
+    *res_out = nullptr;
+    const bool has_values = value_dtype != MX_NONE;
+    const size_t vb = dtype_bytes(value_dtype);
+    return begin_result(res_out, info, value_dtype, [&](mx_result &res) {
+        // the reference reads rows_take_base1[0] unguarded; the R caller never passes an empty selector (:108-125)
+        if (nnz == 0 || n_rows_take == 0 || n_cols_take == 0) { res.set_sizes(0, 0, 0); return 0; }
+        DevBuf sti, psi, stj, psj;
+        mx_coo_axis ai, aj;
+        if (coo_axis_setup(rows_take_base1, n_rows_take, all_i, i_is_seq, i_is_rev_seq, nrows, "row", &ai, sti, psi))
+            return 1;
+        if (coo_axis_setup(cols_take_base1, n_cols_take, all_j, j_is_seq, j_is_rev_seq, ncols, "column", &aj, stj,
+                           psj)) return 1;
+        DevBuf r, c, x, ws;
+        if (r.upload(ii, sizeof(int32_t) * (size_t)nnz)) return 1;
+        if (c.upload(jj, sizeof(int32_t) * (size_t)nnz)) return 1;
+        if (has_values && x.upload(xx, vb * (size_t)nnz)) return 1;
+        if (ws.alloc(mxd_coo_slice_workspace_bytes(nnz))) return 1;
+        int64_t nnz_out = 0;
+        if (mxd_coo_slice_count(nrows, ncols, r.as<int32_t>(), c.as<int32_t>(), nnz, &ai, &aj, ws.p, &nnz_out,
+                                nullptr)) return 1;
+        res.set_sizes(nnz_out, nnz_out, has_values ? nnz_out : 0);     // row ids travel in the indptr vector
+        if (res.indptr.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
+        if (has_values && res.values.alloc(vb * (size_t)nnz_out)) return 1;
+        if (nnz_out == 0) return 0;
+        return mxd_coo_slice_fill(nrows, ncols, r.as<int32_t>(), c.as<int32_t>(), x.p, value_dtype, nnz, &ai, &aj,
+                                  ws.p, res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.p, nullptr);
+    });
+}
+
+int mx_slice_coo_single(const int32_t *ii, const int32_t *jj, const void *xx, int value_dtype, int64_t nnz, int i,
+                        int j, int *found, void *value_out)
+{
+    MX_REQUIRE(found && nnz >= 0, "mx_slice_coo_single: bad arguments");
+    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
+               "mx_slice_coo_single: unsupported value dtype %d", value_dtype);
+    *found = 0;
+    if (nnz == 0) return 0;
+    MX_REQUIRE(ii && jj && (value_dtype == MX_NONE || xx), "mx_slice_coo_single: null pointer");
+    DevBuf r, c, x, ws;
+    if (r.upload(ii, sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (c.upload(jj, sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (value_dtype != MX_NONE && x.upload(xx, dtype_bytes(value_dtype) * (size_t)nnz)) return 1;
+    if (ws.alloc(mxd_coo_single_workspace_bytes())) return 1;
+    int64_t k = -1;
+    if (mxd_coo_single(r.as<int32_t>(), c.as<int32_t>(), x.p, value_dtype, nnz, i, j, ws.p, &k, value_out, nullptr))
+        return 1;
+    *found = k >= 0;
+    return 0;
+}
+
 int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, void *out_values)
 {
     MX_REQUIRE(res, "mx_result_finish: null handle");

@@ -493,6 +493,77 @@ SEXP _MatrixExtra_multiply_coo_by_dense_ignore_NAs_logical(SEXP ii, SEXP jj, SEX
     return out;
 }
 
+// X[i, j] of a COO  (src/slice_coo.cpp:3-706; glue src/RcppExports.cpp:2061-2167): the single-element routines
+// take 5 / 5 / 4 arguments and return a double / bool / bool; the arbitrary ones take 13 / 13 / 12 and return
+// list(ii, jj, xx) (pattern: xx is an empty double vector here, the reference leaves it unset and R never reads it)
+static SEXP slice_coo_single(int dtype, SEXP ii, SEXP jj, SEXP xx, SEXP i, SEXP j)
+{
+    Protect p;
+    ii = as_type(ii, INTSXP, p); jj = as_type(jj, INTSXP, p);
+    if (XLENGTH(ii) != XLENGTH(jj)) Rf_error("slice_coo_single: row and column indices have different length");
+    const void *xv = nullptr;
+    if (dtype == MX_F64) { xx = as_type(xx, REALSXP, p); xv = REAL(xx); }
+    if (dtype == MX_LGL) { xx = as_type(xx, LGLSXP, p); xv = LOGICAL(xx); }
+    if (xv && XLENGTH(xx) != XLENGTH(ii)) Rf_error("slice_coo_single: values and indices have different length");
+    int found = 0;
+    double vd = 0;
+    int vl = 0;
+    if (mx_slice_coo_single(INTEGER(ii), INTEGER(jj), xv, dtype, (int64_t)XLENGTH(ii), Rf_asInteger(i),
+                            Rf_asInteger(j), &found, dtype == MX_F64 ? (void *)&vd : (void *)&vl))
+        fail();
+    if (dtype == MX_F64) return Rf_ScalarReal(found ? vd : 0.0);
+    return Rf_ScalarLogical(found && (dtype == MX_NONE || vl != 0));       // C++ bool: NA reads as TRUE
+}
+SEXP _MatrixExtra_slice_coo_single_numeric(SEXP ii, SEXP jj, SEXP xx, SEXP i, SEXP j)
+{ return slice_coo_single(MX_F64, ii, jj, xx, i, j); }
+SEXP _MatrixExtra_slice_coo_single_logical(SEXP ii, SEXP jj, SEXP xx, SEXP i, SEXP j)
+{ return slice_coo_single(MX_LGL, ii, jj, xx, i, j); }
+SEXP _MatrixExtra_slice_coo_single_binary(SEXP ii, SEXP jj, SEXP i, SEXP j)
+{ return slice_coo_single(MX_NONE, ii, jj, R_NilValue, i, j); }
+
+static SEXP slice_coo_arbitrary(int dtype, SEXP ii, SEXP jj, SEXP xx, SEXP rows, SEXP cols, SEXP all_i, SEXP all_j,
+                                SEXP i_seq, SEXP j_seq, SEXP i_rev, SEXP j_rev, SEXP nrows, SEXP ncols)
+{
+    Protect p;
+    ii = as_type(ii, INTSXP, p); jj = as_type(jj, INTSXP, p);
+    rows = as_type(rows, INTSXP, p); cols = as_type(cols, INTSXP, p);
+    if (XLENGTH(ii) != XLENGTH(jj)) Rf_error("slice_coo_arbitrary: row and column indices have different length");
+    const void *xv = nullptr;
+    if (dtype == MX_F64) { xx = as_type(xx, REALSXP, p); xv = REAL(xx); }
+    if (dtype == MX_LGL) { xx = as_type(xx, LGLSXP, p); xv = LOGICAL(xx); }
+    if (xv && XLENGTH(xx) != XLENGTH(ii)) Rf_error("slice_coo_arbitrary: values and indices have different length");
+    mx_result *res = nullptr;
+    mx_result_info info;
+    if (mx_slice_coo_arbitrary_begin(INTEGER(ii), INTEGER(jj), xv, dtype, (int64_t)XLENGTH(ii), INTEGER(rows),
+                                     (int64_t)XLENGTH(rows), INTEGER(cols), (int64_t)XLENGTH(cols),
+                                     Rf_asLogical(all_i), Rf_asLogical(all_j), Rf_asLogical(i_seq),
+                                     Rf_asLogical(j_seq), Rf_asLogical(i_rev), Rf_asLogical(j_rev),
+                                     Rf_asInteger(nrows), Rf_asInteger(ncols), &res, &info))
+        fail();
+    SEXP out = PROTECT(finish_guarded(res, info, R_NilValue, R_NilValue));
+    SEXP nm = PROTECT(Rf_allocVector(STRSXP, 3));
+    SET_STRING_ELT(nm, 0, Rf_mkChar("ii"));
+    SET_STRING_ELT(nm, 1, Rf_mkChar("jj"));
+    SET_STRING_ELT(nm, 2, Rf_mkChar("xx"));
+    Rf_setAttrib(out, R_NamesSymbol, nm);
+    UNPROTECT(2);
+    return out;
+}
+SEXP _MatrixExtra_slice_coo_arbitrary_numeric(SEXP ii, SEXP jj, SEXP xx, SEXP rows, SEXP cols, SEXP all_i,
+                                              SEXP all_j, SEXP i_seq, SEXP j_seq, SEXP i_rev, SEXP j_rev,
+                                              SEXP nrows, SEXP ncols)
+{ return slice_coo_arbitrary(MX_F64, ii, jj, xx, rows, cols, all_i, all_j, i_seq, j_seq, i_rev, j_rev, nrows, ncols); }
+SEXP _MatrixExtra_slice_coo_arbitrary_logical(SEXP ii, SEXP jj, SEXP xx, SEXP rows, SEXP cols, SEXP all_i,
+                                              SEXP all_j, SEXP i_seq, SEXP j_seq, SEXP i_rev, SEXP j_rev,
+                                              SEXP nrows, SEXP ncols)
+{ return slice_coo_arbitrary(MX_LGL, ii, jj, xx, rows, cols, all_i, all_j, i_seq, j_seq, i_rev, j_rev, nrows, ncols); }
+SEXP _MatrixExtra_slice_coo_arbitrary_binary(SEXP ii, SEXP jj, SEXP rows, SEXP cols, SEXP all_i, SEXP all_j,
+                                             SEXP i_seq, SEXP j_seq, SEXP i_rev, SEXP j_rev, SEXP nrows, SEXP ncols)
+{
+    return slice_coo_arbitrary(MX_NONE, ii, jj, R_NilValue, rows, cols, all_i, all_j, i_seq, j_seq, i_rev, j_rev,
+                               nrows, ncols);
+}
+
 #define MX_ENTRY(name, n) {"_MatrixExtra_" #name, (DL_FUNC)&_MatrixExtra_##name, n}
 static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(matmul_dense_csc_numeric, 5), MX_ENTRY(matmul_dense_csc_float32, 5),
@@ -513,6 +584,9 @@ static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(multiply_csr_by_dvec_no_NAs_numeric, 11), MX_ENTRY(logicaland_csr_by_dvec_internal, 5),
     MX_ENTRY(multiply_csr_by_coo_elemwise, 8), MX_ENTRY(logicaland_csr_by_coo_elemwise, 8),
     MX_ENTRY(multiply_coo_by_dense_ignore_NAs_numeric, 12), MX_ENTRY(multiply_coo_by_dense_ignore_NAs_logical, 6),
+    MX_ENTRY(slice_coo_single_numeric, 5), MX_ENTRY(slice_coo_single_logical, 5), MX_ENTRY(slice_coo_single_binary, 4),
+    MX_ENTRY(slice_coo_arbitrary_numeric, 13), MX_ENTRY(slice_coo_arbitrary_logical, 13),
+    MX_ENTRY(slice_coo_arbitrary_binary, 12),
     {"mxgpu_csr_transpose", (DL_FUNC)&mxgpu_csr_transpose, 4},
     {"mxgpu_coo_to_csr", (DL_FUNC)&mxgpu_coo_to_csr, 5},
     {NULL, NULL, 0}

@@ -260,3 +260,63 @@ def csr_to_coo(A: DeviceCSR):
     rows = torch.empty(max(A.nnz, 1), dtype=torch.int32, device=A.indptr.device)
     check(lib.mxd_csr_to_coo(C.c_int(A.m), C.c_int64(A.nnz), _dp(A.indptr), _dp(rows), _stream()))
     return rows[:A.nnz], A.indices, A.values
+
+
+class CooAxis(C.Structure):
+    """mx_coo_axis (include/mxgpu.h)."""
+    _fields_ = [("kind", C.c_int), ("lo", C.c_int), ("hi", C.c_int), ("reversed", C.c_int), ("nmap", C.c_int),
+                ("start", C.c_void_p), ("pos", C.c_void_p)]
+
+
+def _coo_axis(take_base1: torch.Tensor | None, kind: str, n: int, lo: int = 0, hi: int = -1):
+    """(mx_coo_axis, tensors it points to) for one axis of coo_slice."""
+    if kind == "all":
+        return CooAxis(0, 0, n - 1, 0, 0, None, None), ()
+    if kind in ("seq", "rev"):
+        return CooAxis(0, int(lo), int(hi), int(kind == "rev"), 0, None, None), ()
+    lib = _lib.load()
+    dev = take_base1.device
+    nt = int(take_base1.numel())
+    nmap = int(take_base1.max().item()) + 1 if nt else 1
+    start = torch.empty(nmap + 1, dtype=torch.int32, device=dev)
+    pos = torch.empty(max(nt, 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(lib.mxd_colmap_workspace_bytes(nmap), 16), dtype=torch.uint8, device=dev)
+    check(lib.mxd_colmap_build(_dp(take_base1), C.c_int64(nt), C.c_int(nmap), _dp(start), _dp(pos), _dp(ws),
+                               _stream()))
+    return CooAxis(1, 0, 0, 0, nmap, start.data_ptr(), pos.data_ptr()), (start, pos, ws)
+
+
+def coo_slice(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor | None, m: int, n: int, rows, cols):
+    """X[rows, cols] of an m x n COO held in HBM through mxd_coo_slice_count / _fill, as (i, j, x) of the result.
+    Each selector is ("all",), ("seq", lo, hi) / ("rev", lo, hi) with 0-based bounds (positions r - lo / hi - r),
+    or ("map", take_base1) with a 1-based int32 tensor (any order, repeats allowed)."""
+    lib = _lib.load()
+    dev = i.device
+    nnz = int(i.numel())
+    if int(j.numel()) != nnz or (x is not None and int(x.numel()) != nnz):
+        raise ValueError("i, j and x must have the same length")
+    vd = _value_dtype(x)
+
+    def axis(sel, size):
+        if sel[0] == "map":
+            return _coo_axis(sel[1], "map", size)
+        if sel[0] == "all":
+            return _coo_axis(None, "all", size)
+        return _coo_axis(None, sel[0], size, sel[1], sel[2])
+
+    ai, keep_i = axis(rows, m)
+    aj, keep_j = axis(cols, n)
+    ws = torch.empty(max(lib.mxd_coo_slice_workspace_bytes(nnz), 16), dtype=torch.uint8, device=dev)
+    nnz_out = C.c_int64(0)
+    check(lib.mxd_coo_slice_count(C.c_int(int(m)), C.c_int(int(n)), _dp(i), _dp(j), C.c_int64(nnz), C.byref(ai),
+                                  C.byref(aj), _dp(ws), C.byref(nnz_out), _stream()))
+    k = int(nnz_out.value)
+    oi = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    oj = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    ox = None if x is None else torch.empty(max(k, 1), dtype=x.dtype, device=dev)
+    if k:
+        check(lib.mxd_coo_slice_fill(C.c_int(int(m)), C.c_int(int(n)), _dp(i), _dp(j), _dp(x), C.c_int(vd),
+                                     C.c_int64(nnz), C.byref(ai), C.byref(aj), _dp(ws), _dp(oi), _dp(oj), _dp(ox),
+                                     _stream()))
+    del keep_i, keep_j          # the maps stay alive until both launches are enqueued (torch's caching allocator
+    return oi[:k], oj[:k], None if ox is None else ox[:k]      # reuses the blocks only on this same stream)

@@ -675,3 +675,88 @@ def multiply_coo_by_dense_ignore_NAs_logical(ii, jj, xx, dvec, nrows, ncols):
         ptr(i), ptr(j), ptr(xv), C.c_int64(xv.size), ptr(dv), C.c_int64(dv.size), C.c_int(int(nrows)),
         C.c_int(int(ncols)), ptr(out)))
     return out
+
+
+# ----------------------------------------------------------------------------- COO slicing (X[i, j] of a TsparseMatrix)
+def _slice_coo_arbitrary(ii, jj, xx, vdt, rows_take_base1, cols_take_base1, all_i, all_j, i_is_seq, j_is_seq,
+                         i_is_rev_seq, j_is_rev_seq, nrows, ncols):
+    lib = _lib.load()
+    i, j = _i32(ii), _i32(jj)
+    if i.size != j.size:
+        raise ValueError("row and column indices have different length")
+    v = None
+    if vdt != MX_NONE:
+        v = np.ascontiguousarray(xx, dtype=np.float64 if vdt == MX_F64 else np.int32)
+        if v.size != i.size:
+            raise ValueError("values and indices have different number of entries")
+    rt, ct = _i32(rows_take_base1).reshape(-1), _i32(cols_take_base1).reshape(-1)
+    res = C.c_void_p()
+    info = ResultInfo()
+    check(lib.mx_slice_coo_arbitrary_begin(
+        ptr(i), ptr(j), ptr(v), C.c_int(vdt), C.c_int64(i.size), ptr(rt), C.c_int64(rt.size), ptr(ct),
+        C.c_int64(ct.size), C.c_int(bool(all_i)), C.c_int(bool(all_j)), C.c_int(bool(i_is_seq)),
+        C.c_int(bool(j_is_seq)), C.c_int(bool(i_is_rev_seq)), C.c_int(bool(j_is_rev_seq)), C.c_int(int(nrows)),
+        C.c_int(int(ncols)), C.byref(res), C.byref(info)))
+    out = _finish(res, info, empty_values_dtype=np.float64 if v is None else v.dtype)
+    xx_out = None if v is None else out["values"].astype(v.dtype, copy=False)
+    return dict(ii=out["indptr"], jj=out["indices"], xx=xx_out)
+
+
+def slice_coo_arbitrary_numeric(ii, jj, xx, rows_take_base1, cols_take_base1, all_i, all_j, i_is_seq, j_is_seq,
+                                i_is_rev_seq, j_is_rev_seq, nrows, ncols):
+    """src/slice_coo.cpp:123-706 (f64): dict(ii, jj, xx) of the selected triplets, 0-based in the result's
+    coordinates.  Triplet k gives one output per (position of ii[k]+1 in rows_take_base1, position of jj[k]+1 in
+    cols_take_base1), row positions outer, both ascending, triplets in storage order; values copied bit for bit."""
+    return _slice_coo_arbitrary(ii, jj, xx, MX_F64, rows_take_base1, cols_take_base1, all_i, all_j, i_is_seq,
+                                j_is_seq, i_is_rev_seq, j_is_rev_seq, nrows, ncols)
+
+
+def slice_coo_arbitrary_logical(ii, jj, xx, rows_take_base1, cols_take_base1, all_i, all_j, i_is_seq, j_is_seq,
+                                i_is_rev_seq, j_is_rev_seq, nrows, ncols):
+    """src/slice_coo.cpp:123-706 (R logicals, int32 in and out)."""
+    return _slice_coo_arbitrary(ii, jj, xx, MX_LGL, rows_take_base1, cols_take_base1, all_i, all_j, i_is_seq,
+                                j_is_seq, i_is_rev_seq, j_is_rev_seq, nrows, ncols)
+
+
+def slice_coo_arbitrary_binary(ii, jj, rows_take_base1, cols_take_base1, all_i, all_j, i_is_seq, j_is_seq,
+                               i_is_rev_seq, j_is_rev_seq, nrows, ncols):
+    """src/slice_coo.cpp:123-706 (pattern): dict(ii, jj, xx=None)."""
+    return _slice_coo_arbitrary(ii, jj, None, MX_NONE, rows_take_base1, cols_take_base1, all_i, all_j, i_is_seq,
+                                j_is_seq, i_is_rev_seq, j_is_rev_seq, nrows, ncols)
+
+
+def _slice_coo_single(ii, jj, xx, vdt, i, j):
+    i_, j_ = _i32(ii), _i32(jj)
+    if i_.size != j_.size:
+        raise ValueError("row and column indices have different length")
+    v, val = None, None
+    if vdt == MX_F64:
+        v, val = _f64(xx), C.c_double(0.0)
+    elif vdt == MX_LGL:
+        v, val = np.ascontiguousarray(xx, dtype=np.int32), C.c_int32(0)
+    if v is not None and v.size != i_.size:
+        raise ValueError("values and indices have different number of entries")
+    found = C.c_int(0)
+    check(_lib.load().mx_slice_coo_single(ptr(i_), ptr(j_), ptr(v), C.c_int(vdt), C.c_int64(i_.size),
+                                          C.c_int(int(i)), C.c_int(int(j)), C.byref(found),
+                                          None if val is None else C.byref(val)))
+    return bool(found.value), (None if val is None else val.value)
+
+
+def slice_coo_single_numeric(ii, jj, xx, i, j) -> float:
+    """src/slice_coo.cpp:3-36: the value of the first triplet (storage order) at 0-based (i, j), or 0.  Duplicates
+    are not summed."""
+    hit, val = _slice_coo_single(ii, jj, xx, MX_F64, i, j)
+    return float(val) if hit else 0.0
+
+
+def slice_coo_single_logical(ii, jj, xx, i, j) -> bool:
+    """src/slice_coo.cpp:38-53: the export returns a C++ bool, so the first match's NA reads as TRUE."""
+    hit, val = _slice_coo_single(ii, jj, xx, MX_LGL, i, j)
+    return bool(hit and val != 0)
+
+
+def slice_coo_single_binary(ii, jj, i, j) -> bool:
+    """src/slice_coo.cpp:55-71: TRUE when some triplet sits at (i, j)."""
+    hit, _ = _slice_coo_single(ii, jj, None, MX_NONE, i, j)
+    return hit

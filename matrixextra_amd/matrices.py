@@ -261,6 +261,10 @@ class TsparseMatrix:
     def t(self):                                      # t_masked_coo -> t_shallow (R/trans.R:74-76)
         return t_shallow(self)
 
+    def __getitem__(self, key):                       # `[`  R/slice_coo.R:200-232 (0-based here; subset_coo is 1-based)
+        from . import slice as _slice
+        return _slice.getitem_python(self, key)
+
     # ---- operator wiring
     def __add__(self, other):                         # sparseMatrix + RsparseMatrix, R/operators.R:808-811
         from . import operators

@@ -6,13 +6,17 @@ Path selection follows R/slice.R:439-565: a contiguous ascending run of rows wit
 all columns is sliced on the host exactly as the reference does in pure R
 (:477-483, never reaches native code there either); everything else goes to the
 native routines — row gather, column-range / arbitrary-column slices, reversals.
+
+`subset_coo(x, i, j, drop)` is the same for a TsparseMatrix, after R/slice_coo.R: a scalar (i, j) pair goes to
+slice_coo_single_*, everything else to slice_coo_arbitrary_* (the COO slice kernels).
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import exports
-from .matrices import (RsparseMatrix, check_valid_matrix, dgRMatrix, lgRMatrix, ngRMatrix, stop)
+from .matrices import (RsparseMatrix, TsparseMatrix, check_valid_matrix, dgRMatrix, dgTMatrix, lgRMatrix,
+                       lgTMatrix, ngRMatrix, ngTMatrix, stop)
 
 
 def get_indices_integer(i, max_i, index_names):
@@ -49,6 +53,52 @@ def get_indices_integer(i, max_i, index_names):
     return i.astype(np.int32)
 
 
+class IJProperties:
+    """What get_ij_properties returns (R/slice.R:59-143), without the NA fields: 1-based int32 `i` / `j`, the six
+    classification flags, n_row / n_col, and the selected dimnames (None when the matrix has none)."""
+    __slots__ = ("i", "j", "all_i", "all_j", "i_is_seq", "j_is_seq", "i_is_rev_seq", "j_is_rev_seq", "n_row",
+                 "n_col", "row_names", "col_names")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def get_ij_properties(x, i, j):
+    """R/slice.R:59-143 for integer / logical / name / negative selectors (`None` = missing).  The asymmetry is the
+    reference's (:79-103): a full-range i sets both all_i and i_is_seq, a full-range j sets all_j and leaves
+    j_is_seq FALSE."""
+    row_names, col_names = x.Dimnames[0], x.Dimnames[1]
+    nrow, ncol = x.Dim
+    all_i = all_j = i_is_seq = j_is_seq = i_is_rev_seq = j_is_rev_seq = False
+    if j is None:
+        all_j = True
+        j = np.arange(1, ncol + 1, dtype=np.int32)
+    else:
+        j = get_indices_integer(j, ncol, col_names)
+        if j.size == ncol and ncol > 0 and j[0] == 1 and j[-1] == ncol:
+            all_j = exports.check_is_seq(j)
+        else:
+            j_is_seq = exports.check_is_seq(j)
+    if i is None:
+        i = np.arange(1, nrow + 1, dtype=np.int32)
+        all_i = i_is_seq = True
+    else:
+        i = get_indices_integer(i, nrow, row_names)
+        i_is_seq = exports.check_is_seq(i)
+        if i_is_seq and i.size == nrow and nrow > 0 and i[0] == 1 and i[-1] == nrow:
+            all_i = True
+    if not all_i and not i_is_seq:
+        i_is_rev_seq = exports.check_is_rev_seq(i)
+    if not all_j and not j_is_seq:
+        j_is_rev_seq = exports.check_is_rev_seq(j)
+    new_rn = None if row_names is None or not len(row_names) else [row_names[k - 1] for k in i]
+    new_cn = None if col_names is None or not len(col_names) else [col_names[k - 1] for k in j]
+    return IJProperties(i=i, j=j, all_i=all_i, all_j=all_j, i_is_seq=i_is_seq, j_is_seq=j_is_seq,
+                        i_is_rev_seq=i_is_rev_seq, j_is_rev_seq=j_is_rev_seq, n_row=int(i.size), n_col=int(j.size),
+                        row_names=new_rn, col_names=new_cn)
+
+
 def _empty_like(x, n_row, row_names):
     cls = dgRMatrix if isinstance(x, dgRMatrix) else lgRMatrix if isinstance(x, lgRMatrix) else ngRMatrix
     xv = None if cls is ngRMatrix else np.zeros(0, dtype=cls.value_dtype)
@@ -81,33 +131,13 @@ def subset_csr(x, i=None, j=None, drop=False):
     check_valid_matrix(x)
     if i is None and j is None:
         return x
-    row_names, col_names = x.Dimnames[0], x.Dimnames[1]
+    P = get_ij_properties(x, i, j)
+    i, j = P.i, P.j
     nrow, ncol = x.Dim
-    all_i = all_j = i_is_seq = j_is_seq = i_is_rev_seq = j_is_rev_seq = False
-    if j is None:
-        all_j = True
-        j = np.arange(1, ncol + 1, dtype=np.int32)
-    else:
-        j = get_indices_integer(j, ncol, col_names)
-        if j.size == ncol and ncol > 0 and j[0] == 1 and j[-1] == ncol:
-            all_j = exports.check_is_seq(j)
-        else:
-            j_is_seq = exports.check_is_seq(j)
-    if i is None:
-        i = np.arange(1, nrow + 1, dtype=np.int32)
-        all_i = i_is_seq = True
-    else:
-        i = get_indices_integer(i, nrow, row_names)
-        i_is_seq = exports.check_is_seq(i)
-        if i_is_seq and i.size == nrow and nrow > 0 and i[0] == 1 and i[-1] == nrow:
-            all_i = True
-    n_row, n_col = int(i.size), int(j.size)
-    if not all_i and not i_is_seq:
-        i_is_rev_seq = exports.check_is_rev_seq(i)
-    if not all_j and not j_is_seq:
-        j_is_rev_seq = exports.check_is_rev_seq(j)
-    new_rn = None if row_names is None or not len(row_names) else [row_names[k - 1] for k in i]
-    new_cn = None if col_names is None or not len(col_names) else [col_names[k - 1] for k in j]
+    all_i, all_j, i_is_seq, j_is_seq = P.all_i, P.all_j, P.i_is_seq, P.j_is_seq
+    i_is_rev_seq, j_is_rev_seq = P.i_is_rev_seq, P.j_is_rev_seq
+    n_row, n_col = P.n_row, P.n_col
+    new_rn, new_cn = P.row_names, P.col_names
 
     if n_row == 0 or n_col == 0 or x.j.size == 0:              # R/slice.R:404-421
         out = _empty_like(x, n_row, new_rn)
@@ -177,8 +207,9 @@ def subset_csr(x, i=None, j=None, drop=False):
     return finish(t["indptr"], t["indices"], t.get("values") if has_x else None)
 
 
-def getitem_python(x, key):
-    """Python-style `X[rows]` / `X[rows, :]` (0-based, negative = from the end, bool masks) on top of subset_csr."""
+def canonical_key(x, key):
+    """Python-style key of `X[rows]` / `X[rows, cols]` (0-based, negative = from the end, bool masks, slices) ->
+    (rows, cols) as 1-based int32 selectors, None where the whole axis is taken."""
     def canon(k, n):
         if isinstance(k, slice):
             if k == slice(None):
@@ -200,5 +231,119 @@ def getitem_python(x, key):
             stop("incorrect number of dimensions")
         key, kj = key
     rows, cols = canon(key, x.Dim[0]), canon(kj, x.Dim[1]) if kj is not None else None
-    return subset_csr(x, None if rows is None else (rows + 1).astype(np.int32),
-                      None if cols is None else (cols + 1).astype(np.int32))
+    return (None if rows is None else (rows + 1).astype(np.int32),
+            None if cols is None else (cols + 1).astype(np.int32))
+
+
+def getitem_python(x, key):
+    """Python-style `X[rows]` / `X[rows, :]` (0-based, negative = from the end, bool masks) on top of subset_csr
+    (RsparseMatrix) or subset_coo (TsparseMatrix).  `X[2, 3]` is a 1 x 1 RsparseMatrix; `T[2, 3]` (two integers)
+    takes R's scalar route with drop=FALSE, a 1 x 1 TsparseMatrix holding the first matching triplet; any other key
+    is passed on as vectors."""
+    rows, cols = canonical_key(x, key)
+    if isinstance(x, TsparseMatrix):
+        if isinstance(key, tuple) and all(isinstance(k, (int, np.integer)) and not isinstance(k, (bool, np.bool_))
+                                          for k in key):
+            return subset_coo(x, rows, cols, drop=False)       # X[i, j, drop=FALSE] with integer scalars
+        check_valid_matrix(x)
+        return _subset_coo_vectors(x, rows, cols)
+    return subset_csr(x, rows, cols)
+
+
+# ----------------------------------------------------------------------------- COO: R/slice_coo.R
+def _coo_kind(x):
+    return "d" if isinstance(x, dgTMatrix) else "l" if isinstance(x, lgTMatrix) else "n"
+
+
+_COO_CLS = {"d": dgTMatrix, "l": lgTMatrix, "n": ngTMatrix}
+
+
+def _is_scalar_number(v):
+    """`NROW(v) == 1L && typeof(v) %in% c("integer", "numeric")` (R/slice_coo.R:10-13) for Python values: one int or
+    float, not a bool (a logical) and not a name.  R's typeof() of a double is "double", so strictly only integer
+    scalars take this route there; a Python caller writes plain numbers for both, and both are taken here."""
+    if isinstance(v, (bool, np.bool_)):
+        return False
+    if isinstance(v, (int, float, np.integer, np.floating)):
+        return True
+    a = np.asarray(v) if isinstance(v, (list, tuple, np.ndarray)) else None
+    return a is not None and a.size == 1 and a.dtype.kind in ("i", "u", "f")
+
+
+def _empty_coo(kind, n_row, n_col, row_names, col_names):
+    xv = None if kind == "n" else np.zeros(0, dtype=_COO_CLS[kind].value_dtype)
+    return _COO_CLS[kind](np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), xv, (n_row, n_col),
+                          [row_names, col_names])
+
+
+def _subset_coo_single(x, i, j, drop):
+    """R/slice_coo.R:10-84.  The symmetric / triangular branches (:22-42) have no stand-in class here."""
+    i, j = int(np.asarray(i).reshape(-1)[0]), int(np.asarray(j).reshape(-1)[0])   # as.integer(): truncates
+    nrow, ncol = x.Dim
+    if i > nrow or j > ncol:
+        stop("Subscript out of bounds.")
+    # (sic) a scalar <= 0 is not an exclusion here: it reaches the native routine as i-1 < 0, finds no triplet and
+    # gives 0 / FALSE, as the reference does.
+    kind = _coo_kind(x)
+    if kind == "d":
+        res = exports.slice_coo_single_numeric(x.i, x.j, x.x, i - 1, j - 1)
+    elif kind == "l":
+        res = exports.slice_coo_single_logical(x.i, x.j, x.x, i - 1, j - 1)
+    else:
+        res = exports.slice_coo_single_binary(x.i, x.j, i - 1, j - 1)
+    if drop:
+        return res                              # names(res) <- colnames(x)[j] (:55-56) is not mirrored
+    rn = x.Dimnames[0][i - 1] if x.Dimnames[0] is not None and len(x.Dimnames[0]) and i >= 1 else None
+    cn = x.Dimnames[1][j - 1] if x.Dimnames[1] is not None and len(x.Dimnames[1]) and j >= 1 else None
+    out = _empty_coo(kind, 1, 1, None if rn is None else [rn], None if cn is None else [cn])
+    if (isinstance(res, float) and np.isnan(res)) or res != 0:            # :76-83
+        out.i = np.zeros(1, dtype=np.int32)
+        out.j = np.zeros(1, dtype=np.int32)
+        if kind == "d":
+            out.x = np.array([res], dtype=np.float64)
+        elif kind == "l":
+            out.x = np.array([1], dtype=np.int32)                        # as.logical(TRUE)
+        # ngT: the entry is kept without an x slot (the reference assigns out@x there, which an ngTMatrix lacks)
+    return out
+
+
+def subset_coo(x, i=None, j=None, drop=True):
+    """`x[i, j]` for TsparseMatrix — R/slice_coo.R:1-232 (integer / logical / name / negative indices).  As in
+    subset_csr, NA indices and `drop` to a vector for non-scalar selections are not mirrored; `drop` only matters
+    for the scalar (i, j) route.  Routes:
+      both i and j scalar numbers                 -> slice_coo_single_*, a scalar, or 1 x 1 with drop=False (:10-84)
+      empty i or j, or no entries                 -> empty T-matrix of the same kind                      (:108-125)
+      all rows and all columns                    -> x itself                                             (:127-129)
+      full reversal of both                       -> slice_coo_arbitrary_* with the rev-seq flags; the reference
+                                                     flips (nrow-1) - i, (ncol-1) - j in R (:142-154), which the
+                                                     kernel's affine reversed axes reproduce bit for bit
+      anything else                               -> slice_coo_arbitrary_*                                (:160-196)"""
+    check_valid_matrix(x)
+    if i is None and j is None:
+        return x
+    if i is not None and j is not None and _is_scalar_number(i) and _is_scalar_number(j):
+        return _subset_coo_single(x, i, j, drop)
+    return _subset_coo_vectors(x, i, j)
+
+
+def _subset_coo_vectors(x, i, j):
+    """R/slice_coo.R:87-232: everything but the scalar route."""
+    P = get_ij_properties(x, i, j)
+    kind = _coo_kind(x)
+    if P.n_row == 0 or P.n_col == 0 or x.i.size == 0:                  # :108-125
+        return _empty_coo(kind, P.n_row, P.n_col, P.row_names, P.col_names)
+    if P.all_i and P.all_j:                                             # :127-129
+        return x
+    nrow, ncol = x.Dim
+    flags = (P.all_i, P.all_j, P.i_is_seq, P.j_is_seq, P.i_is_rev_seq, P.j_is_rev_seq, nrow, ncol)
+    if kind == "d":
+        t = exports.slice_coo_arbitrary_numeric(x.i, x.j, x.x, P.i, P.j, *flags)
+    elif kind == "l":
+        t = exports.slice_coo_arbitrary_logical(x.i, x.j, x.x, P.i, P.j, *flags)
+    else:
+        t = exports.slice_coo_arbitrary_binary(x.i, x.j, P.i, P.j, *flags)
+    res = type(x).__new__(type(x))                                      # new(class(x)[1L])  :198
+    res.i, res.j, res.x = t["ii"], t["jj"], t["xx"] if kind != "n" else None
+    res.Dim = (P.n_row, P.n_col)
+    res.Dimnames = [P.row_names, P.col_names]
+    return res
