@@ -115,7 +115,7 @@ int mxd_spmm_csr_dense_ex(int m, int n, int K,
  * so that the panel-sweep kernel reads every entry once, coalesced, while B's current slab-panel stays in L2.
  * The plan depends on A and npanels only; build it once per matrix and run it against any number of B.
  * mxd_spmm_plan_create: *plan = NULL creates, a previous plan re-uses its buffers (grow-only); one internal
- * stream sync (the padded size comes back to the host).  npanels <= 0 picks K*128 B / 2.5 MB.
+ * stream sync (the padded size comes back to the host).  npanels <= 0 picks K*128 B / 1.6 MB.
  * mxd_spmm_plan_run: sync_mode 0 = free running, 1 = the waves of a CU's workgroup meet at every panel boundary,
  * 2 = 1 + one timing barrier per generation among the workgroups of an XCD group; -1 = default (1).
  * Needs 16-B aligned rows of B (and of C when C is row-major).  wg_per_cu 1 / 2 / 4 = that many workgroups of
@@ -126,6 +126,9 @@ int mxd_spmm_plan_create(int m, int K, const int32_t *indptr, const int32_t *ind
                          int npanels, void *stream, mx_spmm_plan **plan);
 int mxd_spmm_plan_destroy(mx_spmm_plan *plan);
 int mxd_spmm_plan_info(const mx_spmm_plan *plan, int *npanels, int64_t *padded_entries);
+/* Read-only copy of a built plan to host memory (tests): step_off[noct * npanels + 1] with noct = ceil(m / 64),
+ * pcol[padded_entries + 512] (column | row inside the bundle << 27) and pval[padded_entries + 512]; synchronises. */
+int mxd_spmm_plan_copy_to_host(const mx_spmm_plan *plan, int32_t *step_off, int32_t *pcol, double *pval, void *stream);
 int mxd_spmm_plan_run(const mx_spmm_plan *plan, int n, const void *B, size_t ldb, void *C, size_t ldc,
                       int dense_dtype, int colmajor_out, int wg_per_cu, int sync_mode, void *stream);
 

@@ -486,12 +486,14 @@ static int pick_panels(int K, size_t l2_budget)
     return p;
 }
 
-// B (K x n row-major, leading dimension ldb) -> slab-major [nslabs][K][W], zero padded past column n.
-// One thread per 16-byte piece; reads are row-contiguous, each 8-lane group writes one full 128-byte line.
+// B (K x n row-major, leading dimension ldb) -> slab-major [nslabs][K][W], zero padded past column n; skipped when
+// `go` (a plan fill's verdict, see plan_fill_kernel) is set and 0.  One thread per 16-byte piece; reads are row-contiguous, each 8-lane group writes one full 128-byte line.
 template <typename real_t>
 __global__ __launch_bounds__(256)
-void repack_slabs_kernel(int K, int Kp, int n, int nslabs, const real_t *__restrict__ B, size_t ldb, real_t *__restrict__ Bp)
+void repack_slabs_kernel(int K, int Kp, int n, int nslabs, const real_t *__restrict__ B, size_t ldb, real_t *__restrict__ Bp,
+                         const int *__restrict__ go)
 {
+    if (go && *go == 0) return;                                      // the plan fill in front of it was skipped
     constexpr int VEC = 16 / (int)sizeof(real_t);
     constexpr int W = SLAB_GROUP * VEC;
     const long long pieces_per_row = (long long)nslabs * SLAB_GROUP;
@@ -573,7 +575,8 @@ static int launch_spmm_slab_rpg(int m, int n, int K, const int32_t *indptr, cons
         if (Bp) {
             const long long pieces = (long long)K * nslabs * SLAB_GROUP;
             const unsigned g = (unsigned)(ceil_div(pieces, 256) < 8192 ? ceil_div(pieces, 256) : 8192);
-            hipLaunchKernelGGL((repack_slabs_kernel<real_t>), dim3(g), dim3(256), 0, stream, K, K, n, nslabs, B, ldb, Bp);
+            hipLaunchKernelGGL((repack_slabs_kernel<real_t>), dim3(g), dim3(256), 0, stream, K, K, n, nslabs, B, ldb, Bp,
+                               (const int *)nullptr);
             MX_LAUNCH_CHECK();
             B = Bp; ldb = W; slab_stride = (size_t)K * W;
         }
@@ -640,12 +643,28 @@ constexpr int PLAN_CHUNK = 4;                      // batches of 8 steps fetched
 constexpr int PLAN_TAIL_SLOTS = 512;               // readable padding behind the last octet (2 chunks)
 constexpr int PLAN_ROW_SHIFT = 27;                 // col < 2^27
 
-// Plan construction: one 512-thread workgroup per octet, one wavefront per bundle.  A bundle's entries are contiguous
-// in the CSR arrays (8 consecutive rows), so the wavefront streams them 64 at a time, fully coalesced; the position
-// of an entry inside its (bundle, panel) stream is a per-panel running count kept in scalar registers plus a
-// ballot prefix — no LDS, no per-row bookkeeping.
-// pass 1: bpo[bundle][p] = where panel p starts in the bundle's stream; steps[oct] = longest bundle of the octet.
+// Plan construction.
+// Sizing: an octet is as long as its longest bundle rounded up to whole chunks, and a bundle's length is
+// indptr[r0 + 8] - indptr[r0], so the sizes (and the AUTO pad-ratio rule) come from indptr alone.  The scan of the
+// octet lengths gives oct_off[] and the step total; the total and nnz go back to the host in one pinned copy.
+// Fill: one 512-thread workgroup per octet, one wavefront per bundle.  The wavefront reads its bundle's entries once
+// (coalesced, 64 per load, PLAN_LD loads in flight), counts them per panel, takes the prefix over the panels (the
+// bundle's panel offsets) and places every entry at (panel offset + rank inside its panel, in CSR order).  Ranks come
+// from a multisplit: ceil(log2 P) ballots of the panel's bits give each lane the mask of its peers, so the cost does
+// not grow with P.  Octets of up to PLAN_STAGE_STEPS steps are assembled in LDS in their final slot order and
+// written out with 16-byte stores; longer ones are scattered straight to global memory.
 constexpr int PLAN_LD = 4;
+constexpr int PLAN_STAGE_STEPS = 384;              // 384 x 64 slots x 12 B = 36 KiB of LDS: four workgroups per CU
+constexpr int PLAN_PAD_NUM = 7, PLAN_PAD_DEN = 4;  // AUTO's pad rule: reject a plan of more than 1.75 x nnz + 65536 slots
+
+// Accept the plan: it fits buffers of cap_slots slots and (pad_rule) is not padded beyond PLAN_PAD_NUM/DEN x nnz.
+// The fill kernel takes this decision from the device-side total, the host repeats it from the read-back copy.
+__host__ __device__ __forceinline__ bool plan_accept(long long total, long long nnz, long long cap_slots, int pad_rule)
+{
+    if (total < 0 || total * 8 + PLAN_TAIL_SLOTS > cap_slots) return false;
+    return !(pad_rule && total * 8 * PLAN_PAD_DEN > nnz * PLAN_PAD_NUM + 65536LL * PLAN_PAD_DEN);
+}
+
 // col / panel_cols without the integer divide: float estimate (col < 2^25 is exact in float up to 2^24, so one
 // correction step either way), clamped to the last panel
 __device__ __forceinline__ int panel_of(int col, int panel_cols, float inv_pc, int npanels)
@@ -656,93 +675,135 @@ __device__ __forceinline__ int panel_of(int col, int panel_cols, float inv_pc, i
     return q < npanels ? q : npanels - 1;
 }
 
-__global__ __launch_bounds__(512)
-void plan_count_kernel(int m, int npanels, int panel_cols, const int32_t *__restrict__ indptr,
-                       const int32_t *__restrict__ indices, int32_t *__restrict__ steps,
-                       int32_t *__restrict__ bpo, int noct, long long *__restrict__ nnz_out)
+// steps[oct] = longest bundle of the octet rounded up to whole chunks; one thread per bundle, 8 per octet
+__global__ __launch_bounds__(256)
+void plan_size_kernel(int m, int noct, const int32_t *__restrict__ indptr, int32_t *__restrict__ steps,
+                      long long *__restrict__ nnz_out)
 {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *nnz_out = indptr[m];     // rides back with the step total (one copy)
-    __shared__ int totals[8];
+    const int b = blockIdx.x * 256 + threadIdx.x;                    // bundle; noct * 8 threads are live
+    if (b == 0) *nnz_out = indptr[m];                                // rides back with the step total (one copy)
+    int len = 0;
+    if (b < noct * 8) {
+        const int r0 = min(b * PLAN_RB, m), r1 = min(b * PLAN_RB + PLAN_RB, m);
+        len = indptr[r1] - indptr[r0];
+    }
+    len = max(len, __shfl_xor(len, 1, 8));
+    len = max(len, __shfl_xor(len, 2, 8));
+    len = max(len, __shfl_xor(len, 4, 8));
+    if (b < noct * 8 && (b & 7) == 0)
+        steps[b >> 3] = (len + 8 * PLAN_CHUNK - 1) & ~(8 * PLAN_CHUNK - 1);    // whole chunks of 4 batches of 8 steps
+}
+
+// lanes whose key agrees with `key` on the low nbits bits, among the lanes in `valid` (bal[b] = ballot of key bit b)
+__device__ __forceinline__ unsigned long long multisplit_peers(int key, const unsigned long long (&bal)[6], int nbits,
+                                                                unsigned long long valid)
+{
+    unsigned long long peers = valid;
+#pragma unroll
+    for (int b = 0; b < 6; b++)
+        if (b < nbits) peers &= ((key >> b) & 1) ? bal[b] : ~bal[b];
+    return peers;
+}
+
+// Slot layout inside a batch of 8 steps: [bundle g][step u] — lane 8g+u of the sweep's reading wavefront holds bundle
+// g's entry for step u, i.e. inside g's own lane group (intra-group DPP broadcast).  Step t of bundle g of an octet
+// lands in slot (t & ~7) * 8 + g * 8 + (t & 7) of the octet.
+__global__ __launch_bounds__(512, 8)
+void plan_fill_kernel(int m, int npanels, int panel_cols, const int32_t *__restrict__ indptr,
+                      const int32_t *__restrict__ indices, const double *__restrict__ values,
+                      const int32_t *__restrict__ oct_off, int32_t *__restrict__ pcol, double *__restrict__ pval,
+                      int noct, int pad_col, int32_t *__restrict__ step_off,
+                      const long long *__restrict__ sizes, long long cap_slots, int pad_rule, int *__restrict__ go)
+{
+    __shared__ int32_t s_col[PLAN_STAGE_STEPS * 8];
+    __shared__ double s_val[PLAN_STAGE_STEPS * 8];
+    __shared__ int s_bpo[8][PLAN_MAXP];
+
+    // sizes = [step total, nnz] from the sizing pass; a plan that does not fit (or that AUTO rejects) is not written
+    // at all, and the repack of B behind this kernel is skipped with it
+    const bool ok = plan_accept(sizes[0], sizes[1], cap_slots, pad_rule);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *go = ok ? 1 : 0;
+    if (!ok) return;
+
     const int g = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int oct = blockIdx.x;
     const int row0 = oct * PLAN_OCT_ROWS + g * PLAN_RB;
-    const int r0 = min(row0, m), r1 = min(row0 + PLAN_RB, m);
-    const int s = indptr[r0], e = indptr[r1];
-    int mine = 0;                                                    // lane p accumulates the count of panel p (+64, ...)
+    int rp[PLAN_RB + 1];                                             // the bundle's row pointers (wave-uniform)
+#pragma unroll
+    for (int r = 0; r <= PLAN_RB; r++) rp[r] = uniform(indptr[min(row0 + r, m)]);
+    const int s = rp[0], e = rp[PLAN_RB];
+    const int base = oct_off[oct];
+    const int steps_oct = oct_off[oct + 1] - base;
+    const bool stage = steps_oct <= PLAN_STAGE_STEPS;                // workgroup-uniform
     const float inv_pc = 1.0f / (float)panel_cols;
-    // PLAN_LD chunks of 64 entries per pass: the loads of a pass are issued together (the kernel is latency-bound:
-    // a bundle is only ~256 entries)
+    const int nbits = npanels > 1 ? 32 - __clz(npanels - 1) : 0;
+    const unsigned long long below = (1ULL << lane) - 1ULL;
+
+    // The first PLAN_LD x 64 entries (all of a cfg2 bundle) stay in registers between the two passes; longer bundles
+    // read the rest again in pass 2 (from L2: the workgroup read it moments before).
+    int col0[PLAN_LD];
+    double val0[PLAN_LD];
+#pragma unroll
+    for (int c = 0; c < PLAN_LD; c++) {
+        const int k = s + 64 * c + lane;
+        col0[c] = -1; val0[c] = 0.0;
+        if (k < e) { col0[c] = indices[k]; val0[c] = values[k]; }
+    }
+    // ballots of the panel bits of one 64-entry chunk (pan < 0: no entry)
+    auto split = [&](int pan, unsigned long long (&bal)[6]) -> unsigned long long {
+#pragma unroll
+        for (int b = 0; b < 6; b++)
+            bal[b] = b < nbits ? __ballot(pan >= 0 && ((pan >> b) & 1)) : 0ULL;
+        return __ballot(pan >= 0);
+    };
+
+    // pass 1: lane q counts the bundle's entries in panel q
+    int mine = 0;
     for (int k0 = s; k0 < e; k0 += 64 * PLAN_LD) {
-        int col[PLAN_LD];
+        int colv[PLAN_LD];
 #pragma unroll
         for (int c = 0; c < PLAN_LD; c++) {
             const int k = k0 + 64 * c + lane;
-            col[c] = k < e ? indices[k] : -1;
+            colv[c] = col0[c];
+            if (k0 != s) colv[c] = k < e ? indices[k] : -1;
         }
 #pragma unroll
         for (int c = 0; c < PLAN_LD; c++) {
             if (k0 + 64 * c >= e) break;                             // uniform
-            const int pan = col[c] >= 0 ? panel_of(col[c], panel_cols, inv_pc, npanels) : -1;
-            for (int q = 0; q < npanels; q++) {
-                const int cnt = __popcll(__ballot(pan == q));
-                if (lane == (q & 63)) mine += cnt;                   // npanels <= 64: one lane per panel
-            }
+            const int pan = colv[c] >= 0 ? panel_of(colv[c], panel_cols, inv_pc, npanels) : -1;
+            unsigned long long bal[6];
+            const unsigned long long valid = split(pan, bal);
+            if (lane < npanels) mine += __popcll(multisplit_peers(lane, bal, nbits, valid));
         }
     }
-    // exclusive prefix over the panels (lanes 0..npanels-1)
+    // exclusive prefix over the panels (lanes 0..npanels-1): where panel q starts in the bundle's stream
     int incl = lane < npanels ? mine : 0;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
         const int up = __shfl_up(incl, off, 64);
         if (lane >= off) incl += up;
     }
-    if (lane < npanels) bpo[((size_t)oct * 8 + g) * npanels + lane] = incl - mine;
-    if (lane == 0) totals[g] = e - s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int mx = 0;
-#pragma unroll
-        for (int gg = 0; gg < 8; gg++) mx = max(mx, totals[gg]);
-        steps[oct] = (mx + 8 * PLAN_CHUNK - 1) & ~(8 * PLAN_CHUNK - 1);    // whole chunks of 4 batches of 8 steps (slot layout below)
-    }
-}
+    int nextstep = incl - mine;                                      // lane q: next free step of panel q
+    s_bpo[g][lane] = nextstep;
 
-// pass 2: scatter the entries to their interleaved slots (batch of 8 steps = 64 slots laid out [bundle][step])
-__global__ __launch_bounds__(512)
-void plan_fill_kernel(int m, int npanels, int panel_cols, const int32_t *__restrict__ indptr,
-                      const int32_t *__restrict__ indices, const double *__restrict__ values,
-                      const int32_t *__restrict__ oct_off, const int32_t *__restrict__ bpo,
-                      int32_t *__restrict__ pcol, double *__restrict__ pval, int noct, int pad_col,
-                      int32_t *__restrict__ step_off)
-{
-    const int g = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int oct = blockIdx.x;
-    // panel boundaries of the octet for the kernel's panel meetings: mean start of the panel over the 8 bundles
-    if (g == 0 && lane < npanels) {
-        int sum = 0;
-#pragma unroll
-        for (int gg = 0; gg < 8; gg++) sum += bpo[((size_t)oct * 8 + gg) * npanels + lane];
-        step_off[(size_t)oct * npanels + lane] = oct_off[oct] + (lane == 0 ? 0 : sum / 8);
-        if (oct == noct - 1 && lane == 0) step_off[(size_t)noct * npanels] = oct_off[noct];
-    }
-    const int row0 = oct * PLAN_OCT_ROWS + g * PLAN_RB;
-    int rp[PLAN_RB + 1];                                             // the bundle's row pointers (wave-uniform)
-#pragma unroll
-    for (int r = 0; r <= PLAN_RB; r++) rp[r] = uniform(indptr[min(row0 + r, m)]);
-    const int s = rp[0], e = rp[PLAN_RB];
-    const long long base = oct_off[oct];
-    // lane q keeps the next free step of panel q's stream
-    int nextstep = lane < npanels ? bpo[((size_t)oct * 8 + g) * npanels + lane] : 0;
-    const unsigned long long below = (1ULL << lane) - 1ULL;
-    const float inv_pc = 1.0f / (float)panel_cols;
+    auto put = [&](int t, int word, double v) {
+        const int slot = (t & ~7) * 8 + g * 8 + (t & 7);
+        if (stage) { s_col[slot] = word; s_val[slot] = v; }
+        else { pcol[(size_t)base * 8 + slot] = word; pval[(size_t)base * 8 + slot] = v; }
+    };
+
+    // pass 2: place every entry at its panel's next step + its rank among the chunk's entries of that panel
     for (int k0 = s; k0 < e; k0 += 64 * PLAN_LD) {
         int colv[PLAN_LD];
         double av[PLAN_LD];
 #pragma unroll
-        for (int c = 0; c < PLAN_LD; c++) {                          // all loads of the pass in flight together
+        for (int c = 0; c < PLAN_LD; c++) {
             const int k = k0 + 64 * c + lane;
-            colv[c] = -1; av[c] = 0.0;
-            if (k < e) { colv[c] = indices[k]; av[c] = values[k]; }
+            colv[c] = col0[c]; av[c] = val0[c];
+            if (k0 != s) {
+                colv[c] = -1; av[c] = 0.0;
+                if (k < e) { colv[c] = indices[k]; av[c] = values[k]; }
+            }
         }
 #pragma unroll
         for (int c = 0; c < PLAN_LD; c++) {
@@ -755,20 +816,11 @@ void plan_fill_kernel(int m, int npanels, int panel_cols, const int32_t *__restr
 #pragma unroll
                 for (int r = 1; r < PLAN_RB; r++) lrow += k >= rp[r];
             }
-            for (int q = 0; q < npanels; q++) {
-                const unsigned long long same = __ballot(pan == q);
-                if (same == 0ULL) continue;                          // uniform
-                const int start = __shfl(nextstep, q & 63, 64);
-                if (pan == q) {
-                    // slot layout inside a batch of 8 steps: [bundle g][step u] — lane 8g+u of the reading wavefront
-                    // holds bundle g's entry for step u, i.e. inside g's own lane group (intra-group DPP broadcast)
-                    const long long t = start + __popcll(same & below);      // step inside the octet
-                    const long long dst = (base + (t & ~7LL)) * 8 + g * 8 + (t & 7);
-                    pcol[dst] = col | (lrow << PLAN_ROW_SHIFT);
-                    pval[dst] = av[c];
-                }
-                if (lane == (q & 63)) nextstep += __popcll(same);
-            }
+            unsigned long long bal[6];
+            const unsigned long long valid = split(pan, bal);
+            const int start = __shfl(nextstep, pan < 0 ? 0 : pan, 64);
+            if (pan >= 0) put(start + __popcll(multisplit_peers(pan, bal, nbits, valid) & below), col | (lrow << PLAN_ROW_SHIFT), av[c]);
+            if (lane < npanels) nextstep += __popcll(multisplit_peers(lane, bal, nbits, valid));
         }
     }
     // Padding up to the octet's length: a no-op entry — value 0, column `pad_col` (the all-zero extra row of the
@@ -779,16 +831,33 @@ void plan_fill_kernel(int m, int npanels, int panel_cols, const int32_t *__restr
 #pragma unroll
         for (int r = 1; r < PLAN_RB; r++) last_lrow += (e - 1) >= rp[r];
     }
-    const int steps_oct = oct_off[oct + 1] - (int)base;
-    for (long long t = (e - s) + lane; t < steps_oct; t += 64) {
-        const long long dst = (base + (t & ~7LL)) * 8 + g * 8 + (t & 7);
-        pcol[dst] = pad_col | (last_lrow << PLAN_ROW_SHIFT);
-        pval[dst] = 0.0;
+    for (int t = (e - s) + lane; t < steps_oct; t += 64) put(t, pad_col | (last_lrow << PLAN_ROW_SHIFT), 0.0);
+
+    __syncthreads();
+    // panel boundaries of the octet for the sweep's panel meetings: mean start of the panel over the 8 bundles
+    if (g == 0 && lane < npanels) {
+        int sum = 0;
+#pragma unroll
+        for (int gg = 0; gg < 8; gg++) sum += s_bpo[gg][lane];
+        step_off[(size_t)oct * npanels + lane] = base + (lane == 0 ? 0 : sum / 8);
+        if (oct == noct - 1 && lane == 0) step_off[(size_t)noct * npanels] = oct_off[noct];
+    }
+    if (stage) {
+        // the octet's image is contiguous: slots [base * 8, (base + steps_oct) * 8), a multiple of 256 slots
+        // starting on a 1 KiB (pcol) / 2 KiB (pval) boundary — 16 bytes per lane per store
+        const int nslots = steps_oct * 8;
+        int4 *gc = reinterpret_cast<int4 *>(pcol + (size_t)base * 8);
+        const int4 *lc = reinterpret_cast<const int4 *>(s_col);
+        for (int i = threadIdx.x; i < nslots / 4; i += 512) gc[i] = lc[i];
+        using d2 = double __attribute__((ext_vector_type(2)));
+        d2 *gv = reinterpret_cast<d2 *>(pval + (size_t)base * 8);
+        const d2 *lv = reinterpret_cast<const d2 *>(s_val);
+        for (int i = threadIdx.x; i < nslots / 2; i += 512) gv[i] = lv[i];
     }
     // PLAN_TAIL_SLOTS padding slots behind the last octet: the kernel's read-ahead runs two batches past an octet
     if (oct == noct - 1) {
         static_assert(PLAN_TAIL_SLOTS == 512, "one slot per thread of the last block");
-        const long long dst = (long long)oct_off[noct] * 8 + threadIdx.x;
+        const size_t dst = (size_t)oct_off[noct] * 8 + threadIdx.x;
         pcol[dst] = pad_col;
         pval[dst] = 0.0;
     }
@@ -1029,9 +1098,17 @@ struct mx_spmm_plan {
     int32_t *step_off = nullptr; size_t step_off_cap = 0;
     int32_t *pcol = nullptr;     size_t pcol_cap = 0;
     double *pval = nullptr;      size_t pval_cap = 0;
-    void *scratch = nullptr;     size_t scratch_cap = 0;       // rowpre + steps + scan workspace (build only)
-    double build_ms = 0.0;
+    void *scratch = nullptr;     size_t scratch_cap = 0;       // steps + oct_off + read-back + scan workspace (build only)
     bool ready = false;                                            // false: sized but not filled (rejected by AUTO)
+    // a build between plan_begin and plan_end: the CSR it reads, device-side sizes / go flag, the capacity the fill saw
+    bool pending = false;
+    const int32_t *indptr = nullptr, *indices = nullptr;
+    const double *values = nullptr;
+    const int32_t *oct_off = nullptr;
+    const long long *sizes = nullptr;
+    int *go = nullptr;
+    long long fill_cap = 0;
+    int pad_rule = 0;
 };
 
 namespace mx {
@@ -1063,14 +1140,22 @@ static PlanReadback *plan_readback()
     return &rb;
 }
 
-// max_pad_ratio > 0: stop after the sizing pass when the plan would hold more than ratio x nnz slots (rows of very
-// uneven length pad the 8-way interleave: an octet is as long as its longest bundle) — pl->ready stays false.
-static int plan_build(mx_spmm_plan *pl, int m, int K, const int32_t *indptr, const int32_t *indices,
-                      const double *values, int npanels, hipStream_t st, double max_pad_ratio = 0.0)
+// Building a plan is split in two so that the GPU never waits for the host.  plan_begin enqueues the sizing pass, the
+// scan, the one read-back of [step total, nnz] and the fill, which decides on the device-side total whether the plan
+// fits the current (grow-only) buffers; the caller may enqueue more work behind it (AUTO packs B).  plan_end waits for
+// the read-back, takes the same decision on the host and, when the buffers were too small (typically the first call),
+// grows them and fills again (*refilled = true).
+// pad_rule: AUTO's rejection of plans that would hold more than 1.75 x nnz slots (rows of very uneven length pad the
+// 8-way interleave: an octet is as long as its longest bundle) — pl->ready then stays false and nothing is written.
+static int plan_begin(mx_spmm_plan *pl, int m, int K, const int32_t *indptr, const int32_t *indices,
+                      const double *values, int npanels, hipStream_t st, int pad_rule = 0)
 {
     pl->ready = false;
+    pl->pending = false;
     MX_REQUIRE(K < (1 << 25), "spmm plan: more than 2^25 columns (32-bit slab offsets)");
-    if (npanels <= 0) npanels = pick_panels(K, (size_t)2600 << 10);     // measured (cfg2): kernel alone is best at 1.6 MB panels (P=8), kernel + plan build at 2.6 MB (P=5)
+    // measured (cfg2, whole call): P = 8 (1.6 MB panels) 2.10 ms, P = 6 2.12 ms, P = 5 2.13 ms — the build no longer
+    // depends on P, so the sweep's best panel size is the default
+    if (npanels <= 0) npanels = pick_panels(K, (size_t)1600 << 10);
     if (npanels > PLAN_MAXP) npanels = PLAN_MAXP;
     pl->m = m; pl->K = K; pl->npanels = npanels;
     pl->panel_cols = (int)ceil_div(K > 0 ? K : 1, npanels);
@@ -1081,41 +1166,57 @@ static int plan_build(mx_spmm_plan *pl, int m, int K, const int32_t *indptr, con
     const size_t al = 255;
     const size_t steps_b = (((size_t)pl->noct * 4) + al) & ~al;
     const size_t octoff_b = ((((size_t)pl->noct + 1) * 4) + al) & ~al;
-    const size_t bpo_b = ((nop * 8 * 4) + al) & ~al;
-    const size_t rb_b = 256;                                        // [total steps][nnz], read back in one copy
-    if (grow(&pl->scratch, &pl->scratch_cap, steps_b + octoff_b + bpo_b + rb_b + scan_workspace_bytes((int64_t)pl->noct))) return 1;
+    const size_t rb_b = 256;                                        // [total steps][nnz][go flag], read back in one copy
+    if (grow(&pl->scratch, &pl->scratch_cap, steps_b + octoff_b + rb_b + scan_workspace_bytes((int64_t)pl->noct))) return 1;
     if (grow((void **)&pl->step_off, &pl->step_off_cap, (nop + 1) * 4)) return 1;
     int32_t *steps = (int32_t *)pl->scratch;
     int32_t *oct_off = (int32_t *)((char *)steps + steps_b);
-    int32_t *bpo = (int32_t *)((char *)oct_off + octoff_b);
-    long long *rb_dev = (long long *)((char *)bpo + bpo_b);
+    long long *rb_dev = (long long *)((char *)oct_off + octoff_b);
     void *scan_ws = (char *)rb_dev + rb_b;
-    const unsigned blocks = (unsigned)pl->noct;
-    hipLaunchKernelGGL(plan_count_kernel, dim3(blocks), dim3(512), 0, st, m, npanels, pl->panel_cols, indptr, indices,
-                       steps, bpo, pl->noct, rb_dev + 1);
+    const unsigned sblocks = (unsigned)ceil_div((long long)pl->noct * 8, 256);
+    hipLaunchKernelGGL(plan_size_kernel, dim3(sblocks), dim3(256), 0, st, m, pl->noct, indptr, steps, rb_dev + 1);
     MX_LAUNCH_CHECK();
     if (exclusive_scan_i32(steps, (int64_t)pl->noct, oct_off, (int64_t *)rb_dev, scan_ws, st)) return 1;
     PlanReadback *rb = plan_readback();
     MX_REQUIRE(rb, "spmm plan: cannot allocate the pinned read-back buffer");
     MX_HIP(hipMemcpyAsync(rb->host, rb_dev, 2 * sizeof(long long), hipMemcpyDeviceToHost, st));
     MX_HIP(hipEventRecord(rb->ev, st));
-    // (Packing B here, behind the read-back, would hide the host round trip — but the fill that follows then
-    // pushes the packed B out of the Infinity Cache and the sweep runs 2.75 ms instead of 2.05 ms.  B is packed right
-    // before the sweep.)
+    pl->indptr = indptr; pl->indices = indices; pl->values = values;
+    pl->oct_off = oct_off; pl->sizes = rb_dev; pl->go = (int *)(rb_dev + 2);
+    pl->pad_rule = pad_rule;
+    pl->fill_cap = (long long)std::min(pl->pcol_cap / 4, pl->pval_cap / 8);
+    hipLaunchKernelGGL(plan_fill_kernel, dim3((unsigned)pl->noct), dim3(512), 0, st, m, npanels, pl->panel_cols, indptr,
+                       indices, values, oct_off, pl->pcol, pl->pval, pl->noct, K, pl->step_off, pl->sizes, pl->fill_cap,
+                       pad_rule, pl->go);
+    MX_LAUNCH_CHECK();
+    pl->pending = true;
+    return 0;
+}
+
+static int plan_end(mx_spmm_plan *pl, hipStream_t st, bool *refilled = nullptr)
+{
+    if (refilled) *refilled = false;
+    if (!pl->pending) return 0;                                     // m == 0 (ready) or plan_begin failed
+    pl->pending = false;
+    PlanReadback *rb = plan_readback();
     MX_HIP(hipEventSynchronize(rb->ev));
     const long long total = rb->host[0];
     pl->nnz = (int32_t)rb->host[1];
     MX_REQUIRE(total >= 0 && total * 8 <= (long long)INT_MAX * 4LL, "spmm plan: too many steps (%lld)", total);
     MX_REQUIRE(total <= (long long)INT_MAX, "spmm plan: step offsets exceed int32");
     pl->total_steps = total;
-    if (max_pad_ratio > 0.0 && (double)total * 8.0 > (double)pl->nnz * max_pad_ratio + 65536.0) return 0;
+    if (plan_accept(total, pl->nnz, pl->fill_cap, pl->pad_rule)) { pl->ready = true; return 0; }   // the fill wrote it
+    if (plan_accept(total, pl->nnz, LLONG_MAX, pl->pad_rule) == false) return 0;                    // rejected by AUTO
     const size_t slots = (size_t)total * 8 + PLAN_TAIL_SLOTS;
     if (grow((void **)&pl->pcol, &pl->pcol_cap, slots * 4)) return 1;
     if (grow((void **)&pl->pval, &pl->pval_cap, slots * 8)) return 1;
-    hipLaunchKernelGGL(plan_fill_kernel, dim3(blocks), dim3(512), 0, st, m, npanels, pl->panel_cols, indptr, indices,
-                       values, oct_off, bpo, pl->pcol, pl->pval, pl->noct, K, pl->step_off);
+    pl->fill_cap = (long long)std::min(pl->pcol_cap / 4, pl->pval_cap / 8);
+    hipLaunchKernelGGL(plan_fill_kernel, dim3((unsigned)pl->noct), dim3(512), 0, st, pl->m, pl->npanels, pl->panel_cols,
+                       pl->indptr, pl->indices, pl->values, pl->oct_off, pl->pcol, pl->pval, pl->noct, pl->K, pl->step_off,
+                       pl->sizes, pl->fill_cap, pl->pad_rule, pl->go);
     MX_LAUNCH_CHECK();
     pl->ready = true;
+    if (refilled) *refilled = true;
     return 0;
 }
 
@@ -1143,7 +1244,7 @@ static void kt_end(hipStream_t st)
 
 // slab-major copy of B with one extra all-zero row (index K) per slab: the plan's padding slots point at it
 template <typename real_t>
-static int plan_repack(int K, int n, const real_t *B, size_t ldb, hipStream_t st, real_t **Bp_out)
+static int plan_repack(int K, int n, const real_t *B, size_t ldb, hipStream_t st, real_t **Bp_out, const int *go = nullptr)
 {
     constexpr int VEC = 16 / (int)sizeof(real_t);
     constexpr int W = SLAB_GROUP * VEC;
@@ -1153,7 +1254,7 @@ static int plan_repack(int K, int n, const real_t *B, size_t ldb, hipStream_t st
     MX_REQUIRE(Bp, "spmm plan: cannot allocate the packed copy of B");
     const long long pieces = (long long)Kp * nslabs * SLAB_GROUP;
     const unsigned gsz = (unsigned)(ceil_div(pieces, 256) < 8192 ? ceil_div(pieces, 256) : 8192);
-    hipLaunchKernelGGL((repack_slabs_kernel<real_t>), dim3(gsz), dim3(256), 0, st, K, Kp, n, nslabs, B, ldb, Bp);
+    hipLaunchKernelGGL((repack_slabs_kernel<real_t>), dim3(gsz), dim3(256), 0, st, K, Kp, n, nslabs, B, ldb, Bp, go);
     MX_LAUNCH_CHECK();
     *Bp_out = Bp;
     return 0;
@@ -1161,15 +1262,18 @@ static int plan_repack(int K, int n, const real_t *B, size_t ldb, hipStream_t st
 
 template <typename real_t>
 static int plan_run(const mx_spmm_plan *pl, int n, const real_t *B, size_t ldb, real_t *C, size_t ldc, int colmajor,
-                    int wg_per_cu, int sync_mode, hipStream_t st)
+                    int wg_per_cu, int sync_mode, hipStream_t st, const real_t *Bp = nullptr)
 {
     constexpr int VEC = 16 / (int)sizeof(real_t);
     constexpr int W = SLAB_GROUP * VEC;
     const int m = pl->m, K = pl->K;
     const int nslabs = (int)ceil_div(n, W);
     const int Kp = K + 1;
-    real_t *Bp = nullptr;
-    if (plan_repack<real_t>(K, n, B, ldb, st, &Bp)) return 1;
+    if (!Bp) {                                                       // else the caller packed B (AUTO, behind the fill)
+        real_t *packed = nullptr;
+        if (plan_repack<real_t>(K, n, B, ldb, st, &packed)) return 1;
+        Bp = packed;
+    }
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) {
         int v = 0;
@@ -1221,7 +1325,8 @@ extern "C" int mxd_spmm_plan_create(int m, int K, const int32_t *indptr, const i
     MX_REQUIRE(plan_out && m >= 0 && K >= 0, "mxd_spmm_plan_create: bad arguments");
     mx_spmm_plan *pl = *plan_out ? *plan_out : new (std::nothrow) mx_spmm_plan();      // pass an old plan to reuse its buffers
     MX_REQUIRE(pl, "out of host memory");
-    if (mx::plan_build(pl, m, K, indptr, indices, values, npanels, mx::as_stream(stream))) {
+    const hipStream_t st = mx::as_stream(stream);
+    if (mx::plan_begin(pl, m, K, indptr, indices, values, npanels, st) || mx::plan_end(pl, st)) {
         if (!*plan_out) { mxd_spmm_plan_destroy(pl); }
         return 1;
     }
@@ -1245,6 +1350,23 @@ extern "C" int mxd_spmm_plan_info(const mx_spmm_plan *pl, int *npanels, int64_t 
     MX_REQUIRE(pl, "mxd_spmm_plan_info: null plan");
     if (npanels) *npanels = pl->npanels;
     if (padded_entries) *padded_entries = pl->total_steps * 8;
+    return 0;
+}
+
+// the plan's arrays as the sweep reads them: step_off[noct * npanels + 1], pcol / pval[padded_entries + 512 tail slots]
+extern "C" int mxd_spmm_plan_copy_to_host(const mx_spmm_plan *pl, int32_t *step_off, int32_t *pcol, double *pval,
+                                          void *stream)
+{
+    MX_REQUIRE(pl && step_off && pcol && pval, "mxd_spmm_plan_copy_to_host: null pointer");
+    MX_REQUIRE(pl->ready, "mxd_spmm_plan_copy_to_host: the plan was sized but not built");
+    if (pl->m == 0) return 0;
+    const hipStream_t st = mx::as_stream(stream);
+    const size_t nso = (size_t)pl->noct * pl->npanels + 1;
+    const size_t slots = (size_t)pl->total_steps * 8 + mx::PLAN_TAIL_SLOTS;
+    MX_HIP(hipMemcpyAsync(step_off, pl->step_off, nso * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipMemcpyAsync(pcol, pl->pcol, slots * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipMemcpyAsync(pval, pl->pval, slots * sizeof(double), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -1319,8 +1441,8 @@ extern "C" int mxd_spmm_csr_dense_ex(int m, int n, int K,
         : mx::slab_ok<float>(n, (const float *)B, ldb, (const float *)C, ldc, colmajor_out);
     bool auto_pick_planned = false;
     if (algo == MX_SPMM_AUTO) {
-        // Measured on MI355X, headline config (profiles/r01_*): row-wave 4.45 ms; one-panel slab kernel on the
-        // slab-major copy of B 4.05 ms; planned panel sweep 1.90 ms + 0.31 ms to build the plan from plain CSR.
+        // Measured on MI355X, headline config (profiles/r01_*, r02_*): row-wave 4.45 ms; one-panel slab kernel on the
+        // slab-major copy of B 4.05 ms; planned panel sweep 1.87 ms + 0.24 ms to build the plan from plain CSR.
         // AUTO = planned (plan rebuilt on every call: nothing is assumed about A between calls) when B outgrows
         // one XCD's L2 and there is enough work to fill the persistent grid, else the row-wave kernel.
         const size_t b_bytes = (size_t)K * (size_t)n * (dense_dtype == MX_F64 ? 8 : 4);
@@ -1336,10 +1458,28 @@ extern "C" int mxd_spmm_csr_dense_ex(int m, int n, int K,
         MX_REQUIRE(auto_plan, "out of host memory");
         // Measured with log-normal row lengths (tools/skew_probe.py): up to ~1.8x the CSR the planned sweep still
         // beats the row-wave kernel even with the plan built per call; beyond that AUTO stops after the sizing pass
-        // (count + scan, ~0.1 ms) and uses the row-wave kernel.
-        if (mx::plan_build(auto_plan, m, K, indptr, indices, values, npanels, st, auto_pick_planned ? 1.75 : 0.0)) return 1;
-        if (auto_plan->ready)
-            return mxd_spmm_plan_run(auto_plan, n, B, ldb, C, ldc, dense_dtype, colmajor_out, 0, -1, stream);
+        // (from indptr alone, plus the scan) and uses the row-wave kernel.
+        if (mx::plan_begin(auto_plan, m, K, indptr, indices, values, npanels, st, auto_pick_planned ? 1 : 0)) return 1;
+        // B is packed behind the fill (and skipped with it) while the host waits for the plan's size: the GPU does not
+        // idle through the round trip, and B is still packed after the fill, right before the sweep (the fill's
+        // traffic would push a B packed earlier out of the Infinity Cache: sweep 2.75 ms instead of 2.05 ms)
+        const bool f64 = dense_dtype == MX_F64;
+        void *Bp = nullptr;
+        auto pack = [&](const int *go) {
+            return f64 ? mx::plan_repack<double>(K, n, (const double *)B, ldb, st, (double **)&Bp, go)
+                       : mx::plan_repack<float>(K, n, (const float *)B, ldb, st, (float **)&Bp, go);
+        };
+        if (pack(auto_plan->go)) return 1;
+        bool refilled = false;
+        if (mx::plan_end(auto_plan, st, &refilled)) return 1;
+        if (auto_plan->ready) {
+            if (refilled && pack(nullptr)) return 1;                    // buffers grown: filled again, pack B behind it
+            g_last_spmm_kernel = "spmm_plan_kernel";
+            return f64 ? mx::plan_run<double>(auto_plan, n, (const double *)B, ldb, (double *)C, ldc, colmajor_out, 0, 1,
+                                              st, (const double *)Bp)
+                       : mx::plan_run<float>(auto_plan, n, (const float *)B, ldb, (float *)C, ldc, colmajor_out, 0, 1, st,
+                                             (const float *)Bp);
+        }
         algo = MX_SPMM_ROWWAVE;
     }
     if (algo == MX_SPMM_SLAB) {
