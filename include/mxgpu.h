@@ -363,6 +363,34 @@ size_t mxd_coo_single_workspace_bytes(void);
 int mxd_coo_single(const int32_t *rows, const int32_t *cols, const void *values, int value_dtype, int64_t nnz,
                    int r, int c, void *workspace, int64_t *k_host, void *value_host, void *stream);
 
+/* Stable compaction of sparse entries (compact.hip), the core of remove_sparse_zeros and filterSparse
+ * (remove_zero_valued_{csr,coo,svec}_*, src/misc.cpp:553-968; rebuild_indptr_after_filter, :1099-1116).
+ * Entry k of n is kept by `rule`, evaluated on values[k] (value_dtype MX_F64, MX_LGL or MX_I32) or on mask[k]:
+ *   MX_KEEP_NONZERO        x != 0 (a NaN / NA value is kept)
+ *   MX_KEEP_NONZERO_NOT_NA x != 0 and x is not NaN (f64) / NA_INTEGER (int32)
+ *   MX_KEEP_NOT_NA         x is not NaN / NA_INTEGER (zeros are kept)
+ *   MX_KEEP_MASK           mask[k] != 0 (R logical; NA keeps the entry and writes the kind's NA as its value:
+ *                          NA_real_ or NA_LOGICAL).  values may then be absent (value_dtype MX_NONE).
+ * count: kept entries per tile, scanned; *kept_host (one 8-byte read-back) = entries kept.
+ * fill: kept entries in input order: out_idx0[q] = idx0[k], out_idx1[q] = idx1[k], out_values[q] = values[k]
+ * (each output skipped when null).  With out_indptr (m + 1 entries; indptr[m] = n, non-decreasing), out_indptr[r]
+ * = kept entries before indptr[r], so a CSR / CSC (indptr, idx0) comes out as a CSR / CSC.  Same arguments in
+ * both passes.  workspace: mxd_compact_workspace_bytes(n), shared by both passes. */
+typedef enum { MX_KEEP_NONZERO = 0, MX_KEEP_NONZERO_NOT_NA = 1, MX_KEEP_NOT_NA = 2, MX_KEEP_MASK = 3 } mx_keep_rule;
+size_t mxd_compact_workspace_bytes(int64_t n);
+int mxd_compact_count(int64_t n, const void *values, int value_dtype, int rule, const int32_t *mask,
+                      void *workspace, int64_t *kept_host, void *stream);
+int mxd_compact_fill(int64_t n, const void *values, int value_dtype, int rule, const int32_t *mask,
+                     const int32_t *idx0, const int32_t *idx1, int m, const int32_t *indptr, const void *workspace,
+                     int32_t *out_idx0, int32_t *out_idx1, void *out_values, int32_t *out_indptr, void *stream);
+/* Index validation of check_sparse_matrix (check_valid_{csr,coo}_matrix, check_valid_svec, src/misc.cpp:970-1097):
+ * *flags_host (one read-back) ORs MX_BAD_NEGATIVE / MX_BAD_BOUND / MX_BAD_NA over indices[0..n) against [0, bound),
+ * MX_BAD_PTR_NA over indptr[0..n_ptr) and MX_BAD_PTR_ORDER for some r < n_mono with indptr[r] > indptr[r+1]
+ * (n_mono < n_ptr, or 0).  workspace4: 4 device bytes. */
+typedef enum { MX_BAD_NEGATIVE = 1, MX_BAD_BOUND = 2, MX_BAD_NA = 4, MX_BAD_PTR_NA = 8, MX_BAD_PTR_ORDER = 16 } mx_bad_flag;
+int mxd_validate_indices(const int32_t *indices, int64_t n, int bound, const int32_t *indptr, int64_t n_ptr,
+                         int64_t n_mono, int32_t *workspace4, int *flags_host, void *stream);
+
 /* ========================================================================== */
 /* (1) export level — host pointers, names follow the Rcpp exports            */
 /* ========================================================================== */
@@ -550,6 +578,54 @@ int mx_slice_coo_arbitrary_begin(const int32_t *ii, const int32_t *jj, const voi
  * the value of the first one in storage order. */
 int mx_slice_coo_single(const int32_t *ii, const int32_t *jj, const void *xx, int value_dtype, int64_t nnz, int i,
                         int j, int *found, void *value_out);
+/* remove_sparse_zeros (R/utils.R:255-346) through mxd_compact_count / _fill.  remove_NAs is the na.rm flag; the
+ * keep rule of each export is the reference's loop, quirks included.  When every entry is kept,
+ * info.alias_structure = MX_ALIAS_ALL: the reference returns the input vectors themselves (src/misc.cpp:586-590,
+ * :735-739, :864-867); nothing is allocated and finish copies nothing.  Otherwise the result is new vectors:
+ *   CSR / CSC  indptr (nrows + 1), indices, values
+ *   COO        the indptr vector holds ii (info.indptr_len = info.nnz), indices jj, values xx
+ *   svec       indptr is empty (info.indptr_len = 0), indices ii, values xx */
+#define MX_ALIAS_ALL 2
+/* remove_zero_valued_csr_numeric / _logical  src/misc.cpp:667-699 (indptr has nrows + 1 entries; a CSC passes
+ * (p, i) and ncol): keep x != 0 (numeric, na.rm: and not NaN; logical: FALSE removed, na.rm: only NA removed) */
+int mx_remove_zero_valued_csr_numeric(const int32_t *indptr, const int32_t *indices, const double *values, int nrows,
+                                      int remove_NAs, mx_result **res, mx_result_info *info);
+int mx_remove_zero_valued_csr_logical(const int32_t *indptr, const int32_t *indices, const int32_t *values,
+                                      int nrows, int remove_NAs, mx_result **res, mx_result_info *info);
+/* remove_zero_valued_coo_numeric / _logical  src/misc.cpp:790-822: keep x != 0 (na.rm: and not NaN / NA) */
+int mx_remove_zero_valued_coo_numeric(const int32_t *ii, const int32_t *jj, const double *xx, int64_t nnz,
+                                      int remove_NAs, mx_result **res, mx_result_info *info);
+int mx_remove_zero_valued_coo_logical(const int32_t *ii, const int32_t *jj, const int32_t *xx, int64_t nnz,
+                                      int remove_NAs, mx_result **res, mx_result_info *info);
+/* remove_zero_valued_svec_numeric / _integer / _logical  src/misc.cpp:925-968: keep x != 0 (numeric, na.rm: NaN
+ * still kept; integer / logical, na.rm: and not NA) */
+int mx_remove_zero_valued_svec_numeric(const int32_t *ii, const double *xx, int64_t nnz, int remove_NAs,
+                                       mx_result **res, mx_result_info *info);
+int mx_remove_zero_valued_svec_integer(const int32_t *ii, const int32_t *xx, int64_t nnz, int remove_NAs,
+                                       mx_result **res, mx_result_info *info);
+int mx_remove_zero_valued_svec_logical(const int32_t *ii, const int32_t *xx, int64_t nnz, int remove_NAs,
+                                       mx_result **res, mx_result_info *info);
+/* filterSparse's x[mask] with the indices taken along (R/utils.R:608-674), through the same compaction:
+ * layout 0 CSR / CSC (indptr with nrows + 1 entries, idx0), 1 COO (idx0 = i, idx1 = j), 2 svec (idx0); mask is
+ * nnz R logicals: FALSE drops the entry, NA keeps it with the kind's NA as its value.  value_dtype MX_F64 / MX_LGL /
+ * MX_I32.  Results are laid out as for the remove_zero_valued_* exports and are always new vectors. */
+int mx_filter_sparse_begin(int layout, const int32_t *indptr, int nrows, const int32_t *idx0, const int32_t *idx1,
+                           const void *values, int value_dtype, int64_t nnz, const int32_t *mask, mx_result **res,
+                           mx_result_info *info);
+/* rebuild_indptr_after_filter  src/misc.cpp:1099-1116: out_indptr[indptr_len]; filter has indptr[indptr_len - 1]
+ * R logicals (0 removes, anything else, NA included, keeps); indptr[0] must be 0. */
+int mx_rebuild_indptr_after_filter(const int32_t *indptr, int64_t indptr_len, const int32_t *filter,
+                                   int32_t *out_indptr);
+/* check_valid_csr_matrix  src/misc.cpp:970-1017: *err receives the reference's message of the first failing check,
+ * or NULL.  indptr has indptr_len entries (all checked for NA); monotonicity is checked over the first
+ * min(nrows, indptr_len - 1) pointers; indices are checked against ncols.  nnz = 0 passes the index checks. */
+int mx_check_valid_csr_matrix(const int32_t *indptr, int64_t indptr_len, const int32_t *indices, int64_t nnz,
+                              int nrows, int ncols, const char **err);
+/* check_valid_coo_matrix  src/misc.cpp:1018-1068: ii against nrows, then jj against ncols */
+int mx_check_valid_coo_matrix(const int32_t *ii, const int32_t *jj, int64_t nnz, int nrows, int ncols,
+                              const char **err);
+/* check_valid_svec  src/misc.cpp:1069-1097: ii against nrows (the R caller passes 1-based ii and the length) */
+int mx_check_valid_svec(const int32_t *ii, int64_t nnz, int nrows, const char **err);
 int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, void *out_values);
 int mx_result_discard(mx_result *res);
 

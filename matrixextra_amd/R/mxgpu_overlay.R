@@ -41,7 +41,12 @@
     "multiply_coo_by_dense_ignore_NAs_numeric", "multiply_coo_by_dense_ignore_NAs_logical",
     ## COO slicing, X[i, j] of a TsparseMatrix (subset_coo, R/slice_coo.R)
     "slice_coo_single_numeric", "slice_coo_single_logical", "slice_coo_single_binary",
-    "slice_coo_arbitrary_numeric", "slice_coo_arbitrary_logical", "slice_coo_arbitrary_binary"
+    "slice_coo_arbitrary_numeric", "slice_coo_arbitrary_logical", "slice_coo_arbitrary_binary",
+    ## remove_sparse_zeros / filterSparse / check_sparse_matrix (R/utils.R): compaction and validation
+    "remove_zero_valued_csr_numeric", "remove_zero_valued_csr_logical",
+    "remove_zero_valued_coo_numeric", "remove_zero_valued_coo_logical",
+    "remove_zero_valued_svec_numeric", "remove_zero_valued_svec_integer", "remove_zero_valued_svec_logical",
+    "check_valid_csr_matrix", "check_valid_coo_matrix", "check_valid_svec", "rebuild_indptr_after_filter"
 )
 
 mxgpu_enable <- function(shim_path, min_nnz = 0L) {

@@ -4,7 +4,7 @@ Layers (SURVEY.md §1 / DESIGN.md):
   csrc/*.hip + include/mxgpu.h   hand-written HIP kernels behind a C-ABI (libmxgpu.so)
   exports.py                     twins of R/RcppExports.R wrappers (ctypes -> C-ABI)
   matrices.py                    dgRMatrix / lgRMatrix / ngRMatrix / dgCMatrix / d/l/ngTMatrix / float32 stand-ins
-  matmul.py operators.py slice.py   mirrors of the R glue (checks, messages, dimnames, classes)
+  matmul.py operators.py slice.py cleanup.py   mirrors of the R glue (checks, messages, dimnames, classes)
   device.py                      device-resident CSR + mxd_* launches on torch tensors (bench, multi-GPU)
   distributed.py                 row-block sharding + RCCL all-gather of C
 
@@ -20,5 +20,6 @@ from .matmul import RLogical, crossprod, tcrossprod  # noqa: F401  (`%*%` is the
 from .operators import (add_csr_matrices, logicalor_csr_matrices, multiply_csr_by_coo,  # noqa: F401
                         multiply_csr_by_csr, xor_csr_matrices)
 from .slice import subset_coo, subset_csr  # noqa: F401
+from .cleanup import check_sparse_matrix, filterSparse, remove_sparse_zeros  # noqa: F401
 
 __version__ = "0.1.0"

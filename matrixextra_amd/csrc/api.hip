@@ -937,6 +937,195 @@ int mx_slice_coo_single(const int32_t *ii, const int32_t *jj, const void *xx, in
     return 0;
 }
 
+// ---- remove_sparse_zeros / filterSparse / check_sparse_matrix (compact.hip) ----------------------------
+// One compaction for every layout: 0 CSR / CSC (indptr, idx0), 1 COO (idx0, idx1; the result's ii travels in the
+// indptr vector), 2 sparse vector (idx0).  Only the values (or the mask) go up before the count; when a zero rule
+// removes nothing the result aliases the inputs and nothing else is moved.
+static int compact_begin(int layout, const int32_t *indptr, int nrows, const int32_t *idx0, const int32_t *idx1,
+                         const void *values, int value_dtype, int64_t nnz, int rule, const int32_t *mask,
+                         mx_result **res_out, mx_result_info *info)
+{
+    MX_REQUIRE(res_out && info, "compaction: null output pointer");
+    MX_REQUIRE(layout >= 0 && layout <= 2 && nrows >= 0 && nrows < INT_MAX, "compaction: bad arguments");
+    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_I32,
+               "compaction: unsupported value dtype %d", value_dtype);
+    if (layout == 0) {
+        MX_REQUIRE(indptr && indptr[0] == 0 && indptr[nrows] >= 0, "compaction: bad index pointer");
+        nnz = indptr[nrows];
+    }
+    MX_REQUIRE(nnz >= 0 && nnz <= INT_MAX, "compaction: bad number of entries");
+    MX_REQUIRE(nnz == 0 || (idx0 && (layout != 1 || idx1) && values && (rule != MX_KEEP_MASK || mask)),
+               "compaction: null pointer");
+    *res_out = nullptr;
+    const size_t vb = dtype_bytes(value_dtype);
+    return begin_result(res_out, info, value_dtype, [&](mx_result &res) {
+        DevBuf x, mk, ws;
+        if (x.upload(values, vb * (size_t)nnz)) return 1;
+        if (rule == MX_KEEP_MASK && mk.upload(mask, sizeof(int32_t) * (size_t)nnz)) return 1;
+        if (ws.alloc(mxd_compact_workspace_bytes(nnz))) return 1;
+        int64_t kept = 0;
+        if (mxd_compact_count(nnz, x.p, value_dtype, rule, mk.as<int32_t>(), ws.p, &kept, nullptr)) return 1;
+        if (kept == nnz && rule != MX_KEEP_MASK) {                  // misc.cpp:586-590, :735-739, :864-867
+            res.info.alias_structure = MX_ALIAS_ALL;
+            res.set_sizes(layout == 0 ? (int64_t)nrows + 1 : layout == 1 ? nnz : 0, nnz, nnz);
+            return 0;
+        }
+        DevBuf p, i0, i1;
+        if (layout == 0 && p.upload(indptr, sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        if (i0.upload(idx0, sizeof(int32_t) * (size_t)nnz)) return 1;
+        if (layout == 1 && i1.upload(idx1, sizeof(int32_t) * (size_t)nnz)) return 1;
+        res.set_sizes(layout == 0 ? (int64_t)nrows + 1 : layout == 1 ? kept : 0, kept, kept);
+        if (layout != 2 && res.indptr.alloc(sizeof(int32_t) * (size_t)res.info.indptr_len)) return 1;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)kept)) return 1;
+        if (res.values.alloc(vb * (size_t)kept)) return 1;
+        int32_t *o0 = layout == 1 ? res.indptr.as<int32_t>() : res.indices.as<int32_t>();
+        int32_t *o1 = layout == 1 ? res.indices.as<int32_t>() : nullptr;
+        return mxd_compact_fill(nnz, x.p, value_dtype, rule, mk.as<int32_t>(), i0.as<int32_t>(),
+                                layout == 1 ? i1.as<int32_t>() : nullptr, layout == 0 ? nrows : 0,
+                                layout == 0 ? p.as<int32_t>() : nullptr, ws.p, o0, o1, res.values.p,
+                                layout == 0 ? res.indptr.as<int32_t>() : nullptr, nullptr);
+    });
+}
+
+// the reference's loops (misc.cpp:600-646) as keep rules: a logical CSR with na.rm removes only NA (:637-648)
+static int csr_rule(int value_dtype, int remove_NAs)
+{
+    if (!remove_NAs) return MX_KEEP_NONZERO;
+    return value_dtype == MX_F64 ? MX_KEEP_NONZERO_NOT_NA : MX_KEEP_NOT_NA;
+}
+
+int mx_remove_zero_valued_csr_numeric(const int32_t *indptr, const int32_t *indices, const double *values, int nrows,
+                                      int remove_NAs, mx_result **res, mx_result_info *info)
+{
+    return compact_begin(0, indptr, nrows, indices, nullptr, values, MX_F64, 0, csr_rule(MX_F64, remove_NAs), nullptr,
+                         res, info);
+}
+int mx_remove_zero_valued_csr_logical(const int32_t *indptr, const int32_t *indices, const int32_t *values,
+                                      int nrows, int remove_NAs, mx_result **res, mx_result_info *info)
+{
+    return compact_begin(0, indptr, nrows, indices, nullptr, values, MX_LGL, 0, csr_rule(MX_LGL, remove_NAs), nullptr,
+                         res, info);
+}
+int mx_remove_zero_valued_coo_numeric(const int32_t *ii, const int32_t *jj, const double *xx, int64_t nnz,
+                                      int remove_NAs, mx_result **res, mx_result_info *info)
+{
+    return compact_begin(1, nullptr, 0, ii, jj, xx, MX_F64, nnz, remove_NAs ? MX_KEEP_NONZERO_NOT_NA : MX_KEEP_NONZERO,
+                         nullptr, res, info);
+}
+int mx_remove_zero_valued_coo_logical(const int32_t *ii, const int32_t *jj, const int32_t *xx, int64_t nnz,
+                                      int remove_NAs, mx_result **res, mx_result_info *info)
+{
+    return compact_begin(1, nullptr, 0, ii, jj, xx, MX_LGL, nnz, remove_NAs ? MX_KEEP_NONZERO_NOT_NA : MX_KEEP_NONZERO,
+                         nullptr, res, info);
+}
+int mx_remove_zero_valued_svec_numeric(const int32_t *ii, const double *xx, int64_t nnz, int remove_NAs,
+                                       mx_result **res, mx_result_info *info)
+{
+    (void)remove_NAs;                                  // misc.cpp:882-886: with na.rm, NaN is still kept (quirk)
+    return compact_begin(2, nullptr, 0, ii, nullptr, xx, MX_F64, nnz, MX_KEEP_NONZERO, nullptr, res, info);
+}
+int mx_remove_zero_valued_svec_integer(const int32_t *ii, const int32_t *xx, int64_t nnz, int remove_NAs,
+                                       mx_result **res, mx_result_info *info)
+{
+    return compact_begin(2, nullptr, 0, ii, nullptr, xx, MX_I32, nnz,
+                         remove_NAs ? MX_KEEP_NONZERO_NOT_NA : MX_KEEP_NONZERO, nullptr, res, info);
+}
+int mx_remove_zero_valued_svec_logical(const int32_t *ii, const int32_t *xx, int64_t nnz, int remove_NAs,
+                                       mx_result **res, mx_result_info *info)
+{
+    return compact_begin(2, nullptr, 0, ii, nullptr, xx, MX_LGL, nnz,
+                         remove_NAs ? MX_KEEP_NONZERO_NOT_NA : MX_KEEP_NONZERO, nullptr, res, info);
+}
+
+int mx_filter_sparse_begin(int layout, const int32_t *indptr, int nrows, const int32_t *idx0, const int32_t *idx1,
+                           const void *values, int value_dtype, int64_t nnz, const int32_t *mask, mx_result **res,
+                           mx_result_info *info)
+{
+    return compact_begin(layout, indptr, nrows, idx0, idx1, values, value_dtype, nnz, MX_KEEP_MASK, mask, res, info);
+}
+
+int mx_rebuild_indptr_after_filter(const int32_t *indptr, int64_t indptr_len, const int32_t *filter,
+                                   int32_t *out_indptr)
+{
+    MX_REQUIRE(indptr_len >= 0 && indptr_len <= INT_MAX, "rebuild_indptr_after_filter: bad size");
+    if (indptr_len == 0) return 0;                     // nrows = -1: an empty vector (misc.cpp:1105-1106)
+    MX_REQUIRE(indptr && out_indptr, "rebuild_indptr_after_filter: null pointer");
+    const int m = (int)(indptr_len - 1);
+    MX_REQUIRE(indptr[0] == 0 && indptr[m] >= 0, "rebuild_indptr_after_filter: bad index pointer");
+    const int64_t nnz = indptr[m];
+    MX_REQUIRE(nnz == 0 || filter, "rebuild_indptr_after_filter: null pointer");
+    DevBuf p, f, ws, o;
+    if (p.upload(indptr, sizeof(int32_t) * (size_t)indptr_len)) return 1;
+    if (f.upload(filter, sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (ws.alloc(mxd_compact_workspace_bytes(nnz))) return 1;
+    if (o.alloc(sizeof(int32_t) * (size_t)indptr_len)) return 1;
+    int64_t kept = 0;
+    if (mxd_compact_count(nnz, nullptr, MX_NONE, MX_KEEP_MASK, f.as<int32_t>(), ws.p, &kept, nullptr)) return 1;
+    if (mxd_compact_fill(nnz, nullptr, MX_NONE, MX_KEEP_MASK, f.as<int32_t>(), nullptr, nullptr, m, p.as<int32_t>(),
+                         ws.p, nullptr, nullptr, nullptr, o.as<int32_t>(), nullptr)) return 1;
+    MX_HIP(hipStreamSynchronize(nullptr));
+    return mx::xfer_d2h(out_indptr, o.p, sizeof(int32_t) * (size_t)indptr_len);
+}
+
+// check_valid_*: the first failing check in the reference's order, with its message (misc.cpp:978-1013)
+static const char *first_failure(int f)
+{
+    if (f & MX_BAD_NEGATIVE) return "Matrix has negative indices.";
+    if (f & MX_BAD_BOUND) return "Matrix has invalid column indices.";     // also for row indices (sic)
+    if (f & MX_BAD_NA) return "Matrix has indices with missing values.";   // NA_INTEGER < 0: never reached
+    if (f & MX_BAD_PTR_NA) return "Matrix has missing values in the index pointer.";
+    if (f & MX_BAD_PTR_ORDER) return "Matrix index pointer is not monotonicaly increasing.";
+    return nullptr;
+}
+
+static int validate_host(const int32_t *idx, int64_t n, int bound, const int32_t *indptr, int64_t n_ptr,
+                         int64_t n_mono, int *flags)
+{
+    DevBuf d, p, ws;
+    if (d.upload(idx, sizeof(int32_t) * (size_t)n)) return 1;
+    if (p.upload(indptr, sizeof(int32_t) * (size_t)n_ptr)) return 1;
+    if (ws.alloc(16)) return 1;
+    return mxd_validate_indices(d.as<int32_t>(), n, bound, p.as<int32_t>(), n_ptr, n_mono, ws.as<int32_t>(), flags,
+                                nullptr);
+}
+
+int mx_check_valid_csr_matrix(const int32_t *indptr, int64_t indptr_len, const int32_t *indices, int64_t nnz,
+                              int nrows, int ncols, const char **err)
+{
+    MX_REQUIRE(err && indptr_len >= 0 && nnz >= 0 && (indptr_len == 0 || indptr) && (nnz == 0 || indices),
+               "check_valid_csr_matrix: bad arguments");
+    *err = nullptr;
+    int64_t mono = (int64_t)nrows < indptr_len - 1 ? (int64_t)nrows : indptr_len - 1;
+    if (mono < 0) mono = 0;
+    int f = 0;
+    if (validate_host(indices, nnz, ncols, indptr, indptr_len, mono, &f)) return 1;
+    *err = first_failure(f);
+    return 0;
+}
+
+int mx_check_valid_coo_matrix(const int32_t *ii, const int32_t *jj, int64_t nnz, int nrows, int ncols,
+                              const char **err)
+{
+    MX_REQUIRE(err && nnz >= 0 && (nnz == 0 || (ii && jj)), "check_valid_coo_matrix: bad arguments");
+    *err = nullptr;
+    int f = 0;
+    if (validate_host(ii, nnz, nrows, nullptr, 0, 0, &f)) return 1;
+    if ((*err = first_failure(f)) != nullptr) return 0;
+    if (validate_host(jj, nnz, ncols, nullptr, 0, 0, &f)) return 1;
+    *err = first_failure(f);
+    return 0;
+}
+
+int mx_check_valid_svec(const int32_t *ii, int64_t nnz, int nrows, const char **err)
+{
+    MX_REQUIRE(err && nnz >= 0 && (nnz == 0 || ii), "check_valid_svec: bad arguments");
+    *err = nullptr;
+    int f = 0;
+    if (validate_host(ii, nnz, nrows, nullptr, 0, 0, &f)) return 1;
+    *err = first_failure(f);
+    return 0;
+}
+
 int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, void *out_values)
 {
     MX_REQUIRE(res, "mx_result_finish: null handle");

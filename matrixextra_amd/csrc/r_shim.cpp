@@ -564,6 +564,166 @@ SEXP _MatrixExtra_slice_coo_arbitrary_binary(SEXP ii, SEXP jj, SEXP rows, SEXP c
                                nrows, ncols);
 }
 
+// remove_sparse_zeros / filterSparse / check_sparse_matrix  (src/misc.cpp:553-1116; glue src/RcppExports.cpp
+// CallEntries :2279-2289).  The zero removers return list(indptr, indices, values) / list(ii, jj, xx) / list(ii, xx)
+// and, when nothing is removed, the input vectors themselves (misc.cpp:586-590, :735-739, :864-867).
+static SEXP named(SEXP out, const char *a, const char *b, const char *c)
+{
+    PROTECT(out);
+    const int n = (int)XLENGTH(out);
+    SEXP nm = PROTECT(Rf_allocVector(STRSXP, n));
+    SET_STRING_ELT(nm, 0, Rf_mkChar(a));
+    SET_STRING_ELT(nm, 1, Rf_mkChar(b));
+    if (n > 2) SET_STRING_ELT(nm, 2, Rf_mkChar(c));
+    Rf_setAttrib(out, R_NamesSymbol, nm);
+    UNPROTECT(2);
+    return out;
+}
+
+static SEXP compacted(mx_result *res, const mx_result_info &info, SEXP a, SEXP b, SEXP x, int layout)
+{
+    if (info.alias_structure == MX_ALIAS_ALL) {
+        mx_result_discard(res);
+        SEXP out = PROTECT(Rf_allocVector(VECSXP, layout == 2 ? 2 : 3));
+        if (layout == 2) { SET_VECTOR_ELT(out, 0, b); SET_VECTOR_ELT(out, 1, x); }
+        else { SET_VECTOR_ELT(out, 0, a); SET_VECTOR_ELT(out, 1, b); SET_VECTOR_ELT(out, 2, x); }
+        UNPROTECT(1);
+        return out;
+    }
+    SEXP l = PROTECT(finish_guarded(res, info, R_NilValue, R_NilValue));   // (indptr-or-ii, indices, values)
+    SEXP out = l;
+    if (layout == 2) {
+        out = PROTECT(Rf_allocVector(VECSXP, 2));
+        SET_VECTOR_ELT(out, 0, VECTOR_ELT(l, 1));
+        SET_VECTOR_ELT(out, 1, VECTOR_ELT(l, 2));
+        UNPROTECT(1);
+    }
+    UNPROTECT(1);
+    return out;
+}
+
+static SEXP rz_csr(int dtype, SEXP p_, SEXP j_, SEXP x_, SEXP na_rm)
+{
+    Protect p;
+    p_ = as_type(p_, INTSXP, p); j_ = as_type(j_, INTSXP, p);
+    x_ = as_type(x_, dtype == MX_F64 ? REALSXP : LGLSXP, p);
+    if (XLENGTH(x_) != XLENGTH(j_)) Rf_error("remove_zero_valued_csr: indices and values have different length");
+    mx_result *res = nullptr;
+    mx_result_info info;
+    const int rc = dtype == MX_F64
+        ? mx_remove_zero_valued_csr_numeric(INTEGER(p_), INTEGER(j_), REAL(x_), (int)XLENGTH(p_) - 1,
+                                            Rf_asLogical(na_rm), &res, &info)
+        : mx_remove_zero_valued_csr_logical(INTEGER(p_), INTEGER(j_), LOGICAL(x_), (int)XLENGTH(p_) - 1,
+                                            Rf_asLogical(na_rm), &res, &info);
+    if (rc) fail();
+    return named(compacted(res, info, p_, j_, x_, 0), "indptr", "indices", "values");
+}
+SEXP _MatrixExtra_remove_zero_valued_csr_numeric(SEXP p_, SEXP j_, SEXP x_, SEXP na_rm)
+{ return rz_csr(MX_F64, p_, j_, x_, na_rm); }
+SEXP _MatrixExtra_remove_zero_valued_csr_logical(SEXP p_, SEXP j_, SEXP x_, SEXP na_rm)
+{ return rz_csr(MX_LGL, p_, j_, x_, na_rm); }
+
+static SEXP rz_coo(int dtype, SEXP ii, SEXP jj, SEXP xx, SEXP na_rm)
+{
+    Protect p;
+    ii = as_type(ii, INTSXP, p); jj = as_type(jj, INTSXP, p);
+    xx = as_type(xx, dtype == MX_F64 ? REALSXP : LGLSXP, p);
+    if (XLENGTH(ii) != XLENGTH(jj) || XLENGTH(ii) != XLENGTH(xx)) Rf_error("remove_zero_valued_coo: bad lengths");
+    mx_result *res = nullptr;
+    mx_result_info info;
+    const int rc = dtype == MX_F64
+        ? mx_remove_zero_valued_coo_numeric(INTEGER(ii), INTEGER(jj), REAL(xx), (int64_t)XLENGTH(ii),
+                                            Rf_asLogical(na_rm), &res, &info)
+        : mx_remove_zero_valued_coo_logical(INTEGER(ii), INTEGER(jj), LOGICAL(xx), (int64_t)XLENGTH(ii),
+                                            Rf_asLogical(na_rm), &res, &info);
+    if (rc) fail();
+    return named(compacted(res, info, ii, jj, xx, 1), "ii", "jj", "xx");
+}
+SEXP _MatrixExtra_remove_zero_valued_coo_numeric(SEXP ii, SEXP jj, SEXP xx, SEXP na_rm)
+{ return rz_coo(MX_F64, ii, jj, xx, na_rm); }
+SEXP _MatrixExtra_remove_zero_valued_coo_logical(SEXP ii, SEXP jj, SEXP xx, SEXP na_rm)
+{ return rz_coo(MX_LGL, ii, jj, xx, na_rm); }
+
+static SEXP rz_svec(int dtype, SEXP ii, SEXP xx, SEXP na_rm)
+{
+    Protect p;
+    ii = as_type(ii, INTSXP, p);
+    xx = as_type(xx, dtype == MX_F64 ? REALSXP : dtype == MX_LGL ? LGLSXP : INTSXP, p);
+    if (XLENGTH(ii) != XLENGTH(xx)) Rf_error("remove_zero_valued_svec: indices and values have different length");
+    mx_result *res = nullptr;
+    mx_result_info info;
+    const int64_t n = (int64_t)XLENGTH(ii);
+    const int na = Rf_asLogical(na_rm);
+    int rc;
+    if (dtype == MX_F64) rc = mx_remove_zero_valued_svec_numeric(INTEGER(ii), REAL(xx), n, na, &res, &info);
+    else if (dtype == MX_LGL) rc = mx_remove_zero_valued_svec_logical(INTEGER(ii), LOGICAL(xx), n, na, &res, &info);
+    else rc = mx_remove_zero_valued_svec_integer(INTEGER(ii), INTEGER(xx), n, na, &res, &info);
+    if (rc) fail();
+    // finish_list allocates REALSXP for MX_I32 results; an integer svec keeps its INTSXP type
+    if (dtype == MX_I32 && info.alias_structure != MX_ALIAS_ALL) {
+        SEXP ni = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)info.nnz));
+        SEXP nx = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)info.values_len));
+        if (mx_result_finish(res, nullptr, INTEGER(ni), INTEGER(nx))) fail();
+        SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
+        SET_VECTOR_ELT(out, 0, ni);
+        SET_VECTOR_ELT(out, 1, nx);
+        UNPROTECT(3);
+        return named(out, "ii", "xx", nullptr);
+    }
+    return named(compacted(res, info, R_NilValue, ii, xx, 2), "ii", "xx", nullptr);
+}
+SEXP _MatrixExtra_remove_zero_valued_svec_numeric(SEXP ii, SEXP xx, SEXP na_rm) { return rz_svec(MX_F64, ii, xx, na_rm); }
+SEXP _MatrixExtra_remove_zero_valued_svec_integer(SEXP ii, SEXP xx, SEXP na_rm) { return rz_svec(MX_I32, ii, xx, na_rm); }
+SEXP _MatrixExtra_remove_zero_valued_svec_logical(SEXP ii, SEXP xx, SEXP na_rm) { return rz_svec(MX_LGL, ii, xx, na_rm); }
+
+static SEXP err_list(const char *err)
+{
+    if (!err) return Rf_allocVector(VECSXP, 0);                     // Rcpp::List()
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 1));
+    SET_VECTOR_ELT(out, 0, Rf_mkString(err));
+    SEXP nm = PROTECT(Rf_mkString("err"));
+    Rf_setAttrib(out, R_NamesSymbol, nm);
+    UNPROTECT(2);
+    return out;
+}
+SEXP _MatrixExtra_check_valid_csr_matrix(SEXP p_, SEXP j_, SEXP nrows, SEXP ncols)
+{
+    Protect p;
+    p_ = as_type(p_, INTSXP, p); j_ = as_type(j_, INTSXP, p);
+    const char *err = nullptr;
+    if (mx_check_valid_csr_matrix(INTEGER(p_), (int64_t)XLENGTH(p_), INTEGER(j_), (int64_t)XLENGTH(j_),
+                                  Rf_asInteger(nrows), Rf_asInteger(ncols), &err))
+        fail();
+    return err_list(err);
+}
+SEXP _MatrixExtra_check_valid_coo_matrix(SEXP ii, SEXP jj, SEXP nrows, SEXP ncols)
+{
+    Protect p;
+    ii = as_type(ii, INTSXP, p); jj = as_type(jj, INTSXP, p);
+    if (XLENGTH(ii) != XLENGTH(jj)) Rf_error("check_valid_coo_matrix: row and column indices have different length");
+    const char *err = nullptr;
+    if (mx_check_valid_coo_matrix(INTEGER(ii), INTEGER(jj), (int64_t)XLENGTH(ii), Rf_asInteger(nrows),
+                                  Rf_asInteger(ncols), &err))
+        fail();
+    return err_list(err);
+}
+SEXP _MatrixExtra_check_valid_svec(SEXP ii, SEXP nrows)
+{
+    Protect p;
+    ii = as_type(ii, INTSXP, p);
+    const char *err = nullptr;
+    if (mx_check_valid_svec(INTEGER(ii), (int64_t)XLENGTH(ii), Rf_asInteger(nrows), &err)) fail();
+    return err_list(err);
+}
+SEXP _MatrixExtra_rebuild_indptr_after_filter(SEXP p_, SEXP filter)
+{
+    Protect p;
+    p_ = as_type(p_, INTSXP, p); filter = as_type(filter, LGLSXP, p);
+    SEXP out = p(Rf_allocVector(INTSXP, XLENGTH(p_)));
+    if (mx_rebuild_indptr_after_filter(INTEGER(p_), (int64_t)XLENGTH(p_), LOGICAL(filter), INTEGER(out))) fail();
+    return out;
+}
+
 #define MX_ENTRY(name, n) {"_MatrixExtra_" #name, (DL_FUNC)&_MatrixExtra_##name, n}
 static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(matmul_dense_csc_numeric, 5), MX_ENTRY(matmul_dense_csc_float32, 5),
@@ -587,6 +747,12 @@ static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(slice_coo_single_numeric, 5), MX_ENTRY(slice_coo_single_logical, 5), MX_ENTRY(slice_coo_single_binary, 4),
     MX_ENTRY(slice_coo_arbitrary_numeric, 13), MX_ENTRY(slice_coo_arbitrary_logical, 13),
     MX_ENTRY(slice_coo_arbitrary_binary, 12),
+    MX_ENTRY(remove_zero_valued_csr_numeric, 4), MX_ENTRY(remove_zero_valued_csr_logical, 4),
+    MX_ENTRY(remove_zero_valued_coo_numeric, 4), MX_ENTRY(remove_zero_valued_coo_logical, 4),
+    MX_ENTRY(remove_zero_valued_svec_numeric, 3), MX_ENTRY(remove_zero_valued_svec_integer, 3),
+    MX_ENTRY(remove_zero_valued_svec_logical, 3),
+    MX_ENTRY(check_valid_csr_matrix, 4), MX_ENTRY(check_valid_coo_matrix, 4), MX_ENTRY(check_valid_svec, 2),
+    MX_ENTRY(rebuild_indptr_after_filter, 2),
     {"mxgpu_csr_transpose", (DL_FUNC)&mxgpu_csr_transpose, 4},
     {"mxgpu_coo_to_csr", (DL_FUNC)&mxgpu_coo_to_csr, 5},
     {NULL, NULL, 0}

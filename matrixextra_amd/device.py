@@ -320,3 +320,49 @@ def coo_slice(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor | None, m: int, 
                                      _stream()))
     del keep_i, keep_j          # the maps stay alive until both launches are enqueued (torch's caching allocator
     return oi[:k], oj[:k], None if ox is None else ox[:k]      # reuses the blocks only on this same stream)
+
+
+def _csr_compact(A: DeviceCSR, rule: int, mask: torch.Tensor | None) -> DeviceCSR:
+    """count (one 8-byte read-back) -> fill through mxd_compact_count / _fill; A itself when a zero rule keeps all."""
+    lib = _lib.load()
+    dev = A.indptr.device
+    vd = _value_dtype(A.values)
+    ws = torch.empty(max(lib.mxd_compact_workspace_bytes(A.nnz), 16), dtype=torch.uint8, device=dev)
+    kept = C.c_int64(0)
+    check(lib.mxd_compact_count(C.c_int64(A.nnz), _dp(A.values), C.c_int(vd), C.c_int(rule), _dp(mask), _dp(ws),
+                                C.byref(kept), _stream()))
+    k = int(kept.value)
+    if k == A.nnz and rule != _lib.MX_KEEP_MASK:
+        return A
+    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
+    out_j = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    out_x = torch.empty(max(k, 1), dtype=A.values.dtype, device=dev)
+    check(lib.mxd_compact_fill(C.c_int64(A.nnz), _dp(A.values), C.c_int(vd), C.c_int(rule), _dp(mask),
+                               _dp(A.indices), None, C.c_int(A.m), _dp(A.indptr), _dp(ws), _dp(out_j), None,
+                               _dp(out_x), _dp(out_p), _stream()))
+    return DeviceCSR(out_p, out_j[:k], out_x[:k], A.m, A.K, k)
+
+
+def csr_remove_zeros(A: DeviceCSR, na_rm: bool = False) -> DeviceCSR:
+    """remove_sparse_zeros of a device-resident CSR (or CSC) with the reference's keep rules (remove_zero_valued_csr_*,
+    src/misc.cpp:553-699): f64 drops 0 (and NaN with na_rm); R logicals drop FALSE, or with na_rm only NA.  Returns
+    A itself when nothing is removed (and for a pattern A)."""
+    if A.values is None:
+        return A
+    vd = _value_dtype(A.values)
+    rule = _lib.MX_KEEP_NONZERO
+    if na_rm:
+        rule = _lib.MX_KEEP_NONZERO_NOT_NA if vd == MX_F64 else _lib.MX_KEEP_NOT_NA
+    return _csr_compact(A, rule, None)
+
+
+def csr_filter(A: DeviceCSR, mask: torch.Tensor) -> DeviceCSR:
+    """filterSparse of a device-resident CSR: keeps entry k where mask[k] (bool, or int32 R logical) is TRUE or NA;
+    an NA writes NA_real_ / NA_LOGICAL as the value."""
+    if A.values is None:
+        raise ValueError("Method is only applicable for sparse objects with values (slot 'x').")
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.int32)
+    if mask.dtype != torch.int32 or mask.numel() != A.nnz or mask.device != A.indptr.device:
+        raise ValueError(f"mask must be {A.nnz} bool / int32 entries on {A.indptr.device}")
+    return _csr_compact(A, _lib.MX_KEEP_MASK, mask.contiguous())

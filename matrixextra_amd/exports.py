@@ -135,7 +135,7 @@ def matmul_csr_dvec_float32(X_csr_indptr, X_csr_indices, X_csr_values, y_dense, 
 
 
 # ----------------------------------------------------------------------------- list results
-_VDT = {MX_F64: np.float64, MX_LGL: np.int32}
+_VDT = {MX_F64: np.float64, MX_LGL: np.int32, _lib.MX_I32: np.int32}
 
 
 def _finish(res, info, alias_from=None, empty_values_dtype=np.float64):
@@ -760,3 +760,154 @@ def slice_coo_single_binary(ii, jj, i, j) -> bool:
     """src/slice_coo.cpp:55-71: TRUE when some triplet sits at (i, j)."""
     hit, _ = _slice_coo_single(ii, jj, None, MX_NONE, i, j)
     return hit
+
+
+# ----------------------------------------------------------------------------- remove_sparse_zeros / filterSparse /
+#                                                                               check_sparse_matrix (compact.hip)
+def _compacted(res, info, inputs, vdt):
+    """(indptr-or-ii, indices, values) of a compaction result: the input objects themselves when nothing was removed
+    (MX_ALIAS_ALL), else the new vectors."""
+    lib = _lib.load()
+    if info.alias_structure == _lib.MX_ALIAS_ALL:
+        lib.mx_result_discard(res)
+        return inputs
+    out = _finish(res, info, empty_values_dtype=vdt)
+    return out["indptr"], out["indices"], out["values"].astype(vdt, copy=False)
+
+
+def _remove_zeros_csr(fn, indptr, indices, values, remove_NAs, vdt):
+    p, j, v = _i32(indptr), _i32(indices), np.ascontiguousarray(values, dtype=vdt)
+    if j.size != v.size or p.size < 1:
+        raise ValueError("indptr, indices and values do not form a CSR")
+    res, info = C.c_void_p(), ResultInfo()
+    check(fn(ptr(p), ptr(j), ptr(v), C.c_int(p.size - 1), C.c_int(int(bool(remove_NAs))), C.byref(res),
+             C.byref(info)))
+    a, b, c = _compacted(res, info, (indptr, indices, values), vdt)
+    return dict(indptr=a, indices=b, values=c)
+
+
+def remove_zero_valued_csr_numeric(indptr, indices, values, remove_NAs):
+    """src/misc.cpp:667-683: dict(indptr, indices, values); the inputs themselves when nothing is removed."""
+    return _remove_zeros_csr(_lib.load().mx_remove_zero_valued_csr_numeric, indptr, indices, values, remove_NAs,
+                             np.float64)
+
+
+def remove_zero_valued_csr_logical(indptr, indices, values, remove_NAs):
+    """src/misc.cpp:684-699 (with remove_NAs only NA is removed, FALSE is kept: misc.cpp:637-648)."""
+    return _remove_zeros_csr(_lib.load().mx_remove_zero_valued_csr_logical, indptr, indices, values, remove_NAs,
+                             np.int32)
+
+
+def _remove_zeros_coo(fn, ii, jj, xx, remove_NAs, vdt):
+    i, j, v = _i32(ii), _i32(jj), np.ascontiguousarray(xx, dtype=vdt)
+    if not (i.size == j.size == v.size):
+        raise ValueError("ii, jj and xx have different lengths")
+    res, info = C.c_void_p(), ResultInfo()
+    check(fn(ptr(i), ptr(j), ptr(v), C.c_int64(i.size), C.c_int(int(bool(remove_NAs))), C.byref(res), C.byref(info)))
+    a, b, c = _compacted(res, info, (ii, jj, xx), vdt)
+    return dict(ii=a, jj=b, xx=c)
+
+
+def remove_zero_valued_coo_numeric(ii, jj, xx, remove_NAs):
+    """src/misc.cpp:790-806: dict(ii, jj, xx)."""
+    return _remove_zeros_coo(_lib.load().mx_remove_zero_valued_coo_numeric, ii, jj, xx, remove_NAs, np.float64)
+
+
+def remove_zero_valued_coo_logical(ii, jj, xx, remove_NAs):
+    """src/misc.cpp:807-822."""
+    return _remove_zeros_coo(_lib.load().mx_remove_zero_valued_coo_logical, ii, jj, xx, remove_NAs, np.int32)
+
+
+def _remove_zeros_svec(fn, ii, xx, remove_NAs, vdt):
+    i, v = _i32(ii), np.ascontiguousarray(xx, dtype=vdt)
+    if i.size != v.size:
+        raise ValueError("ii and xx have different lengths")
+    res, info = C.c_void_p(), ResultInfo()
+    check(fn(ptr(i), ptr(v), C.c_int64(i.size), C.c_int(int(bool(remove_NAs))), C.byref(res), C.byref(info)))
+    _, b, c = _compacted(res, info, (None, ii, xx), vdt)
+    return dict(ii=b, xx=c)
+
+
+def remove_zero_valued_svec_numeric(ii, xx, remove_NAs):
+    """src/misc.cpp:925-938 (with remove_NAs NaN is still kept: misc.cpp:882-886)."""
+    return _remove_zeros_svec(_lib.load().mx_remove_zero_valued_svec_numeric, ii, xx, remove_NAs, np.float64)
+
+
+def remove_zero_valued_svec_integer(ii, xx, remove_NAs):
+    """src/misc.cpp:940-953."""
+    return _remove_zeros_svec(_lib.load().mx_remove_zero_valued_svec_integer, ii, xx, remove_NAs, np.int32)
+
+
+def remove_zero_valued_svec_logical(ii, xx, remove_NAs):
+    """src/misc.cpp:955-968."""
+    return _remove_zeros_svec(_lib.load().mx_remove_zero_valued_svec_logical, ii, xx, remove_NAs, np.int32)
+
+
+def _filter(layout, indptr, idx0, idx1, values, mask):
+    v, vd = _values_kind(values)
+    if v is None:
+        raise TypeError("filtering needs values")
+    i0 = _i32(idx0)
+    i1 = None if idx1 is None else _i32(idx1)
+    mk = _i32(mask)
+    if mk.size != i0.size or v.size != i0.size or (i1 is not None and i1.size != i0.size):
+        raise ValueError("mask, indices and values have different lengths")
+    p = None if indptr is None else _i32(indptr)
+    res, info = C.c_void_p(), ResultInfo()
+    check(_lib.load().mx_filter_sparse_begin(C.c_int(layout), ptr(p), C.c_int(0 if p is None else p.size - 1),
+                                             ptr(i0), ptr(i1), ptr(v), C.c_int(vd), C.c_int64(i0.size), ptr(mk),
+                                             C.byref(res), C.byref(info)))
+    return _compacted(res, info, None, v.dtype)
+
+
+def filter_csr(indptr, indices, values, mask):
+    """filterSparse of a CSR / CSC (R/utils.R:655-674): keeps entry k where the R-logical mask[k] is TRUE or NA (NA
+    writes NA_real_ / NA_LOGICAL as its value); the indptr is rebuilt as rebuild_indptr_after_filter does."""
+    a, b, c = _filter(0, indptr, indices, None, values, mask)
+    return dict(indptr=a, indices=b, values=c)
+
+
+def filter_coo(ii, jj, xx, mask):
+    """filterSparse of a COO (R/utils.R:628-637)."""
+    a, b, c = _filter(1, None, ii, jj, xx, mask)
+    return dict(ii=a, jj=b, xx=c)
+
+
+def rebuild_indptr_after_filter(indptr, filter):
+    """src/misc.cpp:1099-1116: the indptr after dropping the entries whose R-logical filter is FALSE (0)."""
+    p, f = _i32(indptr), _i32(filter)
+    out = np.empty(p.size, dtype=np.int32)
+    check(_lib.load().mx_rebuild_indptr_after_filter(ptr(p), C.c_int64(p.size), ptr(f), ptr(out)))
+    return out
+
+
+def _err(e):
+    return {} if e.value is None else dict(err=e.value.decode())
+
+
+def check_valid_csr_matrix(indptr, indices, nrows, ncols):
+    """src/misc.cpp:970-1017: {} when valid, else dict(err=<the reference's message of the first failing check>)."""
+    p, j = _i32(indptr), _i32(indices)
+    e = C.c_char_p()
+    check(_lib.load().mx_check_valid_csr_matrix(ptr(p), C.c_int64(p.size), ptr(j), C.c_int64(j.size),
+                                                C.c_int(int(nrows)), C.c_int(int(ncols)), C.byref(e)))
+    return _err(e)
+
+
+def check_valid_coo_matrix(ii, jj, nrows, ncols):
+    """src/misc.cpp:1018-1068."""
+    i, j = _i32(ii), _i32(jj)
+    if i.size != j.size:
+        raise ValueError("ii and jj have different lengths")
+    e = C.c_char_p()
+    check(_lib.load().mx_check_valid_coo_matrix(ptr(i), ptr(j), C.c_int64(i.size), C.c_int(int(nrows)),
+                                                C.c_int(int(ncols)), C.byref(e)))
+    return _err(e)
+
+
+def check_valid_svec(ii, nrows):
+    """src/misc.cpp:1069-1097 (the R caller passes the 1-based @i and the length)."""
+    i = _i32(ii)
+    e = C.c_char_p()
+    check(_lib.load().mx_check_valid_svec(ptr(i), C.c_int64(i.size), C.c_int(int(nrows)), C.byref(e)))
+    return _err(e)
