@@ -241,6 +241,31 @@ int mxd_csr_by_dense_elemwise(int m, int64_t nnz, const int32_t *indptr, const i
                               const void *values, const void *dense_colmajor, int kind, void *values_out,
                               void *stream);
 
+/* CSC (.) dense (multiply_csc_by_dense_{ignore,keep}_NAs_*, src/operators.cpp:1061-1460).  X is
+ * nrows x ncols in CSC (indptr[ncols+1], row indices, f64 values; kind 4: int32 R logicals); the dense operand is
+ * column-major nrows x ncols.  kind / dense_kind: 0 double, 1 float32, 2 R integer, 3 R logical, 4 (values only) R's
+ * three-valued & of R logicals.
+ * mxd_csc_by_dense_elemwise: values only, out[k] = x[k] (op) dense[indices[k] + nrows*col(k)] with the arithmetic of
+ *   mxd_csr_by_dense_elemwise (svec.hip's kernel with CSC addressing): f64 / float32 x * d, integer / logical NA ->
+ *   NA_real_.
+ * NA-keeping route, for a CSC whose rows are sorted inside each column: output column c holds the stored rows (a
+ *   repeated row once, with the first entry's value) and every row whose dense cell is NA (any NaN; NA_INTEGER) and
+ *   not stored, with value NA_real_; rows ascending.  count: *nnz_out_host = output entries (64-bit; above INT32_MAX
+ *   the call fails), *na_outside_host = 1 when some NA cell lies outside the pattern, else 0 (one synchronise).  When
+ *   that is 0 and the count equals nnz the structure is unchanged, and mxd_csc_by_dense_elemwise gives the values.  fill: out_indptr[ncols+1],
+ *   out_indices / out_values (that many entries).  workspace: mxd_csc_dense_na_workspace_bytes(nrows, ncols), holding
+ *   a 1-bit-per-cell NA mask; shared by both passes. */
+int mxd_csc_by_dense_elemwise(int ncols, int nrows, int64_t nnz, const int32_t *indptr, const int32_t *indices,
+                              const void *values, const void *dense_colmajor, int kind, void *values_out,
+                              void *stream);
+size_t mxd_csc_dense_na_workspace_bytes(int nrows, int ncols);
+int mxd_csc_dense_na_count(int nrows, int ncols, int64_t nnz, const int32_t *indptr, const int32_t *indices,
+                           const void *dense_colmajor, int dense_kind, void *workspace, int64_t *nnz_out_host,
+                           int64_t *na_outside_host, void *stream);
+int mxd_csc_dense_na_fill(int nrows, int ncols, int64_t nnz, const int32_t *indptr, const int32_t *indices,
+                          const double *values, const void *dense_colmajor, int dense_kind, const void *workspace,
+                          int32_t *out_indptr, int32_t *out_indices, double *out_values, void *stream);
+
 /* CSR (op) dense vector with R's recycling (multiply_csr_by_dvec_no_NAs<>, src/operators.cpp:1604-2140): a
  * values-only transform, out[k] = values[k] op dvec[(row + col*m) mod dvec_len] (`recyle_pos`, :1478; the reference's
  * four length branches :1640,1773,1870,2033 all reduce to it).  op: R's * ^ / %% %/% on f64 values with the sparse
@@ -502,6 +527,42 @@ int mx_matmul_csr_svec(const int32_t *X_indptr, const int32_t *X_indices, const 
  * dense_mat column-major nrows x ncols; values_out has nnz entries (f64, or int32 for kind 4). */
 int mx_multiply_csr_by_dense_elemwise(const int32_t *indptr, const int32_t *indices, const void *values, int nrows,
                                       const void *dense_mat, int64_t ncols, int kind, void *values_out);
+/* multiply_csc_by_dense_ignore_NAs_{numeric,float32,integer,logical}  src/operators.cpp:1125-1189 and
+ * logicaland_csc_by_dense_ignore_NAs  :1191-1206 (RcppExports.cpp:2310-2314): X CSC with ncols columns
+ * (indptr[ncols+1]), dense column-major nrows x ncols; values_out has nnz entries (f64; int32 R logicals for the
+ * logicaland), in storage order. */
+int mx_multiply_csc_by_dense_ignore_NAs_numeric(const int32_t *indptr, int ncols, const int32_t *indices,
+                                                const double *values, const double *dense, int nrows,
+                                                double *values_out);
+int mx_multiply_csc_by_dense_ignore_NAs_float32(const int32_t *indptr, int ncols, const int32_t *indices,
+                                                const double *values, const float *dense, int nrows,
+                                                double *values_out);
+int mx_multiply_csc_by_dense_ignore_NAs_integer(const int32_t *indptr, int ncols, const int32_t *indices,
+                                                const double *values, const int32_t *dense, int nrows,
+                                                double *values_out);
+int mx_multiply_csc_by_dense_ignore_NAs_logical(const int32_t *indptr, int ncols, const int32_t *indices,
+                                                const double *values, const int32_t *dense, int nrows,
+                                                double *values_out);
+int mx_logicaland_csc_by_dense_ignore_NAs(const int32_t *indptr, int ncols, const int32_t *indices,
+                                          const int32_t *values, const int32_t *dense, int nrows,
+                                          int32_t *values_out);
+/* multiply_csc_by_dense_keep_NAs_{numeric,integer,logical,float32}  src/operators.cpp:1388-1458
+ * (RcppExports.cpp:2315-2318), through mxd_csc_dense_na_count / _fill: a new indptr (ncols + 1), indices and f64
+ * values; rows must be sorted inside each column (the R caller sorts, R/operators.R:626-630).  A result of more than
+ * INT32_MAX entries fails before anything is allocated for it.  logicaland_csc_by_dense_keep_NAs (:1460-) is not
+ * provided. */
+int mx_multiply_csc_by_dense_keep_NAs_numeric(const int32_t *indptr, int ncols, const int32_t *indices,
+                                              const double *values, const double *dense, int nrows,
+                                              mx_result **res, mx_result_info *info);
+int mx_multiply_csc_by_dense_keep_NAs_integer(const int32_t *indptr, int ncols, const int32_t *indices,
+                                              const double *values, const int32_t *dense, int nrows,
+                                              mx_result **res, mx_result_info *info);
+int mx_multiply_csc_by_dense_keep_NAs_logical(const int32_t *indptr, int ncols, const int32_t *indices,
+                                              const double *values, const int32_t *dense, int nrows,
+                                              mx_result **res, mx_result_info *info);
+int mx_multiply_csc_by_dense_keep_NAs_float32(const int32_t *indptr, int ncols, const int32_t *indices,
+                                              const double *values, const float *dense, int nrows,
+                                              mx_result **res, mx_result_info *info);
 /* multiply_csr_by_dvec_no_NAs_numeric  src/operators.cpp:2142-2175: exactly one of the five flags is set (as the R
  * caller passes them, R/operators.R:1134-1137); values_out f64[nnz].  The structure-changing NA route
  * (multiply_csr_by_dvec_with_NAs, :2258-) is not provided. */

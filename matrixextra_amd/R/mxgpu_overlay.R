@@ -46,7 +46,13 @@
     "remove_zero_valued_csr_numeric", "remove_zero_valued_csr_logical",
     "remove_zero_valued_coo_numeric", "remove_zero_valued_coo_logical",
     "remove_zero_valued_svec_numeric", "remove_zero_valued_svec_integer", "remove_zero_valued_svec_logical",
-    "check_valid_csr_matrix", "check_valid_coo_matrix", "check_valid_svec", "rebuild_indptr_after_filter"
+    "check_valid_csr_matrix", "check_valid_coo_matrix", "check_valid_svec", "rebuild_indptr_after_filter",
+    ## CsparseMatrix * matrix (multiply_csc_by_dense, R/operators.R:568-710)
+    "multiply_csc_by_dense_ignore_NAs_numeric", "multiply_csc_by_dense_ignore_NAs_float32",
+    "multiply_csc_by_dense_ignore_NAs_integer", "multiply_csc_by_dense_ignore_NAs_logical",
+    "logicaland_csc_by_dense_ignore_NAs",
+    "multiply_csc_by_dense_keep_NAs_numeric", "multiply_csc_by_dense_keep_NAs_integer",
+    "multiply_csc_by_dense_keep_NAs_logical", "multiply_csc_by_dense_keep_NAs_float32"
 )
 
 mxgpu_enable <- function(shim_path, min_nnz = 0L) {

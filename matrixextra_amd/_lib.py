@@ -79,6 +79,8 @@ def load() -> C.CDLL:
     lib.mxd_coo_single_workspace_bytes.argtypes = []
     lib.mxd_compact_workspace_bytes.restype = C.c_size_t
     lib.mxd_compact_workspace_bytes.argtypes = [C.c_int64]
+    lib.mxd_csc_dense_na_workspace_bytes.restype = C.c_size_t
+    lib.mxd_csc_dense_na_workspace_bytes.argtypes = [C.c_int, C.c_int]
     if lib.mx_abi_version() != 1:
         raise MxError("libmxgpu.so ABI version mismatch")
     _lib = lib

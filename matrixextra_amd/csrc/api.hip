@@ -564,6 +564,126 @@ int mx_multiply_csr_by_dense_elemwise(const int32_t *indptr, const int32_t *indi
     return 0;
 }
 
+// ---- CSC (.) dense (svec.hip, cscdense.hip) -------------------------------------------------
+// values only (multiply_csc_by_dense_ignore_NAs<>, operators.cpp:1061-1122): the structure stays the caller's
+static int csc_by_dense_ignore(const int32_t *indptr, int ncols, const int32_t *indices, const void *values,
+                               const void *dense, int nrows, int kind, void *values_out)
+{
+    MX_REQUIRE(indptr && ncols >= 0 && nrows >= 0 && kind >= 0 && kind <= 4, "csc (.) dense: bad arguments");
+    if (ncols == 0) return 0;
+    const size_t vb = kind == 4 ? 4 : 8, db = kind == 0 ? 8 : 4;
+    Csr A;
+    if (A.upload(indptr, indices, values, ncols, vb)) return 1;
+    if (A.nnz == 0) return 0;
+    MX_REQUIRE(nrows > 0 && dense && values_out, "csc (.) dense: entries in a matrix without rows");
+    DevBuf D, o;
+    if (D.upload(dense, db * (size_t)nrows * (size_t)ncols)) return 1;
+    if (o.alloc(vb * (size_t)A.nnz)) return 1;
+    if (mxd_csc_by_dense_elemwise(ncols, nrows, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, D.p, kind, o.p,
+                                  nullptr)) return 1;
+    return mx::xfer_d2h(values_out, o.p, vb * (size_t)A.nnz);
+}
+
+// NA-keeping (multiply_csc_by_dense_keep_NAs_template<>, operators.cpp:1207-1386): count -> scan -> read-back, then
+// the fill, or the values-only kernel when the structure does not change
+static int csc_by_dense_keep(const int32_t *indptr, int ncols, const int32_t *indices, const double *values,
+                             const void *dense, int nrows, int kind, mx_result **res_out, mx_result_info *info)
+{
+    MX_REQUIRE(res_out && info && indptr && ncols >= 0 && nrows >= 0, "csc (.) dense: bad arguments");
+    MX_REQUIRE(indptr[0] == 0 && indptr[ncols] >= 0, "csc (.) dense: bad index pointer");
+    *res_out = nullptr;
+    const size_t db = kind == 0 ? 8 : 4;
+    return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
+        Csr A;
+        if (A.upload(indptr, indices, values, ncols, sizeof(double))) return 1;
+        DevBuf D, ws;
+        if (D.upload(dense, db * (size_t)nrows * (size_t)ncols)) return 1;
+        if (ws.alloc(mxd_csc_dense_na_workspace_bytes(nrows, ncols))) return 1;
+        int64_t total = 0, outside = 0;
+        if (mxd_csc_dense_na_count(nrows, ncols, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), D.p, kind, ws.p, &total,
+                                   &outside, nullptr)) return 1;
+        res.set_sizes((int64_t)ncols + 1, total, total);
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)ncols + 1))) return 1;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
+        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+        if (outside == 0 && total == A.nnz) {           // no NA cell outside the pattern, no repeated row
+            MX_HIP(hipMemcpyAsync(res.indptr.p, A.p.p, sizeof(int32_t) * ((size_t)ncols + 1), hipMemcpyDeviceToDevice,
+                                  nullptr));
+            MX_HIP(hipMemcpyAsync(res.indices.p, A.j.p, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToDevice,
+                                  nullptr));
+            return mxd_csc_by_dense_elemwise(ncols, nrows, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, D.p,
+                                             kind, res.values.p, nullptr);
+        }
+        return mxd_csc_dense_na_fill(nrows, ncols, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.as<double>(), D.p,
+                                     kind, ws.p, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
+                                     res.values.as<double>(), nullptr);
+    });
+}
+
+// multiply_csc_by_dense_ignore_NAs_numeric  src/operators.cpp:1125-1139
+int mx_multiply_csc_by_dense_ignore_NAs_numeric(const int32_t *indptr, int ncols, const int32_t *indices,
+                                                const double *values, const double *dense, int nrows,
+                                                double *values_out)
+{
+    return csc_by_dense_ignore(indptr, ncols, indices, values, dense, nrows, 0, values_out);
+}
+// multiply_csc_by_dense_ignore_NAs_float32  :1140-1155 (float32@Data bit patterns)
+int mx_multiply_csc_by_dense_ignore_NAs_float32(const int32_t *indptr, int ncols, const int32_t *indices,
+                                                const double *values, const float *dense, int nrows,
+                                                double *values_out)
+{
+    return csc_by_dense_ignore(indptr, ncols, indices, values, dense, nrows, 1, values_out);
+}
+// multiply_csc_by_dense_ignore_NAs_integer  :1157-1172
+int mx_multiply_csc_by_dense_ignore_NAs_integer(const int32_t *indptr, int ncols, const int32_t *indices,
+                                                const double *values, const int32_t *dense, int nrows,
+                                                double *values_out)
+{
+    return csc_by_dense_ignore(indptr, ncols, indices, values, dense, nrows, 2, values_out);
+}
+// multiply_csc_by_dense_ignore_NAs_logical  :1174-1189
+int mx_multiply_csc_by_dense_ignore_NAs_logical(const int32_t *indptr, int ncols, const int32_t *indices,
+                                                const double *values, const int32_t *dense, int nrows,
+                                                double *values_out)
+{
+    return csc_by_dense_ignore(indptr, ncols, indices, values, dense, nrows, 3, values_out);
+}
+// logicaland_csc_by_dense_ignore_NAs  :1191-1206
+int mx_logicaland_csc_by_dense_ignore_NAs(const int32_t *indptr, int ncols, const int32_t *indices,
+                                          const int32_t *values, const int32_t *dense, int nrows,
+                                          int32_t *values_out)
+{
+    return csc_by_dense_ignore(indptr, ncols, indices, values, dense, nrows, 4, values_out);
+}
+// multiply_csc_by_dense_keep_NAs_numeric  :1388-1404
+int mx_multiply_csc_by_dense_keep_NAs_numeric(const int32_t *indptr, int ncols, const int32_t *indices,
+                                              const double *values, const double *dense, int nrows,
+                                              mx_result **res, mx_result_info *info)
+{
+    return csc_by_dense_keep(indptr, ncols, indices, values, dense, nrows, 0, res, info);
+}
+// multiply_csc_by_dense_keep_NAs_integer  :1406-1422
+int mx_multiply_csc_by_dense_keep_NAs_integer(const int32_t *indptr, int ncols, const int32_t *indices,
+                                              const double *values, const int32_t *dense, int nrows,
+                                              mx_result **res, mx_result_info *info)
+{
+    return csc_by_dense_keep(indptr, ncols, indices, values, dense, nrows, 2, res, info);
+}
+// multiply_csc_by_dense_keep_NAs_logical  :1424-1440
+int mx_multiply_csc_by_dense_keep_NAs_logical(const int32_t *indptr, int ncols, const int32_t *indices,
+                                              const double *values, const int32_t *dense, int nrows,
+                                              mx_result **res, mx_result_info *info)
+{
+    return csc_by_dense_keep(indptr, ncols, indices, values, dense, nrows, 3, res, info);
+}
+// multiply_csc_by_dense_keep_NAs_float32  :1442-1458
+int mx_multiply_csc_by_dense_keep_NAs_float32(const int32_t *indptr, int ncols, const int32_t *indices,
+                                              const double *values, const float *dense, int nrows,
+                                              mx_result **res, mx_result_info *info)
+{
+    return csc_by_dense_keep(indptr, ncols, indices, values, dense, nrows, 1, res, info);
+}
+
 // ---- CSR (op) dense vector (§8f rank 4) ----------------------------------------------------------------------
 static int csr_by_dvec_export(const int32_t *indptr, const int32_t *indices, const void *values, int nrows,
                               const void *dvec, int64_t dvec_len, int ncols, int op, int lhs, void *values_out)

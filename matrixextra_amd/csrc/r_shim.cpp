@@ -724,6 +724,55 @@ SEXP _MatrixExtra_rebuild_indptr_after_filter(SEXP p_, SEXP filter)
     return out;
 }
 
+// CSC (.) dense  (src/operators.cpp:1061-1458; glue src/RcppExports.cpp:1464-1580, 4 arguments each): dense_ is the
+// matrix (float32: the float32@Data INTSXP bit patterns), its row count nrow(dense_).  The ignore_NAs routines return
+// the values vector, the keep_NAs ones list(indptr, indices, values).
+static SEXP csc_dense(int kind, bool keep, SEXP p_, SEXP i_, SEXP x_, SEXP dense_)
+{
+    Protect p;
+    const int nrows = Rf_nrows(dense_);
+    p_ = as_type(p_, INTSXP, p); i_ = as_type(i_, INTSXP, p);
+    x_ = as_type(x_, kind == 4 ? LGLSXP : REALSXP, p);
+    dense_ = as_type(dense_, kind == 0 ? REALSXP : kind == 3 || kind == 4 ? LGLSXP : INTSXP, p);
+    const int ncols = (int)XLENGTH(p_) - 1;
+    if (XLENGTH(x_) != XLENGTH(i_)) Rf_error("multiply_csc_by_dense: indices and values have different length");
+    if ((R_xlen_t)nrows * ncols != XLENGTH(dense_)) Rf_error("multiply_csc_by_dense: dense matrix does not match");
+    const int32_t *ip = INTEGER(p_), *ii = INTEGER(i_);
+    if (keep) {
+        mx_result *res = nullptr;
+        mx_result_info info;
+        int rc;
+        switch (kind) {
+            case 0: rc = mx_multiply_csc_by_dense_keep_NAs_numeric(ip, ncols, ii, REAL(x_), REAL(dense_), nrows, &res, &info); break;
+            case 1: rc = mx_multiply_csc_by_dense_keep_NAs_float32(ip, ncols, ii, REAL(x_), f32(dense_), nrows, &res, &info); break;
+            case 2: rc = mx_multiply_csc_by_dense_keep_NAs_integer(ip, ncols, ii, REAL(x_), INTEGER(dense_), nrows, &res, &info); break;
+            default: rc = mx_multiply_csc_by_dense_keep_NAs_logical(ip, ncols, ii, REAL(x_), LOGICAL(dense_), nrows, &res, &info); break;
+        }
+        if (rc) fail();
+        return finish_guarded(res, info, R_NilValue, R_NilValue);
+    }
+    SEXP out = p(Rf_allocVector(kind == 4 ? LGLSXP : REALSXP, XLENGTH(x_)));
+    int rc;
+    switch (kind) {
+        case 0: rc = mx_multiply_csc_by_dense_ignore_NAs_numeric(ip, ncols, ii, REAL(x_), REAL(dense_), nrows, REAL(out)); break;
+        case 1: rc = mx_multiply_csc_by_dense_ignore_NAs_float32(ip, ncols, ii, REAL(x_), f32(dense_), nrows, REAL(out)); break;
+        case 2: rc = mx_multiply_csc_by_dense_ignore_NAs_integer(ip, ncols, ii, REAL(x_), INTEGER(dense_), nrows, REAL(out)); break;
+        case 3: rc = mx_multiply_csc_by_dense_ignore_NAs_logical(ip, ncols, ii, REAL(x_), LOGICAL(dense_), nrows, REAL(out)); break;
+        default: rc = mx_logicaland_csc_by_dense_ignore_NAs(ip, ncols, ii, LOGICAL(x_), LOGICAL(dense_), nrows, LOGICAL(out)); break;
+    }
+    if (rc) fail();
+    return out;
+}
+SEXP _MatrixExtra_multiply_csc_by_dense_ignore_NAs_numeric(SEXP p_, SEXP i_, SEXP x_, SEXP d) { return csc_dense(0, false, p_, i_, x_, d); }
+SEXP _MatrixExtra_multiply_csc_by_dense_ignore_NAs_float32(SEXP p_, SEXP i_, SEXP x_, SEXP d) { return csc_dense(1, false, p_, i_, x_, d); }
+SEXP _MatrixExtra_multiply_csc_by_dense_ignore_NAs_integer(SEXP p_, SEXP i_, SEXP x_, SEXP d) { return csc_dense(2, false, p_, i_, x_, d); }
+SEXP _MatrixExtra_multiply_csc_by_dense_ignore_NAs_logical(SEXP p_, SEXP i_, SEXP x_, SEXP d) { return csc_dense(3, false, p_, i_, x_, d); }
+SEXP _MatrixExtra_logicaland_csc_by_dense_ignore_NAs(SEXP p_, SEXP i_, SEXP x_, SEXP d) { return csc_dense(4, false, p_, i_, x_, d); }
+SEXP _MatrixExtra_multiply_csc_by_dense_keep_NAs_numeric(SEXP p_, SEXP i_, SEXP x_, SEXP d) { return csc_dense(0, true, p_, i_, x_, d); }
+SEXP _MatrixExtra_multiply_csc_by_dense_keep_NAs_integer(SEXP p_, SEXP i_, SEXP x_, SEXP d) { return csc_dense(2, true, p_, i_, x_, d); }
+SEXP _MatrixExtra_multiply_csc_by_dense_keep_NAs_logical(SEXP p_, SEXP i_, SEXP x_, SEXP d) { return csc_dense(3, true, p_, i_, x_, d); }
+SEXP _MatrixExtra_multiply_csc_by_dense_keep_NAs_float32(SEXP p_, SEXP i_, SEXP x_, SEXP d) { return csc_dense(1, true, p_, i_, x_, d); }
+
 #define MX_ENTRY(name, n) {"_MatrixExtra_" #name, (DL_FUNC)&_MatrixExtra_##name, n}
 static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(matmul_dense_csc_numeric, 5), MX_ENTRY(matmul_dense_csc_float32, 5),
@@ -753,6 +802,11 @@ static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(remove_zero_valued_svec_logical, 3),
     MX_ENTRY(check_valid_csr_matrix, 4), MX_ENTRY(check_valid_coo_matrix, 4), MX_ENTRY(check_valid_svec, 2),
     MX_ENTRY(rebuild_indptr_after_filter, 2),
+    MX_ENTRY(multiply_csc_by_dense_ignore_NAs_numeric, 4), MX_ENTRY(multiply_csc_by_dense_ignore_NAs_float32, 4),
+    MX_ENTRY(multiply_csc_by_dense_ignore_NAs_integer, 4), MX_ENTRY(multiply_csc_by_dense_ignore_NAs_logical, 4),
+    MX_ENTRY(logicaland_csc_by_dense_ignore_NAs, 4),
+    MX_ENTRY(multiply_csc_by_dense_keep_NAs_numeric, 4), MX_ENTRY(multiply_csc_by_dense_keep_NAs_integer, 4),
+    MX_ENTRY(multiply_csc_by_dense_keep_NAs_logical, 4), MX_ENTRY(multiply_csc_by_dense_keep_NAs_float32, 4),
     {"mxgpu_csr_transpose", (DL_FUNC)&mxgpu_csr_transpose, 4},
     {"mxgpu_coo_to_csr", (DL_FUNC)&mxgpu_coo_to_csr, 5},
     {NULL, NULL, 0}

@@ -3,9 +3,11 @@
 // Replaces:
 //   matmul_csr_svec<>                  src/matmul.cpp:486-641   per-row sorted intersection dot product
 //   multiply_csr_by_dense_elemwise<>   src/operators.cpp:239-334
+//   multiply_csc_by_dense_ignore_NAs<> src/operators.cpp:1061-1206 (the same kernel with CSC addressing)
 // csr x svec: G lanes per row; every entry of the row looks its column up in the (small, L2-resident) index
 // vector of y by binary search, the products are reduced with a butterfly.  NA rules as in SpMV.
 // csr (.) dense: one dense read per entry at [row + nrows*col] (column-major, a gather by construction).
+// With CSC set the compressed axis is the column and the read is at [indices[k] + nrows*col] (contiguous runs).
 #include "mx_common.h"
 
 namespace mx {
@@ -48,18 +50,19 @@ void csr_svec_kernel(int m, const int32_t *__restrict__ indptr, const int32_t *_
 }
 
 // KIND: 0 double, 1 float32, 2 integer, 3 logical (f64 values -> f64), 4 logical AND (int32 -> int32)
-template <int G, int KIND>
+// m compressed rows (CSR rows, or CSC columns); nr = rows of the column-major dense operand
+template <int G, int KIND, bool CSC = false>
 __global__ __launch_bounds__(SV_BLOCK)
-void csr_by_dense_kernel(int m, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+void csr_by_dense_kernel(int m, int64_t nr, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                          const void *__restrict__ values, const void *__restrict__ dense, void *__restrict__ out)
 {
     const int lg = threadIdx.x % G;
     const long long row = (long long)blockIdx.x * (SV_BLOCK / G) + threadIdx.x / G;
     if (row >= m) return;
     const int s = indptr[row], e = indptr[row + 1];
-    const size_t nr = (size_t)m;
     for (int k = s + lg; k < e; k += G) {
-        const size_t at = (size_t)row + nr * (size_t)indices[k];
+        const size_t at = CSC ? (size_t)indices[k] + (size_t)nr * (size_t)row
+                              : (size_t)row + (size_t)nr * (size_t)indices[k];
         if constexpr (KIND == 4) {
             ((int32_t *)out)[k] = r_logical_and(((const int32_t *)values)[k], ((const int32_t *)dense)[at]);
         } else {
@@ -113,12 +116,45 @@ extern "C" int mxd_csr_by_dense_elemwise(int m, int64_t nnz, const int32_t *indp
     if (m == 0 || nnz == 0) return 0;
     hipStream_t st = mx::as_stream(stream);
     const int G = nnz < 0 ? 32 : mx::pick_group((double)nnz / (double)m);
+    const int64_t nr = m;
     switch (kind) {
-        case 0: MX_SV_G(csr_by_dense_kernel, 0, m, indptr, indices, values, dense_colmajor, values_out); break;
-        case 1: MX_SV_G(csr_by_dense_kernel, 1, m, indptr, indices, values, dense_colmajor, values_out); break;
-        case 2: MX_SV_G(csr_by_dense_kernel, 2, m, indptr, indices, values, dense_colmajor, values_out); break;
-        case 3: MX_SV_G(csr_by_dense_kernel, 3, m, indptr, indices, values, dense_colmajor, values_out); break;
-        default: MX_SV_G(csr_by_dense_kernel, 4, m, indptr, indices, values, dense_colmajor, values_out); break;
+        case 0: MX_SV_G(csr_by_dense_kernel, 0, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
+        case 1: MX_SV_G(csr_by_dense_kernel, 1, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
+        case 2: MX_SV_G(csr_by_dense_kernel, 2, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
+        case 3: MX_SV_G(csr_by_dense_kernel, 3, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
+        default: MX_SV_G(csr_by_dense_kernel, 4, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
+    }
+    MX_LAUNCH_CHECK();
+    return 0;
+}
+
+// MX_SV_G for the CSC addressing of csr_by_dense_kernel; `m` is the number of columns there
+#define MX_SV_GC(KIND, ...)                                                                                    \
+    switch (G) {                                                                                               \
+        case 4:  hipLaunchKernelGGL((mx::csr_by_dense_kernel<4, KIND, true>),  dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 4)),  dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
+        case 8:  hipLaunchKernelGGL((mx::csr_by_dense_kernel<8, KIND, true>),  dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 8)),  dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
+        case 16: hipLaunchKernelGGL((mx::csr_by_dense_kernel<16, KIND, true>), dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 16)), dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
+        case 32: hipLaunchKernelGGL((mx::csr_by_dense_kernel<32, KIND, true>), dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 32)), dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
+        default: hipLaunchKernelGGL((mx::csr_by_dense_kernel<64, KIND, true>), dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 64)), dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
+    }
+
+extern "C" int mxd_csc_by_dense_elemwise(int ncols, int nrows, int64_t nnz, const int32_t *indptr,
+                                         const int32_t *indices, const void *values, const void *dense_colmajor,
+                                         int kind, void *values_out, void *stream)
+{
+    MX_REQUIRE(ncols >= 0 && nrows >= 0 && kind >= 0 && kind <= 4, "mxd_csc_by_dense_elemwise: bad arguments");
+    if (ncols == 0 || nnz == 0) return 0;
+    MX_REQUIRE(nrows > 0, "mxd_csc_by_dense_elemwise: entries in a matrix without rows");
+    hipStream_t st = mx::as_stream(stream);
+    const int m = ncols;
+    const int64_t nr = nrows;
+    const int G = nnz < 0 ? 32 : mx::pick_group((double)nnz / (double)m);
+    switch (kind) {
+        case 0: MX_SV_GC(0, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
+        case 1: MX_SV_GC(1, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
+        case 2: MX_SV_GC(2, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
+        case 3: MX_SV_GC(3, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
+        default: MX_SV_GC(4, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
     }
     MX_LAUNCH_CHECK();
     return 0;

@@ -356,6 +356,53 @@ def csr_remove_zeros(A: DeviceCSR, na_rm: bool = False) -> DeviceCSR:
     return _csr_compact(A, rule, None)
 
 
+def csc_by_dense(A: DeviceCSR, D: torch.Tensor, keep_na: bool = True, logical: bool = False):
+    """X * D for a device-resident CSC X and a dense tensor D of X's shape, as (p, i, x) tensors.
+    A holds X's CSC arrays as the CSR of X^T: A.indptr over the A.m columns, A.indices the rows, f64 A.values,
+    A.K = rows.  D: float64, float32, int32 (R integer; R logical with logical=True) or bool (R logical), any strides.
+    keep_na=True: every NA cell of D outside X's pattern becomes an NA_real_ entry and a repeated row is kept once
+    (rows must be sorted inside each column); the result is new tensors.  keep_na=False: values only; the result is
+    A.indptr itself, a copy of A.indices and the new values."""
+    lib = _lib.load()
+    dev = A.indptr.device
+    if A.values is None or A.values.dtype != torch.float64:
+        raise ValueError("csc_by_dense: X needs float64 values")
+    if D.dim() != 2 or tuple(D.shape) != (A.K, A.m):
+        raise ValueError(f"csc_by_dense: D must be {A.K} x {A.m}")
+    if D.dtype == torch.bool:
+        D, kind = D.to(torch.int32), 3
+    elif D.dtype == torch.int32:
+        kind = 3 if logical else 2
+    elif D.dtype in (torch.float64, torch.float32):
+        kind = 0 if D.dtype == torch.float64 else 1
+    else:
+        raise ValueError(f"csc_by_dense: unsupported dense dtype {D.dtype}")
+    Dc = D.t().contiguous()                         # row-major D^T = column-major D
+    out_x = torch.empty(max(A.nnz, 1), dtype=torch.float64, device=dev)
+    if not keep_na:
+        check(lib.mxd_csc_by_dense_elemwise(C.c_int(A.m), C.c_int(A.K), C.c_int64(A.nnz), _dp(A.indptr),
+                                            _dp(A.indices), _dp(A.values), _dp(Dc), C.c_int(kind), _dp(out_x),
+                                            _stream()))
+        return A.indptr, A.indices.clone(), out_x[:A.nnz]
+    ws = torch.empty(max(lib.mxd_csc_dense_na_workspace_bytes(A.K, A.m), 16), dtype=torch.uint8, device=dev)
+    total, outside = C.c_int64(0), C.c_int64(0)
+    check(lib.mxd_csc_dense_na_count(C.c_int(A.K), C.c_int(A.m), C.c_int64(A.nnz), _dp(A.indptr), _dp(A.indices),
+                                     _dp(Dc), C.c_int(kind), _dp(ws), C.byref(total), C.byref(outside), _stream()))
+    k = int(total.value)
+    if outside.value == 0 and k == A.nnz:           # the structure does not change: values only, new p and i
+        check(lib.mxd_csc_by_dense_elemwise(C.c_int(A.m), C.c_int(A.K), C.c_int64(A.nnz), _dp(A.indptr),
+                                            _dp(A.indices), _dp(A.values), _dp(Dc), C.c_int(kind), _dp(out_x),
+                                            _stream()))
+        return A.indptr.clone(), A.indices.clone(), out_x[:k]
+    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
+    out_i = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
+    check(lib.mxd_csc_dense_na_fill(C.c_int(A.K), C.c_int(A.m), C.c_int64(A.nnz), _dp(A.indptr), _dp(A.indices),
+                                    _dp(A.values), _dp(Dc), C.c_int(kind), _dp(ws), _dp(out_p), _dp(out_i),
+                                    _dp(out_x), _stream()))
+    return out_p, out_i[:k], out_x[:k]
+
+
 def csr_filter(A: DeviceCSR, mask: torch.Tensor) -> DeviceCSR:
     """filterSparse of a device-resident CSR: keeps entry k where mask[k] (bool, or int32 R logical) is TRUE or NA;
     an NA writes NA_real_ / NA_LOGICAL as the value."""

@@ -411,6 +411,90 @@ def logicaland_csr_by_dense_cpp(indptr, indices, values, dense_mat):
     return _csr_by_dense(4, indptr, indices, values, dense_mat)
 
 
+# ----------------------------------------------------------------------------- CSC (.) dense (svec.hip, cscdense.hip)
+_CSC_DENSE_DT = {0: np.float64, 1: np.float32, 2: np.int32, 3: np.int32, 4: np.int32}
+
+
+def _csc_dense_args(kind, indptr, indices, values, dense_):
+    p, i = _i32(indptr), _i32(indices)
+    D = _dense(dense_, _CSC_DENSE_DT[kind])
+    if p.size < 1 or D.shape[1] != p.size - 1:
+        raise ValueError("dense operand must have as many columns as the sparse one")
+    xv = np.ascontiguousarray(values, dtype=np.int32 if kind == 4 else np.float64)
+    if xv.size != i.size:
+        raise ValueError("indices and values have different lengths")
+    return p, i, xv, D
+
+
+def _csc_by_dense_ignore(fn, kind, indptr, indices, values, dense_):
+    p, i, xv, D = _csc_dense_args(kind, indptr, indices, values, dense_)
+    out = np.empty(xv.size, dtype=xv.dtype)
+    check(fn(ptr(p), C.c_int(p.size - 1), ptr(i), ptr(xv), ptr(D), C.c_int(D.shape[0]), ptr(out)))
+    return out
+
+
+def _csc_by_dense_keep(fn, kind, indptr, indices, values, dense_):
+    p, i, xv, D = _csc_dense_args(kind, indptr, indices, values, dense_)
+    res, info = C.c_void_p(), ResultInfo()
+    check(fn(ptr(p), C.c_int(p.size - 1), ptr(i), ptr(xv), ptr(D), C.c_int(D.shape[0]), C.byref(res), C.byref(info)))
+    return _finish(res, info)
+
+
+def multiply_csc_by_dense_ignore_NAs_numeric(indptr, indices, values, dense_):
+    """src/operators.cpp:1125-1139: x * d for every entry of the CSC, in storage order (values only)."""
+    return _csc_by_dense_ignore(_lib.load().mx_multiply_csc_by_dense_ignore_NAs_numeric, 0, indptr, indices, values,
+                                dense_)
+
+
+def multiply_csc_by_dense_ignore_NAs_float32(indptr, indices, values, dense_):
+    """src/operators.cpp:1140-1155: dense_ holds the float32 values (float32@Data), widened to f64 per entry."""
+    return _csc_by_dense_ignore(_lib.load().mx_multiply_csc_by_dense_ignore_NAs_float32, 1, indptr, indices, values,
+                                dense_)
+
+
+def multiply_csc_by_dense_ignore_NAs_integer(indptr, indices, values, dense_):
+    """src/operators.cpp:1157-1172: an NA_INTEGER cell gives NA_real_."""
+    return _csc_by_dense_ignore(_lib.load().mx_multiply_csc_by_dense_ignore_NAs_integer, 2, indptr, indices, values,
+                                dense_)
+
+
+def multiply_csc_by_dense_ignore_NAs_logical(indptr, indices, values, dense_):
+    """src/operators.cpp:1174-1189: R logical dense (int32 or bool); NA gives NA_real_."""
+    return _csc_by_dense_ignore(_lib.load().mx_multiply_csc_by_dense_ignore_NAs_logical, 3, indptr, indices, values,
+                                dense_)
+
+
+def logicaland_csc_by_dense_ignore_NAs(indptr, indices, values, dense_):
+    """src/operators.cpp:1191-1206: R logicals in and out, R's three-valued AND."""
+    return _csc_by_dense_ignore(_lib.load().mx_logicaland_csc_by_dense_ignore_NAs, 4, indptr, indices, values, dense_)
+
+
+def multiply_csc_by_dense_keep_NAs_numeric(indptr, indices_, values, dense_):
+    """src/operators.cpp:1388-1404: dict(indptr, indices, values) of the product with the NA cells of dense_ that lie
+    outside the pattern added as NA_real_ entries.  Rows must be sorted inside each column; a repeated row is kept
+    once, with the first entry's value."""
+    return _csc_by_dense_keep(_lib.load().mx_multiply_csc_by_dense_keep_NAs_numeric, 0, indptr, indices_, values,
+                              dense_)
+
+
+def multiply_csc_by_dense_keep_NAs_integer(indptr, indices_, values, dense_):
+    """src/operators.cpp:1406-1422 (NA cells: NA_INTEGER)."""
+    return _csc_by_dense_keep(_lib.load().mx_multiply_csc_by_dense_keep_NAs_integer, 2, indptr, indices_, values,
+                              dense_)
+
+
+def multiply_csc_by_dense_keep_NAs_logical(indptr, indices_, values, dense_):
+    """src/operators.cpp:1424-1440 (NA cells: NA_LOGICAL)."""
+    return _csc_by_dense_keep(_lib.load().mx_multiply_csc_by_dense_keep_NAs_logical, 3, indptr, indices_, values,
+                              dense_)
+
+
+def multiply_csc_by_dense_keep_NAs_float32(indptr, indices_, values, dense_):
+    """src/operators.cpp:1442-1458 (NA cells: any float32 NaN)."""
+    return _csc_by_dense_keep(_lib.load().mx_multiply_csc_by_dense_keep_NAs_float32, 1, indptr, indices_, values,
+                              dense_)
+
+
 # ----------------------------------------------------------------------------- cbind / rbind (§8f-3)
 def _cbind(Xp, Xj, Xx, Yp, Yj_plus_ncol, Yx, value_dtype, vdt):
     lib = _lib.load()

@@ -372,7 +372,8 @@ class ngTMatrix(TsparseMatrix):
 
 
 class dgCMatrix:
-    """Compressed sparse column, numeric: `matrix %*% CsparseMatrix`, t(), and +, -, * with an RsparseMatrix."""
+    """Compressed sparse column, numeric: `matrix %*% CsparseMatrix`, t(), +, -, * with an RsparseMatrix, and * with
+    a dense matrix or float32 on either side."""
     r_class = "dgCMatrix"
     __array_ufunc__ = None
 
@@ -425,14 +426,30 @@ class dgCMatrix:
         from . import operators
         if isinstance(other, TsparseMatrix):
             return t_shallow(operators.multiply_csr_by_coo(t_shallow(self), t_shallow(other), logical=False))
-        if not isinstance(other, RsparseMatrix):
-            return NotImplemented
-        return operators.multiply_csr_by_csr(self, other, logical=False)
+        if isinstance(other, RsparseMatrix):
+            return operators.multiply_csr_by_csr(self, other, logical=False)
+        if _dense_operand(other):                     # CsparseMatrix * matrix / float32, R/operators.R:673-677
+            return operators.multiply_csc_by_dense(self, other)
+        return NotImplemented
+
+    def __rmul__(self, other):                        # matrix * CsparseMatrix, float32 * CsparseMatrix (:681-689)
+        from . import operators
+        if _dense_operand(other):
+            return operators.multiply_csc_by_dense(self, other)
+        return NotImplemented
 
     def __and__(self, other):                         # :208-211
         from . import operators
         if isinstance(other, TsparseMatrix):
             return t_shallow(operators.multiply_csr_by_coo(t_shallow(self), t_shallow(other), logical=True))
+        if _dense_operand(other):                     # :693-709: the result would be an lgCMatrix
+            return operators.logicaland_csc_by_dense(self, other)
+        return NotImplemented
+
+    def __rand__(self, other):
+        from . import operators
+        if _dense_operand(other):
+            return operators.logicaland_csc_by_dense(self, other)
         return NotImplemented
 
 
@@ -470,6 +487,11 @@ class DenseMatrix(np.ndarray):
 
     def __array_finalize__(self, obj):
         self.Dimnames = getattr(obj, "Dimnames", [None, None])
+
+
+def _dense_operand(x):
+    """A dense (or scalar / vector) right operand of a dgCMatrix operator: ndarray, DenseMatrix, float32 or a number."""
+    return isinstance(x, (np.ndarray, float32)) or np.isscalar(x)
 
 
 def dimnames_of(x):

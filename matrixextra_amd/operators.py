@@ -1,7 +1,7 @@
 """Host-side mirror of the CSR (+) CSR part of R/operators.R
 (multiply_csr_by_csr :43-79, add_csr_matrices_internal :713-776 and their registrations), of CSR (.) COO
-(multiply_csr_by_coo :81-110) and of `CSR op vector` / `COO op vector` (multiply_csr_by_dvec_elemwise_internal
-:950-1153)."""
+(multiply_csr_by_coo :81-110), of `CSC * matrix` (multiply_csc_by_dense_internal :568-670) and of `CSR op vector` /
+`COO op vector` (multiply_csr_by_dvec_elemwise_internal :950-1153)."""
 from __future__ import annotations
 
 import warnings
@@ -9,8 +9,9 @@ import warnings
 import numpy as np
 
 from . import exports
-from .matrices import (RsparseMatrix, TsparseMatrix, as_coo_matrix, as_csr_matrix, check_valid_matrix, dgRMatrix,
-                       dgTMatrix, lgRMatrix, lgTMatrix, ngRMatrix, options, sort_sparse_indices, stop)
+from .matrices import (RsparseMatrix, TsparseMatrix, as_coo_matrix, as_csc_matrix, as_csr_matrix, check_valid_matrix,
+                       dgCMatrix, dgRMatrix, dgTMatrix, float32, lgRMatrix, lgTMatrix, ngRMatrix, options,
+                       sort_sparse_indices, stop)
 
 
 def _is_same_ngRMatrix(e1, e2):
@@ -114,6 +115,91 @@ def xor_csr_matrices(e1, e2):
 _NOT_ACCELERATED = ("This combination takes the reference's NA / dense route "
                     "(multiply_csr_by_dvec_with_NAs or a CsparseMatrix fallback, R/operators.R:%s), "
                     "which is not on the accelerated path.")
+
+
+_CSC_AND = "CsparseMatrix & matrix would give an lgCMatrix, which this package does not provide."
+_CSC_VECTOR = ("CsparseMatrix * vector is Matrix's own method (MatrixExtra registers `*` only for a CsparseMatrix "
+               "and a matrix or float32, R/operators.R:673-689), which is not on the accelerated path.")
+
+
+def _recycle_float32_vector(e1, e2):
+    """recycle_float32_vector (R/operators.R:219-235): the vector becomes a one-column matrix; when e1 has more
+    columns, the vector is repeated ncol(e1) times down that one column (sic), so only a one-column e1 passes the
+    dimension check that follows."""
+    data = e2.Data.reshape(-1, 1)
+    if data.shape[1] < e1.Dim[1]:
+        data = np.tile(data.reshape(-1), e1.Dim[1] // data.shape[1]).reshape(-1, 1)
+    return float32(data)
+
+
+def _csc_dense_operand(e2):
+    """(dense array, kind) of the right operand, by R's typeof(e2) (R/operators.R:599-610, 634-645): float64 numeric,
+    int32 integer, bool or RLogical logical, float32 its @Data; any other type goes through as.double (`mode(e2) <-
+    "double"`)."""
+    if isinstance(e2, float32):
+        return e2.Data, "float32"
+    a = np.asarray(e2)
+    if a.ndim != 2:
+        stop(_CSC_VECTOR)
+    if getattr(e2, "r_logical", False) or a.dtype == np.bool_:
+        return a, "logical"
+    if a.dtype == np.float64:
+        return a, "numeric"
+    if a.dtype == np.int32:
+        return a, "integer"
+    return a.astype(np.float64), "numeric"
+
+
+_CSC_IGNORE = {"numeric": "multiply_csc_by_dense_ignore_NAs_numeric", "integer": "multiply_csc_by_dense_ignore_NAs_integer",
+               "logical": "multiply_csc_by_dense_ignore_NAs_logical", "float32": "multiply_csc_by_dense_ignore_NAs_float32"}
+_CSC_KEEP = {"numeric": "multiply_csc_by_dense_keep_NAs_numeric", "integer": "multiply_csc_by_dense_keep_NAs_integer",
+             "logical": "multiply_csc_by_dense_keep_NAs_logical", "float32": "multiply_csc_by_dense_keep_NAs_float32"}
+
+
+def multiply_csc_by_dense_internal(e1, e2, logical=False):
+    """R/operators.R:568-661 for a dgCMatrix `e1` and a dense `e2` (ndarray, DenseMatrix or float32): `e1 * e2`, a
+    dgCMatrix with e1's Dim and Dimnames.  Under MatrixExtra.ignore_na the values-only route keeps e1's `p` object and
+    a copy of `i`; otherwise the columns are sorted (a copy, or e1's own arrays under MatrixExtra.inplace_sort) and
+    every NA cell of e2 outside e1's pattern becomes an NA_real_ entry.  `&` would give an lgCMatrix and raises."""
+    if logical:
+        stop(_CSC_AND)
+    ignore_NAs = bool(options.get("MatrixExtra.ignore_na", False))                # :570
+    if isinstance(e2, float32) and e2.is_vector:                                   # :572-589
+        n2, nrow = e2.Data.size, e1.Dim[0]
+        if n2 == 0:
+            return np.zeros(0, dtype=np.float64)
+        if n2 > nrow * e1.Dim[1]:
+            stop("Vector to multiply with has more entries than matrix dimensions.")
+        if n2 > nrow or (n2 < nrow and n2 % nrow) or (n2 != nrow and not ignore_NAs and bool(np.isnan(e2.Data).any())):
+            stop(_NOT_ACCELERATED % "585")                                         # e1 * float::dbl(e2): Matrix's
+        e2 = _recycle_float32_vector(e1, e2)
+    D, kind = _csc_dense_operand(e2)
+    if e1.Dim[0] != D.shape[0] or e1.Dim[1] != D.shape[1]:                         # :591-592
+        stop("Matrices must have the same dimensions in order to multiply them.")
+    check_valid_matrix(e1)
+    e1 = as_csc_matrix(e1)
+    out = dgCMatrix.__new__(dgCMatrix)
+    out.Dim, out.Dimnames = e1.Dim, list(e1.Dimnames)
+    if ignore_NAs:                                                                 # :595-622
+        out.x = getattr(exports, _CSC_IGNORE[kind])(e1.p, e1.i, e1.x, D)
+        out.p, out.i = e1.p, e1.i.copy()
+        return out
+    if not options.get("MatrixExtra.inplace_sort", False):                         # :626-630
+        e1 = dgCMatrix(e1.p, e1.i.copy(), e1.x.copy(), e1.Dim, e1.Dimnames)
+    exports.sort_sparse_indices_inplace(e1.p, e1.i, e1.x)                          # per column
+    res = getattr(exports, _CSC_KEEP[kind])(e1.p, e1.i, e1.x, D)                   # :632-659
+    out.p, out.i, out.x = res["indptr"], res["indices"], res["values"]
+    return out
+
+
+def multiply_csc_by_dense(e1, e2):
+    """R/operators.R:663-665 (also `matrix * CsparseMatrix` and `float32 * CsparseMatrix`, :681-689)."""
+    return multiply_csc_by_dense_internal(e1, e2, False)
+
+
+def logicaland_csc_by_dense(e1, e2):
+    """R/operators.R:667-669, registered for `&` at :693-709: the result would be an lgCMatrix."""
+    return multiply_csc_by_dense_internal(e1, e2, True)
 
 
 def _as_logical(v):
