@@ -899,6 +899,18 @@ __device__ __forceinline__ void lds_fold(float *d, float (&acc)[VEC])
     for (int v = 0; v < VEC; v++) d[v] += acc[v];
 }
 
+// Profiling build only (make PROBE=1, never the library that ships): lane 0 of every wavefront sums wall_clock64()
+// ticks (100 MHz) from the end of a batch to the completion of consume(0) of the next batch, separately for batches
+// that ended (0) without and (1) with a panel meeting (then from leaving the meeting's barrier), and (2) from the end of a generation's stream loop to the
+// first consume(0) of the next generation that waits for a B line.  Per XCD: [sum, count] x 3, then the wavefronts.
+// The clock reads wait for lgkmcnt(0) twice per batch, so a probe build is a few percent slower than the real one.
+#ifdef MX_SWEEP_PROBE
+__device__ unsigned long long g_sweep_probe[8][8];
+#define MX_PROBE(...) __VA_ARGS__
+#else
+#define MX_PROBE(...)
+#endif
+
 // main kernel
 template <typename real_t, bool COLMAJOR, int PLAN_WAVES>
 __global__ __launch_bounds__(PLAN_WAVES * 64)
@@ -925,6 +937,7 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
     unsigned *const my_ctr = sync_ctr + xcd * 64;
     real_t *const my_oct = accs + (size_t)wave * PLAN_OCT_ROWS * S;                     // this wavefront's 64 rows
     real_t *const my_rows = my_oct + (size_t)g * PLAN_RB * S + lg * VEC;                // this group's bundle
+    MX_PROBE(long long pr_t = 0; int pr_kind = 0; unsigned long long pr_sum[3] = {0, 0, 0}; unsigned pr_cnt[3] = {0, 0, 0};)
 
     for (int it = 0; it < niter; it++) {
         const long long item_raw = lo + wg + (long long)it * nwg;
@@ -945,21 +958,26 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
 
         // One continuous, software-pipelined stream over the octet's entries of ALL panels (they are contiguous in
         // the plan).  Panel boundaries only matter for locality: when the stream crosses one, the 16 waves of the
-        // CU's single workgroup meet at a __syncthreads (no global traffic, no pipeline restart: the prefetched
-        // plan entries stay in flight).  Across the 32 CUs of the XCD group there is ONE global timing barrier per
+        // CU's single workgroup meet at a __syncthreads: a bare s_barrier, nothing is loaded or waited for there, so
+        // the B lines and the plan chunk in flight stay in flight (the boundaries come out of a register, see
+        // so_row below).  Across the 32 CUs of the XCD group there is ONE global timing barrier per
         // generation (32 pollers per counter); in between the CUs run identical code on statistically identical
         // data and drift by a fraction of a panel.
         {
             if (sync_mode >= 2) xcd_timing_barrier(my_ctr, (unsigned)(it + 1) * (unsigned)nwg);
-            int sbeg = 0, send = 0, next_b = 0;
+            // The octet's whole row of step_off is read here, once: lane p holds the start of panel p (npanels <= 64
+            // lanes), the end of the last panel sits in a second register.  Every panel boundary the stream meets
+            // later is a v_readlane of that register: a load at the meeting would have to be waited for with
+            // vmcnt(0), and vector loads return in order, so that wait would drain the B lines and the plan chunk in
+            // flight.
+            int so_row = 0, so_end = 0;
             if (oct_ok) {
-                sbeg = step_off[(size_t)oct * npanels];
-                send = step_off[(size_t)oct * npanels + npanels];
-                next_b = npanels > 1 ? step_off[(size_t)oct * npanels + 1] : send;
+                if (lane < npanels) so_row = step_off[(size_t)oct * npanels + lane];
+                so_end = step_off[(size_t)oct * npanels + npanels];
             }
-            sbeg = __builtin_amdgcn_readfirstlane(sbeg);            // wave-uniform: keep the loop control scalar
-            send = __builtin_amdgcn_readfirstlane(send);
-            next_b = __builtin_amdgcn_readfirstlane(next_b);
+            const int sbeg = __builtin_amdgcn_readfirstlane(so_row);   // wave-uniform: keep the loop control scalar
+            const int send = __builtin_amdgcn_readfirstlane(so_end);
+            int next_b = npanels > 1 ? __builtin_amdgcn_readlane(so_row, 1) : send;
             int p = 0;
             int cur = 0;
             real_t acc[VEC];
@@ -980,8 +998,11 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
             // Vector loads return in order, so a slot read that misses to HBM (the plan is a pure stream) holds back
             // every younger B-line load behind it; fetching one batch per iteration put that full latency into every
             // iteration (measured: 1.95 us per 8 steps per wave, whatever the locality of B).  Now it is paid once
-            // per 32 steps.  Reads run one chunk past the octet (next octet's slots / the padding behind the last
-            // octet): they only ever become addresses of valid B lines, never FMAs.
+            // per 32 steps.  The last read-ahead of an octet runs one chunk past it (the next octet's slots / the
+            // padding behind the last octet): it is fetched and dropped, never used.  Nothing of the NEXT generation
+            // is in flight when this one's stream ends: the turnover (last batch, epilogue, zeroing, step_off row,
+            // first chunk, first batch of B lines, each waited for in turn) measures 11 us per generation and
+            // wavefront, see DESIGN.md 4.1.
             int rc[PLAN_CHUNK], rn[PLAN_CHUNK];
             double rv[PLAN_CHUNK], rvn[PLAN_CHUNK];
             auto load_chunk = [&](int step, int (&c)[PLAN_CHUNK], double (&v)[PLAN_CHUNK]) {
@@ -1038,21 +1059,32 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
                     plan_bcast<UU>(rc[k], rv[k], pc[UU], pv[UU]);                                                     \
                     vload<real_t, VEC>(b[UU], reinterpret_cast<const real_t *>(Bbase + b_offset(pc[UU])));            \
                     __builtin_amdgcn_sched_barrier(0);
-                    MX_PLAN_STEP(0) MX_PLAN_STEP(1) MX_PLAN_STEP(2) MX_PLAN_STEP(3)
+                    MX_PLAN_STEP(0)
+                    MX_PROBE(if (pr_kind && !(pr_kind == 3 && s == sbeg && k == 0)) {   // that first batch is the no-op one
+                        const unsigned long long dt = (unsigned long long)(wall_clock64() - pr_t);
+                        _Pragma("unroll") for (int j = 0; j < 3; j++)
+                            if (pr_kind == j + 1) { pr_sum[j] += dt; pr_cnt[j]++; }
+                        pr_kind = 0;
+                    })
+                    MX_PLAN_STEP(1) MX_PLAN_STEP(2) MX_PLAN_STEP(3)
                     MX_PLAN_STEP(4) MX_PLAN_STEP(5) MX_PLAN_STEP(6) MX_PLAN_STEP(7)
 #undef MX_PLAN_STEP
+                    MX_PROBE(bool pr_met = false;)
                     if (sync_mode > 0) {
                         const int sn = s + U * k;                   // steps consumed so far
                         while (p < npanels - 1 && sn >= next_b) {   // the stream moved into the next panel
                             p++;
                             __syncthreads();
-                            next_b = __builtin_amdgcn_readfirstlane(p < npanels - 1 ? step_off[(size_t)oct * npanels + p + 1] : send);
+                            MX_PROBE(pr_met = true; if (pr_kind != 3) pr_t = wall_clock64();)
+                            next_b = p < npanels - 1 ? __builtin_amdgcn_readlane(so_row, p + 1) : send;
                         }
                     }
+                    MX_PROBE(if (pr_kind != 3) { pr_kind = pr_met ? 2 : 1; if (!pr_met) pr_t = wall_clock64(); })
                 }
 #pragma unroll
                 for (int k = 0; k < PLAN_CHUNK; k++) { rc[k] = rn[k]; rv[k] = rvn[k]; }
             }
+            MX_PROBE(if (send > sbeg) { pr_kind = 3; pr_t = wall_clock64(); })
 #pragma unroll
             for (int u = 0; u < U; u++) consume(u);
             lds_fold<VEC>(my_rows + cur * S, acc);
@@ -1086,6 +1118,13 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
             }
         }
     }
+    MX_PROBE(if (lane == 0) {
+        for (int j = 0; j < 3; j++) {
+            atomicAdd(&g_sweep_probe[xcd][2 * j], pr_sum[j]);
+            atomicAdd(&g_sweep_probe[xcd][2 * j + 1], (unsigned long long)pr_cnt[j]);
+        }
+        atomicAdd(&g_sweep_probe[xcd][6], 1ULL);
+    })
 }
 
 }  // namespace mx
@@ -1424,6 +1463,18 @@ extern "C" int mxd_spmm_plan_run(const mx_spmm_plan *pl, int n, const void *B, s
 }
 
 extern "C" const char *mxd_spmm_last_kernel(void) { return g_last_spmm_kernel; }
+
+#ifdef MX_SWEEP_PROBE
+// probe builds only (tools/sweep_probe.py): copies the 8 x 8 counters of spmm_plan_kernel out and clears them
+extern "C" int mxd_spmm_sweep_probe(unsigned long long *out64)
+{
+    static const unsigned long long zeros[64] = {};
+    MX_HIP(hipDeviceSynchronize());
+    MX_HIP(hipMemcpyFromSymbol(out64, HIP_SYMBOL(mx::g_sweep_probe), sizeof(zeros)));
+    MX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(mx::g_sweep_probe), zeros, sizeof(zeros)));
+    return 0;
+}
+#endif
 
 extern "C" int mxd_spmm_csr_dense_ex(int m, int n, int K,
                                      const int32_t *indptr, const int32_t *indices, const double *values,
