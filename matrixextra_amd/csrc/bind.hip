@@ -6,7 +6,7 @@
 //   concat_csr_batch     src/rbind.cpp:24-173   bulk copy + indptr offset (+ value-type conversion)
 // Pure bandwidth copies: 2*12 bytes per entry + 8 bytes per row.  The output row offsets of cbind are
 // indptrX[r] + indptrY[r] — no scan is needed.
-#include "mx_common.h"
+#include "mx_dispatch.h"
 
 namespace mx {
 
@@ -85,23 +85,14 @@ extern "C" int mxd_csr_cbind(int nX, int nY, const int32_t *Xp, const int32_t *X
     hipStream_t st = mx::as_stream(stream);
     if (nrows == 0) { MX_HIP(hipMemsetAsync(indptr, 0, sizeof(int32_t), st)); return 0; }
     const int G = mx::pick_group(0.5 * (double)nnz_total / (double)nrows);
-#define MX_CB(GG, VT, HV)                                                                                       \
-    hipLaunchKernelGGL((mx::cbind_kernel<GG, VT, HV>), dim3((unsigned)mx::ceil_div(nrows, mx::BIND_BLOCK / GG)), \
-                       dim3(mx::BIND_BLOCK), 0, st, nX, nY, Xp, Xj, (const VT *)Xx, Yp, Yj_plus_ncol,           \
-                       (const VT *)Yx, indptr, indices, (VT *)values)
-#define MX_CB_G(VT, HV)                                                                                         \
-    switch (G) { case 4: MX_CB(4, VT, HV); break; case 8: MX_CB(8, VT, HV); break; case 16: MX_CB(16, VT, HV); break; \
-                 case 32: MX_CB(32, VT, HV); break; default: MX_CB(64, VT, HV); break; }
-    switch (value_dtype) {
-        case MX_F64: MX_CB_G(double, true); break;
-        case MX_LGL: case MX_I32: MX_CB_G(int32_t, true); break;
-        case MX_NONE: MX_CB_G(int32_t, false); break;
-        default: return mx::set_error("mxd_csr_cbind: unsupported value dtype %d", value_dtype);
-    }
-#undef MX_CB_G
-#undef MX_CB
-    MX_LAUNCH_CHECK();
-    return 0;
+    return mx::dispatch_values("mxd_csr_cbind", value_dtype, [&](auto vk) {
+        using VT = typename decltype(vk)::VT;
+        return mx::launch_rows(mx::lane_groups{}, "mxd_csr_cbind", G, nrows, mx::BIND_BLOCK,
+                               [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((mx::cbind_kernel<g(), VT, vk.has_values>), grid, block, 0, st, nX, nY, Xp, Xj,
+                               (const VT *)Xx, Yp, Yj_plus_ncol, (const VT *)Yx, indptr, indices, (VT *)values);
+        });
+    });
 }
 
 // Appends one operand of an rbind at (row_offset, entry_offset) of the output arrays.
@@ -134,12 +125,13 @@ extern "C" int mxd_csr_rbind_append(int in_kind, const int32_t *indptr_in, const
     const int vin = (in_kind == 0 || in_kind == 3) ? 0 : (in_kind == 1 || in_kind == 5) ? 1 : (in_kind == 4) ? 4 : 2;
     void *vo = out_kind == 0 ? (void *)((double *)out_values + entry_offset)
              : out_kind == 1 ? (void *)((int32_t *)out_values + entry_offset) : nullptr;
-#define MX_CE(IN, OUT) hipLaunchKernelGGL((mx::concat_entries_kernel<IN, OUT>), dim3(grid), dim3(256), 0, st, nnz_in, \
-                                          indices_in, values_in, add, jo, vo)
-#define MX_CE_IN(OUT) switch (vin) { case 0: MX_CE(0, OUT); break; case 1: MX_CE(1, OUT); break; case 4: MX_CE(4, OUT); break; default: MX_CE(2, OUT); break; }
-    if (out_kind == 0) { MX_CE_IN(0) } else if (out_kind == 1) { MX_CE_IN(1) } else { MX_CE_IN(2) }
-#undef MX_CE_IN
-#undef MX_CE
-    MX_LAUNCH_CHECK();
-    return 0;
+    const char *what = "mxd_csr_rbind_append";
+    return mx::dispatch_int(mx::int_list<0, 1, 2>{}, what, "output kind", out_kind, [&](auto out) {
+        return mx::dispatch_int(mx::int_list<0, 1, 4, 2>{}, what, "input value kind", vin, [&](auto in) {
+            hipLaunchKernelGGL((mx::concat_entries_kernel<in(), out()>), dim3(grid), dim3(256), 0, st, nnz_in,
+                               indices_in, values_in, add, jo, vo);
+            MX_LAUNCH_CHECK();
+            return 0;
+        });
+    });
 }

@@ -12,19 +12,11 @@
 // The arbitrary selector uses a dense column map (start[c]..start[c+1] = positions of column c in cols_take,
 // ascending) instead of the reference's hash map; rows are re-ordered by new column id afterwards unless
 // cols_take is non-decreasing, as the reference does.
-#include "mx_common.h"
+#include "mx_dispatch.h"
 
 namespace mx {
 
 constexpr int CS_BLOCK = 256;
-
-template <int G>
-__device__ __forceinline__ unsigned long long cs_group_ballot(bool pred)
-{
-    const unsigned long long b = __ballot(pred);
-    if constexpr (G == 64) return b;
-    else return (b >> (lane_id() & ~(G - 1))) & ((1ULL << G) - 1ULL);
-}
 
 // ---- column range -----------------------------------------------------------------------------------
 template <int G>
@@ -42,7 +34,7 @@ void colrange_count_kernel(int r, const int32_t *__restrict__ indptr, const int3
         const int k = k0 + lg;
         bool keep = false;
         if (k < e) { const int c = indices[k]; keep = c >= min_col && c <= max_col; }
-        cnt += __popcll(cs_group_ballot<G>(keep));
+        cnt += __popcll(group_ballot<G>(keep));
     }
     if (valid && lg == 0) lens[i] = cnt;
 }
@@ -66,7 +58,7 @@ void colrange_fill_kernel(int r, const int32_t *__restrict__ indptr, const int32
         bool keep = false;
         int c = 0;
         if (k < e) { c = indices[k]; keep = c >= min_col && c <= max_col; }
-        const unsigned long long kb = cs_group_ballot<G>(keep);
+        const unsigned long long kb = group_ballot<G>(keep);
         if (keep) {
             const int pos = o + __popcll(kb & below);
             new_indices[pos] = c - min_col;
@@ -197,19 +189,6 @@ void reversed_iota_kernel(int n, int32_t *__restrict__ out)
 
 }  // namespace mx
 
-#define MX_GROUP_SWITCH(G, ...)                                                              \
-    switch (G) {                                                                             \
-        case 4:  { constexpr int GG = 4;  __VA_ARGS__; break; }                              \
-        case 8:  { constexpr int GG = 8;  __VA_ARGS__; break; }                              \
-        case 16: { constexpr int GG = 16; __VA_ARGS__; break; }                              \
-        case 32: { constexpr int GG = 32; __VA_ARGS__; break; }                              \
-        case 64: { constexpr int GG = 64; __VA_ARGS__; break; }                              \
-        default: return mx::set_error("bad lane-group size %d", G);                          \
-    }
-
-// lanes per picked row: the source rows' mean length is what matters (nnz_src / nrows_src)
-static int group_for(double avg) { return mx::pick_group(avg); }
-
 extern "C" int mxd_csr_colrange_count(int r, const int32_t *indptr, const int32_t *indices, const int32_t *rows_take,
                                       int min_col, int max_col, double avg_row_len, int32_t *new_indptr,
                                       void *workspace, int64_t *nnz_out_host, void *stream)
@@ -218,10 +197,13 @@ extern "C" int mxd_csr_colrange_count(int r, const int32_t *indptr, const int32_
     hipStream_t st = mx::as_stream(stream);
     int32_t *lens = (int32_t *)workspace;
     if (r > 0) {
-        const int G = group_for(avg_row_len);
-        MX_GROUP_SWITCH(G, hipLaunchKernelGGL((mx::colrange_count_kernel<GG>), dim3((unsigned)mx::ceil_div(r, mx::CS_BLOCK / GG)),
-                                              dim3(mx::CS_BLOCK), 0, st, r, indptr, indices, rows_take, min_col, max_col, lens));
-        MX_LAUNCH_CHECK();
+        const int G = mx::pick_group(avg_row_len);
+        const int rc = mx::launch_rows(mx::lane_groups{}, "mxd_csr_colrange_count", G, r, mx::CS_BLOCK,
+                                       [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((mx::colrange_count_kernel<g()>), grid, block, 0, st, r, indptr, indices, rows_take,
+                               min_col, max_col, lens);
+        });
+        if (rc) return rc;
     }
     return mx::finish_count(r, workspace, new_indptr, nnz_out_host, st);
 }
@@ -234,20 +216,15 @@ extern "C" int mxd_csr_colrange_fill(int r, const int32_t *indptr, const int32_t
     MX_REQUIRE(r >= 0, "mxd_csr_colrange_fill: negative r");
     if (r == 0) return 0;
     hipStream_t st = mx::as_stream(stream);
-    const int G = group_for(avg_row_len);
-#define MX_CR_LAUNCH(KIND)                                                                                          \
-    MX_GROUP_SWITCH(G, hipLaunchKernelGGL((mx::colrange_fill_kernel<GG, KIND>), dim3((unsigned)mx::ceil_div(r, mx::CS_BLOCK / GG)), \
-                                          dim3(mx::CS_BLOCK), 0, st, r, indptr, indices, values, rows_take, min_col, \
-                                          max_col, new_indptr, new_indices, new_values))
-    switch (value_dtype) {
-        case MX_F64: MX_CR_LAUNCH(MX_F64); break;
-        case MX_LGL: MX_CR_LAUNCH(MX_LGL); break;
-        case MX_NONE: MX_CR_LAUNCH(MX_NONE); break;
-        default: return mx::set_error("mxd_csr_colrange_fill: unsupported value dtype %d", value_dtype);
-    }
-#undef MX_CR_LAUNCH
-    MX_LAUNCH_CHECK();
-    return 0;
+    const int G = mx::pick_group(avg_row_len);
+    using kinds = mx::int_list<MX_F64, MX_LGL, MX_NONE>;
+    return mx::dispatch_int(kinds{}, "mxd_csr_colrange_fill", "value dtype", value_dtype, [&](auto kind) {
+        return mx::launch_rows(mx::lane_groups{}, "mxd_csr_colrange_fill", G, r, mx::CS_BLOCK,
+                               [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((mx::colrange_fill_kernel<g(), kind()>), grid, block, 0, st, r, indptr, indices, values,
+                               rows_take, min_col, max_col, new_indptr, new_indices, new_values);
+        });
+    });
 }
 
 extern "C" size_t mxd_colmap_workspace_bytes(int ncol_map)
@@ -291,10 +268,13 @@ extern "C" int mxd_csr_colmap_count(int r, const int32_t *indptr, const int32_t 
     hipStream_t st = mx::as_stream(stream);
     int32_t *lens = (int32_t *)workspace;
     if (r > 0) {
-        const int G = group_for(avg_row_len);
-        MX_GROUP_SWITCH(G, hipLaunchKernelGGL((mx::colmap_rows_count_kernel<GG>), dim3((unsigned)mx::ceil_div(r, mx::CS_BLOCK / GG)),
-                                              dim3(mx::CS_BLOCK), 0, st, r, indptr, indices, rows_take, ncol_map, start, lens));
-        MX_LAUNCH_CHECK();
+        const int G = mx::pick_group(avg_row_len);
+        const int rc = mx::launch_rows(mx::lane_groups{}, "mxd_csr_colmap_count", G, r, mx::CS_BLOCK,
+                                       [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((mx::colmap_rows_count_kernel<g()>), grid, block, 0, st, r, indptr, indices, rows_take,
+                               ncol_map, start, lens);
+        });
+        if (rc) return rc;
     }
     return mx::finish_count(r, workspace, new_indptr, nnz_out_host, st);
 }
@@ -307,20 +287,16 @@ extern "C" int mxd_csr_colmap_fill(int r, const int32_t *indptr, const int32_t *
     MX_REQUIRE(r >= 0, "mxd_csr_colmap_fill: negative r");
     if (r == 0) return 0;
     hipStream_t st = mx::as_stream(stream);
-    const int G = group_for(avg_row_len);
-#define MX_CM_LAUNCH(VT, HV)                                                                                         \
-    MX_GROUP_SWITCH(G, hipLaunchKernelGGL((mx::colmap_rows_fill_kernel<GG, VT, HV>), dim3((unsigned)mx::ceil_div(r, mx::CS_BLOCK / GG)), \
-                                          dim3(mx::CS_BLOCK), 0, st, r, indptr, indices, (const VT *)values, rows_take, \
-                                          ncol_map, start, pos, new_indptr, new_indices, (VT *)new_values))
-    switch (value_dtype) {
-        case MX_F64: MX_CM_LAUNCH(double, true); break;
-        case MX_LGL: case MX_I32: MX_CM_LAUNCH(int32_t, true); break;
-        case MX_NONE: MX_CM_LAUNCH(int32_t, false); break;
-        default: return mx::set_error("mxd_csr_colmap_fill: unsupported value dtype %d", value_dtype);
-    }
-#undef MX_CM_LAUNCH
-    MX_LAUNCH_CHECK();
-    return 0;
+    const int G = mx::pick_group(avg_row_len);
+    return mx::dispatch_values("mxd_csr_colmap_fill", value_dtype, [&](auto vk) {
+        using VT = typename decltype(vk)::VT;
+        return mx::launch_rows(mx::lane_groups{}, "mxd_csr_colmap_fill", G, r, mx::CS_BLOCK,
+                               [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((mx::colmap_rows_fill_kernel<g(), VT, vk.has_values>), grid, block, 0, st, r, indptr,
+                               indices, (const VT *)values, rows_take, ncol_map, start, pos, new_indptr, new_indices,
+                               (VT *)new_values);
+        });
+    });
 }
 
 extern "C" int mxd_csr_reverse_columns(int m, int64_t nnz, const int32_t *indptr, int32_t *indices, void *values,
@@ -329,19 +305,15 @@ extern "C" int mxd_csr_reverse_columns(int m, int64_t nnz, const int32_t *indptr
     MX_REQUIRE(m >= 0, "mxd_csr_reverse_columns: negative m");
     if (m == 0 || nnz == 0) return 0;
     hipStream_t st = mx::as_stream(stream);
-    const int G = group_for(0.5 * (double)nnz / (double)m);
-#define MX_RC_LAUNCH(VT, HV)                                                                                        \
-    MX_GROUP_SWITCH(G, hipLaunchKernelGGL((mx::reverse_columns_kernel<GG, VT, HV>), dim3((unsigned)mx::ceil_div(m, mx::CS_BLOCK / GG)), \
-                                          dim3(mx::CS_BLOCK), 0, st, m, indptr, indices, (VT *)values, ncol))
-    switch (value_dtype) {
-        case MX_F64: MX_RC_LAUNCH(double, true); break;
-        case MX_LGL: case MX_I32: MX_RC_LAUNCH(int32_t, true); break;
-        case MX_NONE: MX_RC_LAUNCH(int32_t, false); break;
-        default: return mx::set_error("mxd_csr_reverse_columns: unsupported value dtype %d", value_dtype);
-    }
-#undef MX_RC_LAUNCH
-    MX_LAUNCH_CHECK();
-    return 0;
+    const int G = mx::pick_group(0.5 * (double)nnz / (double)m);
+    return mx::dispatch_values("mxd_csr_reverse_columns", value_dtype, [&](auto vk) {
+        using VT = typename decltype(vk)::VT;
+        return mx::launch_rows(mx::lane_groups{}, "mxd_csr_reverse_columns", G, m, mx::CS_BLOCK,
+                               [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((mx::reverse_columns_kernel<g(), VT, vk.has_values>), grid, block, 0, st, m, indptr,
+                               indices, (VT *)values, ncol);
+        });
+    });
 }
 
 extern "C" int mxd_reversed_iota(int n, int32_t *out, void *stream)

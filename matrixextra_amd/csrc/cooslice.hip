@@ -25,7 +25,7 @@
 //        while 63 lanes idle (a divergent loop holds the whole wave64).  No global atomics.
 // single: smallest k with (rows[k], cols[k]) == (r, c) by a per-block minimum and one final block; the final block
 //        also reads the value, so the host reads back 16 bytes.
-#include "mx_common.h"
+#include "mx_dispatch.h"
 
 #include <cstring>
 
@@ -237,15 +237,21 @@ static int csl_check_axis(const mx_coo_axis *a, int n, const char *what)
     return 0;
 }
 
-}  // namespace mx
+// f(map_i, map_j): the two axis kinds (checked by csl_check_axis) as compile-time bools
+template <typename F>
+static int csl_dispatch_axes(const mx_coo_axis *axis_i, const mx_coo_axis *axis_j, F &&f)
+{
+    using kinds = int_list<MX_AXIS_MAP, MX_AXIS_AFFINE>;
+    return dispatch_int(kinds{}, "mxd_coo_slice", "row axis kind", axis_i->kind, [&](auto ki) {
+        return dispatch_int(kinds{}, "mxd_coo_slice", "column axis kind", axis_j->kind, [&](auto kj) {
+            f(std::bool_constant<ki() == MX_AXIS_MAP>{}, std::bool_constant<kj() == MX_AXIS_MAP>{});
+            MX_LAUNCH_CHECK();
+            return 0;
+        });
+    });
+}
 
-#define MX_CSL_AXES(MI, MJ, ...)                                                                        \
-    do {                                                                                                \
-        if (MI && MJ) { constexpr bool A = true, B = true; __VA_ARGS__; }                               \
-        else if (MI) { constexpr bool A = true, B = false; __VA_ARGS__; }                               \
-        else if (MJ) { constexpr bool A = false, B = true; __VA_ARGS__; }                               \
-        else { constexpr bool A = false, B = false; __VA_ARGS__; }                                      \
-    } while (0)
+}  // namespace mx
 
 extern "C" size_t mxd_coo_slice_workspace_bytes(int64_t nnz)
 {
@@ -266,10 +272,11 @@ extern "C" int mxd_coo_slice_count(int nrow, int ncol, const int32_t *rows, cons
     MX_HIP(hipMemsetAsync(flags, 0, 16, st));
     const mx::CslAxis ai = mx::csl_axis(*axis_i), aj = mx::csl_axis(*axis_j);
     const unsigned g = (unsigned)mx::ceil_div(nnz, mx::CSL_BLOCK);
-    MX_CSL_AXES(axis_i->kind == MX_AXIS_MAP, axis_j->kind == MX_AXIS_MAP,
-                hipLaunchKernelGGL((mx::coo_slice_count_kernel<A, B>), dim3(g), dim3(mx::CSL_BLOCK), 0, st, nrow,
-                                   ncol, rows, cols, nnz, ai, aj, (int32_t *)workspace, flags));
-    MX_LAUNCH_CHECK();
+    const int lrc = mx::csl_dispatch_axes(axis_i, axis_j, [&](auto mi, auto mj) {
+        hipLaunchKernelGGL((mx::coo_slice_count_kernel<mi(), mj()>), dim3(g), dim3(mx::CSL_BLOCK), 0, st, nrow, ncol,
+                           rows, cols, nnz, ai, aj, (int32_t *)workspace, flags);
+    });
+    if (lrc) return lrc;
     const int rc = mx::finish_count(nnz, workspace, mx::csl_offsets(workspace, nnz), nnz_out_host, st);
     int32_t hf[4] = {0, 0, 0, 0};
     MX_HIP(hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, st));
@@ -295,20 +302,13 @@ extern "C" int mxd_coo_slice_fill(int nrow, int ncol, const int32_t *rows, const
     const int32_t *off = mx::csl_offsets(const_cast<void *>(workspace), nnz);
     const mx::CslAxis ai = mx::csl_axis(*axis_i), aj = mx::csl_axis(*axis_j);
     const unsigned g = (unsigned)mx::ceil_div(nnz, mx::CSL_BLOCK);
-#define MX_CSL_FILL(VK)                                                                                       \
-    MX_CSL_AXES(axis_i->kind == MX_AXIS_MAP, axis_j->kind == MX_AXIS_MAP,                                     \
-                hipLaunchKernelGGL((mx::coo_slice_fill_kernel<A, B, VK>), dim3(g), dim3(mx::CSL_BLOCK), 0, st, \
-                                   nrow, ncol, rows, cols, values, nnz, ai, aj, off, out_rows, out_cols,      \
-                                   out_values))
-    switch (value_dtype) {
-        case MX_F64: MX_CSL_FILL(MX_F64); break;
-        case MX_LGL: MX_CSL_FILL(MX_LGL); break;
-        case MX_NONE: MX_CSL_FILL(MX_NONE); break;
-        default: return mx::set_error("mxd_coo_slice_fill: unsupported value dtype %d", value_dtype);
-    }
-#undef MX_CSL_FILL
-    MX_LAUNCH_CHECK();
-    return 0;
+    using kinds = mx::int_list<MX_F64, MX_LGL, MX_NONE>;
+    return mx::dispatch_int(kinds{}, "mxd_coo_slice_fill", "value dtype", value_dtype, [&](auto vk) {
+        return mx::csl_dispatch_axes(axis_i, axis_j, [&](auto mi, auto mj) {
+            hipLaunchKernelGGL((mx::coo_slice_fill_kernel<mi(), mj(), vk()>), dim3(g), dim3(mx::CSL_BLOCK), 0, st, nrow,
+                               ncol, rows, cols, values, nnz, ai, aj, off, out_rows, out_cols, out_values);
+        });
+    });
 }
 
 extern "C" size_t mxd_coo_single_workspace_bytes(void)

@@ -21,7 +21,7 @@
 // reference's lower_bound skip does (:1329-1331).  Every write position comes from the same bitmaps in both passes,
 // and an entry whose cell falls outside its tile (an index outside [0, m)) is ignored in both, so that nothing is
 // written or read out of bounds whatever the input.
-#include "mx_common.h"
+#include "mx_dispatch.h"
 
 namespace mx {
 
@@ -267,15 +267,9 @@ static unsigned long long *cd_outside(void *ws, int64_t t)
 static unsigned long long *cd_mask(void *ws, int64_t t) { return cd_outside(ws, t) + 2; }
 static int32_t *cd_first(void *ws, int64_t t) { return (int32_t *)(cd_mask(ws, t) + t * CD_WORDS); }
 
-}  // namespace mx
+using cd_kinds = int_list<0, 1, 2, 3>;
 
-#define MX_CD_KIND(KERNEL, ...)                                                                                \
-    switch (dense_kind) {                                                                                      \
-        case 0: hipLaunchKernelGGL(mx::KERNEL<0>, dim3((unsigned)t), dim3(mx::CD_BLOCK), 0, st, __VA_ARGS__); break; \
-        case 1: hipLaunchKernelGGL(mx::KERNEL<1>, dim3((unsigned)t), dim3(mx::CD_BLOCK), 0, st, __VA_ARGS__); break; \
-        case 2: hipLaunchKernelGGL(mx::KERNEL<2>, dim3((unsigned)t), dim3(mx::CD_BLOCK), 0, st, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL(mx::KERNEL<3>, dim3((unsigned)t), dim3(mx::CD_BLOCK), 0, st, __VA_ARGS__); break; \
-    }
+}  // namespace mx
 
 extern "C" size_t mxd_csc_dense_na_workspace_bytes(int m, int n)
 {
@@ -301,9 +295,14 @@ extern "C" int mxd_csc_dense_na_count(int m, int n, int64_t nnz, const int32_t *
     unsigned long long *outside = mx::cd_outside(workspace, t);
     MX_HIP(hipMemsetAsync(outside, 0, sizeof(unsigned long long), st));
     const int64_t F = (int64_t)m * (int64_t)n;
-    MX_CD_KIND(cd_count_kernel, (int64_t)m, n, F, indptr, indices, nnz, dense_colmajor, mx::cd_mask(workspace, t),
-               (int32_t *)workspace, mx::cd_first(workspace, t), outside);
-    MX_LAUNCH_CHECK();
+    const int rc = mx::dispatch_int(mx::cd_kinds{}, "mxd_csc_dense_na_count", "dense kind", dense_kind, [&](auto dk) {
+        hipLaunchKernelGGL(mx::cd_count_kernel<dk()>, dim3((unsigned)t), dim3(mx::CD_BLOCK), 0, st, (int64_t)m, n, F,
+                           indptr, indices, nnz, dense_colmajor, mx::cd_mask(workspace, t), (int32_t *)workspace,
+                           mx::cd_first(workspace, t), outside);
+        MX_LAUNCH_CHECK();
+        return 0;
+    });
+    if (rc) return rc;
     MX_HIP(hipMemcpyAsync(na_outside_host, outside, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     // the 64-bit total is read back (one synchronise) and refused above INT_MAX before any output exists
     return mx::finish_count(t, workspace, mx::cd_offsets(workspace, t), nnz_out_host, st);
@@ -327,8 +326,11 @@ extern "C" int mxd_csc_dense_na_fill(int m, int n, int64_t nnz, const int32_t *i
     const int64_t t = mx::cd_ntiles(m, n);
     void *ws = const_cast<void *>(workspace);
     const int64_t F = (int64_t)m * (int64_t)n;
-    MX_CD_KIND(cd_fill_kernel, (int64_t)m, n, F, t, indptr, indices, nnz, values, dense_colmajor, mx::cd_mask(ws, t),
-               mx::cd_offsets(ws, t), mx::cd_first(ws, t), out_indptr, out_indices, out_values);
-    MX_LAUNCH_CHECK();
-    return 0;
+    return mx::dispatch_int(mx::cd_kinds{}, "mxd_csc_dense_na_fill", "dense kind", dense_kind, [&](auto dk) {
+        hipLaunchKernelGGL(mx::cd_fill_kernel<dk()>, dim3((unsigned)t), dim3(mx::CD_BLOCK), 0, st, (int64_t)m, n, F, t,
+                           indptr, indices, nnz, values, dense_colmajor, mx::cd_mask(ws, t), mx::cd_offsets(ws, t),
+                           mx::cd_first(ws, t), out_indptr, out_indices, out_values);
+        MX_LAUNCH_CHECK();
+        return 0;
+    });
 }

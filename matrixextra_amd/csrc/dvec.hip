@@ -15,7 +15,7 @@
 //
 // The COO twin (multiply_coo_by_dense_ignore_NAs_{numeric,logical}, :2856-3425, same four branches) runs the
 // same arithmetic and the same recycling position with the row read from i[k]: one lane per entry.
-#include "mx_common.h"
+#include "mx_dispatch.h"
 
 namespace mx {
 
@@ -151,15 +151,6 @@ static int dv_mode(int m, int ncols, unsigned long long len)
 
 }  // namespace mx
 
-#define MX_DV_G(LOGICAL)                                                                                        \
-    switch (G) {                                                                                                \
-        case 4:  hipLaunchKernelGGL((mx::csr_by_dvec_kernel<4, LOGICAL>),  dim3((unsigned)mx::ceil_div(m, mx::DV_BLOCK / 4)),  dim3(mx::DV_BLOCK), 0, st, m, indptr, indices, values, dvec, len, mode, op, x_is_lhs, values_out); break; \
-        case 8:  hipLaunchKernelGGL((mx::csr_by_dvec_kernel<8, LOGICAL>),  dim3((unsigned)mx::ceil_div(m, mx::DV_BLOCK / 8)),  dim3(mx::DV_BLOCK), 0, st, m, indptr, indices, values, dvec, len, mode, op, x_is_lhs, values_out); break; \
-        case 16: hipLaunchKernelGGL((mx::csr_by_dvec_kernel<16, LOGICAL>), dim3((unsigned)mx::ceil_div(m, mx::DV_BLOCK / 16)), dim3(mx::DV_BLOCK), 0, st, m, indptr, indices, values, dvec, len, mode, op, x_is_lhs, values_out); break; \
-        case 32: hipLaunchKernelGGL((mx::csr_by_dvec_kernel<32, LOGICAL>), dim3((unsigned)mx::ceil_div(m, mx::DV_BLOCK / 32)), dim3(mx::DV_BLOCK), 0, st, m, indptr, indices, values, dvec, len, mode, op, x_is_lhs, values_out); break; \
-        default: hipLaunchKernelGGL((mx::csr_by_dvec_kernel<64, LOGICAL>), dim3((unsigned)mx::ceil_div(m, mx::DV_BLOCK / 64)), dim3(mx::DV_BLOCK), 0, st, m, indptr, indices, values, dvec, len, mode, op, x_is_lhs, values_out); break; \
-    }
-
 extern "C" int mxd_csr_by_dvec(int m, int ncols, int64_t nnz, const int32_t *indptr, const int32_t *indices,
                                const void *values, const void *dvec, int64_t dvec_len, int op, int x_is_lhs,
                                void *values_out, void *stream)
@@ -173,9 +164,13 @@ extern "C" int mxd_csr_by_dvec(int m, int ncols, int64_t nnz, const int32_t *ind
     const unsigned long long len = (unsigned long long)dvec_len;
     const int mode = mx::dv_mode(m, ncols, len);
     const int G = nnz < 0 ? 32 : mx::pick_group((double)nnz / (double)m);
-    if (op == MX_DV_LOGICAL_AND) { MX_DV_G(true) } else { MX_DV_G(false) }
-    MX_LAUNCH_CHECK();
-    return 0;
+    return mx::dispatch_int(mx::int_list<1, 0>{}, "mxd_csr_by_dvec", "logical", op == MX_DV_LOGICAL_AND, [&](auto lgl) {
+        return mx::launch_rows(mx::lane_groups{}, "mxd_csr_by_dvec", G, m, mx::DV_BLOCK,
+                               [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((mx::csr_by_dvec_kernel<g(), lgl() != 0>), grid, block, 0, st, m, indptr, indices,
+                               values, dvec, len, mode, op, x_is_lhs, values_out);
+        });
+    });
 }
 
 extern "C" int mxd_coo_by_dvec(int m, int ncols, int64_t nnz, const int32_t *rows, const int32_t *cols,

@@ -9,7 +9,7 @@
 // Gather: lengths -> exclusive scan -> one G-lane group per output row copies
 // indices and values (contiguous source and destination segments, so both
 // sides are coalesced inside a row).  HBM-bound: 4r + 8r + 4(r+1) + 2*12*nnz_out bytes.
-#include "mx_common.h"
+#include "mx_dispatch.h"
 
 namespace mx {
 
@@ -41,26 +41,6 @@ void gather_copy_kernel(int r, const int32_t *__restrict__ indptr, const int32_t
         new_indices[dst + k] = indices[src + k];
         if constexpr (HAS_VALUES) new_values[dst + k] = values[src + k];
     }
-}
-
-template <typename VT, bool HAS_VALUES>
-static int launch_gather_copy(int G, int r, const int32_t *indptr, const int32_t *indices, const void *values,
-                              const int32_t *rows, const int32_t *new_indptr, int32_t *new_indices,
-                              void *new_values, hipStream_t st)
-{
-#define MX_CASE(GG)                                                                                      \
-    case GG: {                                                                                           \
-        const unsigned grid = (unsigned)ceil_div(r, GATHER_BLOCK / GG);                                  \
-        hipLaunchKernelGGL((gather_copy_kernel<GG, VT, HAS_VALUES>), dim3(grid), dim3(GATHER_BLOCK), 0,  \
-                           st, r, indptr, indices, (const VT *)values, rows, new_indptr, new_indices,    \
-                           (VT *)new_values);                                                            \
-        break;                                                                                           \
-    }
-    switch (G) { MX_CASE(4) MX_CASE(8) MX_CASE(16) MX_CASE(32) MX_CASE(64)
-                 default: return set_error("gather: bad group %d", G); }
-#undef MX_CASE
-    MX_LAUNCH_CHECK();
-    return 0;
 }
 
 // ---- check_is_seq / check_is_rev_seq ---------------------------------------------------------
@@ -118,21 +98,18 @@ void sort_rows_kernel(int m, const int32_t *__restrict__ indptr, const int32_t *
     }
 }
 
-template <typename VT, bool HAS_VALUES>
-static int launch_sort_rows(int G, int m, const int32_t *indptr, const int32_t *indices, const void *values,
-                            int32_t *tmp_idx, void *tmp_val, hipStream_t st)
+// flag word = 1, launch (the kernel clears the word on a violation), read the word back
+template <typename F>
+static int run_flag_check(int32_t *flag_dev, int *flag_host, hipStream_t st, F &&launch)
 {
-#define MX_CASE(GG)                                                                                     \
-    case GG: {                                                                                          \
-        const unsigned grid = (unsigned)ceil_div(m, GATHER_BLOCK / GG);                                 \
-        hipLaunchKernelGGL((sort_rows_kernel<GG, VT, HAS_VALUES>), dim3(grid), dim3(GATHER_BLOCK), 0, st, \
-                           m, indptr, indices, (const VT *)values, tmp_idx, (VT *)tmp_val);             \
-        break;                                                                                          \
-    }
-    switch (G) { MX_CASE(4) MX_CASE(8) MX_CASE(16) MX_CASE(32) MX_CASE(64)
-                 default: return set_error("sort: bad group %d", G); }
-#undef MX_CASE
+    const int32_t one = 1;
+    MX_HIP(hipMemcpyAsync(flag_dev, &one, sizeof(one), hipMemcpyHostToDevice, st));
+    launch();
     MX_LAUNCH_CHECK();
+    int32_t flag = 0;
+    MX_HIP(hipMemcpyAsync(&flag, flag_dev, sizeof(flag), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipStreamSynchronize(st));
+    *flag_host = flag != 0;
     return 0;
 }
 
@@ -162,15 +139,15 @@ extern "C" int mxd_csr_gather_fill(int r, const int32_t *indptr, const int32_t *
     if (r == 0) return 0;
     hipStream_t st = mx::as_stream(stream);
     const int G = nnz_out < 0 ? 32 : mx::pick_group((double)nnz_out / (double)r);
-    switch (value_dtype) {
-        case MX_F64: return mx::launch_gather_copy<double, true>(G, r, indptr, indices, values, rows_take, new_indptr,
-                                                                 new_indices, new_values, st);
-        case MX_LGL: return mx::launch_gather_copy<int32_t, true>(G, r, indptr, indices, values, rows_take, new_indptr,
-                                                                  new_indices, new_values, st);
-        case MX_NONE: return mx::launch_gather_copy<int32_t, false>(G, r, indptr, indices, nullptr, rows_take,
-                                                                    new_indptr, new_indices, nullptr, st);
-        default: return mx::set_error("mxd_csr_gather_fill: unsupported value dtype %d", value_dtype);
-    }
+    MX_REQUIRE(value_dtype != MX_I32, "mxd_csr_gather_fill: unsupported value dtype %d", value_dtype);
+    return mx::dispatch_values("mxd_csr_gather_fill", value_dtype, [&](auto vk) {
+        using VT = typename decltype(vk)::VT;
+        return mx::launch_rows(mx::lane_groups{}, "gather", G, r, mx::GATHER_BLOCK,
+                               [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((mx::gather_copy_kernel<g(), VT, vk.has_values>), grid, block, 0, st, r, indptr, indices,
+                               (const VT *)values, rows_take, new_indptr, new_indices, (VT *)new_values);
+        });
+    });
 }
 
 extern "C" int mxd_check_is_seq(const int32_t *idx, int64_t n, int reversed, int32_t *workspace4, int *flag_host,
@@ -180,16 +157,10 @@ extern "C" int mxd_check_is_seq(const int32_t *idx, int64_t n, int reversed, int
     if (n < 2) { *flag_host = 1; return 0; }     // slice.cpp:27,39
     MX_REQUIRE(idx && workspace4, "mxd_check_is_seq: null pointer");
     hipStream_t st = mx::as_stream(stream);
-    const int32_t one = 1;
-    MX_HIP(hipMemcpyAsync(workspace4, &one, sizeof(one), hipMemcpyHostToDevice, st));
     const unsigned grid = (unsigned)(mx::ceil_div(n, 256) < 2048 ? mx::ceil_div(n, 256) : 2048);
-    hipLaunchKernelGGL(mx::is_seq_kernel, dim3(grid), dim3(256), 0, st, idx, n, reversed ? -1 : 1, workspace4);
-    MX_LAUNCH_CHECK();
-    int32_t flag = 0;
-    MX_HIP(hipMemcpyAsync(&flag, workspace4, sizeof(flag), hipMemcpyDeviceToHost, st));
-    MX_HIP(hipStreamSynchronize(st));
-    *flag_host = flag != 0;
-    return 0;
+    return mx::run_flag_check(workspace4, flag_host, st, [&] {
+        hipLaunchKernelGGL(mx::is_seq_kernel, dim3(grid), dim3(256), 0, st, idx, n, reversed ? -1 : 1, workspace4);
+    });
 }
 
 extern "C" int mxd_csr_rows_sorted(int m, const int32_t *indptr, const int32_t *indices, int32_t *workspace4,
@@ -204,16 +175,10 @@ extern "C" int mxd_csr_rows_sorted(int m, const int32_t *indptr, const int32_t *
     MX_HIP(hipStreamSynchronize(st));
     const int64_t nnz = ends[0];
     if (nnz < 2) { *flag_host = 1; return 0; }
-    const int32_t one = 1;
-    MX_HIP(hipMemcpyAsync(workspace4, &one, sizeof(one), hipMemcpyHostToDevice, st));
     const unsigned grid = (unsigned)(mx::ceil_div(nnz, 256) < 4096 ? mx::ceil_div(nnz, 256) : 4096);
-    hipLaunchKernelGGL(mx::rows_sorted_kernel, dim3(grid), dim3(256), 0, st, m, indptr, indices, nnz, workspace4);
-    MX_LAUNCH_CHECK();
-    int32_t flag = 0;
-    MX_HIP(hipMemcpyAsync(&flag, workspace4, sizeof(flag), hipMemcpyDeviceToHost, st));
-    MX_HIP(hipStreamSynchronize(st));
-    *flag_host = flag != 0;
-    return 0;
+    return mx::run_flag_check(workspace4, flag_host, st, [&] {
+        hipLaunchKernelGGL(mx::rows_sorted_kernel, dim3(grid), dim3(256), 0, st, m, indptr, indices, nnz, workspace4);
+    });
 }
 
 extern "C" int mxd_csr_sort_rows(int m, int64_t nnz, const int32_t *indptr, int32_t *indices, void *values,
@@ -224,20 +189,17 @@ extern "C" int mxd_csr_sort_rows(int m, int64_t nnz, const int32_t *indptr, int3
     MX_REQUIRE(indptr && indices && tmp_indices, "mxd_csr_sort_rows: null pointer");
     hipStream_t st = mx::as_stream(stream);
     const int G = mx::pick_group((double)nnz / (double)m);
-    int rc;
-    size_t vbytes = 0;
-    switch (value_dtype) {
-        case MX_F64: rc = mx::launch_sort_rows<double, true>(G, m, indptr, indices, values, tmp_indices, tmp_values, st);
-                     vbytes = 8; break;
-        case MX_LGL: case MX_I32:
-                     rc = mx::launch_sort_rows<int32_t, true>(G, m, indptr, indices, values, tmp_indices, tmp_values, st);
-                     vbytes = 4; break;
-        case MX_NONE: rc = mx::launch_sort_rows<int32_t, false>(G, m, indptr, indices, nullptr, tmp_indices, nullptr, st);
-                     break;
-        default: return mx::set_error("mxd_csr_sort_rows: unsupported value dtype %d", value_dtype);
-    }
-    if (rc) return rc;
-    MX_HIP(hipMemcpyAsync(indices, tmp_indices, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    if (vbytes) MX_HIP(hipMemcpyAsync(values, tmp_values, (size_t)nnz * vbytes, hipMemcpyDeviceToDevice, st));
-    return 0;
+    return mx::dispatch_values("mxd_csr_sort_rows", value_dtype, [&](auto vk) {
+        using VT = typename decltype(vk)::VT;
+        const int rc = mx::launch_rows(mx::lane_groups{}, "sort", G, m, mx::GATHER_BLOCK,
+                                       [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((mx::sort_rows_kernel<g(), VT, vk.has_values>), grid, block, 0, st, m, indptr, indices,
+                               (const VT *)values, tmp_indices, (VT *)tmp_values);
+        });
+        if (rc) return rc;
+        MX_HIP(hipMemcpyAsync(indices, tmp_indices, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        if (vk.has_values)
+            MX_HIP(hipMemcpyAsync(values, tmp_values, (size_t)nnz * sizeof(VT), hipMemcpyDeviceToDevice, st));
+        return 0;
+    });
 }

@@ -26,23 +26,11 @@
 //
 // Roofline: HBM-bound; algorithmic bytes = 2*(12 nnz + 4(m+1)) read + 12 nnz_out + 4(m+1)
 // written; the count pass re-reads the indices (8 nnz) on top of that.
-#include "mx_common.h"
+#include "mx_dispatch.h"
 
 namespace mx {
 
 constexpr int MERGE_BLOCK = 256;
-
-// ballot restricted to this lane's G-wide group
-template <int G>
-__device__ __forceinline__ unsigned long long group_ballot(bool pred)
-{
-    const unsigned long long b = __ballot(pred);
-    if constexpr (G == 64) return b;
-    else {
-        const int shift = lane_id() & ~(G - 1);
-        return (b >> shift) & ((1ULL << G) - 1ULL);
-    }
-}
 
 // lower_bound(key) in a sorted row held one entry per lane (lane u of the group holds tbl = entry u, lanes past
 // the row's end hold INT_MAX): binary search whose probes are cross-lane reads (ds_bpermute), not memory loads.
@@ -239,7 +227,12 @@ void values_elemwise_kernel(int64_t nnz, const VT *__restrict__ a, const VT *__r
         out[i] = combine<OP, VT>(a[i], b[i]);
 }
 
+using merge_groups = int_list<8, 16, 32, 64>;          // what merge_group can return
+using merge_ops = int_list<MX_OP_ADD, MX_OP_SUB, MX_OP_MUL, MX_OP_OR, MX_OP_XOR, MX_OP_AND>;
+template <int OP> using merge_vt = std::conditional_t<(OP >= MX_OP_OR), int32_t, double>;
+
 static inline bool op_is_intersect(int op) { return op == MX_OP_MUL || op == MX_OP_AND; }
+static inline bool op_known(int op) { return op >= MX_OP_ADD && op <= MX_OP_AND; }
 
 // G from the mean length of the longer operand's rows; nnz hints < 0 => 32
 int merge_group(int m, int64_t nnz1, int64_t nnz2)
@@ -253,50 +246,23 @@ int merge_count_launch(int op, int G, int m, const int32_t *p1, const int32_t *j
                        const int32_t *j2, int32_t *counts, hipStream_t st)
 {
     const bool isect = op_is_intersect(op);
-#define MX_CASE(GG)                                                                                   \
-    case GG: {                                                                                        \
-        const unsigned grid = (unsigned)ceil_div(m, MERGE_BLOCK / GG);                                \
-        if (isect) hipLaunchKernelGGL((merge_count_kernel<GG, true>), dim3(grid), dim3(MERGE_BLOCK), 0, st, \
-                                      m, p1, j1, p2, j2, counts);                                     \
-        else hipLaunchKernelGGL((merge_count_kernel<GG, false>), dim3(grid), dim3(MERGE_BLOCK), 0, st, \
-                                m, p1, j1, p2, j2, counts);                                           \
-        break;                                                                                        \
-    }
-    switch (G) { MX_CASE(8) MX_CASE(16) MX_CASE(32) MX_CASE(64) default: return set_error("merge: bad group %d", G); }
-#undef MX_CASE
-    MX_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int OP, typename VT>
-static int merge_fill_op(int G, int m, const int32_t *p1, const int32_t *j1, const void *x1, const int32_t *p2,
-                         const int32_t *j2, const void *x2, const int32_t *po, int32_t *jo, void *xo, hipStream_t st)
-{
-#define MX_CASE(GG)                                                                                   \
-    case GG: {                                                                                        \
-        const unsigned grid = (unsigned)ceil_div(m, MERGE_BLOCK / GG);                                \
-        hipLaunchKernelGGL((merge_fill_kernel<GG, OP, VT>), dim3(grid), dim3(MERGE_BLOCK), 0, st, m,  \
-                           p1, j1, (const VT *)x1, p2, j2, (const VT *)x2, po, jo, (VT *)xo);         \
-        break;                                                                                        \
-    }
-    switch (G) { MX_CASE(8) MX_CASE(16) MX_CASE(32) MX_CASE(64) default: return set_error("merge: bad group %d", G); }
-#undef MX_CASE
-    MX_LAUNCH_CHECK();
-    return 0;
+    return launch_rows(merge_groups{}, "merge", G, m, MERGE_BLOCK, [&](auto g, dim3 grid, dim3 block) {
+        if (isect) hipLaunchKernelGGL((merge_count_kernel<g(), true>), grid, block, 0, st, m, p1, j1, p2, j2, counts);
+        else hipLaunchKernelGGL((merge_count_kernel<g(), false>), grid, block, 0, st, m, p1, j1, p2, j2, counts);
+    });
 }
 
 int merge_fill_launch(int op, int G, int m, const int32_t *p1, const int32_t *j1, const void *x1, const int32_t *p2,
                       const int32_t *j2, const void *x2, const int32_t *po, int32_t *jo, void *xo, hipStream_t st)
 {
-    switch (op) {
-        case MX_OP_ADD: return merge_fill_op<MX_OP_ADD, double>(G, m, p1, j1, x1, p2, j2, x2, po, jo, xo, st);
-        case MX_OP_SUB: return merge_fill_op<MX_OP_SUB, double>(G, m, p1, j1, x1, p2, j2, x2, po, jo, xo, st);
-        case MX_OP_MUL: return merge_fill_op<MX_OP_MUL, double>(G, m, p1, j1, x1, p2, j2, x2, po, jo, xo, st);
-        case MX_OP_OR:  return merge_fill_op<MX_OP_OR, int32_t>(G, m, p1, j1, x1, p2, j2, x2, po, jo, xo, st);
-        case MX_OP_XOR: return merge_fill_op<MX_OP_XOR, int32_t>(G, m, p1, j1, x1, p2, j2, x2, po, jo, xo, st);
-        case MX_OP_AND: return merge_fill_op<MX_OP_AND, int32_t>(G, m, p1, j1, x1, p2, j2, x2, po, jo, xo, st);
-        default: return set_error("merge: unknown op %d", op);
-    }
+    MX_REQUIRE(op_known(op), "merge: unknown op %d", op);
+    return dispatch_int(merge_ops{}, "merge", "op", op, [&](auto o) {
+        using VT = merge_vt<o()>;
+        return launch_rows(merge_groups{}, "merge", G, m, MERGE_BLOCK, [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((merge_fill_kernel<g(), o(), VT>), grid, block, 0, st, m, p1, j1, (const VT *)x1, p2,
+                               j2, (const VT *)x2, po, jo, (VT *)xo);
+        });
+    });
 }
 
 }  // namespace mx
@@ -336,17 +302,12 @@ extern "C" int mxd_values_elemwise(int op, int64_t nnz, const void *values1, con
     if (nnz <= 0) return 0;
     hipStream_t st = mx::as_stream(stream);
     const unsigned grid = (unsigned)(mx::ceil_div(nnz, 256) < 4096 ? mx::ceil_div(nnz, 256) : 4096);
-#define MX_CASE(OPV, VT)                                                                             \
-    case OPV:                                                                                         \
-        hipLaunchKernelGGL((mx::values_elemwise_kernel<VT, OPV>), dim3(grid), dim3(256), 0, st, nnz,  \
-                           (const VT *)values1, (const VT *)values2, (VT *)out_values);               \
-        break;
-    switch (op) {
-        MX_CASE(MX_OP_ADD, double) MX_CASE(MX_OP_SUB, double) MX_CASE(MX_OP_MUL, double)
-        MX_CASE(MX_OP_OR, int32_t) MX_CASE(MX_OP_XOR, int32_t) MX_CASE(MX_OP_AND, int32_t)
-        default: return mx::set_error("mxd_values_elemwise: unknown op %d", op);
-    }
-#undef MX_CASE
-    MX_LAUNCH_CHECK();
-    return 0;
+    MX_REQUIRE(mx::op_known(op), "mxd_values_elemwise: unknown op %d", op);
+    return mx::dispatch_int(mx::merge_ops{}, "mxd_values_elemwise", "op", op, [&](auto o) {
+        using VT = mx::merge_vt<o()>;
+        hipLaunchKernelGGL((mx::values_elemwise_kernel<VT, o()>), dim3(grid), dim3(256), 0, st, nnz,
+                           (const VT *)values1, (const VT *)values2, (VT *)out_values);
+        MX_LAUNCH_CHECK();
+        return 0;
+    });
 }

@@ -77,6 +77,15 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & (MX_WAVE - 1); }
 // wave-uniform broadcast of a value known to be uniform (moves it to an SGPR)
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// ballot restricted to this lane's G-wide group
+template <int G>
+__device__ __forceinline__ unsigned long long group_ballot(bool pred)
+{
+    const unsigned long long b = __ballot(pred);
+    if constexpr (G == 64) return b;
+    else return (b >> (lane_id() & ~(G - 1))) & ((1ULL << G) - 1ULL);
+}
+
 __device__ __forceinline__ double readlane_f64(double v, int lane)
 {
     union { double d; int i[2]; } u;

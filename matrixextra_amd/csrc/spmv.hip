@@ -11,7 +11,7 @@
 // (coalesced (j, a) reads, gathered v[j] reads served by L2 — v is 0.8 MB for
 // the headline config), then a butterfly __shfl_xor reduction inside the group.
 // HBM-bound: algorithmic bytes = 4(m+1) + 12 nnz + s*K + s*m.
-#include "mx_common.h"
+#include "mx_dispatch.h"
 
 namespace mx {
 
@@ -118,38 +118,16 @@ void spmv_group_kernel(int m, const int32_t *__restrict__ indptr, const int32_t 
     }
 }
 
-template <int KIND>
-static int launch_spmv(int G, int m, const int32_t *indptr, const int32_t *indices, const double *values,
-                       const void *v, void *y, hipStream_t st)
-{
-#define MX_SPMV_CASE(GG)                                                                        \
-    case GG: {                                                                                  \
-        const unsigned grid = (unsigned)ceil_div(m, (SPMV_BLOCK / GG) * SPMV_ROWS);             \
-        hipLaunchKernelGGL((spmv_group_kernel<GG, KIND>), dim3(grid), dim3(SPMV_BLOCK), 0, st,  \
-                           m, indptr, indices, values, v, y);                                   \
-        break;                                                                                  \
-    }
-    switch (G) {
-        MX_SPMV_CASE(4) MX_SPMV_CASE(8) MX_SPMV_CASE(16) MX_SPMV_CASE(32) MX_SPMV_CASE(64)
-        default: return set_error("spmv: bad group size %d", G);
-    }
-#undef MX_SPMV_CASE
-    MX_LAUNCH_CHECK();
-    return 0;
-}
-
 // nnz is only used to pick the group width; pass <0 when unknown (=> 32 lanes per row)
 int spmv_launch(int m, int64_t nnz, const int32_t *indptr, const int32_t *indices, const double *values,
                 const void *v, int v_dtype, void *y, hipStream_t st)
 {
     const int G = nnz < 0 ? 32 : pick_group((double)nnz / (double)(m > 0 ? m : 1));
-    switch (v_dtype) {
-        case MX_F64: return launch_spmv<MX_F64>(G, m, indptr, indices, values, v, y, st);
-        case MX_I32: return launch_spmv<MX_I32>(G, m, indptr, indices, values, v, y, st);
-        case MX_LGL: return launch_spmv<MX_LGL>(G, m, indptr, indices, values, v, y, st);
-        case MX_F32: return launch_spmv<MX_F32>(G, m, indptr, indices, values, v, y, st);
-        default: return set_error("spmv: unsupported vector dtype %d", v_dtype);
-    }
+    return dispatch_int(int_list<MX_F64, MX_I32, MX_LGL, MX_F32>{}, "spmv", "vector dtype", v_dtype, [&](auto kind) {
+        return launch_rows(lane_groups{}, "spmv", G, m, SPMV_BLOCK, [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((spmv_group_kernel<g(), kind()>), grid, block, 0, st, m, indptr, indices, values, v, y);
+        }, SPMV_ROWS);
+    });
 }
 
 }  // namespace mx

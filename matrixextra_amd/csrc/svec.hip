@@ -8,7 +8,7 @@
 // vector of y by binary search, the products are reduced with a butterfly.  NA rules as in SpMV.
 // csr (.) dense: one dense read per entry at [row + nrows*col] (column-major, a gather by construction).
 // With CSC set the compressed axis is the column and the read is at [indices[k] + nrows*col] (contiguous runs).
-#include "mx_common.h"
+#include "mx_dispatch.h"
 
 namespace mx {
 
@@ -77,16 +77,24 @@ void csr_by_dense_kernel(int m, int64_t nr, const int32_t *__restrict__ indptr, 
     }
 }
 
-}  // namespace mx
+using sv_kinds = int_list<0, 1, 2, 3, 4>;
 
-#define MX_SV_G(KERNEL, KIND, ...)                                                                             \
-    switch (G) {                                                                                               \
-        case 4:  hipLaunchKernelGGL((mx::KERNEL<4, KIND>),  dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 4)),  dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
-        case 8:  hipLaunchKernelGGL((mx::KERNEL<8, KIND>),  dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 8)),  dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
-        case 16: hipLaunchKernelGGL((mx::KERNEL<16, KIND>), dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 16)), dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
-        case 32: hipLaunchKernelGGL((mx::KERNEL<32, KIND>), dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 32)), dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL((mx::KERNEL<64, KIND>), dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 64)), dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
-    }
+// csr_by_dense_kernel over m compressed rows (CSR rows, or CSC columns) of mean length nnz / m; nnz < 0: unknown
+template <bool CSC>
+static int launch_by_dense(const char *what, int m, int64_t nr, int64_t nnz, const int32_t *indptr,
+                           const int32_t *indices, const void *values, const void *dense, int kind, void *out,
+                           hipStream_t st)
+{
+    const int G = nnz < 0 ? 32 : pick_group((double)nnz / (double)m);
+    return dispatch_int(sv_kinds{}, what, "kind", kind, [&](auto k) {
+        return launch_rows(lane_groups{}, what, G, m, SV_BLOCK, [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((csr_by_dense_kernel<g(), k(), CSC>), grid, block, 0, st, m, nr, indptr, indices, values,
+                               dense, out);
+        });
+    });
+}
+
+}  // namespace mx
 
 extern "C" int mxd_spmv_csr_svec(int m, int64_t nnz, const int32_t *indptr, const int32_t *indices, const double *values,
                                  const int32_t *y_indices_base1, int ny, const void *y_values, int kind, double *out,
@@ -97,15 +105,13 @@ extern "C" int mxd_spmv_csr_svec(int m, int64_t nnz, const int32_t *indptr, cons
     hipStream_t st = mx::as_stream(stream);
     if (ny == 0) { MX_HIP(hipMemsetAsync(out, 0, sizeof(double) * (size_t)m, st)); return 0; }     // matmul.cpp:495-496
     const int G = nnz < 0 ? 32 : mx::pick_group((double)nnz / (double)m);
-    switch (kind) {
-        case 0: MX_SV_G(csr_svec_kernel, 0, m, indptr, indices, values, y_indices_base1, ny, y_values, out); break;
-        case 1: MX_SV_G(csr_svec_kernel, 1, m, indptr, indices, values, y_indices_base1, ny, y_values, out); break;
-        case 2: MX_SV_G(csr_svec_kernel, 2, m, indptr, indices, values, y_indices_base1, ny, y_values, out); break;
-        case 3: MX_SV_G(csr_svec_kernel, 3, m, indptr, indices, values, y_indices_base1, ny, y_values, out); break;
-        default: MX_SV_G(csr_svec_kernel, 4, m, indptr, indices, values, y_indices_base1, ny, y_values, out); break;
-    }
-    MX_LAUNCH_CHECK();
-    return 0;
+    return mx::dispatch_int(mx::sv_kinds{}, "mxd_spmv_csr_svec", "kind", kind, [&](auto k) {
+        return mx::launch_rows(mx::lane_groups{}, "mxd_spmv_csr_svec", G, m, mx::SV_BLOCK,
+                               [&](auto g, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL((mx::csr_svec_kernel<g(), k()>), grid, block, 0, st, m, indptr, indices, values,
+                               y_indices_base1, ny, y_values, out);
+        });
+    });
 }
 
 extern "C" int mxd_csr_by_dense_elemwise(int m, int64_t nnz, const int32_t *indptr, const int32_t *indices,
@@ -114,29 +120,9 @@ extern "C" int mxd_csr_by_dense_elemwise(int m, int64_t nnz, const int32_t *indp
 {
     MX_REQUIRE(m >= 0 && kind >= 0 && kind <= 4, "mxd_csr_by_dense_elemwise: bad arguments");
     if (m == 0 || nnz == 0) return 0;
-    hipStream_t st = mx::as_stream(stream);
-    const int G = nnz < 0 ? 32 : mx::pick_group((double)nnz / (double)m);
-    const int64_t nr = m;
-    switch (kind) {
-        case 0: MX_SV_G(csr_by_dense_kernel, 0, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
-        case 1: MX_SV_G(csr_by_dense_kernel, 1, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
-        case 2: MX_SV_G(csr_by_dense_kernel, 2, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
-        case 3: MX_SV_G(csr_by_dense_kernel, 3, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
-        default: MX_SV_G(csr_by_dense_kernel, 4, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
-    }
-    MX_LAUNCH_CHECK();
-    return 0;
+    return mx::launch_by_dense<false>("mxd_csr_by_dense_elemwise", m, m, nnz, indptr, indices, values, dense_colmajor,
+                                      kind, values_out, mx::as_stream(stream));
 }
-
-// MX_SV_G for the CSC addressing of csr_by_dense_kernel; `m` is the number of columns there
-#define MX_SV_GC(KIND, ...)                                                                                    \
-    switch (G) {                                                                                               \
-        case 4:  hipLaunchKernelGGL((mx::csr_by_dense_kernel<4, KIND, true>),  dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 4)),  dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
-        case 8:  hipLaunchKernelGGL((mx::csr_by_dense_kernel<8, KIND, true>),  dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 8)),  dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
-        case 16: hipLaunchKernelGGL((mx::csr_by_dense_kernel<16, KIND, true>), dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 16)), dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
-        case 32: hipLaunchKernelGGL((mx::csr_by_dense_kernel<32, KIND, true>), dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 32)), dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL((mx::csr_by_dense_kernel<64, KIND, true>), dim3((unsigned)mx::ceil_div(m, mx::SV_BLOCK / 64)), dim3(mx::SV_BLOCK), 0, st, __VA_ARGS__); break; \
-    }
 
 extern "C" int mxd_csc_by_dense_elemwise(int ncols, int nrows, int64_t nnz, const int32_t *indptr,
                                          const int32_t *indices, const void *values, const void *dense_colmajor,
@@ -145,17 +131,6 @@ extern "C" int mxd_csc_by_dense_elemwise(int ncols, int nrows, int64_t nnz, cons
     MX_REQUIRE(ncols >= 0 && nrows >= 0 && kind >= 0 && kind <= 4, "mxd_csc_by_dense_elemwise: bad arguments");
     if (ncols == 0 || nnz == 0) return 0;
     MX_REQUIRE(nrows > 0, "mxd_csc_by_dense_elemwise: entries in a matrix without rows");
-    hipStream_t st = mx::as_stream(stream);
-    const int m = ncols;
-    const int64_t nr = nrows;
-    const int G = nnz < 0 ? 32 : mx::pick_group((double)nnz / (double)m);
-    switch (kind) {
-        case 0: MX_SV_GC(0, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
-        case 1: MX_SV_GC(1, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
-        case 2: MX_SV_GC(2, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
-        case 3: MX_SV_GC(3, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
-        default: MX_SV_GC(4, m, nr, indptr, indices, values, dense_colmajor, values_out); break;
-    }
-    MX_LAUNCH_CHECK();
-    return 0;
+    return mx::launch_by_dense<true>("mxd_csc_by_dense_elemwise", ncols, nrows, nnz, indptr, indices, values,
+                                     dense_colmajor, kind, values_out, mx::as_stream(stream));
 }
