@@ -266,6 +266,38 @@ int mxd_csc_dense_na_fill(int nrows, int ncols, int64_t nnz, const int32_t *indp
                           const double *values, const void *dense_colmajor, int dense_kind, const void *workspace,
                           int32_t *out_indptr, int32_t *out_indices, double *out_values, void *stream);
 
+/* CSR * sparse vector, the masked row scaling (multiply_csr_by_svec_no_NAs / _keep_NAs, src/operators.cpp:3426-3697;
+ * DESIGN.md §4.11).  X is m x ncol in CSR with f64 values and sorted rows; the vector is vi_base1[nv] (sorted 1-based
+ * positions), vx[nv] f64 values (NULL: an nsparseVector) and its length, recycled down the rows: output row r is
+ * ruled by position r mod length.  Not stored: no entries, or with keep_na the row's NaN / +-Inf entries (NaN as it
+ * is, +-Inf as the default NaN).  Stored: the row times the value (copied without values); with keep_na a NaN / +-Inf
+ * value fills all ncol columns (NaN: the value everywhere; +-Inf: the default NaN, and value * x at the stored
+ * columns, the last entry of a repeated column winning).
+ * count: out_indptr[m+1] (the scanned counts), *nnz_out_host = output entries (64-bit; above INT32_MAX the call
+ *   fails, which the reference does not check), *x_na_host = 1 when a row that the vector does not store holds a NaN
+ *   / +-Inf (only looked for under keep_na), else 0; one synchronise.  It stands in for the reference's
+ *   contains_any_nas_or_inf(values) where that flag matters (rows the vector drops): with 0 the dropped rows left
+ *   nothing behind.  It is information for the caller; the result does not depend on it and mx_* does not use it.  fill: out_indices / out_values of that many
+ *   entries.  workspace: mxd_csr_by_svec_workspace_bytes(m); the count leaves each row's position in the vector
+ *   there for the fill. */
+size_t mxd_csr_by_svec_workspace_bytes(int m);
+int mxd_csr_by_svec_count(int m, int ncol, int64_t nnz, const int32_t *indptr, const double *values,
+                          const int32_t *vi_base1, int64_t nv, const double *vx, int length, int keep_na,
+                          void *workspace, int32_t *out_indptr, int64_t *nnz_out_host, int64_t *x_na_host,
+                          void *stream);
+int mxd_csr_by_svec_fill(int m, int ncol, int64_t nnz, const int32_t *indptr, const int32_t *indices,
+                         const double *values, const int32_t *vi_base1, int64_t nv, const double *vx, int length,
+                         int keep_na, const void *workspace, const int32_t *out_indptr, int32_t *out_indices,
+                         double *out_values, void *stream);
+
+/* sort_sparse_indices of a sparse vector (sort_vector_indices_*, src/misc.cpp:460-527): ii[n] (non-negative) and
+ * its values xx[n] (MX_F64, MX_I32 / MX_LGL, or MX_NONE with xx NULL) sorted by ii in place, stably, by the LSD
+ * radix passes of the transpose.  One reduction first: *was_sorted_host = 1 and nothing is
+ * written when ii is already non-decreasing.  workspace: mxd_sort_vector_indices_workspace_bytes(n). */
+size_t mxd_sort_vector_indices_workspace_bytes(int64_t n);
+int mxd_sort_vector_indices(int32_t *ii, void *xx, int64_t n, int value_dtype, void *workspace,
+                            int *was_sorted_host, void *stream);
+
 /* CSR (op) dense vector with R's recycling (multiply_csr_by_dvec_no_NAs<>, src/operators.cpp:1604-2140): a
  * values-only transform, out[k] = values[k] op dvec[(row + col*m) mod dvec_len] (`recyle_pos`, :1478; the reference's
  * four length branches :1640,1773,1870,2033 all reduce to it).  op: R's * ^ / %% %/% on f64 values with the sparse
@@ -699,6 +731,16 @@ int mx_check_is_rev_seq(const int32_t *indices, int64_t n, int *result);
 int mx_check_indices_are_sorted(const int32_t *indptr, const int32_t *indices, int nrows, int *result);
 int mx_sort_sparse_indices(const int32_t *indptr, int32_t *indices, void *values,
                            int value_dtype, int nrows);
+/* sort_vector_indices_{numeric,integer,logical,binary}  src/misc.cpp:460-527 (R/utils.R:126-155): a sparse vector's
+ * ii (and xx; MX_NONE with NULL for an nsparseVector) in host memory, sorted in place; left alone when sorted. */
+int mx_sort_vector_indices(int32_t *ii, void *xx, int64_t n, int value_dtype);
+/* multiply_csr_by_svec_no_NAs (keep_NAs = 0) and multiply_csr_by_svec_keep_NAs  src/operators.cpp:3426-3697,
+ * through mxd_csr_by_svec_count / _fill: a new indptr (nrows + 1), indices and f64 values.  ii_base1 sorted, xx NULL
+ * for an nsparseVector, length dividing nrows.  A result above INT32_MAX entries (dense-filled rows) fails before
+ * anything is allocated for it; the reference does not check. */
+int mx_multiply_csr_by_svec_begin(const int32_t *indptr, int nrows, const int32_t *indices, const double *values,
+                                  const int32_t *ii_base1, const double *xx, int64_t nnz_v, int ncols, int length,
+                                  int keep_NAs, mx_result **res, mx_result_info *info);
 
 #ifdef __cplusplus
 }

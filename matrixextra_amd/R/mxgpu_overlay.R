@@ -52,7 +52,12 @@
     "multiply_csc_by_dense_ignore_NAs_integer", "multiply_csc_by_dense_ignore_NAs_logical",
     "logicaland_csc_by_dense_ignore_NAs",
     "multiply_csc_by_dense_keep_NAs_numeric", "multiply_csc_by_dense_keep_NAs_integer",
-    "multiply_csc_by_dense_keep_NAs_logical", "multiply_csc_by_dense_keep_NAs_float32"
+    "multiply_csc_by_dense_keep_NAs_logical", "multiply_csc_by_dense_keep_NAs_float32",
+    ## RsparseMatrix * sparseVector (multiply_csr_by_svec_elemwise_internal, R/operators.R:1564-1622) and the
+    ## sparse-vector branch of sort_sparse_indices (R/utils.R:126-155), which sorts its arguments in place
+    "multiply_csr_by_svec_no_NAs", "multiply_csr_by_svec_keep_NAs",
+    "sort_vector_indices_numeric", "sort_vector_indices_integer", "sort_vector_indices_logical",
+    "sort_vector_indices_binary"
 )
 
 mxgpu_enable <- function(shim_path, min_nnz = 0L) {

@@ -3,7 +3,8 @@
 Layers (SURVEY.md §1 / DESIGN.md):
   csrc/*.hip + include/mxgpu.h   hand-written HIP kernels behind a C-ABI (libmxgpu.so)
   exports.py                     twins of R/RcppExports.R wrappers (ctypes -> C-ABI)
-  matrices.py                    dgRMatrix / lgRMatrix / ngRMatrix / dgCMatrix / d/l/ngTMatrix / float32 stand-ins
+  matrices.py                    dgRMatrix / lgRMatrix / ngRMatrix / dgCMatrix / d/l/ngTMatrix / d/i/l/nsparseVector / float32
+                                 stand-ins
   matmul.py operators.py slice.py cleanup.py   mirrors of the R glue (checks, messages, dimnames, classes)
   device.py                      device-resident CSR + mxd_* launches on torch tensors (bench, multi-GPU)
   distributed.py                 row-block sharding + RCCL all-gather of C
@@ -16,9 +17,11 @@ from .matrices import (DenseMatrix, MatrixExtraError, NA_INTEGER, NA_LOGICAL, NA
                        lgRMatrix, ngRMatrix, options, sort_sparse_indices)
 from .matrices import as_csc_matrix, t_deep, t_shallow  # noqa: F401
 from .matrices import TsparseMatrix, as_coo_matrix, dgTMatrix, lgTMatrix, ngTMatrix  # noqa: F401
+from .matrices import (as_sparse_vector, dsparseVector, isparseVector, lsparseVector, nsparseVector,  # noqa: F401
+                       sparseVector)
 from .matmul import RLogical, crossprod, tcrossprod  # noqa: F401  (`%*%` is the @ operator)
 from .operators import (add_csr_matrices, logicalor_csr_matrices, multiply_csr_by_coo,  # noqa: F401
-                        multiply_csr_by_csr, xor_csr_matrices)
+                        multiply_csr_by_csr, multiply_csr_by_svec_elemwise, xor_csr_matrices)
 from .slice import subset_coo, subset_csr  # noqa: F401
 from .cleanup import check_sparse_matrix, filterSparse, remove_sparse_zeros  # noqa: F401
 

@@ -81,6 +81,10 @@ def load() -> C.CDLL:
     lib.mxd_compact_workspace_bytes.argtypes = [C.c_int64]
     lib.mxd_csc_dense_na_workspace_bytes.restype = C.c_size_t
     lib.mxd_csc_dense_na_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.mxd_csr_by_svec_workspace_bytes.restype = C.c_size_t
+    lib.mxd_csr_by_svec_workspace_bytes.argtypes = [C.c_int]
+    lib.mxd_sort_vector_indices_workspace_bytes.restype = C.c_size_t
+    lib.mxd_sort_vector_indices_workspace_bytes.argtypes = [C.c_int64]
     if lib.mx_abi_version() != 1:
         raise MxError("libmxgpu.so ABI version mismatch")
     _lib = lib

@@ -684,6 +684,43 @@ int mx_multiply_csc_by_dense_keep_NAs_float32(const int32_t *indptr, int ncols, 
     return csc_by_dense_keep(indptr, ncols, indices, values, dense, nrows, 1, res, info);
 }
 
+// ---- CSR * sparse vector (svecmul.hip) --------------------------------------------------------
+// multiply_csr_by_svec_no_NAs (operators.cpp:3426-3498, keep_NAs = 0) and multiply_csr_by_svec_keep_NAs
+// (:3500-3697): ii_base1 sorted, xx NULL for an nsparseVector; the rows of X sorted
+int mx_multiply_csr_by_svec_begin(const int32_t *indptr, int nrows, const int32_t *indices, const double *values,
+                                  const int32_t *ii_base1, const double *xx, int64_t nnz_v, int ncols, int length,
+                                  int keep_NAs, mx_result **res_out, mx_result_info *info)
+{
+    MX_REQUIRE(res_out && info && indptr && nrows >= 0 && ncols >= 0 && nnz_v >= 0,
+               "mx_multiply_csr_by_svec_begin: bad arguments");
+    MX_REQUIRE(indptr[0] == 0 && indptr[nrows] >= 0, "mx_multiply_csr_by_svec_begin: bad index pointer");
+    // :3532-3533 (throw_internal_err), asked of both routes here
+    MX_REQUIRE(nrows == 0 || (length > 0 && nnz_v <= length && length <= nrows && nrows % length == 0),
+               "mx_multiply_csr_by_svec_begin: the vector's length must divide the number of rows");
+    *res_out = nullptr;
+    return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
+        Csr A;
+        if (A.upload(indptr, indices, values, nrows, sizeof(double))) return 1;
+        DevBuf vi, vx, ws;
+        if (vi.upload(ii_base1, sizeof(int32_t) * (size_t)nnz_v)) return 1;
+        if (xx && vx.upload(xx, sizeof(double) * (size_t)nnz_v)) return 1;
+        if (ws.alloc(mxd_csr_by_svec_workspace_bytes(nrows))) return 1;
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        int64_t total = 0, x_na = 0;
+        if (mxd_csr_by_svec_count(nrows, ncols, A.nnz, A.p.as<int32_t>(), A.x.as<double>(), vi.as<int32_t>(), nnz_v,
+                                  xx ? vx.as<double>() : nullptr, length, keep_NAs, ws.p, res.indptr.as<int32_t>(),
+                                  &total, &x_na, nullptr)) return 1;
+        res.set_sizes((int64_t)nrows + 1, total, total);
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
+        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+        if (total == 0) return 0;
+        return mxd_csr_by_svec_fill(nrows, ncols, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.as<double>(),
+                                    vi.as<int32_t>(), nnz_v, xx ? vx.as<double>() : nullptr, length, keep_NAs, ws.p,
+                                    res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.as<double>(),
+                                    nullptr);
+    });
+}
+
 // ---- CSR (op) dense vector (§8f rank 4) ----------------------------------------------------------------------
 static int csr_by_dvec_export(const int32_t *indptr, const int32_t *indices, const void *values, int nrows,
                               const void *dvec, int64_t dvec_len, int ncols, int op, int lhs, void *values_out)
@@ -1314,6 +1351,26 @@ int mx_sort_sparse_indices(const int32_t *indptr, int32_t *indices, void *values
                           vb ? value_dtype : MX_NONE, tj.as<int32_t>(), tx.p, nullptr)) return 1;
     if (mx::xfer_d2h(indices, A.j.p, sizeof(int32_t) * (size_t)A.nnz)) return 1;
     if (vb && mx::xfer_d2h(values, A.x.p, vb * (size_t)A.nnz)) return 1;
+    return 0;
+}
+
+// sort_vector_indices_{numeric,integer,logical,binary}  src/misc.cpp:460-527: sorts ii (and xx) in place
+int mx_sort_vector_indices(int32_t *ii, void *xx, int64_t n, int value_dtype)
+{
+    MX_REQUIRE(n >= 0 && n <= INT_MAX, "mx_sort_vector_indices: bad size");
+    if (n < 2) return 0;
+    const size_t vb = value_dtype == MX_NONE ? 0 : dtype_bytes(value_dtype);
+    MX_REQUIRE(ii && (vb || value_dtype == MX_NONE) && (!vb || xx), "mx_sort_vector_indices: bad arguments");
+    DevBuf di, dx, ws;
+    if (di.upload(ii, sizeof(int32_t) * (size_t)n)) return 1;
+    if (vb && dx.upload(xx, vb * (size_t)n)) return 1;
+    if (ws.alloc(mxd_sort_vector_indices_workspace_bytes(n))) return 1;
+    int was_sorted = 1;
+    if (mxd_sort_vector_indices(di.as<int32_t>(), vb ? dx.p : nullptr, n, value_dtype, ws.p, &was_sorted, nullptr))
+        return 1;
+    if (was_sorted) return 0;                  // nothing to do, inputs untouched
+    if (mx::xfer_d2h(ii, di.p, sizeof(int32_t) * (size_t)n)) return 1;
+    if (vb && mx::xfer_d2h(xx, dx.p, vb * (size_t)n)) return 1;
     return 0;
 }
 

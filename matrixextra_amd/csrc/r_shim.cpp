@@ -773,6 +773,49 @@ SEXP _MatrixExtra_multiply_csc_by_dense_keep_NAs_integer(SEXP p_, SEXP i_, SEXP 
 SEXP _MatrixExtra_multiply_csc_by_dense_keep_NAs_logical(SEXP p_, SEXP i_, SEXP x_, SEXP d) { return csc_dense(3, true, p_, i_, x_, d); }
 SEXP _MatrixExtra_multiply_csc_by_dense_keep_NAs_float32(SEXP p_, SEXP i_, SEXP x_, SEXP d) { return csc_dense(1, true, p_, i_, x_, d); }
 
+// RsparseMatrix * sparseVector  (src/operators.cpp:3426-3697; 6 and 7 arguments): ii_base1 sorted, an empty xx is an
+// nsparseVector.  Both return list(indptr, indices, values).
+static SEXP csr_by_svec(int keep, SEXP p_, SEXP j_, SEXP x_, SEXP ii, SEXP xx, int ncols, SEXP length)
+{
+    Protect p;
+    p_ = as_type(p_, INTSXP, p); j_ = as_type(j_, INTSXP, p); x_ = as_type(x_, REALSXP, p);
+    ii = as_type(ii, INTSXP, p); xx = as_type(xx, REALSXP, p);
+    if (XLENGTH(x_) != XLENGTH(j_)) Rf_error("multiply_csr_by_svec: indices and values have different length");
+    if (XLENGTH(xx) && XLENGTH(xx) != XLENGTH(ii)) Rf_error("multiply_csr_by_svec: vector indices and values differ");
+    mx_result *res = nullptr;
+    mx_result_info info;
+    if (mx_multiply_csr_by_svec_begin(INTEGER(p_), (int)XLENGTH(p_) - 1, INTEGER(j_), REAL(x_), INTEGER(ii),
+                                      XLENGTH(xx) ? REAL(xx) : nullptr, (int64_t)XLENGTH(ii), ncols,
+                                      Rf_asInteger(length), keep, &res, &info))
+        fail();
+    return finish_guarded(res, info, R_NilValue, R_NilValue);
+}
+SEXP _MatrixExtra_multiply_csr_by_svec_no_NAs(SEXP p_, SEXP j_, SEXP x_, SEXP ii, SEXP xx, SEXP length)
+{
+    return csr_by_svec(0, p_, j_, x_, ii, xx, 0, length);
+}
+SEXP _MatrixExtra_multiply_csr_by_svec_keep_NAs(SEXP p_, SEXP j_, SEXP x_, SEXP ii, SEXP xx, SEXP ncols, SEXP length)
+{
+    return csr_by_svec(1, p_, j_, x_, ii, xx, Rf_asInteger(ncols), length);
+}
+
+// sort_vector_indices_*  (src/misc.cpp:489-527): the caller's vectors are sorted where they are, so no coercion
+static SEXP sort_svec(SEXP ii, SEXP xx, int xtype, int dtype)
+{
+    if (TYPEOF(ii) != INTSXP) Rf_error("sort_vector_indices: indices must be an integer vector");
+    void *xv = nullptr;
+    if (dtype != MX_NONE) {
+        if (TYPEOF(xx) != xtype || XLENGTH(xx) != XLENGTH(ii)) Rf_error("sort_vector_indices: values do not match");
+        xv = xtype == REALSXP ? (void *)REAL(xx) : xtype == LGLSXP ? (void *)LOGICAL(xx) : (void *)INTEGER(xx);
+    }
+    if (mx_sort_vector_indices(INTEGER(ii), xv, (int64_t)XLENGTH(ii), dtype)) fail();
+    return R_NilValue;
+}
+SEXP _MatrixExtra_sort_vector_indices_numeric(SEXP ii, SEXP xx) { return sort_svec(ii, xx, REALSXP, MX_F64); }
+SEXP _MatrixExtra_sort_vector_indices_integer(SEXP ii, SEXP xx) { return sort_svec(ii, xx, INTSXP, MX_I32); }
+SEXP _MatrixExtra_sort_vector_indices_logical(SEXP ii, SEXP xx) { return sort_svec(ii, xx, LGLSXP, MX_LGL); }
+SEXP _MatrixExtra_sort_vector_indices_binary(SEXP ii) { return sort_svec(ii, R_NilValue, NILSXP, MX_NONE); }
+
 #define MX_ENTRY(name, n) {"_MatrixExtra_" #name, (DL_FUNC)&_MatrixExtra_##name, n}
 static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(matmul_dense_csc_numeric, 5), MX_ENTRY(matmul_dense_csc_float32, 5),
@@ -807,6 +850,9 @@ static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(logicaland_csc_by_dense_ignore_NAs, 4),
     MX_ENTRY(multiply_csc_by_dense_keep_NAs_numeric, 4), MX_ENTRY(multiply_csc_by_dense_keep_NAs_integer, 4),
     MX_ENTRY(multiply_csc_by_dense_keep_NAs_logical, 4), MX_ENTRY(multiply_csc_by_dense_keep_NAs_float32, 4),
+    MX_ENTRY(multiply_csr_by_svec_no_NAs, 6), MX_ENTRY(multiply_csr_by_svec_keep_NAs, 7),
+    MX_ENTRY(sort_vector_indices_numeric, 2), MX_ENTRY(sort_vector_indices_integer, 2),
+    MX_ENTRY(sort_vector_indices_logical, 2), MX_ENTRY(sort_vector_indices_binary, 1),
     {"mxgpu_csr_transpose", (DL_FUNC)&mxgpu_csr_transpose, 4},
     {"mxgpu_coo_to_csr", (DL_FUNC)&mxgpu_coo_to_csr, 5},
     {NULL, NULL, 0}

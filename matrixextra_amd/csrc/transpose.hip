@@ -31,7 +31,8 @@
 // Each run is merged by one thread, sequentially, because an f64 sum in source order is sequential.
 //
 // COO -> CSR (mxd_coo_to_csr, at the end of this file) runs the same passes twice: pass 0 can take the source
-// rows from the caller instead of an indptr search (TP_SRC_ROWS).
+// rows from the caller instead of an indptr search (TP_SRC_ROWS).  The sort of a sparse vector
+// (mxd_sort_vector_indices, after it) runs them once, on one key.
 #include "mx_common.h"
 
 namespace mx {
@@ -46,6 +47,10 @@ static_assert(TP_BLOCK == TP_RADIX, "the per-digit prefix step uses one thread p
 
 // flags in the workspace: [0] a column index outside [0, n), [1] duplicates present
 constexpr size_t TP_FLAG_BYTES = 256;
+// the sparse-vector sort keeps its words in the same block, clear of the transpose's [0..1] and of COO stage 1's [4..7]
+constexpr int TP_SV_PASS_FLAGS = 8;      // [8..11] the radix passes' flags (bad key, duplicates, bad row)
+constexpr int TP_SV_WORDS = 16;          // [16..18] the sortedness reduction: descents, largest index, negative index
+static_assert((TP_SV_WORDS + 3) * sizeof(int32_t) <= TP_FLAG_BYTES, "the sort's words lie inside the flag block");
 
 // last row r in [lo, m) with indptr[r] <= k (indptr[lo] <= k holds for every caller)
 __device__ __forceinline__ int tp_row_of(const int32_t *__restrict__ indptr, int lo, int m, int64_t k)
@@ -557,7 +562,96 @@ void csr_rows_of_entries_kernel(const int32_t *__restrict__ indptr, int m, int64
     if (k < nnz) rows[k] = tp_row_of(indptr, 0, m, k);
 }
 
+// ---- sparse vector: one segment sorted by its index, values carried ----------------------------------------
+// sort_vector_indices_* (src/misc.cpp:460-527) sorts a permutation with std::sort and applies it.  Here one
+// reduction finds out whether anything is out of order and how many key bits there are (words[0] descents,
+// words[1] largest index, words[2] a negative index); only an unsorted vector goes through the radix passes
+// above (one key, the entry index carried for the values; the pass-0 "row" payload is the key itself).
+__global__ __launch_bounds__(256)
+void sv_sorted_kernel(const int32_t *__restrict__ ii, int64_t n, int32_t *__restrict__ words)
+{
+    bool desc = false, neg = false;
+    int mx_key = 0;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        const int key = ii[k];
+        desc |= k > 0 && key < ii[k - 1];
+        neg |= key < 0;
+        mx_key = key > mx_key ? key : mx_key;
+    }
+#pragma unroll
+    for (int off = MX_WAVE / 2; off > 0; off >>= 1) {
+        const int o = __shfl_down(mx_key, off, MX_WAVE);
+        mx_key = o > mx_key ? o : mx_key;
+    }
+    const bool any_desc = __ballot(desc) != 0ULL, any_neg = __ballot(neg) != 0ULL;
+    if (lane_id() == 0) {
+        if (any_desc) words[0] = 1;
+        if (any_neg) words[2] = 1;
+        atomicMax(&words[1], mx_key);
+    }
+}
+
+static size_t sv_sort_ws_bytes(int64_t n)
+{
+    return TpLayout(nullptr, n).bytes + (((size_t)8 * (size_t)(n > 0 ? n : 1) + 15) & ~(size_t)15);
+}
+
+static int sort_vector(int32_t *ii, void *xx, int64_t n, int value_dtype, void *workspace, int *was_sorted_host,
+                       hipStream_t st)
+{
+    MX_REQUIRE(n >= 0 && n <= INT_MAX, "mxd_sort_vector_indices: bad size");
+    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_I32 || value_dtype == MX_LGL || value_dtype == MX_NONE,
+               "mxd_sort_vector_indices: unsupported value dtype %d", value_dtype);
+    MX_REQUIRE(was_sorted_host, "mxd_sort_vector_indices: null pointer");
+    *was_sorted_host = 1;
+    if (n < 2) return 0;
+    const bool has_values = value_dtype != MX_NONE;
+    MX_REQUIRE(ii && workspace && (!has_values || xx), "mxd_sort_vector_indices: null pointer");
+    TpLayout L(workspace, n);
+    void *tmp_values = (char *)workspace + L.bytes;
+    // the passes' own flags (F[0] bad key, F[2] bad row) cannot fire once the reduction below has passed (no
+    // negative index, keys < nkeys), and the gather's duplicate flag F[1] means nothing here: none is read back
+    int32_t *F = L.flags + TP_SV_PASS_FLAGS, *words = L.flags + TP_SV_WORDS;
+    MX_HIP(hipMemsetAsync(L.flags, 0, TP_FLAG_BYTES, st));
+    hipLaunchKernelGGL(sv_sorted_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, st, ii, n, words);
+    MX_LAUNCH_CHECK();
+    int32_t w[3] = {0, 0, 0};
+    MX_HIP(hipMemcpyAsync(w, words, sizeof(w), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipStreamSynchronize(st));
+    if (!w[0]) return 0;                                    // already sorted: nothing is touched
+    *was_sorted_host = 0;
+    MX_REQUIRE(!w[2] && w[1] < INT_MAX, "mxd_sort_vector_indices: index outside [0, %d)", INT_MAX);
+    const int nkeys = w[1] + 1;
+
+    int fin = 0;
+    if (tp_sort_passes(TP_SRC_ROWS, ii, ii, nullptr, nkeys, nkeys, n, L, F, &fin, st)) return 1;
+    const int32_t *skeys = L.keys[fin], *sperm = L.perm[fin], *srows = L.rows[fin];
+    const unsigned gq = (unsigned)ceil_div(n, 256);
+    if (value_dtype == MX_F64)
+        hipLaunchKernelGGL((tp_gather_kernel<double, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, n, srows,
+                           (const double *)xx, ii, (double *)tmp_values, F);
+    else if (has_values)
+        hipLaunchKernelGGL((tp_gather_kernel<int32_t, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, n, srows,
+                           (const int32_t *)xx, ii, (int32_t *)tmp_values, F);
+    else
+        hipLaunchKernelGGL((tp_gather_kernel<int32_t, false>), dim3(gq), dim3(256), 0, st, skeys, sperm, n, srows,
+                           nullptr, ii, nullptr, F);
+    MX_LAUNCH_CHECK();
+    if (has_values)
+        MX_HIP(hipMemcpyAsync(xx, tmp_values, (value_dtype == MX_F64 ? 8 : 4) * (size_t)n, hipMemcpyDeviceToDevice,
+                              st));
+    return 0;
+}
+
 }  // namespace mx
+
+extern "C" size_t mxd_sort_vector_indices_workspace_bytes(int64_t n) { return mx::sv_sort_ws_bytes(n > 0 ? n : 0); }
+
+extern "C" int mxd_sort_vector_indices(int32_t *ii, void *xx, int64_t n, int value_dtype, void *workspace,
+                                       int *was_sorted_host, void *stream)
+{
+    return mx::sort_vector(ii, xx, n, value_dtype, workspace, was_sorted_host, mx::as_stream(stream));
+}
 
 extern "C" size_t mxd_coo_to_csr_workspace_bytes(int64_t nnz, int n)
 {

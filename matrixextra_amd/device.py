@@ -403,6 +403,42 @@ def csc_by_dense(A: DeviceCSR, D: torch.Tensor, keep_na: bool = True, logical: b
     return out_p, out_i[:k], out_x[:k]
 
 
+def csr_by_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, length: int, keep_na: bool = True):
+    """X * v for a device-resident CSR X (f64 values, sorted rows) and a sparse vector recycled down its rows
+    (DESIGN.md §4.11), as (p, j, x) tensors.  vi: sorted 1-based int32 positions; vx: their f64 values, or None for
+    an nsparseVector; length must divide A.m.  Rows whose position v does not store drop out, the others are scaled.
+    keep_na=True also keeps the NaN / Inf entries of dropped rows (as NaN) and fills every column of a row whose
+    vector value is NaN / Inf."""
+    lib = _lib.load()
+    dev = A.indptr.device
+    if A.values is None or A.values.dtype != torch.float64:
+        raise ValueError("csr_by_svec: X needs float64 values")
+    if vi.dtype != torch.int32 or vi.dim() != 1 or vi.device != dev:
+        raise ValueError(f"csr_by_svec: vi must be a 1-d int32 tensor on {dev}")
+    if vx is not None and (vx.dtype != torch.float64 or vx.shape != vi.shape or vx.device != dev):
+        raise ValueError("csr_by_svec: vx must be float64, of vi's shape and on its device")
+    length, nv = int(length), int(vi.numel())
+    if A.m and (length <= 0 or length > A.m or A.m % length or nv > length):
+        raise ValueError("csr_by_svec: the vector's length must divide the number of rows")
+    vi = vi.contiguous()
+    vx = None if vx is None else vx.contiguous()
+    ws = torch.empty(max(lib.mxd_csr_by_svec_workspace_bytes(A.m), 16), dtype=torch.uint8, device=dev)
+    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
+    total, x_na = C.c_int64(0), C.c_int64(0)
+    check(lib.mxd_csr_by_svec_count(C.c_int(A.m), C.c_int(A.K), C.c_int64(A.nnz), _dp(A.indptr), _dp(A.values),
+                                    _dp(vi), C.c_int64(nv), _dp(vx), C.c_int(length), C.c_int(int(bool(keep_na))),
+                                    _dp(ws), _dp(out_p), C.byref(total), C.byref(x_na), _stream()))
+    k = int(total.value)
+    out_j = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
+    if k:
+        check(lib.mxd_csr_by_svec_fill(C.c_int(A.m), C.c_int(A.K), C.c_int64(A.nnz), _dp(A.indptr), _dp(A.indices),
+                                       _dp(A.values), _dp(vi), C.c_int64(nv), _dp(vx), C.c_int(length),
+                                       C.c_int(int(bool(keep_na))), _dp(ws), _dp(out_p), _dp(out_j), _dp(out_x),
+                                       _stream()))
+    return out_p, out_j[:k], out_x[:k]
+
+
 def csr_filter(A: DeviceCSR, mask: torch.Tensor) -> DeviceCSR:
     """filterSparse of a device-resident CSR: keeps entry k where mask[k] (bool, or int32 R logical) is TRUE or NA;
     an NA writes NA_real_ / NA_LOGICAL as the value."""

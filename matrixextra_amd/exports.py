@@ -595,6 +595,64 @@ def sort_sparse_indices_inplace(indptr, indices, values=None):
     check(_lib.load().mx_sort_sparse_indices(ptr(p), ptr(indices), ptr(values), C.c_int(vd), C.c_int(p.size - 1)))
 
 
+def _sort_vector(ii, xx, vd, vdt):
+    if not (isinstance(ii, np.ndarray) and ii.dtype == np.int32 and ii.flags.c_contiguous):
+        raise TypeError("ii must be a contiguous int32 numpy array (sorted in place)")
+    if vdt is not None:
+        if not (isinstance(xx, np.ndarray) and xx.dtype == vdt and xx.flags.c_contiguous):
+            raise TypeError(f"xx must be a contiguous {np.dtype(vdt).name} numpy array (sorted in place)")
+        if xx.size != ii.size:
+            raise ValueError("ii and xx have different lengths")
+    check(_lib.load().mx_sort_vector_indices(ptr(ii), None if vdt is None else ptr(xx), C.c_int64(ii.size),
+                                             C.c_int(vd)))
+
+
+def sort_vector_indices_numeric(ii, xx):
+    """src/misc.cpp:489-497: sorts a sparse vector's `ii` and f64 `xx` IN PLACE by ii; left alone when sorted."""
+    _sort_vector(ii, xx, MX_F64, np.float64)
+
+
+def sort_vector_indices_integer(ii, xx):
+    """src/misc.cpp:499-507."""
+    _sort_vector(ii, xx, _lib.MX_I32, np.int32)
+
+
+def sort_vector_indices_logical(ii, xx):
+    """src/misc.cpp:509-517."""
+    _sort_vector(ii, xx, MX_LGL, np.int32)
+
+
+def sort_vector_indices_binary(ii):
+    """src/misc.cpp:519-527."""
+    _sort_vector(ii, None, MX_NONE, None)
+
+
+def _csr_by_svec(indptr, indices, values, ii_base1, xx, ncols, length, keep_NAs):
+    p, j, x, vi = _i32(indptr), _i32(indices), _f64(values), _i32(ii_base1)
+    vx = None if xx is None or (np.asarray(xx).size == 0 and vi.size != 0) else _f64(xx)
+    if x.size != j.size:
+        raise ValueError("indices and values have different lengths")
+    if vx is not None and vx.size != vi.size:
+        raise ValueError("ii and xx have different lengths")
+    res, info = C.c_void_p(), ResultInfo()
+    check(_lib.load().mx_multiply_csr_by_svec_begin(ptr(p), C.c_int(p.size - 1), ptr(j), ptr(x), ptr(vi), ptr(vx),
+                                                    C.c_int64(vi.size), C.c_int(int(ncols)), C.c_int(int(length)),
+                                                    C.c_int(int(bool(keep_NAs))), C.byref(res), C.byref(info)))
+    return _finish(res, info)
+
+
+def multiply_csr_by_svec_no_NAs(indptr, indices, values, ii_base1, xx, length):
+    """src/operators.cpp:3426-3498: the rows that the sorted sparse vector stores (recycled every `length` rows),
+    scaled by its values; an empty `xx` with a non-empty `ii_base1` is an nsparseVector (values copied)."""
+    return _csr_by_svec(indptr, indices, values, ii_base1, xx, 0, length, False)
+
+
+def multiply_csr_by_svec_keep_NAs(indptr, indices, values, ii_base1, xx, ncols, length):
+    """src/operators.cpp:3500-3697: as above, keeping what R's arithmetic makes NA: the NaN / Inf entries of the rows
+    the vector does not store, and every column of a row whose vector value is NaN / Inf."""
+    return _csr_by_svec(indptr, indices, values, ii_base1, xx, ncols, length, True)
+
+
 def multiply_csr_by_dvec_no_NAs_numeric(indptr, indices, values, dvec, ncols, multiply, powerto, divide, divrest,
                                         intdiv, X_is_LHS):
     """src/operators.cpp:2142-2175 (R/RcppExports.R:480-482): values-only `X op v` / `v op X` with R's recycling."""

@@ -9,8 +9,9 @@ from __future__ import annotations
 import numpy as np
 
 from . import exports
-from .matrices import (DenseMatrix, RsparseMatrix, as_csr_matrix, check_valid_matrix, dgCMatrix,
-                       dimnames_of, float32, options, stop)
+from .matrices import (DenseMatrix, RsparseMatrix, as_csr_matrix, check_valid_matrix, dgCMatrix, dgRMatrix,
+                       dimnames_of, dsparseVector, float32, isparseVector, lsparseVector, nsparseVector, options,
+                       sort_sparse_indices, sparseVector, stop)
 
 
 def _nthreads():
@@ -146,8 +147,10 @@ def tcrossprod_f32_csr(x, y):
 
 # ---- CSR x dense vector ------------------------------------------------------------------------------
 def gemv_csr_vec(x, y):
-    """RsparseMatrix %*% numeric/integer/logical/float32 vector — R/matmul.R:545-657 (dense branch).
+    """RsparseMatrix %*% numeric/integer/logical/float32 vector or sparseVector — R/matmul.R:545-657.
     Returns an (nrow, 1) matrix like `matrix(res, ncol=1)`; float32 input -> float32 result."""
+    if isinstance(y, sparseVector):
+        return _gemv_csr_svec(x, y)
     is_f32 = isinstance(y, float32)
     yv = y.Data.reshape(-1) if is_f32 else np.asarray(y)
     if yv.ndim != 1:
@@ -177,6 +180,36 @@ def gemv_csr_vec(x, y):
     return DenseMatrix(res.reshape(-1, 1), [rn, None])
 
 
+_SVEC_OUTER = ("A one-column RsparseMatrix times a sparseVector is the reference's outer product "
+               "(outerprod_csrsinglecol_by_dvec, R/matmul.R:659-752), which is not on the accelerated path.")
+
+
+def _gemv_csr_svec(x, y):
+    """The sparse branch of gemv_csr_vec, R/matmul.R:595-646: x and y sorted (copies, unless MatrixExtra.inplace_sort
+    lets a dgRMatrix / the vector be sorted where they are), then matmul_csr_svec_* by the vector's class."""
+    if x.Dim[1] != len(y):
+        stop("Matrix-vector dimensions do not match.")
+    nthreads = options.get("MatrixExtra.nthreads", 1)
+    check_valid_matrix(x)
+    inplace_sort = bool(options.get("MatrixExtra.inplace_sort", False))
+    if inplace_sort and not isinstance(x, dgRMatrix):                 # deepcopy_before_sort, R/utils.R:164-191
+        x = x.copy()
+    x = as_csr_matrix(x)
+    x = sort_sparse_indices(x, copy=not inplace_sort)
+    y = sort_sparse_indices(y, copy=not inplace_sort)
+    if isinstance(y, dsparseVector):
+        res = exports.matmul_csr_svec_numeric(x.p, x.j, x.x, y.i, y.x, nthreads)
+    elif isinstance(y, isparseVector):
+        res = exports.matmul_csr_svec_integer(x.p, x.j, x.x, y.i, y.x, nthreads)
+    elif isinstance(y, lsparseVector):
+        res = exports.matmul_csr_svec_logical(x.p, x.j, x.x, y.i, y.x, nthreads)
+    elif isinstance(y, nsparseVector):
+        res = exports.matmul_csr_svec_binary(x.p, x.j, x.x, y.i, nthreads)
+    else:
+        return gemv_csr_vec(x, y.toarray())                           # as.numeric(y), :641-644
+    return DenseMatrix(res.reshape(-1, 1), [dimnames_of(x)[0], None])
+
+
 class RLogical(np.ndarray):
     """An int32 vector tagged as an R logical ({0,1,NA_LOGICAL}) so `%*%` picks the logical kernel."""
     r_logical = True
@@ -191,6 +224,10 @@ def matmul(x, y):
     if isinstance(x, RsparseMatrix):
         if isinstance(y, float32):
             return gemv_csr_vec(x, y) if y.is_vector else gemm_csr_f32(x, y)
+        if isinstance(y, sparseVector):               # R/matmul.R:755-767: one column -> the outer product
+            if x.Dim[1] == 1:
+                stop(_SVEC_OUTER)
+            return gemv_csr_vec(x, y)
         y_arr = np.asarray(y)
         if y_arr.ndim == 1:
             return gemv_csr_vec(x, y)

@@ -6,6 +6,7 @@ R is not available in this image, so the S4 objects the reference dispatches on
     dgRMatrix / lgRMatrix / ngRMatrix   @p int32[nrow+1], @j int32[nnz] (0-based), @x, @Dim, @Dimnames
     dgCMatrix                           @p int32[ncol+1], @i int32[nnz], @x
     dgTMatrix / lgTMatrix / ngTMatrix   @i, @j int32[nnz] (0-based triplets, any order, duplicates allowed), @x
+    d/i/l/nsparseVector                 @i int32[nnz] (1-based, as in Matrix), @x, @length
     float32                             @Data  (numpy float32, column-major)
 
 R logicals are int32 {0, 1, NA_LOGICAL}.  The classes hold data only; all
@@ -120,12 +121,16 @@ class RsparseMatrix:
         from . import operators
         if isinstance(other, TsparseMatrix):          # R/operators.R:81-135, :169-180
             return operators.multiply_csr_by_coo(self, other, logical=False)
+        if isinstance(other, sparseVector):           # :1634
+            return operators.multiply_csr_by_svec_elemwise(self, other)
         if not isinstance(other, (RsparseMatrix, dgCMatrix)):
             return operators.csr_op_vector(self, other, "*")
         return operators.multiply_csr_by_csr(self, other, logical=False)
 
     def __rmul__(self, other):                        # v * X  (multiplication commutes: R/operators.R:1155-1161)
         from . import operators
+        if isinstance(other, sparseVector):           # :1638
+            return operators.multiply_csr_by_svec_elemwise(other, self)
         return operators.csr_op_vector(self, other, "*")
 
     def __and__(self, other):                         # R/operators.R:183 (CSR), :1163-1169 (vector)
@@ -453,6 +458,73 @@ class dgCMatrix:
         return NotImplemented
 
 
+class sparseVector:
+    """Matrix's sparseVector: @i 1-based positions (int32, any order until sorted), @x the values of the stored
+    positions (none for an nsparseVector) and @length.  Subclasses fix the value type.  `X * v`, `v * X` and
+    `X %*% v` with an RsparseMatrix are wired on the matrix side (R/operators.R:1634-1638, R/matmul.R:755-767)."""
+    value_dtype = None
+    r_class = "sparseVector"
+    __array_ufunc__ = None
+
+    def __init__(self, i, x=None, length=None):
+        self.i = np.ascontiguousarray(i, dtype=np.int32).reshape(-1)
+        if self.value_dtype is None:
+            self.x = None
+        else:
+            self.x = np.ascontiguousarray(x if x is not None else np.zeros(0), dtype=self.value_dtype).reshape(-1)
+        if length is None:
+            length = int(self.i.max()) if self.i.size else 0
+        self.length = int(length)
+
+    def __len__(self):
+        return self.length
+
+    def has_x(self):
+        return self.x is not None
+
+    def copy(self):
+        return type(self)(self.i.copy(), None if self.x is None else self.x.copy(), self.length)
+
+    def toarray(self):
+        """as.numeric(): dense float64 (NA_integer_ / NA -> nan; an nsparseVector gives 1)."""
+        out = np.zeros(self.length, dtype=np.float64)
+        if self.x is None:
+            vals = 1.0
+        elif self.value_dtype == np.int32:
+            vals = np.where(self.x == NA_INTEGER, np.nan, self.x.astype(np.float64))
+        else:
+            vals = self.x
+        out[self.i.astype(np.int64) - 1] = vals
+        return out
+
+    def __rmatmul__(self, other):                     # X %*% v when X defers
+        from . import matmul
+        return matmul.matmul(other, self)
+
+    def __repr__(self):
+        return f"<{self.r_class} of length {self.length}, {self.i.size} entries>"
+
+
+class dsparseVector(sparseVector):
+    value_dtype = np.float64
+    r_class = "dsparseVector"
+
+
+class isparseVector(sparseVector):
+    value_dtype = np.int32
+    r_class = "isparseVector"
+
+
+class lsparseVector(sparseVector):
+    value_dtype = np.int32
+    r_class = "lsparseVector"
+
+
+class nsparseVector(sparseVector):
+    value_dtype = None
+    r_class = "nsparseVector"
+
+
 class float32:
     """The `float` package's float32: @Data holds binary32 values, column-major (R/matmul.R:260,276)."""
     r_class = "float32"
@@ -683,8 +755,105 @@ def _t_masked(x):
     return t_shallow(x) if options.get("MatrixExtra.fast_transpose", False) else t_deep(x)
 
 
+def _svec_values_as(v, target):
+    """@x of sparse vector `v` in the kind `target` ("d", "i", "l"), by R's as.double / as.integer / as.logical."""
+    n = v.i.size
+    if v.x is None:
+        return np.ones(n, dtype=np.float64 if target == "d" else np.int32)
+    if isinstance(v, dsparseVector):
+        if target == "d":
+            return v.x
+        nan = np.isnan(v.x)
+        if target == "l":
+            return np.where(nan, NA_LOGICAL, (v.x != 0).astype(np.int32)).astype(np.int32)
+        with np.errstate(invalid="ignore"):
+            return np.where(nan | np.isinf(v.x), NA_INTEGER, np.trunc(np.where(nan, 0.0, v.x))).astype(np.int32)
+    na = v.x == NA_INTEGER
+    if target == "d":
+        return np.where(na, NA_REAL, v.x.astype(np.float64))
+    if target == "l" and isinstance(v, isparseVector):
+        return np.where(na, NA_LOGICAL, (v.x != 0).astype(np.int32)).astype(np.int32)
+    return v.x
+
+
+def _cells_colmajor(i, j, nrow, ncol):
+    """1-based column-major cell numbers of the entries (i, j) of an nrow x ncol matrix, and the order that sorts
+    them, as as(x, "sparseVector") numbers the cells of a sparse matrix."""
+    if nrow * ncol > 2147483647:
+        stop("Matrix has too many cells for the int32 positions of a sparse vector.")
+    cell = i.astype(np.int64) + j.astype(np.int64) * nrow + 1
+    order = np.argsort(cell, kind="stable")
+    return cell[order].astype(np.int32), order
+
+
+def as_sparse_vector(x, binary=False, logical=False, integer=False):
+    """as.sparse.vector (R/conversions.R:593-619): a dsparseVector by default, else the kind asked for.  Dense input
+    (a vector, or a matrix / float32 read column-major) stores its non-zero cells, NA included; a sparse vector
+    changes kind (NA_integer_ / NA become NA_real_ on the way to a dsparseVector); a CSR, COO or CSC object gives its
+    stored cells in column-major order, with the kind of its values."""
+    if (binary and logical) or (logical and integer) or (binary and integer):
+        stop("Can pass at most one of 'binary', 'logical', 'integer'.")
+    if isinstance(x, float32):
+        x = x.Data.astype(np.float64)                                 # float::dbl(x)
+    if isinstance(x, TsparseMatrix):
+        check_valid_matrix(x)
+        x = _coo_to_compressed(x)                                     # repeated triplets merge first, as Matrix does
+    if isinstance(x, (RsparseMatrix, dgCMatrix)):
+        check_valid_matrix(x)
+        if isinstance(x, dgCMatrix):
+            rows, cols = x.i, np.repeat(np.arange(x.Dim[1], dtype=np.int64), np.diff(x.p))
+        else:
+            rows, cols = np.repeat(np.arange(x.Dim[0], dtype=np.int64), np.diff(x.p)), x.j
+        cell, order = _cells_colmajor(rows, cols, x.Dim[0], x.Dim[1])
+        n = x.Dim[0] * x.Dim[1]
+        xv = getattr(x, "x", None)
+        if xv is None:
+            v = nsparseVector(cell, None, n)
+        elif xv.dtype == np.int32:
+            v = lsparseVector(cell, xv[order], n)
+        else:
+            v = dsparseVector(cell, xv[order], n)
+    elif isinstance(x, sparseVector):
+        v = x
+    else:
+        a = np.asarray(x)
+        is_lgl = bool(getattr(x, "r_logical", False)) or a.dtype == np.bool_
+        if a.ndim > 2:
+            stop("Cannot convert an array of more than two dimensions to a sparse vector.")
+        a = a.reshape(-1, order="F")
+        if a.dtype == np.bool_:
+            a = a.astype(np.int32)
+        elif a.dtype != np.int32:
+            a = a.astype(np.float64)
+        keep = np.flatnonzero(a != 0)                                 # NaN != 0 and NA_integer_ != 0: NA cells stay
+        cls = lsparseVector if is_lgl else isparseVector if a.dtype == np.int32 else dsparseVector
+        v = cls(keep + 1, a[keep], a.size)
+    if binary:
+        return v if isinstance(v, nsparseVector) else nsparseVector(v.i, None, v.length)
+    cls, target = ((isparseVector, "i") if integer else (lsparseVector, "l") if logical else (dsparseVector, "d"))
+    if type(v) is cls:
+        return v
+    return cls(v.i, _svec_values_as(v, target), v.length)
+
+
+def _check_valid_svec(X):
+    """R/utils.R:456-468."""
+    from . import exports
+    if X.length is None:
+        stop("Vector has invalid length.")
+    if X.length < 0:
+        stop("Vector has negative length.")
+    if not isinstance(X, nsparseVector) and X.i.size != X.x.size:
+        stop("Vector indices and values have different length.")
+    res = exports.check_valid_svec(X.i, X.length)
+    if res:
+        stop(res["err"])
+
+
 def check_valid_matrix(X):
-    """R/utils.R:349-410, TsparseMatrix / RsparseMatrix / CsparseMatrix branches."""
+    """R/utils.R:349-410, TsparseMatrix / RsparseMatrix / CsparseMatrix branches, and :456-468 for a sparseVector."""
+    if isinstance(X, sparseVector):
+        return _check_valid_svec(X)
     nrows, ncols = X.Dim
     if nrows < 0:
         stop("Matrix has invalid number of rows.")
@@ -719,8 +888,21 @@ def check_valid_matrix(X):
 
 def sort_sparse_indices(X, copy=False):
     """sort_sparse_indices (R/utils.R:22-161) for RsparseMatrix: per-row index sort on the
-    device (src/misc.cpp:261-298).  copy=TRUE sorts deep copies of @j/@x and returns a new object."""
+    device (src/misc.cpp:261-298).  copy=TRUE sorts deep copies of @j/@x and returns a new object.
+    A sparseVector (:126-155) is sorted by @i, @x carried, by the device radix sort (src/misc.cpp:460-527)."""
     from . import exports
+    if isinstance(X, sparseVector):
+        if copy:
+            X = X.copy()
+        kind = {dsparseVector: "numeric", isparseVector: "integer", lsparseVector: "logical",
+                nsparseVector: "binary"}.get(type(X))
+        if kind is None:
+            stop("Method is only applicable to sparse matrices in CSR, CSC, and COO formats, and to sparse vectors.")
+        if kind == "binary":
+            exports.sort_vector_indices_binary(X.i)
+        else:
+            getattr(exports, "sort_vector_indices_" + kind)(X.i, X.x)
+        return X
     check_valid_matrix(X)
     if copy:
         X = type(X)(X.p, X.j.copy(), None if X.x is None else X.x.copy(), X.Dim, list(X.Dimnames))

@@ -1,7 +1,8 @@
 """Host-side mirror of the CSR (+) CSR part of R/operators.R
 (multiply_csr_by_csr :43-79, add_csr_matrices_internal :713-776 and their registrations), of CSR (.) COO
 (multiply_csr_by_coo :81-110), of `CSC * matrix` (multiply_csc_by_dense_internal :568-670) and of `CSR op vector` /
-`COO op vector` (multiply_csr_by_dvec_elemwise_internal :950-1153)."""
+`COO op vector` (multiply_csr_by_dvec_elemwise_internal :950-1153) and of `CSR * sparseVector`
+(multiply_csr_by_svec_elemwise_internal :1564-1622)."""
 from __future__ import annotations
 
 import warnings
@@ -9,9 +10,10 @@ import warnings
 import numpy as np
 
 from . import exports
-from .matrices import (RsparseMatrix, TsparseMatrix, as_coo_matrix, as_csc_matrix, as_csr_matrix, check_valid_matrix,
-                       dgCMatrix, dgRMatrix, dgTMatrix, float32, lgRMatrix, lgTMatrix, ngRMatrix, options,
-                       sort_sparse_indices, stop)
+from .matrices import (RsparseMatrix, TsparseMatrix, as_coo_matrix, as_csc_matrix, as_csr_matrix, as_sparse_vector,
+                       check_valid_matrix, dgCMatrix, dgRMatrix, dgTMatrix, dsparseVector, float32, lgRMatrix, lgTMatrix,
+                       ngRMatrix, nsparseVector, options, sort_sparse_indices, sparseVector,
+                       stop)
 
 
 def _is_same_ngRMatrix(e1, e2):
@@ -287,3 +289,57 @@ def csr_op_vector(e1, e2, op, X_is_LHS=True):
     if op == "&":
         return multiply_csr_by_dvec_elemwise_internal(e1, e2, logical=True)
     return multiply_csr_by_dvec_elemwise_internal(e1, e2, logical=False, X_is_LHS=X_is_LHS, op=op)
+
+
+_SVEC_CSC = ("A sparseVector longer than nrow(X), or whose length does not divide nrow(X), goes through as.csc.matrix "
+             "and Matrix's own method (R/operators.R:1587-1588), which is not on the accelerated path.")
+
+
+def _deepcopy_unless_numeric(e):
+    """deepcopy_before_sort (R/utils.R:164-191) as the sparse-vector routes use it: an object that is not of the
+    numeric kind is about to be converted into one that shares its index array, so it is copied first; a dgRMatrix
+    or dsparseVector stays itself and is then sorted in place."""
+    return e if isinstance(e, (dgRMatrix, dsparseVector)) else e.copy()
+
+
+def multiply_csr_by_svec_elemwise_internal(X, v):
+    """R/operators.R:1564-1622: `X * v` for an RsparseMatrix and a sparseVector recycled down the rows.  Rows at
+    positions that `v` does not store drop out, the stored ones are scaled; unless MatrixExtra.ignore_na is set, the
+    NaN / Inf entries of dropped rows stay (as NaN) and a NaN / Inf value of `v` fills its rows.  The result is a
+    dgRMatrix with X's Dim and Dimnames."""
+    if not len(v):                                                            # :1565-1566
+        return np.zeros(0, dtype=np.float64)
+    inplace_sort = bool(options.get("MatrixExtra.inplace_sort", False))
+    if len(v) == 1 or len(v) == v.i.size:                                     # :1570-1582
+        if len(v) == 1:
+            dv = v.toarray()
+        elif v.x is not None:
+            if inplace_sort:
+                v = _deepcopy_unless_numeric(v)
+            dv = sort_sparse_indices(v, copy=not inplace_sort).x
+        else:
+            return X
+        return csr_op_vector(X, dv, "*")
+    if (len(v) < X.Dim[0] and X.Dim[0] % len(v) != 0) or len(v) > X.Dim[0]:  # :1584-1589
+        stop(_SVEC_CSC)
+    check_valid_matrix(X)
+    if inplace_sort:                                                          # :1594-1597
+        X = _deepcopy_unless_numeric(X)
+        v = _deepcopy_unless_numeric(v)
+    X = as_csr_matrix(X)
+    X = sort_sparse_indices(X, copy=not inplace_sort)
+    v = as_sparse_vector(v, binary=isinstance(v, nsparseVector))              # :1601
+    v = sort_sparse_indices(v, copy=not inplace_sort)
+    keep_NAs = not bool(options.get("MatrixExtra.ignore_na", False))
+    if v.x is not None and keep_NAs:                                          # :1606-1614
+        res = exports.multiply_csr_by_svec_keep_NAs(X.p, X.j, X.x, v.i, v.x, X.Dim[1], len(v))
+    else:
+        res = exports.multiply_csr_by_svec_no_NAs(X.p, X.j, X.x, v.i, v.x, len(v))
+    return _assemble(dgRMatrix, X, res)
+
+
+def multiply_csr_by_svec_elemwise(e1, e2):
+    """R/operators.R:1624-1638: `RsparseMatrix * sparseVector` and `sparseVector * RsparseMatrix`."""
+    if isinstance(e2, sparseVector):
+        return multiply_csr_by_svec_elemwise_internal(e1, e2)
+    return multiply_csr_by_svec_elemwise_internal(e2, e1)
