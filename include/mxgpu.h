@@ -143,6 +143,11 @@ int mxd_spmm_kernel_times(float *out_ms, int max_out, int *count);
 /* name of the SpMM kernel the last mxd_spmm_csr_dense_ex call of this thread launched (reporting only) */
 const char *mxd_spmm_last_kernel(void);
 
+/* label and lane-group width G (4, 8, 16, 32 or 64 lanes per row) of the last row-group kernel this thread launched:
+ * SpMV, merge, gather, sort, column slices, cbind, CSR x / (.) vector.  "none" and 0 before the first one.  Either
+ * pointer may be null (reporting only). */
+int mxd_last_row_launch(const char **what, int *G);
+
 /* SpMV  y = A * v  (matmul_csr_dvec<>, src/matmul.cpp:381-419).
  * v_dtype MX_F64 / MX_I32 / MX_LGL -> y f64[m];  MX_F32 -> y f32[m]
  * (float accumulate).  NA_INTEGER / NA_LOGICAL entries contribute NA_REAL. */

@@ -91,6 +91,13 @@ def load() -> C.CDLL:
     return lib
 
 
+def last_row_launch() -> tuple[str, int]:
+    """(label, lanes per row) of the last row-group kernel this thread launched (mxd_last_row_launch)."""
+    what, G = C.c_char_p(), C.c_int(0)
+    check(load().mxd_last_row_launch(C.byref(what), C.byref(G)))
+    return (what.value or b"").decode(), G.value
+
+
 def check(rc: int) -> None:
     if rc != 0:
         raise MxError(load().mx_last_error().decode("utf-8", "replace"))

@@ -2,7 +2,7 @@
 // Rcpp export of the reference's hot path, marshalling host vectors to the
 // device, running the HIP kernels and bringing the result back.  There is no
 // CPU fallback: without a usable GPU every call fails with an error.
-#include "mx_common.h"
+#include "mx_dispatch.h"
 
 #include <cstdlib>
 #include <chrono>
@@ -21,6 +21,15 @@ int set_error(const char *fmt, ...)
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return 1;
+}
+
+static thread_local const char *g_row_what = "none";
+static thread_local int g_row_group = 0;
+
+void note_row_launch(const char *what, int G)
+{
+    g_row_what = what;
+    g_row_group = G;
 }
 
 // MXGPU_TRACE=1: wall-clock phases of an export-level call on stderr
@@ -178,6 +187,13 @@ static int begin_result(mx_result **res_out, mx_result_info *info, int values_dt
 }
 
 extern "C" {
+
+int mxd_last_row_launch(const char **what, int *G)
+{
+    if (what) *what = mx::g_row_what;
+    if (G) *G = mx::g_row_group;
+    return 0;
+}
 
 const char *mx_last_error(void) { return mx::g_err; }
 int mx_abi_version(void) { return MXGPU_ABI_VERSION; }

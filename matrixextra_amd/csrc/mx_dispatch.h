@@ -20,6 +20,9 @@ inline int dispatch_int(int_list<Vs...>, const char *what, const char *name, int
     return found ? rc : set_error("%s: unsupported %s %d", what, name, v);
 }
 
+// what the last launch_rows of this thread launched (mxd_last_row_launch; reporting only, set in api.hip)
+void note_row_launch(const char *what, int G);
+
 // One G-lane group per `rows_per_group` rows, `block` threads per block: launch(g, grid, block) holds the one
 // hipLaunchKernelGGL of a kernel templated on g().
 template <int... Gs, typename F>
@@ -29,6 +32,7 @@ inline int launch_rows(int_list<Gs...> groups, const char *what, int G, int64_t 
     return dispatch_int(groups, what, "lane group", G, [&](auto g) {
         launch(g, dim3((unsigned)ceil_div(rows, (block / g()) * rows_per_group)), dim3((unsigned)block));
         MX_LAUNCH_CHECK();
+        note_row_launch(what, g());
         return 0;
     });
 }
