@@ -1,6 +1,6 @@
 // mx_dispatch.h — host side only: turns a run-time launch choice (lane-group width, operand kind, value type)
-// into a template argument.  Every kernel outside spmm.hip that is templated on such a choice is launched through
-// these helpers; a value outside the list given at the call is an error, never a silent default.
+// into a template argument.  Every kernel that is templated on such a choice is launched through these helpers; a
+// value outside the list given at the call is an error, never a silent default.
 #pragma once
 #include <type_traits>
 #include "mx_common.h"
@@ -51,6 +51,19 @@ inline int dispatch_values(const char *what, int value_dtype, F &&f)
         case MX_LGL: case MX_I32: return f(value_kind<int32_t, true>{});
         case MX_NONE: return f(value_kind<int32_t, false>{});
         default: return set_error("%s: unsupported value dtype %d", what, value_dtype);
+    }
+}
+
+// element type of a dense operand: f(tag<double>{}) or f(tag<float>{}); the casts of its void pointers belong in f
+template <typename T> struct tag { using type = T; };
+
+template <typename F>
+inline int dispatch_dense(const char *what, int dense_dtype, F &&f)
+{
+    switch (dense_dtype) {
+        case MX_F64: return f(tag<double>{});
+        case MX_F32: return f(tag<float>{});
+        default: return set_error("%s: unsupported dense dtype %d", what, dense_dtype);
     }
 }
 

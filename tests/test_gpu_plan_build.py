@@ -1,6 +1,6 @@
 """The planned kernel's plan, byte for byte.
 
-The plan layout is restated here in numpy from its documented rules (spmm.hip, "v3 planned panel sweep" and "Plan
+The plan layout is restated here in numpy from its documented rules (spmm_plan.hip, "v3 planned panel sweep" and "Plan
 construction"):
   * rows are cut into bundles of 8 and octets of 8 bundles (64 rows); column panels are ceil(K / P) columns wide,
     the last one takes the rest;

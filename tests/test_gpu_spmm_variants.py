@@ -71,7 +71,7 @@ def layout_args(name, dtype, m, n, colmajor):
 
 
 def qualifies(dtype, n, colmajor, b_offset, ldb, c_offset, ldc):
-    """The slab / planned kernels' 16-byte rules (slab_ok in spmm.hip), restated."""
+    """The slab / planned kernels' 16-byte rules (slab_ok in spmm_common.h), restated."""
     v, isz = vec(dtype), np.dtype(dtype).itemsize
     if n < v or n % v or ldb % v or (b_offset * isz) % 16:
         return False

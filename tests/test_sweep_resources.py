@@ -24,7 +24,7 @@ def kernel_metadata(tmp_path_factory):
         pytest.skip("hipcc not found")
     asm = tmp_path_factory.mktemp("sweep") / "spmm.s"
     flags = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=on".split()          # as in csrc/Makefile
-    subprocess.run([HIPCC, *flags, "--cuda-device-only", "-S", os.path.join(CSRC, "spmm.hip"), "-o", str(asm)],
+    subprocess.run([HIPCC, *flags, "--cuda-device-only", "-S", os.path.join(CSRC, "spmm_plan.hip"), "-o", str(asm)],
                    check=True, capture_output=True, timeout=600)
     text = asm.read_text()
     meta = text[text.index("amdhsa.kernels:"):]

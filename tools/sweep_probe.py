@@ -3,7 +3,7 @@
 
     make -C matrixextra_amd/csrc PROBE=1 && python tools/sweep_probe.py [--lib PATH] [--out FILE]
 
-Loads the probe build of the library (MX_SWEEP_PROBE in spmm.hip), runs the headline product with a kept plan and
+Loads the probe build of the library (MX_SWEEP_PROBE in spmm_plan.hip), runs the headline product with a kept plan and
 prints, per wavefront and launch: the time from the end of a batch of 8 steps to the completion of consume(0) of the
 next batch, for batches without and with a panel meeting behind them, and the time from the end of a generation's
 stream loop to the first consume(0) of the next generation that waits for a B line.  The meeting's cost is the
