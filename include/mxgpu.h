@@ -314,6 +314,56 @@ int mxd_csr_by_dvec(int m, int ncols, int64_t nnz, const int32_t *indptr, const 
                     const void *values, const void *dvec, int64_t dvec_len, int op, int x_is_lhs,
                     void *values_out, void *stream);
 
+/* CSR (op) dense vector keeping R's NA cells (multiply_csr_by_dvec_with_NAs, src/operators.cpp:2258-2852; DESIGN.md
+ * §4.12).  X is m x ncols in CSR, f64 values, rows sorted by column; op is one of the five arithmetic mx_dvec_op,
+ * applied with X on the left.
+ *
+ * Row-ruled regime (:2314-2513), dvec_len <= m and m % dvec_len == 0: row r is ruled by val = dvec[r % dvec_len].  A
+ * plain row keeps its entries with x op val; a filled row has all ncols columns: under * a NaN val (NA_real_ for an
+ * NA val, else the default NaN, everywhere) or a +-Inf val (the default NaN, x * val where stored); under / %% %/% a
+ * zero val (the default NaN, x op val where stored) or a NaN val (val everywhere); under ^ a NaN val (val), a zero
+ * val (1) or a negative val (+Inf), R_pow(x, val) where stored.  The last entry of a repeated column wins.
+ * count: out_indptr[m+1] from indptr and dvec alone, *nnz_out_host = output entries (64-bit; above INT32_MAX the call
+ * fails, which the reference does not check); one synchronise.  fill: out_indices / out_values of that many entries.
+ * workspace: mxd_csr_by_dvec_na_rows_workspace_bytes(m), used by the count only. */
+size_t mxd_csr_by_dvec_na_rows_workspace_bytes(int m);
+int mxd_csr_by_dvec_na_rows_count(int m, int ncols, int64_t nnz, const int32_t *indptr, const double *dvec,
+                                  int64_t dvec_len, int op, void *workspace, int32_t *out_indptr,
+                                  int64_t *nnz_out_host, void *stream);
+int mxd_csr_by_dvec_na_rows_fill(int m, int ncols, int64_t nnz, const int32_t *indptr, const int32_t *indices,
+                                 const double *values, const double *dvec, int64_t dvec_len, int op,
+                                 const int32_t *out_indptr, int32_t *out_indices, double *out_values, void *stream);
+/* Flat regime (:2515-2841), any other dvec_len <= m * ncols (and <= INT32_MAX here): the stored entries get
+ * mxd_csr_by_dvec's values; a position ix of the vector is special when dvec[ix] is NaN, 0 under / %% %/% ^, negative
+ * under ^ or +-Inf under *, and every flat cell ix + rep * dvec_len < m * ncols of a special position (row = flat % m,
+ * col = flat / m) outside X's pattern is a new entry: the default NaN for an NA or a zero divisor, 1 for a zero
+ * exponent, +Inf for a negative one, NA_real_ for anything else (:2618-2636).
+ * mxd_dvec_na_special: flags, scans and compacts the special positions into special_ws
+ *   (mxd_dvec_na_special_workspace_bytes(dvec_len)); *nspecial_host = their number, *candidates_host = the closed-form
+ *   number of their cells, sum of ceil((m * ncols - ix) / dvec_len).  INT32_MAX candidates or more fail with the
+ *   reference's message (:2654-2660), since every candidate is a new entry or one of X's.  Two read-backs.
+ * mxd_dvec_na_cells_count: one lane per candidate cell searches its row of X; *new_host = the new entries (one
+ *   read-back); new + nnz >= INT32_MAX fails with the same message.  cells_ws:
+ *   mxd_dvec_na_cells_workspace_bytes(candidates), shared with the fill.
+ * mxd_dvec_na_cells_fill: the new entries as COO triplets (row, col, value), *new_host of them, in no particular
+ *   order and without repeats; mxd_coo_to_csr sorts them.
+ * mxd_csr_join_disjoint: the union of two CSR matrices with disjoint patterns and sorted rows, here X's transformed
+ *   values and the new entries: out_indptr = indptr1 + indptr2, values copied bit for bit (mxd_csr_merge_fill places
+ *   them); out_indices / out_values hold nnz1 + nnz2 entries.  No synchronise. */
+size_t mxd_dvec_na_special_workspace_bytes(int64_t dvec_len);
+int mxd_dvec_na_special(int m, int ncols, const double *dvec, int64_t dvec_len, int op, void *special_ws,
+                        int64_t *nspecial_host, int64_t *candidates_host, void *stream);
+size_t mxd_dvec_na_cells_workspace_bytes(int64_t candidates);
+int mxd_dvec_na_cells_count(int m, int ncols, int64_t nnz, const int32_t *indptr, const int32_t *indices,
+                            int64_t dvec_len, const void *special_ws, int64_t nspecial, int64_t candidates,
+                            void *cells_ws, int64_t *new_host, void *stream);
+int mxd_dvec_na_cells_fill(int m, int ncols, const double *dvec, int64_t dvec_len, int op, const void *special_ws,
+                           int64_t nspecial, int64_t candidates, const void *cells_ws, int32_t *out_rows,
+                           int32_t *out_cols, double *out_values, void *stream);
+int mxd_csr_join_disjoint(int m, const int32_t *indptr1, const int32_t *indices1, const double *values1, int64_t nnz1,
+                          const int32_t *indptr2, const int32_t *indices2, const double *values2, int64_t nnz2,
+                          int32_t *out_indptr, int32_t *out_indices, double *out_values, void *stream);
+
 /* check_is_seq / check_is_rev_seq (src/slice.cpp:25-47) on a device vector.
  * *flag_host receives 0/1 after an internal stream sync. */
 int mxd_check_is_seq(const int32_t *idx, int64_t n, int reversed, int32_t *workspace4,
@@ -601,12 +651,24 @@ int mx_multiply_csc_by_dense_keep_NAs_float32(const int32_t *indptr, int ncols, 
                                               const double *values, const float *dense, int nrows,
                                               mx_result **res, mx_result_info *info);
 /* multiply_csr_by_dvec_no_NAs_numeric  src/operators.cpp:2142-2175: exactly one of the five flags is set (as the R
- * caller passes them, R/operators.R:1134-1137); values_out f64[nnz].  The structure-changing NA route
- * (multiply_csr_by_dvec_with_NAs, :2258-) is not provided. */
+ * caller passes them, R/operators.R:1134-1137); values_out f64[nnz].  The structure-changing NA route is
+ * mx_multiply_csr_by_dvec_with_NAs_begin below. */
 int mx_multiply_csr_by_dvec_no_NAs_numeric(const int32_t *indptr, const int32_t *indices, const double *values,
                                            int nrows, const double *dvec, int64_t dvec_len, int ncols, int multiply,
                                            int powerto, int divide, int divrest, int intdiv, int X_is_LHS,
                                            double *values_out);
+/* multiply_csr_by_dvec_with_NAs  src/operators.cpp:2258-2852 (RcppExports.cpp:1628-1645): the
+ * route the R caller takes when the vector makes cells outside X's pattern NA / NaN / 1 / Inf (R/operators.R:981-988).
+ * Rows of X sorted by column (the R caller sorts, :1113); 1 <= dvec_len <= nrows * ncols; exactly one of the five
+ * flags set; ^ / %% with X_is_LHS = 0 fail as the reference's throw_internal_err does (:2275).  Result: a new indptr
+ * (nrows + 1), indices and f64 values, rows sorted.  When the flat regime adds no entry, info->alias_structure = 1:
+ * the reference returns the INPUT indptr / indices objects (:2643-2651) and finish fills only the values.  Too many
+ * entries fail before the result is allocated: the row-ruled regime through the count's int32 check (the reference
+ * does not check there), the flat regime with the reference's message (:2654-2660). */
+int mx_multiply_csr_by_dvec_with_NAs_begin(const int32_t *indptr, const int32_t *indices, const double *values,
+                                           int nrows, const double *dvec, int64_t dvec_len, int ncols, int multiply,
+                                           int powerto, int divide, int divrest, int intdiv, int X_is_LHS,
+                                           mx_result **res, mx_result_info *info);
 /* logicaland_csr_by_dvec_internal  src/operators.cpp:2177-2200: R logicals (int32), values_out int32[nnz] */
 int mx_logicaland_csr_by_dvec_internal(const int32_t *indptr, const int32_t *indices, const int32_t *values,
                                        int nrows, const int32_t *dvec, int64_t dvec_len, int ncols,

@@ -36,6 +36,8 @@
     "reverse_columns_inplace_numeric", "reverse_columns_inplace_logical", "reverse_columns_inplace_binary",
     ## rank 4: values-only CSR (op) vector
     "multiply_csr_by_dvec_no_NAs_numeric", "logicaland_csr_by_dvec_internal",
+    ## the NA-keeping route of CSR (op) vector (multiply_csr_by_dvec_elemwise_internal, R/operators.R:996-1129)
+    "multiply_csr_by_dvec_with_NAs",
     ## COO (TsparseMatrix) operands
     "multiply_csr_by_coo_elemwise", "logicaland_csr_by_coo_elemwise",
     "multiply_coo_by_dense_ignore_NAs_numeric", "multiply_coo_by_dense_ignore_NAs_logical",

@@ -19,6 +19,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu.h")
 # mx_dtype / mx_merge_op (include/mxgpu.h)
 MX_F64, MX_F32, MX_I32, MX_LGL, MX_NONE = 0, 1, 2, 3, 4
 MX_OP_ADD, MX_OP_SUB, MX_OP_MUL, MX_OP_OR, MX_OP_XOR, MX_OP_AND = range(6)
+# mx_dvec_op, by R's operator (include/mxgpu.h)
+MX_DV_OPS = {"*": 0, "^": 1, "/": 2, "%%": 3, "%/%": 4}
 # mx_keep_rule and MX_ALIAS_ALL (include/mxgpu.h)
 MX_KEEP_NONZERO, MX_KEEP_NONZERO_NOT_NA, MX_KEEP_NOT_NA, MX_KEEP_MASK = range(4)
 MX_ALIAS_ALL = 2
@@ -83,6 +85,12 @@ def load() -> C.CDLL:
     lib.mxd_csc_dense_na_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.mxd_csr_by_svec_workspace_bytes.restype = C.c_size_t
     lib.mxd_csr_by_svec_workspace_bytes.argtypes = [C.c_int]
+    lib.mxd_csr_by_dvec_na_rows_workspace_bytes.restype = C.c_size_t
+    lib.mxd_csr_by_dvec_na_rows_workspace_bytes.argtypes = [C.c_int]
+    lib.mxd_dvec_na_special_workspace_bytes.restype = C.c_size_t
+    lib.mxd_dvec_na_special_workspace_bytes.argtypes = [C.c_int64]
+    lib.mxd_dvec_na_cells_workspace_bytes.restype = C.c_size_t
+    lib.mxd_dvec_na_cells_workspace_bytes.argtypes = [C.c_int64]
     lib.mxd_sort_vector_indices_workspace_bytes.restype = C.c_size_t
     lib.mxd_sort_vector_indices_workspace_bytes.argtypes = [C.c_int64]
     if lib.mx_abi_version() != 1:

@@ -773,6 +773,103 @@ int mx_multiply_csr_by_dvec_no_NAs_numeric(const int32_t *indptr, const int32_t 
     return csr_by_dvec_export(indptr, indices, values, nrows, dvec, dvec_len, ncols, op, X_is_LHS, values_out);
 }
 
+// multiply_csr_by_dvec_with_NAs (operators.cpp:2258-2852; dvecna.hip)
+int mx_multiply_csr_by_dvec_with_NAs_begin(const int32_t *indptr, const int32_t *indices, const double *values,
+                                           int nrows, const double *dvec, int64_t dvec_len, int ncols, int multiply,
+                                           int powerto, int divide, int divrest, int intdiv, int X_is_LHS,
+                                           mx_result **res_out, mx_result_info *info)
+{
+    MX_REQUIRE(res_out && info && indptr && dvec && nrows >= 0 && ncols >= 0,
+               "mx_multiply_csr_by_dvec_with_NAs_begin: bad arguments");
+    *res_out = nullptr;
+    // :2275-2289
+    if ((powerto || divide || divrest) && !X_is_LHS) return set_error("Internal error. Please file an issue in GitHub.");
+    int op;
+    if (multiply) op = MX_DV_MULTIPLY;
+    else if (powerto) op = MX_DV_POWERTO;
+    else if (divide) op = MX_DV_DIVIDE;
+    else if (divrest) op = MX_DV_DIVREST;
+    else if (intdiv) op = MX_DV_INTDIV;
+    else return set_error("Internal error. Please file an issue in GitHub.");
+    MX_REQUIRE(indptr[0] == 0 && indptr[nrows] >= 0, "mx_multiply_csr_by_dvec_with_NAs_begin: bad index pointer");
+    MX_REQUIRE(dvec_len >= 1, "mx_multiply_csr_by_dvec_with_NAs_begin: empty vector");   // R/operators.R:961-966
+    const bool row_ruled = dvec_len <= nrows && nrows % dvec_len == 0;                    // :2314
+    MX_REQUIRE(row_ruled || dvec_len <= (int64_t)nrows * ncols,
+               "mx_multiply_csr_by_dvec_with_NAs_begin: the vector has more entries than the matrix");
+    return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
+        Csr A;
+        if (A.upload(indptr, indices, values, nrows, sizeof(double))) return 1;
+        DevBuf D;
+        if (D.upload(dvec, sizeof(double) * (size_t)dvec_len)) return 1;
+        const int32_t *Ap = A.p.as<int32_t>(), *Aj = A.j.as<int32_t>();
+        const size_t pbytes = sizeof(int32_t) * ((size_t)nrows + 1);
+        if (row_ruled) {
+            DevBuf ws;
+            if (ws.alloc(mxd_csr_by_dvec_na_rows_workspace_bytes(nrows))) return 1;
+            if (res.indptr.alloc(pbytes)) return 1;
+            int64_t total = 0;
+            if (mxd_csr_by_dvec_na_rows_count(nrows, ncols, A.nnz, Ap, D.as<double>(), dvec_len, op, ws.p,
+                                              res.indptr.as<int32_t>(), &total, nullptr)) return 1;
+            res.set_sizes((int64_t)nrows + 1, total, total);
+            if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
+            if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+            if (total == 0) return 0;
+            return mxd_csr_by_dvec_na_rows_fill(nrows, ncols, A.nnz, Ap, Aj, A.x.as<double>(), D.as<double>(), dvec_len,
+                                                op, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
+                                                res.values.as<double>(), nullptr);
+        }
+        // the flat regime: the new cells first, as COO triplets
+        int64_t nspecial = 0, candidates = 0, n_new = 0;
+        DevBuf nr, nc, nx;
+        {
+            DevBuf sws, cws;
+            if (sws.alloc(mxd_dvec_na_special_workspace_bytes(dvec_len))) return 1;
+            if (mxd_dvec_na_special(nrows, ncols, D.as<double>(), dvec_len, op, sws.p, &nspecial, &candidates, nullptr))
+                return 1;
+            if (candidates > 0) {
+                if (cws.alloc(mxd_dvec_na_cells_workspace_bytes(candidates))) return 1;
+                if (mxd_dvec_na_cells_count(nrows, ncols, A.nnz, Ap, Aj, dvec_len, sws.p, nspecial, candidates, cws.p,
+                                            &n_new, nullptr)) return 1;
+            }
+            if (n_new > 0) {
+                if (nr.alloc(sizeof(int32_t) * (size_t)n_new) || nc.alloc(sizeof(int32_t) * (size_t)n_new) ||
+                    nx.alloc(sizeof(double) * (size_t)n_new)) return 1;
+                if (mxd_dvec_na_cells_fill(nrows, ncols, D.as<double>(), dvec_len, op, sws.p, nspecial, candidates, cws.p,
+                                           nr.as<int32_t>(), nc.as<int32_t>(), nx.as<double>(), nullptr)) return 1;
+            }
+        }
+        if (n_new == 0) {
+            // :2643-2651: the input structure itself and the values-only product, with X on the side it was given
+            res.info.alias_structure = 1;
+            res.set_sizes((int64_t)nrows + 1, A.nnz, A.nnz);
+            if (res.values.alloc(sizeof(double) * (size_t)A.nnz)) return 1;
+            return mxd_csr_by_dvec(nrows, ncols, A.nnz, Ap, Aj, A.x.p, D.p, dvec_len, op, X_is_LHS, res.values.p, nullptr);
+        }
+        DevBuf Bp, Bj, Bx, Ax;
+        {
+            DevBuf ws;
+            if (ws.alloc(mxd_coo_to_csr_workspace_bytes(n_new, ncols))) return 1;
+            if (Bp.alloc(pbytes) || Bj.alloc(sizeof(int32_t) * (size_t)n_new) || Bx.alloc(sizeof(double) * (size_t)n_new))
+                return 1;
+            int64_t kept = 0;
+            if (mxd_coo_to_csr(nrows, ncols, nr.as<int32_t>(), nc.as<int32_t>(), nx.p, MX_F64, n_new, Bp.as<int32_t>(),
+                               Bj.as<int32_t>(), Bx.p, ws.p, &kept, nullptr)) return 1;
+            MX_REQUIRE(kept == n_new, "mx_multiply_csr_by_dvec_with_NAs_begin: repeated new cells");
+        }
+        // :2705-2743: the stored entries, always with X on the left
+        if (Ax.alloc(sizeof(double) * (size_t)A.nnz)) return 1;
+        if (mxd_csr_by_dvec(nrows, ncols, A.nnz, Ap, Aj, A.x.p, D.p, dvec_len, op, 1, Ax.p, nullptr)) return 1;
+        const int64_t total = A.nnz + n_new;
+        res.set_sizes((int64_t)nrows + 1, total, total);
+        if (res.indptr.alloc(pbytes)) return 1;
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
+        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+        return mxd_csr_join_disjoint(nrows, Ap, Aj, Ax.as<double>(), A.nnz, Bp.as<int32_t>(), Bj.as<int32_t>(),
+                                     Bx.as<double>(), n_new, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
+                                     res.values.as<double>(), nullptr);
+    });
+}
+
 int mx_logicaland_csr_by_dvec_internal(const int32_t *indptr, const int32_t *indices, const int32_t *values,
                                        int nrows, const int32_t *dvec, int64_t dvec_len, int ncols,
                                        int32_t *values_out)

@@ -374,6 +374,24 @@ SEXP _MatrixExtra_multiply_csr_by_dvec_no_NAs_numeric(SEXP p_, SEXP j_, SEXP x_,
         fail();
     return out;
 }
+// CSR (op) vector keeping R's NA cells  (src/operators.cpp:2258-2852; glue src/RcppExports.cpp:1628-1645, 11
+// arguments): list(indptr, indices, values); when the flat regime adds no entry, indptr / indices are the arguments
+// themselves, as the reference returns them (:2643-2651)
+SEXP _MatrixExtra_multiply_csr_by_dvec_with_NAs(SEXP p_, SEXP j_, SEXP x_, SEXP dvec, SEXP ncols, SEXP multiply,
+                                                SEXP powerto, SEXP divide, SEXP divrest, SEXP intdiv, SEXP lhs)
+{
+    Protect p;
+    p_ = as_type(p_, INTSXP, p); j_ = as_type(j_, INTSXP, p); x_ = as_type(x_, REALSXP, p); dvec = as_type(dvec, REALSXP, p);
+    if (XLENGTH(x_) != XLENGTH(j_)) Rf_error("multiply_csr_by_dvec_with_NAs: indices and values have different length");
+    mx_result *res = nullptr;
+    mx_result_info info;
+    if (mx_multiply_csr_by_dvec_with_NAs_begin(INTEGER(p_), INTEGER(j_), REAL(x_), (int)XLENGTH(p_) - 1, REAL(dvec),
+                                               (int64_t)XLENGTH(dvec), Rf_asInteger(ncols), Rf_asLogical(multiply),
+                                               Rf_asLogical(powerto), Rf_asLogical(divide), Rf_asLogical(divrest),
+                                               Rf_asLogical(intdiv), Rf_asLogical(lhs), &res, &info))
+        fail();
+    return finish_guarded(res, info, p_, j_);
+}
 SEXP _MatrixExtra_logicaland_csr_by_dvec_internal(SEXP p_, SEXP j_, SEXP x_, SEXP dvec, SEXP ncols)
 {
     Protect p;
@@ -834,6 +852,7 @@ static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(reverse_columns_inplace_numeric, 4), MX_ENTRY(reverse_columns_inplace_logical, 4),
     MX_ENTRY(reverse_columns_inplace_binary, 4),
     MX_ENTRY(multiply_csr_by_dvec_no_NAs_numeric, 11), MX_ENTRY(logicaland_csr_by_dvec_internal, 5),
+    MX_ENTRY(multiply_csr_by_dvec_with_NAs, 11),
     MX_ENTRY(multiply_csr_by_coo_elemwise, 8), MX_ENTRY(logicaland_csr_by_coo_elemwise, 8),
     MX_ENTRY(multiply_coo_by_dense_ignore_NAs_numeric, 12), MX_ENTRY(multiply_coo_by_dense_ignore_NAs_logical, 6),
     MX_ENTRY(slice_coo_single_numeric, 5), MX_ENTRY(slice_coo_single_logical, 5), MX_ENTRY(slice_coo_single_binary, 4),

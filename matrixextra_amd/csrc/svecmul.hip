@@ -20,12 +20,14 @@
 // when X is clean, so no pass over all of X is made for it: the count pass reads the values of the rows that v
 // does not store (it has to, to count them) and raises one flag word when it meets a NaN / Inf there.
 //
-// A dense-filled row is written by the whole wave, 64 consecutive columns per store instruction, whatever G is.
-// Under an Inf val the value of column c comes from a binary search of the (sorted) row for its last entry with
-// that column: with a repeated column the last one wins, as in the reference's scatter, without two stores racing.
+// A dense-filled row is written by the whole wave, 64 consecutive columns per store instruction, whatever G is
+// (mx_dense_row.h, shared with dvecna.hip).  Under an Inf val the value of column c comes from a binary search of
+// the (sorted) row for its last entry with that column: with a repeated column the last one wins, as in the
+// reference's scatter, without two stores racing.
 // Row bounds are clamped into [0, nnz] in both passes and every write position comes from the scanned counts, so
 // nothing is read or written out of bounds whatever the input.
 #include "mx_dispatch.h"
+#include "mx_dense_row.h"
 
 namespace mx {
 
@@ -103,6 +105,13 @@ void sv_count_kernel(int m, int ncol, int64_t nnz, const int32_t *__restrict__ i
     if (lg == 0) { counts[r] = cnt; vpos[r] = pos; }       // the fill reads the position back: one search a row
 }
 
+// a dense-filled row (mx_dense_row.h): NaN val -> val everywhere; +-Inf val -> the default NaN, val * x where stored
+struct SvDenseRule {
+    __device__ __forceinline__ bool looks_up(double val) const { return isinf(val); }
+    __device__ __forceinline__ double fill(double val) const { return isinf(val) ? sv_nan() : val; }
+    __device__ __forceinline__ double at(double x, double val) const { return val * x; }
+};
+
 template <int G>
 __global__ __launch_bounds__(SV_BLOCK)
 void sv_fill_kernel(int m, int ncol, int64_t nnz, const int32_t *__restrict__ indptr,
@@ -111,7 +120,7 @@ void sv_fill_kernel(int m, int ncol, int64_t nnz, const int32_t *__restrict__ in
                     const int32_t *__restrict__ out_indptr, int32_t *__restrict__ out_indices,
                     double *__restrict__ out_values)
 {
-    const int lg = threadIdx.x % G, lane = lane_id();
+    const int lg = threadIdx.x % G;
     const long long r = (long long)blockIdx.x * (SV_BLOCK / G) + threadIdx.x / G;
     int64_t dst = 0;
     int cnt = 0;
@@ -142,32 +151,9 @@ void sv_fill_kernel(int m, int ncol, int64_t nnz, const int32_t *__restrict__ in
         }
     }
 
-    // dense-filled rows: the wave takes them one after another, 64 consecutive columns per store
-    unsigned long long todo = __ballot(w.dense && lg == 0);
-    while (todo) {
-        const int src = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const int64_t d0 = __shfl(dst, src, MX_WAVE);
-        const int s = __shfl(w.s, src, MX_WAVE), len = __shfl(w.len, src, MX_WAVE);
-        const double val = __shfl(w.val, src, MX_WAVE);
-        const bool scaled = isinf(val);
-        const double fill = scaled ? sv_nan() : val;
-        for (int c = lane; c < ncol; c += MX_WAVE) {
-            double v = fill;
-            if (scaled) {                                   // last entry of the row with column c, if any
-                const int32_t *__restrict__ row = indices + s;
-                int lo = 0, n = len;
-                while (n > 0) {                             // first position with row[.] > c
-                    const int step = n >> 1;
-                    if (row[lo + step] <= c) { lo += step + 1; n -= step + 1; }
-                    else n = step;
-                }
-                if (lo > 0 && row[lo - 1] == c) v = val * values[s + lo - 1];
-            }
-            out_indices[d0 + c] = c;
-            out_values[d0 + c] = v;
-        }
-    }
+    // dense-filled rows: the wave takes them one after another, 64 consecutive columns per store (mx_dense_row.h)
+    write_dense_rows(w.dense && lg == 0, dst, w.s, w.len, w.val, ncol, indices, values, out_indices, out_values,
+                     SvDenseRule{});
 }
 
 // workspace: [count workspace of m][NA flag, 16 B][position in v of each row, or -1: m]

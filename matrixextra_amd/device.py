@@ -439,6 +439,69 @@ def csr_by_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, length:
     return out_p, out_j[:k], out_x[:k]
 
 
+def csr_by_dvec_keep_na(A: DeviceCSR, v: torch.Tensor, op: str = "*"):
+    """X op v (op one of * ^ / %% %/%) for a device-resident CSR X (f64 values, sorted rows) and a dense f64 vector
+    recycled over the matrix, keeping the cells that R makes NA / NaN / 1 / Inf outside X's pattern,
+    as (p, j, x) tensors.  A length that divides A.m rules whole rows; any other length up to A.m * A.K goes over the
+    flat cells, and when that adds no entry the result's p and j are A's own tensors."""
+    lib = _lib.load()
+    dev = A.indptr.device
+    if op not in _lib.MX_DV_OPS:
+        raise ValueError(f"csr_by_dvec_keep_na: unknown operation {op!r}")
+    if A.values is None or A.values.dtype != torch.float64:
+        raise ValueError("csr_by_dvec_keep_na: X needs float64 values")
+    if v.dtype != torch.float64 or v.dim() != 1 or v.device != dev:
+        raise ValueError(f"csr_by_dvec_keep_na: v must be a 1-d float64 tensor on {dev}")
+    v = v.contiguous()
+    L, code = int(v.numel()), C.c_int(_lib.MX_DV_OPS[op])
+    m, K, nnz = C.c_int(A.m), C.c_int(A.K), C.c_int64(A.nnz)
+    if L < 1 or (A.m % L and L > A.m * A.K):
+        raise ValueError("csr_by_dvec_keep_na: v needs between 1 and nrow * ncol entries")
+
+    def buf(nbytes):
+        return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+    def entries(k):
+        return (torch.empty(max(k, 1), dtype=torch.int32, device=dev),
+                torch.empty(max(k, 1), dtype=torch.float64, device=dev))
+
+    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
+    if L <= A.m and A.m % L == 0:                                       # row-ruled
+        ws = buf(lib.mxd_csr_by_dvec_na_rows_workspace_bytes(m))
+        total = C.c_int64(0)
+        check(lib.mxd_csr_by_dvec_na_rows_count(m, K, nnz, _dp(A.indptr), _dp(v), C.c_int64(L), code, _dp(ws),
+                                                _dp(out_p), C.byref(total), _stream()))
+        k = int(total.value)
+        out_j, out_x = entries(k)
+        if k:
+            check(lib.mxd_csr_by_dvec_na_rows_fill(m, K, nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v),
+                                                   C.c_int64(L), code, _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
+        return out_p, out_j[:k], out_x[:k]
+    sws = buf(lib.mxd_dvec_na_special_workspace_bytes(C.c_int64(L)))
+    nsp, cand, new = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    check(lib.mxd_dvec_na_special(m, K, _dp(v), C.c_int64(L), code, _dp(sws), C.byref(nsp), C.byref(cand), _stream()))
+    if cand.value:
+        cws = buf(lib.mxd_dvec_na_cells_workspace_bytes(cand))
+        check(lib.mxd_dvec_na_cells_count(m, K, nnz, _dp(A.indptr), _dp(A.indices), C.c_int64(L), _dp(sws), nsp, cand,
+                                          _dp(cws), C.byref(new), _stream()))
+    n_new = int(new.value)
+    _, ax = entries(A.nnz)
+    check(lib.mxd_csr_by_dvec(m, K, nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v), C.c_int64(L), code,
+                              C.c_int(1), _dp(ax), _stream()))
+    if n_new == 0:
+        return A.indptr, A.indices, ax[:A.nnz]
+    ni, nx = entries(n_new)
+    nj = torch.empty_like(ni)
+    check(lib.mxd_dvec_na_cells_fill(m, K, _dp(v), C.c_int64(L), code, _dp(sws), nsp, cand, _dp(cws), _dp(ni), _dp(nj),
+                                     _dp(nx), _stream()))
+    B = coo_to_csr(ni[:n_new], nj[:n_new], nx[:n_new], A.m, A.K)
+    k = A.nnz + n_new
+    out_j, out_x = entries(k)
+    check(lib.mxd_csr_join_disjoint(m, _dp(A.indptr), _dp(A.indices), _dp(ax), nnz, _dp(B.indptr), _dp(B.indices),
+                                    _dp(B.values), C.c_int64(n_new), _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
+    return out_p, out_j[:k], out_x[:k]
+
+
 def csr_filter(A: DeviceCSR, mask: torch.Tensor) -> DeviceCSR:
     """filterSparse of a device-resident CSR: keeps entry k where mask[k] (bool, or int32 R logical) is TRUE or NA;
     an NA writes NA_real_ / NA_LOGICAL as the value."""

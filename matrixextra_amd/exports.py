@@ -667,6 +667,23 @@ def multiply_csr_by_dvec_no_NAs_numeric(indptr, indices, values, dvec, ncols, mu
     return out
 
 
+def multiply_csr_by_dvec_with_NAs(indptr, indices, values, dvec, ncols, multiply, powerto, divide, divrest, intdiv,
+                                  X_is_LHS):
+    """src/operators.cpp:2258-2852 (R/RcppExports.R `multiply_csr_by_dvec_with_NAs`): `X op v` with the cells that R
+    makes NA / NaN / 1 / Inf outside X's pattern added; rows of X sorted.  When the flat regime adds nothing, `indptr`
+    and `indices` of the result are the argument objects themselves, as in the reference (:2643-2651)."""
+    p, j, x = _i32(indptr), _i32(indices), _f64(values)
+    dv = np.ascontiguousarray(dvec, dtype=np.float64).reshape(-1)
+    if x.size != j.size:
+        raise ValueError("indices and values have different lengths")
+    res, info = C.c_void_p(), ResultInfo()
+    check(_lib.load().mx_multiply_csr_by_dvec_with_NAs_begin(
+        ptr(p), ptr(j), ptr(x), C.c_int(p.size - 1), ptr(dv), C.c_int64(dv.size), C.c_int(int(ncols)),
+        C.c_int(bool(multiply)), C.c_int(bool(powerto)), C.c_int(bool(divide)), C.c_int(bool(divrest)),
+        C.c_int(bool(intdiv)), C.c_int(bool(X_is_LHS)), C.byref(res), C.byref(info)))
+    return _finish(res, info, alias_from=(indptr, indices))
+
+
 def logicaland_csr_by_dvec_internal(indptr, indices, values, dvec, ncols):
     """src/operators.cpp:2177-2200 (R/RcppExports.R:484-486): R logicals in, R logicals out."""
     p, j = _i32(indptr), _i32(indices)

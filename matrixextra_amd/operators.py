@@ -214,11 +214,42 @@ def _as_logical(v):
     return (v != 0).astype(np.int32)
 
 
+def _csr_by_dvec_keep_na_route(e1, e2, X_is_LHS, op):
+    """The take_route_NAs branch of R/operators.R:996-1129, taken under options["mxgpu.dvec_na_route"]: `e2` (float64)
+    holds an NA / NaN, a zero under / %% %/% ^, an Inf under * or a negative exponent under ^, and the cells that R
+    makes NA / NaN / 1 / Inf outside e1's pattern are added (multiply_csr_by_dvec_with_NAs).  The result is a
+    dgRMatrix with e1's Dim and Dimnames; e1 is sorted in a copy unless MatrixExtra.inplace_sort is set.  What the
+    reference hands to a CsparseMatrix here (a vector that is all NA, a vector of length one) raises."""
+    if bool(np.isnan(e2).all()):                                              # :998-1006
+        stop(_NOT_ACCELERATED % "998-1006")
+    if isinstance(e1, TsparseMatrix):                                         # :1008-1011
+        e1 = as_csr_matrix(e1, logical=False)
+    inplace_sort = bool(options.get("MatrixExtra.inplace_sort", False))
+    if inplace_sort:                                                          # :1013-1014
+        e1 = _deepcopy_unless_numeric(e1)
+    e1 = as_csr_matrix(e1, logical=False)                                     # :1022-1030
+    if e2.size == 1:                                                          # always one of the CsparseMatrix fallbacks
+        if op == "*":
+            stop(_NOT_ACCELERATED % "1052-1056")
+        if op in ("/", "%%", "%/%"):
+            if X_is_LHS:
+                warnings.warn("Warning: division by zero.")
+            stop(_NOT_ACCELERATED % "1063-1069")
+        stop(_NOT_ACCELERATED % "1085-1089")
+    e1 = sort_sparse_indices(e1, copy=not inplace_sort)                       # :1112-1114
+    if e1.Dim[0] % e2.size != 0:                                              # :1116-1117
+        warnings.warn("Number of elements in vector is not a multiple of matrix dimension.")
+    res = exports.multiply_csr_by_dvec_with_NAs(e1.p, e1.j, e1.x, e2, e1.Dim[1], op == "*", op == "^", op == "/",
+                                                op == "%%", op == "%/%", X_is_LHS)   # :1119-1129
+    return _assemble(type(e1), e1, res)
+
+
 def multiply_csr_by_dvec_elemwise_internal(e1, e2, logical=False, X_is_LHS=True, op="*"):
     """R/operators.R:950-1153 for RsparseMatrix or TsparseMatrix `e1`: `e1 op e2` (or `e2 op e1` when X_is_LHS is false) with a dense
     vector (or a same-shape dense matrix read as a vector), R's recycling, values-only result.  The routes the
     reference sends through multiply_csr_by_dvec_with_NAs or through a CsparseMatrix (vector with NA, division by
-    zero, multiplication by Inf, `v op X` for ^ / %% %/% while NAs are kept) raise: they stay on the CPU."""
+    zero, multiplication by Inf, `v op X` for ^ / %% %/% while NAs are kept) raise, unless
+    options["mxgpu.dvec_na_route"] is set: then the first of them runs on the device (_csr_by_dvec_keep_na_route)."""
     e2 = np.asarray(e2)
     if e2.ndim == 2:                                                          # :952-959
         if e1.Dim[0] != e2.shape[0] or e2.shape[1] != e2.shape[1]:            # (sic: the reference compares ncol(e2) with itself)
@@ -240,7 +271,9 @@ def multiply_csr_by_dvec_elemwise_internal(e1, e2, logical=False, X_is_LHS=True,
         or (op == "*" and bool(np.isinf(e2f).any()))
         or (op == "^" and bool((e2f < 0).any())))                             # :981-988
     if take_route_NAs:
-        stop(_NOT_ACCELERATED % "981-1131")
+        if not options.get("mxgpu.dvec_na_route", False):
+            stop(_NOT_ACCELERATED % "981-1131")
+        return _csr_by_dvec_keep_na_route(e1, e2f, X_is_LHS, op)
     e2 = _as_logical(e2) if logical else e2f
     is_coo = isinstance(e1, TsparseMatrix)                                    # :990
     e1 = as_coo_matrix(e1, logical=logical) if is_coo else as_csr_matrix(e1, logical=logical)   # :1020-1029
