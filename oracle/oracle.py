@@ -8,8 +8,8 @@ Functions carry the names and argument order of the reference's Rcpp exports
 the dense results, a dict(indptr=, indices=, values=) for the list results.
 Dense matrices are numpy arrays in Fortran (column-major) order, as R holds them.
 
-Parity status: see the header of mx_oracle.c ("parity unpinned by
-reference-run outputs"; pinned by the reference's literal KATs + dense numpy).
+Parity status: pinned by reference-run outputs (oracle/ref.py over the reference's own compiled C++,
+tests/test_reference_pin.py); see the header of mx_oracle.c and DESIGN.md §2.
 """
 from __future__ import annotations
 

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generates tests/golden/hotpath_golden.npz — small input/output vectors for every hot-path export.
 
-Provenance: the reference (R + Rcpp) cannot run in this image, so these are NOT outputs of the reference
-itself.  Inputs come from numpy's PCG64 with the seeds below (plus the literal matrices the reference tree
+Provenance: these are outputs of the CPU restatement, NOT of the reference itself; the reference-run fixture is
+reference_golden.npz (make_reference_golden.py), and tests/test_reference_pin.py holds the restatement to it.  Inputs come from numpy's PCG64 with the seeds below (plus the literal matrices the reference tree
 prints: vignette 3x3, test-utilities.R sort KAT); outputs come from the CPU restatement oracle/mx_oracle.c
 AFTER it was checked against dense numpy / scipy and the reference's literal known answers
 (tests/test_oracle.py).  Dense products are additionally cross-checked here against numpy before saving.
