@@ -11,39 +11,105 @@ from __future__ import annotations
 import ctypes as C
 import os
 import re
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmxgpu.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu.h")
-
-# mx_dtype / mx_merge_op (include/mxgpu.h)
-MX_F64, MX_F32, MX_I32, MX_LGL, MX_NONE = 0, 1, 2, 3, 4
-MX_OP_ADD, MX_OP_SUB, MX_OP_MUL, MX_OP_OR, MX_OP_XOR, MX_OP_AND = range(6)
-# mx_dvec_op, by R's operator (include/mxgpu.h)
-MX_DV_OPS = {"*": 0, "^": 1, "/": 2, "%%": 3, "%/%": 4}
-# mx_keep_rule and MX_ALIAS_ALL (include/mxgpu.h)
-MX_KEEP_NONZERO, MX_KEEP_NONZERO_NOT_NA, MX_KEEP_NOT_NA, MX_KEEP_MASK = range(4)
-MX_ALIAS_ALL = 2
 
 
 class MxError(RuntimeError):
     """An mx_* / mxd_* call returned non-zero (the .Call shim would Rf_error here)."""
 
 
-class ResultInfo(C.Structure):
-    _fields_ = [("indptr_len", C.c_int64), ("nnz", C.c_int64), ("values_len", C.c_int64),
-                ("values_dtype", C.c_int), ("alias_structure", C.c_int)]
+# ---- include/mxgpu.h is the one declaration of the ABI: signatures, constants and structs are read from it ----------
+_SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "size_t": C.c_size_t, "double": C.c_double}
+_INT = r"-?(?:0x[0-9a-fA-F]+|\d+)"
 
+
+class Header(NamedTuple):
+    functions: dict     # name -> (restype, (argtypes...)) as ctypes types
+    constants: dict     # enumerators and integer #defines, by their C names
+    structs: dict       # typedef struct {...} name; -> ctypes.Structure class
+
+
+def _ctype(spelling: str, where: str, returned: bool = False):
+    """The ctypes type of one C type.  Every pointer is a c_void_p, which takes None, an address, a c_void_p, a ctypes
+    array and byref(...) alike; only a returned `const char *` is a c_char_p."""
+    t = re.sub(r"\s*\*\s*", "*", " ".join(spelling.split()))
+    if returned and t == "const char*":
+        return C.c_char_p
+    if not returned and t.endswith("*"):
+        return C.c_void_p
+    if t not in _SCALARS:
+        raise MxError(f"include/mxgpu.h: {where}: no ctypes mapping for type '{t}'")
+    return _SCALARS[t]
+
+
+def _struct(name: str, body: str):
+    fields = []
+    for member in filter(None, (m.strip() for m in body.split(";"))):
+        first, *rest = (d.strip() for d in member.split(","))
+        base, first = re.match(r"(.*?)(\**\s*\w+)$", first).groups()  # "const void *x" -> "const void ", "*x"
+        for d in (first, *rest):                                        # "int lo, hi, reversed" declares three
+            field = d.lstrip("* ")
+            fields.append((field, _ctype(base + "*" * d.count("*"), f"{name}.{field}")))
+    return type(name, (C.Structure,), {"_fields_": fields, "__doc__": f"{name} (include/mxgpu.h)."})
+
+
+def parse_header(text: str) -> Header:
+    """Everything the binding needs from the text of mxgpu.h.  Strict: a type outside the map, an enumerator without
+    a value, or an mx_* / mxd_* name followed by `(` that is not a plain prototype, raises MxError."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    defines = re.findall(rf"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+({_INT})[ \t]*$", text, flags=re.M)
+    constants = {name: int(value, 0) for name, value in defines}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    for body, name in re.findall(r"typedef\s+enum\s*\{([^}]*)\}\s*(\w+)\s*;", text):
+        for item in filter(None, (e.strip() for e in body.split(","))):
+            m = re.fullmatch(rf"(\w+)\s*=\s*({_INT})", item)
+            if m is None:
+                raise MxError(f"include/mxgpu.h: enum {name}: '{item}' carries no explicit integer value")
+            constants[m.group(1)] = int(m.group(2), 0)
+    structs = {name: _struct(name, body)
+               for body, name in re.findall(r"typedef\s+struct\s*\{([^}]*)\}\s*(\w+)\s*;", text)}
+    functions = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s*]*?)\b(mxd?_\w+)\s*\(([^()]*)\)\s*;", text):
+        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
+        named = (re.fullmatch(r"(.*[\s*])\w+", p) for p in params)          # "const void *B" -> "const void *"
+        argtypes = tuple(_ctype(m.group(1) if m else p, f"{name}(), parameter {k + 1}")
+                         for k, (p, m) in enumerate(zip(params, named)))
+        functions[name] = (_ctype(ret, f"{name}(), return type", returned=True), argtypes)
+    stray = sorted(set(re.findall(r"\b(mxd?_\w+)\s*\(", text)) - set(functions))
+    if stray:
+        raise MxError(f"include/mxgpu.h: not a prototype the binding can read: {stray}")
+    return Header(functions, constants, structs)
+
+
+def _read_header() -> Header:
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise MxError(f"{HEADER_PATH} not readable ({e}): the ctypes signatures, constants and structs of "
+                      "libmxgpu.so are bound from it") from e
+
+
+HEADER = _read_header()
+globals().update(HEADER.constants)        # MX_F64 ... MX_NONE, MX_OP_*, MX_KEEP_*, MX_ALIAS_ALL, MXGPU_ABI_VERSION, ...
+# mx_dvec_op, by R's operator
+MX_DV_OPS = {"*": HEADER.constants["MX_DV_MULTIPLY"], "^": HEADER.constants["MX_DV_POWERTO"],
+             "/": HEADER.constants["MX_DV_DIVIDE"], "%%": HEADER.constants["MX_DV_DIVREST"],
+             "%/%": HEADER.constants["MX_DV_INTDIV"]}
+ResultInfo = HEADER.structs["mx_result_info"]
+CooAxis = HEADER.structs["mx_coo_axis"]
+RbindInput = HEADER.structs["mx_rbind_input"]
 
 _lib = None
 
 
 def declared_symbols() -> list[str]:
     """Every function name include/mxgpu.h declares (used by the export test)."""
-    with open(HEADER_PATH) as f:
-        text = f.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(mxd?_[a-z0-9_]+)\s*\(", text)))
+    return sorted(HEADER.functions)
 
 
 def load() -> C.CDLL:
@@ -59,41 +125,13 @@ def load() -> C.CDLL:
     except Exception:  # pragma: no cover - torch is optional for the plain C-ABI
         pass
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    lib.mx_last_error.restype = C.c_char_p
-    lib.mxd_spmm_last_kernel.restype = C.c_char_p
-    lib.mxd_merge_workspace_bytes.restype = C.c_size_t
-    lib.mxd_gather_workspace_bytes.restype = C.c_size_t
-    lib.mxd_scan_workspace_bytes.restype = C.c_size_t
-    lib.mxd_merge_workspace_bytes.argtypes = [C.c_int]
-    lib.mxd_gather_workspace_bytes.argtypes = [C.c_int]
-    lib.mxd_scan_workspace_bytes.argtypes = [C.c_int64]
-    lib.mxd_colmap_workspace_bytes.restype = C.c_size_t
-    lib.mxd_colmap_workspace_bytes.argtypes = [C.c_int]
-    lib.mxd_csr_transpose_workspace_bytes.restype = C.c_size_t
-    lib.mxd_csr_transpose_workspace_bytes.argtypes = [C.c_int64]
-    lib.mxd_coo_to_csr_workspace_bytes.restype = C.c_size_t
-    lib.mxd_coo_to_csr_workspace_bytes.argtypes = [C.c_int64, C.c_int]
-    lib.mxd_csr_by_coo_workspace_bytes.restype = C.c_size_t
-    lib.mxd_csr_by_coo_workspace_bytes.argtypes = [C.c_int64]
-    lib.mxd_coo_slice_workspace_bytes.restype = C.c_size_t
-    lib.mxd_coo_slice_workspace_bytes.argtypes = [C.c_int64]
-    lib.mxd_coo_single_workspace_bytes.restype = C.c_size_t
-    lib.mxd_coo_single_workspace_bytes.argtypes = []
-    lib.mxd_compact_workspace_bytes.restype = C.c_size_t
-    lib.mxd_compact_workspace_bytes.argtypes = [C.c_int64]
-    lib.mxd_csc_dense_na_workspace_bytes.restype = C.c_size_t
-    lib.mxd_csc_dense_na_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.mxd_csr_by_svec_workspace_bytes.restype = C.c_size_t
-    lib.mxd_csr_by_svec_workspace_bytes.argtypes = [C.c_int]
-    lib.mxd_csr_by_dvec_na_rows_workspace_bytes.restype = C.c_size_t
-    lib.mxd_csr_by_dvec_na_rows_workspace_bytes.argtypes = [C.c_int]
-    lib.mxd_dvec_na_special_workspace_bytes.restype = C.c_size_t
-    lib.mxd_dvec_na_special_workspace_bytes.argtypes = [C.c_int64]
-    lib.mxd_dvec_na_cells_workspace_bytes.restype = C.c_size_t
-    lib.mxd_dvec_na_cells_workspace_bytes.argtypes = [C.c_int64]
-    lib.mxd_sort_vector_indices_workspace_bytes.restype = C.c_size_t
-    lib.mxd_sort_vector_indices_workspace_bytes.argtypes = [C.c_int64]
-    if lib.mx_abi_version() != 1:
+    missing = [name for name in HEADER.functions if not hasattr(lib, name)]
+    if missing:
+        raise MxError(f"libmxgpu.so lacks symbols declared in include/mxgpu.h: {missing}")
+    for name, (restype, argtypes) in HEADER.functions.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    if lib.mx_abi_version() != HEADER.constants["MXGPU_ABI_VERSION"]:
         raise MxError("libmxgpu.so ABI version mismatch")
     _lib = lib
     return lib
@@ -124,5 +162,5 @@ def device_count() -> int:
 
 def device_name() -> str:
     buf = C.create_string_buffer(256)
-    check(load().mx_device_name(buf, C.c_size_t(256)))
+    check(load().mx_device_name(buf, 256))
     return buf.value.decode()

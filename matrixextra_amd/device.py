@@ -43,8 +43,8 @@ class DeviceCSR:
         lib = _lib.load()
         if self._plan is None or rebuild or self._plan_panels != npanels:
             handle = self._plan if self._plan is not None else C.c_void_p()
-            check(lib.mxd_spmm_plan_create(C.c_int(self.m), C.c_int(self.K), _dp(self.indptr), _dp(self.indices),
-                                           _dp(self.values), C.c_int(npanels), _stream(), C.byref(handle)))
+            check(lib.mxd_spmm_plan_create(self.m, self.K, _dp(self.indptr), _dp(self.indices), _dp(self.values),
+                                           npanels, _stream(), C.byref(handle)))
             self._plan, self._plan_panels = handle, npanels
         return self._plan
 
@@ -67,8 +67,8 @@ class DeviceCSR:
             lib = _lib.load()
             ws = torch.empty(4, dtype=torch.int32, device=self.indptr.device)
             flag = C.c_int(0)
-            check(lib.mxd_csr_rows_sorted(C.c_int(self.m), _dp(self.indptr), _dp(self.indices), _dp(ws),
-                                          C.byref(flag), _stream()))
+            check(lib.mxd_csr_rows_sorted(self.m, _dp(self.indptr), _dp(self.indices), _dp(ws), C.byref(flag),
+                                          _stream()))
             self._sorted = bool(flag.value)
         return self._sorted
 
@@ -117,10 +117,9 @@ def spmm(A: DeviceCSR, B: torch.Tensor, out: torch.Tensor | None = None, colmajo
         out.zero_()
         return out.t() if colmajor else out
     sorted_rows = A.rows_sorted() if algo != 1 else False
-    check(lib.mxd_spmm_csr_dense_ex(C.c_int(A.m), C.c_int(n), C.c_int(A.K), _dp(A.indptr), _dp(A.indices),
-                                    _dp(A.values), _dp(B), C.c_size_t(B.stride(0)), _dp(out), C.c_size_t(ldc),
-                                    C.c_int(dt), C.c_int(1 if colmajor else 0), C.c_int(algo),
-                                    C.c_int(int(sorted_rows)), C.c_int(npanels), C.c_int(wg_per_cu), _stream()))
+    check(lib.mxd_spmm_csr_dense_ex(A.m, n, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(B), B.stride(0),
+                                    _dp(out), ldc, dt, 1 if colmajor else 0, algo, int(sorted_rows), npanels, wg_per_cu,
+                                    _stream()))
     return out.t() if colmajor else out
 
 
@@ -136,9 +135,8 @@ def spmm_planned(A: DeviceCSR, B: torch.Tensor, out: torch.Tensor | None = None,
         out.zero_()
         return out.t() if colmajor else out
     plan = A.plan(npanels, rebuild=rebuild_plan)
-    check(lib.mxd_spmm_plan_run(plan, C.c_int(n), _dp(B), C.c_size_t(B.stride(0)), _dp(out), C.c_size_t(ldc),
-                                C.c_int(dt), C.c_int(1 if colmajor else 0), C.c_int(wg_per_cu), C.c_int(sync_mode),
-                                _stream()))
+    check(lib.mxd_spmm_plan_run(plan, n, _dp(B), B.stride(0), _dp(out), ldc, dt, 1 if colmajor else 0, wg_per_cu,
+                                sync_mode, _stream()))
     return out.t() if colmajor else out
 
 
@@ -150,8 +148,8 @@ def spmv(A: DeviceCSR, v: torch.Tensor, v_dtype=None, out=None):
     odt = torch.float32 if v_dtype == MX_F32 else torch.float64
     if out is None:
         out = torch.empty(A.m, dtype=odt, device=v.device)
-    check(lib.mxd_spmv_csr_dvec(C.c_int(A.m), C.c_int64(A.nnz), _dp(A.indptr), _dp(A.indices), _dp(A.values),
-                                _dp(v), C.c_int(v_dtype), _dp(out), _stream()))
+    check(lib.mxd_spmv_csr_dvec(A.m, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v), v_dtype, _dp(out),
+                                _stream()))
     return out
 
 
@@ -163,15 +161,13 @@ def csr_elemwise(op, A: DeviceCSR, B: DeviceCSR):
     ws = torch.empty(lib.mxd_merge_workspace_bytes(A.m), dtype=torch.uint8, device=dev)
     out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
     nnz_out = C.c_int64(0)
-    check(lib.mxd_csr_merge_count(C.c_int(op), C.c_int(A.m), _dp(A.indptr), _dp(A.indices), C.c_int64(A.nnz),
-                                  _dp(B.indptr), _dp(B.indices), C.c_int64(B.nnz), _dp(out_p), _dp(ws),
-                                  C.byref(nnz_out), _stream()))
+    check(lib.mxd_csr_merge_count(op, A.m, _dp(A.indptr), _dp(A.indices), A.nnz, _dp(B.indptr), _dp(B.indices), B.nnz,
+                                  _dp(out_p), _dp(ws), C.byref(nnz_out), _stream()))
     logical = op in (_lib.MX_OP_OR, _lib.MX_OP_XOR, _lib.MX_OP_AND)
     out_j = torch.empty(nnz_out.value, dtype=torch.int32, device=dev)
     out_x = torch.empty(nnz_out.value, dtype=torch.int32 if logical else torch.float64, device=dev)
-    check(lib.mxd_csr_merge_fill(C.c_int(op), C.c_int(A.m), _dp(A.indptr), _dp(A.indices), _dp(A.values),
-                                 C.c_int64(A.nnz), _dp(B.indptr), _dp(B.indices), _dp(B.values), C.c_int64(B.nnz),
-                                 _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
+    check(lib.mxd_csr_merge_fill(op, A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values), A.nnz, _dp(B.indptr),
+                                 _dp(B.indices), _dp(B.values), B.nnz, _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
     return DeviceCSR(out_p, out_j, out_x, A.m, A.K, int(nnz_out.value))
 
 
@@ -183,16 +179,15 @@ def csr_gather_rows(A: DeviceCSR, rows: torch.Tensor):
     ws = torch.empty(lib.mxd_gather_workspace_bytes(r), dtype=torch.uint8, device=dev)
     new_p = torch.empty(r + 1, dtype=torch.int32, device=dev)
     nnz_out = C.c_int64(0)
-    check(lib.mxd_csr_gather_count(C.c_int(r), _dp(A.indptr), _dp(rows), _dp(new_p), _dp(ws),
-                                   C.byref(nnz_out), _stream()))
+    check(lib.mxd_csr_gather_count(r, _dp(A.indptr), _dp(rows), _dp(new_p), _dp(ws), C.byref(nnz_out), _stream()))
     new_j = torch.empty(nnz_out.value, dtype=torch.int32, device=dev)
     if A.values is None:
         vd, new_x = MX_NONE, None
     else:
         vd = MX_F64 if A.values.dtype == torch.float64 else MX_LGL
         new_x = torch.empty(nnz_out.value, dtype=A.values.dtype, device=dev)
-    check(lib.mxd_csr_gather_fill(C.c_int(r), _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(rows), _dp(new_p),
-                                  _dp(new_j), _dp(new_x), C.c_int(vd), C.c_int64(nnz_out.value), _stream()))
+    check(lib.mxd_csr_gather_fill(r, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(rows), _dp(new_p), _dp(new_j),
+                                  _dp(new_x), vd, nnz_out.value, _stream()))
     return DeviceCSR(new_p, new_j, new_x, r, A.K, int(nnz_out.value))
 
 
@@ -214,9 +209,8 @@ def csr_transpose(A: DeviceCSR) -> DeviceCSR:
     out_j = torch.empty(max(A.nnz, 1), dtype=torch.int32, device=dev)
     out_x = None if A.values is None else torch.empty(max(A.nnz, 1), dtype=A.values.dtype, device=dev)
     nnz_out = C.c_int64(0)
-    check(lib.mxd_csr_transpose(C.c_int(A.m), C.c_int(A.K), _dp(A.indptr), _dp(A.indices), _dp(A.values),
-                                C.c_int(vd), C.c_int64(A.nnz), _dp(out_p), _dp(out_j), _dp(out_x), _dp(ws),
-                                C.byref(nnz_out), _stream()))
+    check(lib.mxd_csr_transpose(A.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), vd, A.nnz, _dp(out_p),
+                                _dp(out_j), _dp(out_x), _dp(ws), C.byref(nnz_out), _stream()))
     nnz = int(nnz_out.value)
     return DeviceCSR(out_p, out_j[:nnz], None if out_x is None else out_x[:nnz], A.K, A.m, nnz)
 
@@ -248,8 +242,8 @@ def coo_to_csr(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor | None, m: int,
     out_j = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
     out_x = None if x is None else torch.empty(max(nnz, 1), dtype=x.dtype, device=dev)
     nnz_out = C.c_int64(0)
-    check(lib.mxd_coo_to_csr(C.c_int(int(m)), C.c_int(int(n)), _dp(i), _dp(j), _dp(x), C.c_int(vd), C.c_int64(nnz),
-                             _dp(out_p), _dp(out_j), _dp(out_x), _dp(ws), C.byref(nnz_out), _stream()))
+    check(lib.mxd_coo_to_csr(int(m), int(n), _dp(i), _dp(j), _dp(x), vd, nnz, _dp(out_p), _dp(out_j), _dp(out_x),
+                             _dp(ws), C.byref(nnz_out), _stream()))
     k = int(nnz_out.value)
     return DeviceCSR(out_p, out_j[:k], None if out_x is None else out_x[:k], int(m), int(n), k)
 
@@ -258,14 +252,11 @@ def csr_to_coo(A: DeviceCSR):
     """(i, j, x) of a device CSR in storage order through mxd_csr_to_coo: i is new, j and x are A's own tensors."""
     lib = _lib.load()
     rows = torch.empty(max(A.nnz, 1), dtype=torch.int32, device=A.indptr.device)
-    check(lib.mxd_csr_to_coo(C.c_int(A.m), C.c_int64(A.nnz), _dp(A.indptr), _dp(rows), _stream()))
+    check(lib.mxd_csr_to_coo(A.m, A.nnz, _dp(A.indptr), _dp(rows), _stream()))
     return rows[:A.nnz], A.indices, A.values
 
 
-class CooAxis(C.Structure):
-    """mx_coo_axis (include/mxgpu.h)."""
-    _fields_ = [("kind", C.c_int), ("lo", C.c_int), ("hi", C.c_int), ("reversed", C.c_int), ("nmap", C.c_int),
-                ("start", C.c_void_p), ("pos", C.c_void_p)]
+CooAxis = _lib.CooAxis      # mx_coo_axis, as include/mxgpu.h declares it
 
 
 def _coo_axis(take_base1: torch.Tensor | None, kind: str, n: int, lo: int = 0, hi: int = -1):
@@ -281,8 +272,7 @@ def _coo_axis(take_base1: torch.Tensor | None, kind: str, n: int, lo: int = 0, h
     start = torch.empty(nmap + 1, dtype=torch.int32, device=dev)
     pos = torch.empty(max(nt, 1), dtype=torch.int32, device=dev)
     ws = torch.empty(max(lib.mxd_colmap_workspace_bytes(nmap), 16), dtype=torch.uint8, device=dev)
-    check(lib.mxd_colmap_build(_dp(take_base1), C.c_int64(nt), C.c_int(nmap), _dp(start), _dp(pos), _dp(ws),
-                               _stream()))
+    check(lib.mxd_colmap_build(_dp(take_base1), nt, nmap, _dp(start), _dp(pos), _dp(ws), _stream()))
     return CooAxis(1, 0, 0, 0, nmap, start.data_ptr(), pos.data_ptr()), (start, pos, ws)
 
 
@@ -308,16 +298,15 @@ def coo_slice(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor | None, m: int, 
     aj, keep_j = axis(cols, n)
     ws = torch.empty(max(lib.mxd_coo_slice_workspace_bytes(nnz), 16), dtype=torch.uint8, device=dev)
     nnz_out = C.c_int64(0)
-    check(lib.mxd_coo_slice_count(C.c_int(int(m)), C.c_int(int(n)), _dp(i), _dp(j), C.c_int64(nnz), C.byref(ai),
-                                  C.byref(aj), _dp(ws), C.byref(nnz_out), _stream()))
+    check(lib.mxd_coo_slice_count(int(m), int(n), _dp(i), _dp(j), nnz, C.byref(ai), C.byref(aj), _dp(ws),
+                                  C.byref(nnz_out), _stream()))
     k = int(nnz_out.value)
     oi = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
     oj = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
     ox = None if x is None else torch.empty(max(k, 1), dtype=x.dtype, device=dev)
     if k:
-        check(lib.mxd_coo_slice_fill(C.c_int(int(m)), C.c_int(int(n)), _dp(i), _dp(j), _dp(x), C.c_int(vd),
-                                     C.c_int64(nnz), C.byref(ai), C.byref(aj), _dp(ws), _dp(oi), _dp(oj), _dp(ox),
-                                     _stream()))
+        check(lib.mxd_coo_slice_fill(int(m), int(n), _dp(i), _dp(j), _dp(x), vd, nnz, C.byref(ai), C.byref(aj), _dp(ws),
+                                     _dp(oi), _dp(oj), _dp(ox), _stream()))
     del keep_i, keep_j          # the maps stay alive until both launches are enqueued (torch's caching allocator
     return oi[:k], oj[:k], None if ox is None else ox[:k]      # reuses the blocks only on this same stream)
 
@@ -329,17 +318,15 @@ def _csr_compact(A: DeviceCSR, rule: int, mask: torch.Tensor | None) -> DeviceCS
     vd = _value_dtype(A.values)
     ws = torch.empty(max(lib.mxd_compact_workspace_bytes(A.nnz), 16), dtype=torch.uint8, device=dev)
     kept = C.c_int64(0)
-    check(lib.mxd_compact_count(C.c_int64(A.nnz), _dp(A.values), C.c_int(vd), C.c_int(rule), _dp(mask), _dp(ws),
-                                C.byref(kept), _stream()))
+    check(lib.mxd_compact_count(A.nnz, _dp(A.values), vd, rule, _dp(mask), _dp(ws), C.byref(kept), _stream()))
     k = int(kept.value)
     if k == A.nnz and rule != _lib.MX_KEEP_MASK:
         return A
     out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
     out_j = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
     out_x = torch.empty(max(k, 1), dtype=A.values.dtype, device=dev)
-    check(lib.mxd_compact_fill(C.c_int64(A.nnz), _dp(A.values), C.c_int(vd), C.c_int(rule), _dp(mask),
-                               _dp(A.indices), None, C.c_int(A.m), _dp(A.indptr), _dp(ws), _dp(out_j), None,
-                               _dp(out_x), _dp(out_p), _stream()))
+    check(lib.mxd_compact_fill(A.nnz, _dp(A.values), vd, rule, _dp(mask), _dp(A.indices), None, A.m, _dp(A.indptr),
+                               _dp(ws), _dp(out_j), None, _dp(out_x), _dp(out_p), _stream()))
     return DeviceCSR(out_p, out_j[:k], out_x[:k], A.m, A.K, k)
 
 
@@ -380,26 +367,23 @@ def csc_by_dense(A: DeviceCSR, D: torch.Tensor, keep_na: bool = True, logical: b
     Dc = D.t().contiguous()                         # row-major D^T = column-major D
     out_x = torch.empty(max(A.nnz, 1), dtype=torch.float64, device=dev)
     if not keep_na:
-        check(lib.mxd_csc_by_dense_elemwise(C.c_int(A.m), C.c_int(A.K), C.c_int64(A.nnz), _dp(A.indptr),
-                                            _dp(A.indices), _dp(A.values), _dp(Dc), C.c_int(kind), _dp(out_x),
-                                            _stream()))
+        check(lib.mxd_csc_by_dense_elemwise(A.m, A.K, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(Dc),
+                                            kind, _dp(out_x), _stream()))
         return A.indptr, A.indices.clone(), out_x[:A.nnz]
     ws = torch.empty(max(lib.mxd_csc_dense_na_workspace_bytes(A.K, A.m), 16), dtype=torch.uint8, device=dev)
     total, outside = C.c_int64(0), C.c_int64(0)
-    check(lib.mxd_csc_dense_na_count(C.c_int(A.K), C.c_int(A.m), C.c_int64(A.nnz), _dp(A.indptr), _dp(A.indices),
-                                     _dp(Dc), C.c_int(kind), _dp(ws), C.byref(total), C.byref(outside), _stream()))
+    check(lib.mxd_csc_dense_na_count(A.K, A.m, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(Dc), kind, _dp(ws),
+                                     C.byref(total), C.byref(outside), _stream()))
     k = int(total.value)
     if outside.value == 0 and k == A.nnz:           # the structure does not change: values only, new p and i
-        check(lib.mxd_csc_by_dense_elemwise(C.c_int(A.m), C.c_int(A.K), C.c_int64(A.nnz), _dp(A.indptr),
-                                            _dp(A.indices), _dp(A.values), _dp(Dc), C.c_int(kind), _dp(out_x),
-                                            _stream()))
+        check(lib.mxd_csc_by_dense_elemwise(A.m, A.K, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(Dc),
+                                            kind, _dp(out_x), _stream()))
         return A.indptr.clone(), A.indices.clone(), out_x[:k]
     out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
     out_i = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
     out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
-    check(lib.mxd_csc_dense_na_fill(C.c_int(A.K), C.c_int(A.m), C.c_int64(A.nnz), _dp(A.indptr), _dp(A.indices),
-                                    _dp(A.values), _dp(Dc), C.c_int(kind), _dp(ws), _dp(out_p), _dp(out_i),
-                                    _dp(out_x), _stream()))
+    check(lib.mxd_csc_dense_na_fill(A.K, A.m, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(Dc), kind,
+                                    _dp(ws), _dp(out_p), _dp(out_i), _dp(out_x), _stream()))
     return out_p, out_i[:k], out_x[:k]
 
 
@@ -425,16 +409,14 @@ def csr_by_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, length:
     ws = torch.empty(max(lib.mxd_csr_by_svec_workspace_bytes(A.m), 16), dtype=torch.uint8, device=dev)
     out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
     total, x_na = C.c_int64(0), C.c_int64(0)
-    check(lib.mxd_csr_by_svec_count(C.c_int(A.m), C.c_int(A.K), C.c_int64(A.nnz), _dp(A.indptr), _dp(A.values),
-                                    _dp(vi), C.c_int64(nv), _dp(vx), C.c_int(length), C.c_int(int(bool(keep_na))),
-                                    _dp(ws), _dp(out_p), C.byref(total), C.byref(x_na), _stream()))
+    check(lib.mxd_csr_by_svec_count(A.m, A.K, A.nnz, _dp(A.indptr), _dp(A.values), _dp(vi), nv, _dp(vx), length,
+                                    int(bool(keep_na)), _dp(ws), _dp(out_p), C.byref(total), C.byref(x_na), _stream()))
     k = int(total.value)
     out_j = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
     out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
     if k:
-        check(lib.mxd_csr_by_svec_fill(C.c_int(A.m), C.c_int(A.K), C.c_int64(A.nnz), _dp(A.indptr), _dp(A.indices),
-                                       _dp(A.values), _dp(vi), C.c_int64(nv), _dp(vx), C.c_int(length),
-                                       C.c_int(int(bool(keep_na))), _dp(ws), _dp(out_p), _dp(out_j), _dp(out_x),
+        check(lib.mxd_csr_by_svec_fill(A.m, A.K, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(vi), nv,
+                                       _dp(vx), length, int(bool(keep_na)), _dp(ws), _dp(out_p), _dp(out_j), _dp(out_x),
                                        _stream()))
     return out_p, out_j[:k], out_x[:k]
 
@@ -453,8 +435,8 @@ def csr_by_dvec_keep_na(A: DeviceCSR, v: torch.Tensor, op: str = "*"):
     if v.dtype != torch.float64 or v.dim() != 1 or v.device != dev:
         raise ValueError(f"csr_by_dvec_keep_na: v must be a 1-d float64 tensor on {dev}")
     v = v.contiguous()
-    L, code = int(v.numel()), C.c_int(_lib.MX_DV_OPS[op])
-    m, K, nnz = C.c_int(A.m), C.c_int(A.K), C.c_int64(A.nnz)
+    L, code = int(v.numel()), _lib.MX_DV_OPS[op]
+    m, K, nnz = A.m, A.K, A.nnz
     if L < 1 or (A.m % L and L > A.m * A.K):
         raise ValueError("csr_by_dvec_keep_na: v needs between 1 and nrow * ncol entries")
 
@@ -469,36 +451,36 @@ def csr_by_dvec_keep_na(A: DeviceCSR, v: torch.Tensor, op: str = "*"):
     if L <= A.m and A.m % L == 0:                                       # row-ruled
         ws = buf(lib.mxd_csr_by_dvec_na_rows_workspace_bytes(m))
         total = C.c_int64(0)
-        check(lib.mxd_csr_by_dvec_na_rows_count(m, K, nnz, _dp(A.indptr), _dp(v), C.c_int64(L), code, _dp(ws),
-                                                _dp(out_p), C.byref(total), _stream()))
+        check(lib.mxd_csr_by_dvec_na_rows_count(m, K, nnz, _dp(A.indptr), _dp(v), L, code, _dp(ws), _dp(out_p),
+                                                C.byref(total), _stream()))
         k = int(total.value)
         out_j, out_x = entries(k)
         if k:
-            check(lib.mxd_csr_by_dvec_na_rows_fill(m, K, nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v),
-                                                   C.c_int64(L), code, _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
+            check(lib.mxd_csr_by_dvec_na_rows_fill(m, K, nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v), L,
+                                                   code, _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
         return out_p, out_j[:k], out_x[:k]
-    sws = buf(lib.mxd_dvec_na_special_workspace_bytes(C.c_int64(L)))
+    sws = buf(lib.mxd_dvec_na_special_workspace_bytes(L))
     nsp, cand, new = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    check(lib.mxd_dvec_na_special(m, K, _dp(v), C.c_int64(L), code, _dp(sws), C.byref(nsp), C.byref(cand), _stream()))
+    check(lib.mxd_dvec_na_special(m, K, _dp(v), L, code, _dp(sws), C.byref(nsp), C.byref(cand), _stream()))
     if cand.value:
-        cws = buf(lib.mxd_dvec_na_cells_workspace_bytes(cand))
-        check(lib.mxd_dvec_na_cells_count(m, K, nnz, _dp(A.indptr), _dp(A.indices), C.c_int64(L), _dp(sws), nsp, cand,
+        cws = buf(lib.mxd_dvec_na_cells_workspace_bytes(cand.value))
+        check(lib.mxd_dvec_na_cells_count(m, K, nnz, _dp(A.indptr), _dp(A.indices), L, _dp(sws), nsp.value, cand.value,
                                           _dp(cws), C.byref(new), _stream()))
     n_new = int(new.value)
     _, ax = entries(A.nnz)
-    check(lib.mxd_csr_by_dvec(m, K, nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v), C.c_int64(L), code,
-                              C.c_int(1), _dp(ax), _stream()))
+    check(lib.mxd_csr_by_dvec(m, K, nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v), L, code, 1, _dp(ax),
+                              _stream()))
     if n_new == 0:
         return A.indptr, A.indices, ax[:A.nnz]
     ni, nx = entries(n_new)
     nj = torch.empty_like(ni)
-    check(lib.mxd_dvec_na_cells_fill(m, K, _dp(v), C.c_int64(L), code, _dp(sws), nsp, cand, _dp(cws), _dp(ni), _dp(nj),
+    check(lib.mxd_dvec_na_cells_fill(m, K, _dp(v), L, code, _dp(sws), nsp.value, cand.value, _dp(cws), _dp(ni), _dp(nj),
                                      _dp(nx), _stream()))
     B = coo_to_csr(ni[:n_new], nj[:n_new], nx[:n_new], A.m, A.K)
     k = A.nnz + n_new
     out_j, out_x = entries(k)
     check(lib.mxd_csr_join_disjoint(m, _dp(A.indptr), _dp(A.indices), _dp(ax), nnz, _dp(B.indptr), _dp(B.indices),
-                                    _dp(B.values), C.c_int64(n_new), _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
+                                    _dp(B.values), n_new, _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
     return out_p, out_j[:k], out_x[:k]
 
 

@@ -46,7 +46,7 @@ def _tcrossprod_csr_dense(X_csr_indptr, X_csr_indices, X_csr_values, Y_colmajor,
     Y = _dense(Y_colmajor, dtype)
     m, n, K = p.size - 1, Y.shape[0], Y.shape[1]
     out = np.empty((m, n), dtype=dtype, order="F")
-    check(fn(ptr(p), ptr(j), ptr(x), C.c_int(m), ptr(Y), C.c_int(n), C.c_int(K), C.c_int(int(nthreads)), ptr(out)))
+    check(fn(ptr(p), ptr(j), ptr(x), m, ptr(Y), n, K, int(nthreads), ptr(out)))
     return out
 
 
@@ -67,10 +67,9 @@ def _dense_times_sparse(X_colmajor, indptr, indices, values, nthreads, dtype, fn
     p, i, x = _i32(indptr), _i32(indices), _f64(values)
     nrows_X, ncols_X, nout = X.shape[0], X.shape[1], p.size - 1
     out = np.empty((nrows_X, nout), dtype=dtype, order="F")
-    args = [ptr(X), C.c_int(nrows_X), C.c_int(ncols_X), ptr(p), ptr(i), ptr(x), C.c_int(nout),
-            C.c_int(int(nthreads))]
+    args = [ptr(X), nrows_X, ncols_X, ptr(p), ptr(i), ptr(x), nout, int(nthreads)]
     if extra is not None:
-        args.append(C.c_int(int(extra)))
+        args.append(int(extra))
     args.append(ptr(out))
     check(fn(*args))
     return out
@@ -106,7 +105,7 @@ def _dvec(X_csr_indptr, X_csr_indices, X_csr_values, y_dense, nthreads, ydt, odt
     y = np.ascontiguousarray(y_dense, dtype=ydt)
     m = p.size - 1
     out = np.empty(m, dtype=odt)
-    check(fn(ptr(p), ptr(j), ptr(x), C.c_int(m), ptr(y), C.c_int(y.size), C.c_int(int(nthreads)), ptr(out)))
+    check(fn(ptr(p), ptr(j), ptr(x), m, ptr(y), y.size, int(nthreads), ptr(out)))
     return out
 
 
@@ -153,6 +152,14 @@ def _finish(res, info, alias_from=None, empty_values_dtype=np.float64):
     return dict(indptr=indptr, indices=indices, values=values)
 
 
+def _begin(fn, *args, finish=_finish, **finish_kw):
+    """One *_begin export: fn(*args, &result handle, &info), then `finish` copies the result out and releases the
+    handle.  Returns (what `finish` returned, info)."""
+    res, info = C.c_void_p(), ResultInfo()
+    check(fn(*args, C.byref(res), C.byref(info)))
+    return finish(res, info, **finish_kw), info
+
+
 def _same(a, b):
     return a is b
 
@@ -166,12 +173,8 @@ def _elemwise(op, indptr1, indptr2, indices1, indices2, values1, values2, vdt):
     j2 = j1 if _same(indices1, indices2) else _i32(indices2)
     v1 = np.ascontiguousarray(values1, dtype=vdt)
     v2 = v1 if _same(values1, values2) else np.ascontiguousarray(values2, dtype=vdt)
-    res = C.c_void_p()
-    info = ResultInfo()
-    check(lib.mx_csr_elemwise_begin(C.c_int(op), C.c_int(p1.size - 1), ptr(p1), ptr(p2), ptr(j1), ptr(j2),
-                                    ptr(v1), ptr(v2), C.c_int64(j1.size), C.c_int64(j2.size),
-                                    C.byref(res), C.byref(info)))
-    return _finish(res, info, alias_from=(indptr1, indices1))
+    return _begin(lib.mx_csr_elemwise_begin, op, p1.size - 1, ptr(p1), ptr(p2), ptr(j1), ptr(j2), ptr(v1), ptr(v2),
+                  j1.size, j2.size, alias_from=(indptr1, indices1))[0]
 
 
 def multiply_csr_elemwise(indptr1, indptr2, indices1, indices2, values1, values2):
@@ -200,12 +203,9 @@ def _copy_rows(indptr, indices, values, rows_take, value_dtype, vdt):
     lib = _lib.load()
     p, j, rows = _i32(indptr), _i32(indices), _i32(rows_take)
     v = None if values is None else np.ascontiguousarray(values, dtype=vdt)
-    res = C.c_void_p()
-    info = ResultInfo()
-    check(lib.mx_copy_csr_rows_begin(ptr(p), C.c_int(p.size - 1), ptr(j), ptr(v), C.c_int(value_dtype),
-                                     C.c_int64(0 if v is None else v.size), ptr(rows), C.c_int64(rows.size),
-                                     C.byref(res), C.byref(info)))
-    return _finish(res, info, empty_values_dtype=vdt if vdt is not None else np.float64)
+    return _begin(lib.mx_copy_csr_rows_begin, ptr(p), p.size - 1, ptr(j), ptr(v), value_dtype,
+                  0 if v is None else v.size, ptr(rows), rows.size,
+                  empty_values_dtype=vdt if vdt is not None else np.float64)[0]
 
 
 def copy_csr_rows_numeric(indptr, indices, values, rows_take):
@@ -228,13 +228,9 @@ def _col_seq(indptr, indices, values, rows_take, cols_take, index1, value_dtype,
     lib = _lib.load()
     p, j, rows, cols = _i32(indptr), _i32(indices), _i32(rows_take), _i32(cols_take)
     v = None if values is None else np.ascontiguousarray(values, dtype=vdt)
-    res = C.c_void_p()
-    info = ResultInfo()
-    check(lib.mx_copy_csr_rows_col_seq_begin(ptr(p), C.c_int(p.size - 1), ptr(j), ptr(v), C.c_int(value_dtype),
-                                             C.c_int64(0 if v is None else v.size), ptr(rows), C.c_int64(rows.size),
-                                             ptr(cols), C.c_int64(cols.size), C.c_int(int(bool(index1))),
-                                             C.byref(res), C.byref(info)))
-    return _finish(res, info)          # values are always a numeric (float64) vector, slice.cpp:363
+    # values are always a numeric (float64) vector, slice.cpp:363
+    return _begin(lib.mx_copy_csr_rows_col_seq_begin, ptr(p), p.size - 1, ptr(j), ptr(v), value_dtype,
+                  0 if v is None else v.size, ptr(rows), rows.size, ptr(cols), cols.size, int(bool(index1)))[0]
 
 
 def copy_csr_rows_col_seq_numeric(indptr, indices, values, rows_take, cols_take, index1):
@@ -256,12 +252,9 @@ def _arbitrary(indptr, indices, values, rows_take, cols_take, value_dtype, vdt):
     lib = _lib.load()
     p, j, rows, cols = _i32(indptr), _i32(indices), _i32(rows_take), _i32(cols_take)
     v = None if values is None else np.ascontiguousarray(values, dtype=vdt)
-    res = C.c_void_p()
-    info = ResultInfo()
-    check(lib.mx_copy_csr_arbitrary_begin(ptr(p), C.c_int(p.size - 1), ptr(j), ptr(v), C.c_int(value_dtype),
-                                          C.c_int64(0 if v is None else v.size), ptr(rows), C.c_int64(rows.size),
-                                          ptr(cols), C.c_int64(cols.size), C.byref(res), C.byref(info)))
-    out = _finish(res, info, empty_values_dtype=vdt if vdt is not None else np.float64)
+    out, info = _begin(lib.mx_copy_csr_arbitrary_begin, ptr(p), p.size - 1, ptr(j), ptr(v), value_dtype,
+                       0 if v is None else v.size, ptr(rows), rows.size, ptr(cols), cols.size,
+                       empty_values_dtype=vdt if vdt is not None else np.float64)
     if info.values_dtype == MX_NONE:
         del out["values"]              # the reference's list has no `values` element then (slice.cpp:565)
     return out
@@ -286,11 +279,8 @@ def _reverse_rows(indptr, indices, values, value_dtype, vdt):
     lib = _lib.load()
     p, j = _i32(indptr), _i32(indices)
     v = None if values is None else np.ascontiguousarray(values, dtype=vdt)
-    res = C.c_void_p()
-    info = ResultInfo()
-    check(lib.mx_reverse_rows_begin(ptr(p), C.c_int(p.size - 1), ptr(j), ptr(v), C.c_int(value_dtype),
-                                    C.c_int64(0 if v is None else v.size), C.byref(res), C.byref(info)))
-    return _finish(res, info, empty_values_dtype=vdt if vdt is not None else np.float64)
+    return _begin(lib.mx_reverse_rows_begin, ptr(p), p.size - 1, ptr(j), ptr(v), value_dtype,
+                  0 if v is None else v.size, empty_values_dtype=vdt if vdt is not None else np.float64)[0]
 
 
 def reverse_rows_numeric(indptr, indices, values):
@@ -312,9 +302,8 @@ def _reverse_columns_inplace(indptr, indices, values, ncol, value_dtype):
     p = _i32(indptr)
     if not (isinstance(indices, np.ndarray) and indices.dtype == np.int32 and indices.flags.c_contiguous):
         raise TypeError("indices must be a contiguous int32 numpy array (modified in place)")
-    check(_lib.load().mx_reverse_columns_inplace(ptr(p), C.c_int(p.size - 1), ptr(indices), ptr(values),
-                                                 C.c_int(value_dtype), C.c_int64(0 if values is None else values.size),
-                                                 C.c_int(int(ncol))))
+    check(_lib.load().mx_reverse_columns_inplace(ptr(p), p.size - 1, ptr(indices), ptr(values), value_dtype,
+                                                 0 if values is None else values.size, int(ncol)))
 
 
 def reverse_columns_inplace_numeric(indptr, indices, values, ncol):
@@ -343,8 +332,8 @@ def _svec(kind, X_csr_indptr, X_csr_indices, X_csr_values, y_indices_base1, y_va
     elif kind == 4:
         yv = np.ascontiguousarray(y_values, dtype=np.float32)
     out = np.empty(p.size - 1, dtype=np.float64)
-    check(_lib.load().mx_matmul_csr_svec(ptr(p), ptr(j), ptr(x), C.c_int(p.size - 1), ptr(yi), C.c_int64(yi.size),
-                                         ptr(yv), C.c_int(kind), C.c_int(int(nthreads)), ptr(out)))
+    check(_lib.load().mx_matmul_csr_svec(ptr(p), ptr(j), ptr(x), p.size - 1, ptr(yi), yi.size, ptr(yv), kind,
+                                         int(nthreads), ptr(out)))
     return out
 
 
@@ -381,8 +370,8 @@ def _csr_by_dense(kind, indptr, indices, values, dense_mat):
         raise ValueError("dense operand must have as many rows as the sparse one")
     xv = np.ascontiguousarray(values, dtype=np.int32 if kind == 4 else np.float64)
     out = np.empty(xv.size, dtype=xv.dtype)
-    check(_lib.load().mx_multiply_csr_by_dense_elemwise(ptr(p), ptr(j), ptr(xv), C.c_int(p.size - 1), ptr(D),
-                                                        C.c_int64(D.shape[1]), C.c_int(kind), ptr(out)))
+    check(_lib.load().mx_multiply_csr_by_dense_elemwise(ptr(p), ptr(j), ptr(xv), p.size - 1, ptr(D), D.shape[1], kind,
+                                                        ptr(out)))
     return out
 
 
@@ -429,15 +418,13 @@ def _csc_dense_args(kind, indptr, indices, values, dense_):
 def _csc_by_dense_ignore(fn, kind, indptr, indices, values, dense_):
     p, i, xv, D = _csc_dense_args(kind, indptr, indices, values, dense_)
     out = np.empty(xv.size, dtype=xv.dtype)
-    check(fn(ptr(p), C.c_int(p.size - 1), ptr(i), ptr(xv), ptr(D), C.c_int(D.shape[0]), ptr(out)))
+    check(fn(ptr(p), p.size - 1, ptr(i), ptr(xv), ptr(D), D.shape[0], ptr(out)))
     return out
 
 
 def _csc_by_dense_keep(fn, kind, indptr, indices, values, dense_):
     p, i, xv, D = _csc_dense_args(kind, indptr, indices, values, dense_)
-    res, info = C.c_void_p(), ResultInfo()
-    check(fn(ptr(p), C.c_int(p.size - 1), ptr(i), ptr(xv), ptr(D), C.c_int(D.shape[0]), C.byref(res), C.byref(info)))
-    return _finish(res, info)
+    return _begin(fn, ptr(p), p.size - 1, ptr(i), ptr(xv), ptr(D), D.shape[0])[0]
 
 
 def multiply_csc_by_dense_ignore_NAs_numeric(indptr, indices, values, dense_):
@@ -501,12 +488,8 @@ def _cbind(Xp, Xj, Xx, Yp, Yj_plus_ncol, Yx, value_dtype, vdt):
     Xp, Xj, Yp, Yj = _i32(Xp), _i32(Xj), _i32(Yp), _i32(Yj_plus_ncol)
     xv = None if Xx is None else np.ascontiguousarray(Xx, dtype=vdt)
     yv = None if Yx is None else np.ascontiguousarray(Yx, dtype=vdt)
-    res = C.c_void_p()
-    info = ResultInfo()
-    check(lib.mx_cbind_csr_begin(ptr(Xp), C.c_int(Xp.size - 1), ptr(Xj), ptr(xv), C.c_int64(0 if xv is None else xv.size),
-                                 ptr(Yp), C.c_int(Yp.size - 1), ptr(Yj), ptr(yv), C.c_int64(0 if yv is None else yv.size),
-                                 C.c_int(value_dtype), C.byref(res), C.byref(info)))
-    return _finish(res, info)
+    return _begin(lib.mx_cbind_csr_begin, ptr(Xp), Xp.size - 1, ptr(Xj), ptr(xv), 0 if xv is None else xv.size,
+                  ptr(Yp), Yp.size - 1, ptr(Yj), ptr(yv), 0 if yv is None else yv.size, value_dtype)[0]
 
 
 def cbind_csr_numeric(X_csr_indptr, X_csr_indices, X_csr_values, Y_csr_indptr, Y_csr_indices_plus_ncol, Y_csr_values):
@@ -526,9 +509,7 @@ def cbind_csr_binary(X_csr_indptr, X_csr_indices, Y_csr_indptr, Y_csr_indices_pl
     return _cbind(X_csr_indptr, X_csr_indices, None, Y_csr_indptr, Y_csr_indices_plus_ncol, None, MX_NONE, None)
 
 
-class _RbindInput(C.Structure):
-    _fields_ = [("kind", C.c_int), ("indptr", C.c_void_p), ("indices", C.c_void_p), ("values", C.c_void_p),
-                ("nrows", C.c_int), ("nnz", C.c_int64)]
+_RbindInput = _lib.RbindInput      # mx_rbind_input, as include/mxgpu.h declares it
 
 
 def concat_csr_batch(objects, out_kind):
@@ -544,10 +525,7 @@ def concat_csr_batch(objects, out_kind):
         keep += [jj, pp, xx]
         arr[k] = _RbindInput(kind, None if pp is None else pp.ctypes.data, jj.ctypes.data,
                              None if xx is None else xx.ctypes.data, int(nr), jj.size)
-    res = C.c_void_p()
-    info = ResultInfo()
-    check(lib.mx_concat_csr_batch_begin(arr, C.c_int(len(objects)), C.c_int(out_kind), C.byref(res), C.byref(info)))
-    out = _finish(res, info)
+    out = _begin(lib.mx_concat_csr_batch_begin, arr, len(objects), out_kind)[0]
     if out_kind == 2:
         out["values"] = None
     return out
@@ -557,7 +535,7 @@ def check_is_seq(indices) -> bool:
     """src/slice.cpp:25-35."""
     a = _i32(indices)
     r = C.c_int(0)
-    check(_lib.load().mx_check_is_seq(ptr(a), C.c_int64(a.size), C.byref(r)))
+    check(_lib.load().mx_check_is_seq(ptr(a), a.size, C.byref(r)))
     return bool(r.value)
 
 
@@ -565,7 +543,7 @@ def check_is_rev_seq(indices) -> bool:
     """src/slice.cpp:37-47."""
     a = _i32(indices)
     r = C.c_int(0)
-    check(_lib.load().mx_check_is_rev_seq(ptr(a), C.c_int64(a.size), C.byref(r)))
+    check(_lib.load().mx_check_is_rev_seq(ptr(a), a.size, C.byref(r)))
     return bool(r.value)
 
 
@@ -574,7 +552,7 @@ def check_indices_are_sorted(indptr, indices) -> bool:
     """Per-row check_is_sorted, src/misc.cpp:118-128."""
     p, j = _i32(indptr), _i32(indices)
     r = C.c_int(0)
-    check(_lib.load().mx_check_indices_are_sorted(ptr(p), ptr(j), C.c_int(p.size - 1), C.byref(r)))
+    check(_lib.load().mx_check_indices_are_sorted(ptr(p), ptr(j), p.size - 1, C.byref(r)))
     return bool(r.value)
 
 
@@ -592,7 +570,7 @@ def sort_sparse_indices_inplace(indptr, indices, values=None):
         vd = MX_LGL
     else:
         raise TypeError("values must be float64 or int32 (R logical)")
-    check(_lib.load().mx_sort_sparse_indices(ptr(p), ptr(indices), ptr(values), C.c_int(vd), C.c_int(p.size - 1)))
+    check(_lib.load().mx_sort_sparse_indices(ptr(p), ptr(indices), ptr(values), vd, p.size - 1))
 
 
 def _sort_vector(ii, xx, vd, vdt):
@@ -603,8 +581,7 @@ def _sort_vector(ii, xx, vd, vdt):
             raise TypeError(f"xx must be a contiguous {np.dtype(vdt).name} numpy array (sorted in place)")
         if xx.size != ii.size:
             raise ValueError("ii and xx have different lengths")
-    check(_lib.load().mx_sort_vector_indices(ptr(ii), None if vdt is None else ptr(xx), C.c_int64(ii.size),
-                                             C.c_int(vd)))
+    check(_lib.load().mx_sort_vector_indices(ptr(ii), None if vdt is None else ptr(xx), ii.size, vd))
 
 
 def sort_vector_indices_numeric(ii, xx):
@@ -634,11 +611,8 @@ def _csr_by_svec(indptr, indices, values, ii_base1, xx, ncols, length, keep_NAs)
         raise ValueError("indices and values have different lengths")
     if vx is not None and vx.size != vi.size:
         raise ValueError("ii and xx have different lengths")
-    res, info = C.c_void_p(), ResultInfo()
-    check(_lib.load().mx_multiply_csr_by_svec_begin(ptr(p), C.c_int(p.size - 1), ptr(j), ptr(x), ptr(vi), ptr(vx),
-                                                    C.c_int64(vi.size), C.c_int(int(ncols)), C.c_int(int(length)),
-                                                    C.c_int(int(bool(keep_NAs))), C.byref(res), C.byref(info)))
-    return _finish(res, info)
+    return _begin(_lib.load().mx_multiply_csr_by_svec_begin, ptr(p), p.size - 1, ptr(j), ptr(x), ptr(vi), ptr(vx),
+                  vi.size, int(ncols), int(length), int(bool(keep_NAs)))[0]
 
 
 def multiply_csr_by_svec_no_NAs(indptr, indices, values, ii_base1, xx, length):
@@ -661,9 +635,8 @@ def multiply_csr_by_dvec_no_NAs_numeric(indptr, indices, values, dvec, ncols, mu
     dv = np.ascontiguousarray(dvec, dtype=np.float64).reshape(-1)
     out = np.empty(xv.size, dtype=np.float64)
     check(_lib.load().mx_multiply_csr_by_dvec_no_NAs_numeric(
-        ptr(p), ptr(j), ptr(xv), C.c_int(p.size - 1), ptr(dv), C.c_int64(dv.size), C.c_int(int(ncols)),
-        C.c_int(bool(multiply)), C.c_int(bool(powerto)), C.c_int(bool(divide)), C.c_int(bool(divrest)),
-        C.c_int(bool(intdiv)), C.c_int(bool(X_is_LHS)), ptr(out)))
+        ptr(p), ptr(j), ptr(xv), p.size - 1, ptr(dv), dv.size, int(ncols), bool(multiply), bool(powerto), bool(divide),
+        bool(divrest), bool(intdiv), bool(X_is_LHS), ptr(out)))
     return out
 
 
@@ -676,12 +649,9 @@ def multiply_csr_by_dvec_with_NAs(indptr, indices, values, dvec, ncols, multiply
     dv = np.ascontiguousarray(dvec, dtype=np.float64).reshape(-1)
     if x.size != j.size:
         raise ValueError("indices and values have different lengths")
-    res, info = C.c_void_p(), ResultInfo()
-    check(_lib.load().mx_multiply_csr_by_dvec_with_NAs_begin(
-        ptr(p), ptr(j), ptr(x), C.c_int(p.size - 1), ptr(dv), C.c_int64(dv.size), C.c_int(int(ncols)),
-        C.c_int(bool(multiply)), C.c_int(bool(powerto)), C.c_int(bool(divide)), C.c_int(bool(divrest)),
-        C.c_int(bool(intdiv)), C.c_int(bool(X_is_LHS)), C.byref(res), C.byref(info)))
-    return _finish(res, info, alias_from=(indptr, indices))
+    return _begin(_lib.load().mx_multiply_csr_by_dvec_with_NAs_begin, ptr(p), ptr(j), ptr(x), p.size - 1, ptr(dv),
+                  dv.size, int(ncols), bool(multiply), bool(powerto), bool(divide), bool(divrest), bool(intdiv),
+                  bool(X_is_LHS), alias_from=(indptr, indices))[0]
 
 
 def logicaland_csr_by_dvec_internal(indptr, indices, values, dvec, ncols):
@@ -690,8 +660,8 @@ def logicaland_csr_by_dvec_internal(indptr, indices, values, dvec, ncols):
     xv = np.ascontiguousarray(values, dtype=np.int32)
     dv = np.ascontiguousarray(dvec, dtype=np.int32).reshape(-1)
     out = np.empty(xv.size, dtype=np.int32)
-    check(_lib.load().mx_logicaland_csr_by_dvec_internal(ptr(p), ptr(j), ptr(xv), C.c_int(p.size - 1), ptr(dv),
-                                                         C.c_int64(dv.size), C.c_int(int(ncols)), ptr(out)))
+    check(_lib.load().mx_logicaland_csr_by_dvec_internal(ptr(p), ptr(j), ptr(xv), p.size - 1, ptr(dv), dv.size,
+                                                         int(ncols), ptr(out)))
     return out
 
 
@@ -715,16 +685,10 @@ def csr_transpose(indptr, indices, values, ncol):
         else:
             raise TypeError(f"values must be float64 or int32 (R logical), got {v.dtype}")
         v = np.ascontiguousarray(v)
-    res = C.c_void_p()
-    info = ResultInfo()
-    check(lib.mx_csr_transpose_begin(ptr(p), C.c_int(p.size - 1), C.c_int(int(ncol)), ptr(j), ptr(v), C.c_int(vdt),
-                                     C.c_int64(0 if v is None else v.size), C.byref(res), C.byref(info)))
-    if v is None:
-        out = _finish(res, info)
-        out["values"] = None
-        return out
-    out = _finish(res, info, empty_values_dtype=v.dtype)
-    out["values"] = out["values"].astype(v.dtype, copy=False)     # no entries: an empty vector of the input's type
+    out = _begin(lib.mx_csr_transpose_begin, ptr(p), p.size - 1, int(ncol), ptr(j), ptr(v), vdt,
+                 0 if v is None else v.size, empty_values_dtype=np.float64 if v is None else v.dtype)[0]
+    # no entries: an empty vector of the input's type
+    out["values"] = None if v is None else out["values"].astype(v.dtype, copy=False)
     return out
 
 
@@ -753,16 +717,9 @@ def coo_to_csr(i, j, values, nrow, ncol):
     v, vdt = _values_kind(values)
     if v is not None and v.size != ri.size:
         raise ValueError("values and indices have different number of entries")
-    res = C.c_void_p()
-    info = ResultInfo()
-    check(lib.mx_coo_to_csr_begin(ptr(ri), ptr(cj), ptr(v), C.c_int(vdt), C.c_int64(ri.size), C.c_int(int(nrow)),
-                                  C.c_int(int(ncol)), C.byref(res), C.byref(info)))
-    if v is None:
-        out = _finish(res, info)
-        out["values"] = None
-        return out
-    out = _finish(res, info, empty_values_dtype=v.dtype)
-    out["values"] = out["values"].astype(v.dtype, copy=False)
+    out = _begin(lib.mx_coo_to_csr_begin, ptr(ri), ptr(cj), ptr(v), vdt, ri.size, int(nrow), int(ncol),
+                 empty_values_dtype=np.float64 if v is None else v.dtype)[0]
+    out["values"] = None if v is None else out["values"].astype(v.dtype, copy=False)
     return out
 
 
@@ -771,7 +728,7 @@ def csr_to_coo(indptr):
     adds (R/conversions.R:515-590)."""
     p = _i32(indptr)
     out = np.empty(int(p[-1]) if p.size else 0, dtype=np.int32)
-    check(_lib.load().mx_csr_to_coo(ptr(p), C.c_int(p.size - 1), ptr(out)))
+    check(_lib.load().mx_csr_to_coo(ptr(p), p.size - 1, ptr(out)))
     return out
 
 
@@ -787,12 +744,8 @@ def _csr_by_coo(logical, X_csr_indptr, X_csr_indices, X_csr_values, Y_coo_row, Y
         raise ValueError("COO row, column and value vectors have different lengths")
     if p.size != int(max_row_X) + 1:
         raise ValueError("X_csr_indptr must have max_row_X + 1 entries")
-    res = C.c_void_p()
-    info = ResultInfo()
-    check(lib.mx_multiply_csr_by_coo_begin(C.c_int(int(bool(logical))), ptr(p), ptr(xj), ptr(xv), ptr(yi), ptr(yj),
-                                           ptr(yv), C.c_int64(yi.size), C.c_int(int(max_row_X)),
-                                           C.c_int(int(max_col_X)), C.byref(res), C.byref(info)))
-    out = _finish(res, info, empty_values_dtype=vdt)
+    out = _begin(lib.mx_multiply_csr_by_coo_begin, int(bool(logical)), ptr(p), ptr(xj), ptr(xv), ptr(yi), ptr(yj),
+                 ptr(yv), yi.size, int(max_row_X), int(max_col_X), empty_values_dtype=vdt)[0]
     return dict(row=out["indptr"], col=out["indices"], val=out["values"].astype(vdt, copy=False))
 
 
@@ -818,9 +771,8 @@ def multiply_coo_by_dense_ignore_NAs_numeric(ii, jj, xx, dvec, nrows, ncols, mul
     dv = np.ascontiguousarray(dvec, dtype=np.float64).reshape(-1)
     out = np.empty(xv.size, dtype=np.float64)
     check(_lib.load().mx_multiply_coo_by_dense_ignore_NAs_numeric(
-        ptr(i), ptr(j), ptr(xv), C.c_int64(xv.size), ptr(dv), C.c_int64(dv.size), C.c_int(int(nrows)),
-        C.c_int(int(ncols)), C.c_int(bool(multiply)), C.c_int(bool(powerto)), C.c_int(bool(divide)),
-        C.c_int(bool(divrest)), C.c_int(bool(intdiv)), C.c_int(bool(X_is_LHS)), ptr(out)))
+        ptr(i), ptr(j), ptr(xv), xv.size, ptr(dv), dv.size, int(nrows), int(ncols), bool(multiply), bool(powerto),
+        bool(divide), bool(divrest), bool(intdiv), bool(X_is_LHS), ptr(out)))
     return out
 
 
@@ -831,8 +783,7 @@ def multiply_coo_by_dense_ignore_NAs_logical(ii, jj, xx, dvec, nrows, ncols):
     dv = np.ascontiguousarray(dvec, dtype=np.int32).reshape(-1)
     out = np.empty(xv.size, dtype=np.int32)
     check(_lib.load().mx_multiply_coo_by_dense_ignore_NAs_logical(
-        ptr(i), ptr(j), ptr(xv), C.c_int64(xv.size), ptr(dv), C.c_int64(dv.size), C.c_int(int(nrows)),
-        C.c_int(int(ncols)), ptr(out)))
+        ptr(i), ptr(j), ptr(xv), xv.size, ptr(dv), dv.size, int(nrows), int(ncols), ptr(out)))
     return out
 
 
@@ -849,14 +800,10 @@ def _slice_coo_arbitrary(ii, jj, xx, vdt, rows_take_base1, cols_take_base1, all_
         if v.size != i.size:
             raise ValueError("values and indices have different number of entries")
     rt, ct = _i32(rows_take_base1).reshape(-1), _i32(cols_take_base1).reshape(-1)
-    res = C.c_void_p()
-    info = ResultInfo()
-    check(lib.mx_slice_coo_arbitrary_begin(
-        ptr(i), ptr(j), ptr(v), C.c_int(vdt), C.c_int64(i.size), ptr(rt), C.c_int64(rt.size), ptr(ct),
-        C.c_int64(ct.size), C.c_int(bool(all_i)), C.c_int(bool(all_j)), C.c_int(bool(i_is_seq)),
-        C.c_int(bool(j_is_seq)), C.c_int(bool(i_is_rev_seq)), C.c_int(bool(j_is_rev_seq)), C.c_int(int(nrows)),
-        C.c_int(int(ncols)), C.byref(res), C.byref(info)))
-    out = _finish(res, info, empty_values_dtype=np.float64 if v is None else v.dtype)
+    out = _begin(lib.mx_slice_coo_arbitrary_begin, ptr(i), ptr(j), ptr(v), vdt, i.size, ptr(rt), rt.size, ptr(ct),
+                 ct.size, bool(all_i), bool(all_j), bool(i_is_seq), bool(j_is_seq), bool(i_is_rev_seq),
+                 bool(j_is_rev_seq), int(nrows), int(ncols),
+                 empty_values_dtype=np.float64 if v is None else v.dtype)[0]
     xx_out = None if v is None else out["values"].astype(v.dtype, copy=False)
     return dict(ii=out["indptr"], jj=out["indices"], xx=xx_out)
 
@@ -896,8 +843,7 @@ def _slice_coo_single(ii, jj, xx, vdt, i, j):
     if v is not None and v.size != i_.size:
         raise ValueError("values and indices have different number of entries")
     found = C.c_int(0)
-    check(_lib.load().mx_slice_coo_single(ptr(i_), ptr(j_), ptr(v), C.c_int(vdt), C.c_int64(i_.size),
-                                          C.c_int(int(i)), C.c_int(int(j)), C.byref(found),
+    check(_lib.load().mx_slice_coo_single(ptr(i_), ptr(j_), ptr(v), vdt, i_.size, int(i), int(j), C.byref(found),
                                           None if val is None else C.byref(val)))
     return bool(found.value), (None if val is None else val.value)
 
@@ -938,10 +884,8 @@ def _remove_zeros_csr(fn, indptr, indices, values, remove_NAs, vdt):
     p, j, v = _i32(indptr), _i32(indices), np.ascontiguousarray(values, dtype=vdt)
     if j.size != v.size or p.size < 1:
         raise ValueError("indptr, indices and values do not form a CSR")
-    res, info = C.c_void_p(), ResultInfo()
-    check(fn(ptr(p), ptr(j), ptr(v), C.c_int(p.size - 1), C.c_int(int(bool(remove_NAs))), C.byref(res),
-             C.byref(info)))
-    a, b, c = _compacted(res, info, (indptr, indices, values), vdt)
+    a, b, c = _begin(fn, ptr(p), ptr(j), ptr(v), p.size - 1, int(bool(remove_NAs)), finish=_compacted,
+                     inputs=(indptr, indices, values), vdt=vdt)[0]
     return dict(indptr=a, indices=b, values=c)
 
 
@@ -961,9 +905,8 @@ def _remove_zeros_coo(fn, ii, jj, xx, remove_NAs, vdt):
     i, j, v = _i32(ii), _i32(jj), np.ascontiguousarray(xx, dtype=vdt)
     if not (i.size == j.size == v.size):
         raise ValueError("ii, jj and xx have different lengths")
-    res, info = C.c_void_p(), ResultInfo()
-    check(fn(ptr(i), ptr(j), ptr(v), C.c_int64(i.size), C.c_int(int(bool(remove_NAs))), C.byref(res), C.byref(info)))
-    a, b, c = _compacted(res, info, (ii, jj, xx), vdt)
+    a, b, c = _begin(fn, ptr(i), ptr(j), ptr(v), i.size, int(bool(remove_NAs)), finish=_compacted,
+                     inputs=(ii, jj, xx), vdt=vdt)[0]
     return dict(ii=a, jj=b, xx=c)
 
 
@@ -981,9 +924,8 @@ def _remove_zeros_svec(fn, ii, xx, remove_NAs, vdt):
     i, v = _i32(ii), np.ascontiguousarray(xx, dtype=vdt)
     if i.size != v.size:
         raise ValueError("ii and xx have different lengths")
-    res, info = C.c_void_p(), ResultInfo()
-    check(fn(ptr(i), ptr(v), C.c_int64(i.size), C.c_int(int(bool(remove_NAs))), C.byref(res), C.byref(info)))
-    _, b, c = _compacted(res, info, (None, ii, xx), vdt)
+    _, b, c = _begin(fn, ptr(i), ptr(v), i.size, int(bool(remove_NAs)), finish=_compacted,
+                     inputs=(None, ii, xx), vdt=vdt)[0]
     return dict(ii=b, xx=c)
 
 
@@ -1012,11 +954,8 @@ def _filter(layout, indptr, idx0, idx1, values, mask):
     if mk.size != i0.size or v.size != i0.size or (i1 is not None and i1.size != i0.size):
         raise ValueError("mask, indices and values have different lengths")
     p = None if indptr is None else _i32(indptr)
-    res, info = C.c_void_p(), ResultInfo()
-    check(_lib.load().mx_filter_sparse_begin(C.c_int(layout), ptr(p), C.c_int(0 if p is None else p.size - 1),
-                                             ptr(i0), ptr(i1), ptr(v), C.c_int(vd), C.c_int64(i0.size), ptr(mk),
-                                             C.byref(res), C.byref(info)))
-    return _compacted(res, info, None, v.dtype)
+    return _begin(_lib.load().mx_filter_sparse_begin, layout, ptr(p), 0 if p is None else p.size - 1, ptr(i0), ptr(i1),
+                  ptr(v), vd, i0.size, ptr(mk), finish=_compacted, inputs=None, vdt=v.dtype)[0]
 
 
 def filter_csr(indptr, indices, values, mask):
@@ -1036,7 +975,7 @@ def rebuild_indptr_after_filter(indptr, filter):
     """src/misc.cpp:1099-1116: the indptr after dropping the entries whose R-logical filter is FALSE (0)."""
     p, f = _i32(indptr), _i32(filter)
     out = np.empty(p.size, dtype=np.int32)
-    check(_lib.load().mx_rebuild_indptr_after_filter(ptr(p), C.c_int64(p.size), ptr(f), ptr(out)))
+    check(_lib.load().mx_rebuild_indptr_after_filter(ptr(p), p.size, ptr(f), ptr(out)))
     return out
 
 
@@ -1048,8 +987,7 @@ def check_valid_csr_matrix(indptr, indices, nrows, ncols):
     """src/misc.cpp:970-1017: {} when valid, else dict(err=<the reference's message of the first failing check>)."""
     p, j = _i32(indptr), _i32(indices)
     e = C.c_char_p()
-    check(_lib.load().mx_check_valid_csr_matrix(ptr(p), C.c_int64(p.size), ptr(j), C.c_int64(j.size),
-                                                C.c_int(int(nrows)), C.c_int(int(ncols)), C.byref(e)))
+    check(_lib.load().mx_check_valid_csr_matrix(ptr(p), p.size, ptr(j), j.size, int(nrows), int(ncols), C.byref(e)))
     return _err(e)
 
 
@@ -1059,8 +997,7 @@ def check_valid_coo_matrix(ii, jj, nrows, ncols):
     if i.size != j.size:
         raise ValueError("ii and jj have different lengths")
     e = C.c_char_p()
-    check(_lib.load().mx_check_valid_coo_matrix(ptr(i), ptr(j), C.c_int64(i.size), C.c_int(int(nrows)),
-                                                C.c_int(int(ncols)), C.byref(e)))
+    check(_lib.load().mx_check_valid_coo_matrix(ptr(i), ptr(j), i.size, int(nrows), int(ncols), C.byref(e)))
     return _err(e)
 
 
@@ -1068,5 +1005,5 @@ def check_valid_svec(ii, nrows):
     """src/misc.cpp:1069-1097 (the R caller passes the 1-based @i and the length)."""
     i = _i32(ii)
     e = C.c_char_p()
-    check(_lib.load().mx_check_valid_svec(ptr(i), C.c_int64(i.size), C.c_int(int(nrows)), C.byref(e)))
+    check(_lib.load().mx_check_valid_svec(ptr(i), i.size, int(nrows), C.byref(e)))
     return _err(e)

@@ -16,16 +16,16 @@ class Dev:
         self.host = None if arr is None else np.ascontiguousarray(arr)
         self.nbytes = int(nbytes if arr is None else self.host.nbytes)
         self.ptr = C.c_void_p()
-        check(lib.mx_dev_malloc(C.byref(self.ptr), C.c_size_t(max(self.nbytes, 16))))
+        check(lib.mx_dev_malloc(C.byref(self.ptr), max(self.nbytes, 16)))
         if self.host is not None and self.nbytes:
-            check(lib.mx_memcpy_h2d(self.ptr, C.c_void_p(self.host.ctypes.data), C.c_size_t(self.nbytes), None))
+            check(lib.mx_memcpy_h2d(self.ptr, C.c_void_p(self.host.ctypes.data), self.nbytes, None))
             check(lib.mx_stream_sync(None))
 
     def download(self, dtype, shape):
         lib = _lib.load()
         out = np.empty(shape, dtype=dtype)
         if out.nbytes:
-            check(lib.mx_memcpy_d2h(C.c_void_p(out.ctypes.data), self.ptr, C.c_size_t(out.nbytes), None))
+            check(lib.mx_memcpy_d2h(C.c_void_p(out.ctypes.data), self.ptr, out.nbytes, None))
             check(lib.mx_stream_sync(None))
         return out
 
@@ -43,10 +43,9 @@ def spmm_device(p, j, x, B_rowmajor, colmajor, algo, rows_sorted, npanels=0, wg_
     dt = _lib.MX_F64 if B_rowmajor.dtype == np.float64 else _lib.MX_F32
     dp, dj, dx, dB = Dev(p.astype(np.int32)), Dev(j.astype(np.int32)), Dev(x.astype(np.float64)), Dev(B_rowmajor)
     dC = Dev(nbytes=m * n * B_rowmajor.dtype.itemsize)
-    check(lib.mx_dev_memset(dC.ptr, 0xFF, C.c_size_t(dC.nbytes), None))      # poison: every element must be written
-    check(lib.mxd_spmm_csr_dense_ex(C.c_int(m), C.c_int(n), C.c_int(K), dp.ptr, dj.ptr, dx.ptr, dB.ptr, C.c_size_t(n),
-                                    dC.ptr, C.c_size_t(m if colmajor else n), C.c_int(dt), C.c_int(int(colmajor)),
-                                    C.c_int(algo), C.c_int(int(rows_sorted)), C.c_int(npanels), C.c_int(wg_per_cu), None))
+    check(lib.mx_dev_memset(dC.ptr, 0xFF, dC.nbytes, None))      # poison: every element must be written
+    check(lib.mxd_spmm_csr_dense_ex(m, n, K, dp.ptr, dj.ptr, dx.ptr, dB.ptr, n, dC.ptr, m if colmajor else n, dt,
+                                    int(colmajor), algo, int(rows_sorted), npanels, wg_per_cu, None))
     check(lib.mx_stream_sync(None))
     out = dC.download(B_rowmajor.dtype, (n, m) if colmajor else (m, n))
     return out.T if colmajor else out
@@ -59,12 +58,12 @@ def spmm_planned_device(p, j, x, B_rowmajor, colmajor, npanels=0, wg_per_cu=0, s
     dt = _lib.MX_F64 if B_rowmajor.dtype == np.float64 else _lib.MX_F32
     dp, dj, dx, dB = Dev(p.astype(np.int32)), Dev(j.astype(np.int32)), Dev(x.astype(np.float64)), Dev(B_rowmajor)
     dC = Dev(nbytes=m * n * B_rowmajor.dtype.itemsize)
-    check(lib.mx_dev_memset(dC.ptr, 0xFF, C.c_size_t(dC.nbytes), None))
+    check(lib.mx_dev_memset(dC.ptr, 0xFF, dC.nbytes, None))
     plan = C.c_void_p()
-    check(lib.mxd_spmm_plan_create(C.c_int(m), C.c_int(K), dp.ptr, dj.ptr, dx.ptr, C.c_int(npanels), None, C.byref(plan)))
+    check(lib.mxd_spmm_plan_create(m, K, dp.ptr, dj.ptr, dx.ptr, npanels, None, C.byref(plan)))
     try:
-        check(lib.mxd_spmm_plan_run(plan, C.c_int(n), dB.ptr, C.c_size_t(n), dC.ptr, C.c_size_t(m if colmajor else n),
-                                    C.c_int(dt), C.c_int(int(colmajor)), C.c_int(wg_per_cu), C.c_int(sync_mode), None))
+        check(lib.mxd_spmm_plan_run(plan, n, dB.ptr, n, dC.ptr, m if colmajor else n, dt, int(colmajor), wg_per_cu,
+                                    sync_mode, None))
         check(lib.mx_stream_sync(None))
     finally:
         lib.mxd_spmm_plan_destroy(plan)
@@ -144,8 +143,7 @@ def plan_create(A, npanels=0, plan=None):
     """mxd_spmm_plan_create; pass a previous plan to rebuild it in place (its buffers are re-used)."""
     lib = _lib.load()
     handle = plan if plan is not None else C.c_void_p()
-    check(lib.mxd_spmm_plan_create(C.c_int(A.m), C.c_int(A.K), A.dp.ptr, A.dj.ptr, A.dx.ptr, C.c_int(npanels), None,
-                                   C.byref(handle)))
+    check(lib.mxd_spmm_plan_create(A.m, A.K, A.dp.ptr, A.dj.ptr, A.dx.ptr, npanels, None, C.byref(handle)))
     return handle
 
 
@@ -164,13 +162,10 @@ def spmm_guarded(A, B, colmajor, algo=0, rows_sorted=False, npanels=0, wg_per_cu
     gB = Guarded(B.dtype, K, n, ldb, b_offset, data=B, pad=np.nan)
     gC = Guarded(B.dtype, n if colmajor else m, m if colmajor else n, ldc, c_offset)
     if plan is None:
-        rc = lib.mxd_spmm_csr_dense_ex(C.c_int(m), C.c_int(n), C.c_int(K), A.dp.ptr, A.dj.ptr, A.dx.ptr, gB.ptr,
-                                       C.c_size_t(ldb), gC.ptr, C.c_size_t(ldc), C.c_int(dt), C.c_int(int(colmajor)),
-                                       C.c_int(algo), C.c_int(int(rows_sorted)), C.c_int(npanels), C.c_int(wg_per_cu),
-                                       None)
+        rc = lib.mxd_spmm_csr_dense_ex(m, n, K, A.dp.ptr, A.dj.ptr, A.dx.ptr, gB.ptr, ldb, gC.ptr, ldc, dt,
+                                       int(colmajor), algo, int(rows_sorted), npanels, wg_per_cu, None)
     else:
-        rc = lib.mxd_spmm_plan_run(plan, C.c_int(n), gB.ptr, C.c_size_t(ldb), gC.ptr, C.c_size_t(ldc), C.c_int(dt),
-                                   C.c_int(int(colmajor)), C.c_int(wg_per_cu), C.c_int(sync_mode), None)
+        rc = lib.mxd_spmm_plan_run(plan, n, gB.ptr, ldb, gC.ptr, ldc, dt, int(colmajor), wg_per_cu, sync_mode, None)
     err = None if rc == 0 else lib.mx_last_error().decode("utf-8", "replace")
     check(lib.mx_stream_sync(None))
     gB.assert_untouched()
@@ -290,8 +285,7 @@ def dev_spmv(A, v, v_dtype, hint):
     lib = _lib.load()
     gv = GuardedVec(_VAL_DTYPE[v_dtype], data=v)
     gy = GuardedVec(np.float32 if v_dtype == _lib.MX_F32 else np.float64, n=A.m)
-    check(lib.mxd_spmv_csr_dvec(C.c_int(A.m), C.c_int64(hint), A.p.ptr, A.j.ptr, A.xptr, gv.ptr, C.c_int(v_dtype),
-                                gy.ptr, None))
+    check(lib.mxd_spmv_csr_dvec(A.m, hint, A.p.ptr, A.j.ptr, A.xptr, gv.ptr, v_dtype, gy.ptr, None))
     _sync()
     launch = last_row_launch()
     _untouched(A, gv)
@@ -306,15 +300,15 @@ def dev_merge(op, A, B, hint1, hint2):
     gws = GuardedVec(np.uint8, n=lib.mxd_merge_workspace_bytes(m))
     gp = GuardedVec(np.int32, n=m + 1)
     total = C.c_int64(-1)
-    check(lib.mxd_csr_merge_count(C.c_int(op), C.c_int(m), A.p.ptr, A.j.ptr, C.c_int64(hint1), B.p.ptr, B.j.ptr,
-                                  C.c_int64(hint2), gp.ptr, gws.ptr, C.byref(total), None))
+    check(lib.mxd_csr_merge_count(op, m, A.p.ptr, A.j.ptr, hint1, B.p.ptr, B.j.ptr, hint2, gp.ptr, gws.ptr,
+                                  C.byref(total), None))
     launches = [last_row_launch()]
     indptr = gp.result()
     gws._download()
     nout = int(total.value)
     gj, gx = GuardedVec(np.int32, n=nout + SLACK), GuardedVec(vdt, n=nout + SLACK)
-    check(lib.mxd_csr_merge_fill(C.c_int(op), C.c_int(m), A.p.ptr, A.j.ptr, A.xptr, C.c_int64(hint1), B.p.ptr, B.j.ptr,
-                                 B.xptr, C.c_int64(hint2), gp.ptr, gj.ptr, gx.ptr, None))
+    check(lib.mxd_csr_merge_fill(op, m, A.p.ptr, A.j.ptr, A.xptr, hint1, B.p.ptr, B.j.ptr, B.xptr, hint2, gp.ptr,
+                                 gj.ptr, gx.ptr, None))
     _sync()
     launches.append(last_row_launch())
     _untouched(A, B)
@@ -333,14 +327,14 @@ def dev_gather(A, rows, value_dtype, hint):
     r = int(rows.size)
     grows = GuardedVec(np.int32, data=rows)
     gws, gp, total = _count_outputs(r)
-    check(lib.mxd_csr_gather_count(C.c_int(r), A.p.ptr, grows.ptr, gp.ptr, gws.ptr, C.byref(total), None))
+    check(lib.mxd_csr_gather_count(r, A.p.ptr, grows.ptr, gp.ptr, gws.ptr, C.byref(total), None))
     indptr = gp.result()
     gws._download()
     nout = int(total.value)
     gj = GuardedVec(np.int32, n=nout + SLACK)
     gx = None if value_dtype == _lib.MX_NONE else GuardedVec(_VAL_DTYPE[value_dtype], n=nout + SLACK)
-    check(lib.mxd_csr_gather_fill(C.c_int(r), A.p.ptr, A.j.ptr, A.xptr, grows.ptr, gp.ptr, gj.ptr,
-                                  None if gx is None else gx.ptr, C.c_int(value_dtype), C.c_int64(hint), None))
+    check(lib.mxd_csr_gather_fill(r, A.p.ptr, A.j.ptr, A.xptr, grows.ptr, gp.ptr, gj.ptr,
+                                  None if gx is None else gx.ptr, value_dtype, hint, None))
     _sync()
     launch = last_row_launch()
     _untouched(A, grows)
@@ -354,17 +348,16 @@ def dev_colrange(A, rows, min_col, max_col, value_dtype, avg):
     r = int(rows.size)
     grows = GuardedVec(np.int32, data=rows)
     gws, gp, total = _count_outputs(r)
-    check(lib.mxd_csr_colrange_count(C.c_int(r), A.p.ptr, A.j.ptr, grows.ptr, C.c_int(min_col), C.c_int(max_col),
-                                     C.c_double(avg), gp.ptr, gws.ptr, C.byref(total), None))
+    check(lib.mxd_csr_colrange_count(r, A.p.ptr, A.j.ptr, grows.ptr, min_col, max_col, avg, gp.ptr, gws.ptr,
+                                     C.byref(total), None))
     launches = [last_row_launch()]
     indptr = gp.result()
     gws._download()
     nout = int(total.value)
     gj = GuardedVec(np.int32, n=nout + SLACK)
     gx = None if value_dtype == _lib.MX_NONE else GuardedVec(np.float64, n=nout + SLACK)
-    check(lib.mxd_csr_colrange_fill(C.c_int(r), A.p.ptr, A.j.ptr, A.xptr, C.c_int(value_dtype), grows.ptr,
-                                    C.c_int(min_col), C.c_int(max_col), C.c_double(avg), gp.ptr, gj.ptr,
-                                    None if gx is None else gx.ptr, None))
+    check(lib.mxd_csr_colrange_fill(r, A.p.ptr, A.j.ptr, A.xptr, value_dtype, grows.ptr, min_col, max_col, avg, gp.ptr,
+                                    gj.ptr, None if gx is None else gx.ptr, None))
     _sync()
     launches.append(last_row_launch())
     _untouched(A, grows)
@@ -380,22 +373,21 @@ def dev_colmap(A, rows, cols, value_dtype, avg):
     grows, gcols = GuardedVec(np.int32, data=rows), GuardedVec(np.int32, data=cols)
     gstart, gpos = GuardedVec(np.int32, n=ncol_map + 1), GuardedVec(np.int32, n=cols.size)
     gmws = GuardedVec(np.uint8, n=lib.mxd_colmap_workspace_bytes(ncol_map))
-    check(lib.mxd_colmap_build(gcols.ptr, C.c_int64(cols.size), C.c_int(ncol_map), gstart.ptr, gpos.ptr, gmws.ptr, None))
+    check(lib.mxd_colmap_build(gcols.ptr, cols.size, ncol_map, gstart.ptr, gpos.ptr, gmws.ptr, None))
     _sync()
     start, pos = gstart.result(), gpos.result()
     gmws._download()
     gws, gp, total = _count_outputs(r)
-    check(lib.mxd_csr_colmap_count(C.c_int(r), A.p.ptr, A.j.ptr, grows.ptr, C.c_int(ncol_map), gstart.ptr,
-                                   C.c_double(avg), gp.ptr, gws.ptr, C.byref(total), None))
+    check(lib.mxd_csr_colmap_count(r, A.p.ptr, A.j.ptr, grows.ptr, ncol_map, gstart.ptr, avg, gp.ptr, gws.ptr,
+                                   C.byref(total), None))
     launches = [last_row_launch()]
     indptr = gp.result()
     gws._download()
     nout = int(total.value)
     gj = GuardedVec(np.int32, n=nout + SLACK)
     gx = None if value_dtype == _lib.MX_NONE else GuardedVec(_VAL_DTYPE[value_dtype], n=nout + SLACK)
-    check(lib.mxd_csr_colmap_fill(C.c_int(r), A.p.ptr, A.j.ptr, A.xptr, C.c_int(value_dtype), grows.ptr,
-                                  C.c_int(ncol_map), gstart.ptr, gpos.ptr, C.c_double(avg), gp.ptr, gj.ptr,
-                                  None if gx is None else gx.ptr, None))
+    check(lib.mxd_csr_colmap_fill(r, A.p.ptr, A.j.ptr, A.xptr, value_dtype, grows.ptr, ncol_map, gstart.ptr, gpos.ptr,
+                                  avg, gp.ptr, gj.ptr, None if gx is None else gx.ptr, None))
     _sync()
     launches.append(last_row_launch())
     _untouched(A, grows, gcols)
@@ -410,8 +402,8 @@ def dev_cbind(X, Y, value_dtype, hint):
     nrows, nout = max(X.m, Y.m), X.nnz + Y.nnz
     gp, gj = GuardedVec(np.int32, n=nrows + 1), GuardedVec(np.int32, n=nout + SLACK)
     gx = None if value_dtype == _lib.MX_NONE else GuardedVec(_VAL_DTYPE[value_dtype], n=nout + SLACK)
-    check(lib.mxd_csr_cbind(C.c_int(X.m), C.c_int(Y.m), X.p.ptr, X.j.ptr, X.xptr, Y.p.ptr, Y.j.ptr, Y.xptr,
-                            C.c_int(value_dtype), C.c_int64(hint), gp.ptr, gj.ptr, None if gx is None else gx.ptr, None))
+    check(lib.mxd_csr_cbind(X.m, Y.m, X.p.ptr, X.j.ptr, X.xptr, Y.p.ptr, Y.j.ptr, Y.xptr, value_dtype, hint, gp.ptr,
+                            gj.ptr, None if gx is None else gx.ptr, None))
     _sync()
     launch = last_row_launch()
     _untouched(X, Y)
@@ -423,8 +415,8 @@ def dev_sort_rows(A, value_dtype):
     lib = _lib.load()
     gtj = GuardedVec(np.int32, n=A.nnz)
     gtx = None if value_dtype == _lib.MX_NONE else GuardedVec(_VAL_DTYPE[value_dtype], n=A.nnz)
-    check(lib.mxd_csr_sort_rows(C.c_int(A.m), C.c_int64(A.nnz), A.p.ptr, A.j.ptr, A.xptr, C.c_int(value_dtype),
-                                gtj.ptr, None if gtx is None else gtx.ptr, None))
+    check(lib.mxd_csr_sort_rows(A.m, A.nnz, A.p.ptr, A.j.ptr, A.xptr, value_dtype, gtj.ptr,
+                                None if gtx is None else gtx.ptr, None))
     _sync()
     launch = last_row_launch()
     A.p.assert_untouched()
@@ -437,9 +429,8 @@ def dev_sort_rows(A, value_dtype):
 def dev_reverse_columns(A, value_dtype, ncol, hint):
     """mxd_csr_reverse_columns, in place: (indices, values or None, launch)"""
     lib = _lib.load()
-    check(lib.mxd_csr_reverse_columns(C.c_int(A.m), C.c_int64(hint), A.p.ptr, A.j.ptr,
-                                      None if value_dtype == _lib.MX_NONE else A.xptr, C.c_int(value_dtype),
-                                      C.c_int(ncol), None))
+    check(lib.mxd_csr_reverse_columns(A.m, hint, A.p.ptr, A.j.ptr, None if value_dtype == _lib.MX_NONE else A.xptr,
+                                      value_dtype, ncol, None))
     _sync()
     launch = last_row_launch()
     A.p.assert_untouched()
@@ -452,8 +443,8 @@ def dev_spmv_svec(A, yi_base1, yv, kind, hint):
     gyi = GuardedVec(np.int32, data=yi_base1)
     gyv = None if yv is None else GuardedVec(np.asarray(yv).dtype, data=yv)
     gout = GuardedVec(np.float64, n=A.m)
-    check(lib.mxd_spmv_csr_svec(C.c_int(A.m), C.c_int64(hint), A.p.ptr, A.j.ptr, A.xptr, gyi.ptr,
-                                C.c_int(yi_base1.size), None if gyv is None else gyv.ptr, C.c_int(kind), gout.ptr, None))
+    check(lib.mxd_spmv_csr_svec(A.m, hint, A.p.ptr, A.j.ptr, A.xptr, gyi.ptr, yi_base1.size,
+                                None if gyv is None else gyv.ptr, kind, gout.ptr, None))
     _sync()
     launch = last_row_launch()
     _untouched(A, gyi, gyv)
@@ -465,8 +456,8 @@ def dev_by_dvec(A, ncols, dvec, op, x_is_lhs, hint):
     lib = _lib.load()
     gd = GuardedVec(np.asarray(dvec).dtype, data=dvec)
     gout = GuardedVec(gd.dtype, n=A.nnz + SLACK)
-    check(lib.mxd_csr_by_dvec(C.c_int(A.m), C.c_int(ncols), C.c_int64(hint), A.p.ptr, A.j.ptr, A.xptr, gd.ptr,
-                              C.c_int64(gd.n), C.c_int(op), C.c_int(int(x_is_lhs)), gout.ptr, None))
+    check(lib.mxd_csr_by_dvec(A.m, ncols, hint, A.p.ptr, A.j.ptr, A.xptr, gd.ptr, gd.n, op, int(x_is_lhs), gout.ptr,
+                              None))
     _sync()
     launch = last_row_launch()
     _untouched(A, gd)
@@ -483,17 +474,15 @@ def dev_by_svec(A, ncol, vi_base1, vx, length, keep_na):
     gws = GuardedVec(np.uint8, n=lib.mxd_csr_by_svec_workspace_bytes(m))
     gp = GuardedVec(np.int32, n=m + 1)
     total, x_na = C.c_int64(-1), C.c_int64(-1)
-    check(lib.mxd_csr_by_svec_count(C.c_int(m), C.c_int(ncol), C.c_int64(A.nnz), A.p.ptr, A.xptr, gvi.ptr,
-                                    C.c_int64(vi_base1.size), vxp, C.c_int(length), C.c_int(int(keep_na)), gws.ptr,
-                                    gp.ptr, C.byref(total), C.byref(x_na), None))
+    check(lib.mxd_csr_by_svec_count(m, ncol, A.nnz, A.p.ptr, A.xptr, gvi.ptr, vi_base1.size, vxp, length, int(keep_na),
+                                    gws.ptr, gp.ptr, C.byref(total), C.byref(x_na), None))
     launches = [last_row_launch()]
     indptr = gp.result()
     gws._download()
     nout = int(total.value)
     gj, gx = GuardedVec(np.int32, n=nout + SLACK), GuardedVec(np.float64, n=nout + SLACK)
-    check(lib.mxd_csr_by_svec_fill(C.c_int(m), C.c_int(ncol), C.c_int64(A.nnz), A.p.ptr, A.j.ptr, A.xptr, gvi.ptr,
-                                   C.c_int64(vi_base1.size), vxp, C.c_int(length), C.c_int(int(keep_na)), gws.ptr,
-                                   gp.ptr, gj.ptr, gx.ptr, None))
+    check(lib.mxd_csr_by_svec_fill(m, ncol, A.nnz, A.p.ptr, A.j.ptr, A.xptr, gvi.ptr, vi_base1.size, vxp, length,
+                                   int(keep_na), gws.ptr, gp.ptr, gj.ptr, gx.ptr, None))
     _sync()
     launches.append(last_row_launch())
     _untouched(A, gvi, gvx)
@@ -508,7 +497,7 @@ def dev_scan(counts):
     gc = GuardedVec(np.int32, data=counts)
     gout, gtotal = GuardedVec(np.int32, n=n + 1), GuardedVec(np.int64, n=1)
     gws = GuardedVec(np.uint8, n=lib.mxd_scan_workspace_bytes(n))
-    check(lib.mxd_exclusive_scan_i32(gc.ptr, C.c_int64(n), gout.ptr, gtotal.ptr, gws.ptr, None))
+    check(lib.mxd_exclusive_scan_i32(gc.ptr, n, gout.ptr, gtotal.ptr, gws.ptr, None))
     _sync()
     gc.assert_untouched()
     gws._download()

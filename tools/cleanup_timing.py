@@ -82,9 +82,8 @@ def main():
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def validate():
-        _lib.check(lib.mxd_validate_indices(C.c_void_p(A.indices.data_ptr()), C.c_int64(nnz), C.c_int(n),
-                                            C.c_void_p(A.indptr.data_ptr()), C.c_int64(m + 1), C.c_int64(m),
-                                            C.c_void_p(ws.data_ptr()), C.byref(flags), stream))
+        _lib.check(lib.mxd_validate_indices(C.c_void_p(A.indices.data_ptr()), nnz, n, C.c_void_p(A.indptr.data_ptr()),
+                                            m + 1, m, C.c_void_p(ws.data_ptr()), C.byref(flags), stream))
 
     med, best = timed(validate, a.warmup, a.iters)
     assert flags.value == 0

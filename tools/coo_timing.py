@@ -53,10 +53,10 @@ def time_one(name, i, j, x, m, n, warmup, iters):
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def run():
-        _lib.check(lib.mxd_coo_to_csr(C.c_int(m), C.c_int(n), C.c_void_p(di.data_ptr()), C.c_void_p(dj.data_ptr()),
-                                      C.c_void_p(dx.data_ptr()), C.c_int(_lib.MX_F64), C.c_int64(nnz),
-                                      C.c_void_p(op.data_ptr()), C.c_void_p(oj.data_ptr()), C.c_void_p(ox.data_ptr()),
-                                      C.c_void_p(ws.data_ptr()), C.byref(out_nnz), stream))
+        _lib.check(lib.mxd_coo_to_csr(m, n, C.c_void_p(di.data_ptr()), C.c_void_p(dj.data_ptr()),
+                                      C.c_void_p(dx.data_ptr()), _lib.MX_F64, nnz, C.c_void_p(op.data_ptr()),
+                                      C.c_void_p(oj.data_ptr()), C.c_void_p(ox.data_ptr()), C.c_void_p(ws.data_ptr()),
+                                      C.byref(out_nnz), stream))
 
     for _ in range(warmup):
         run()

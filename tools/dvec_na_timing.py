@@ -52,9 +52,8 @@ def report(name, t, **extra):
 
 def yardstick(A, v):
     out = torch.empty(max(A.nnz, 1), dtype=torch.float64, device=v.device)
-    _lib.check(_lib.load().mxd_csr_by_dvec(C.c_int(A.m), C.c_int(A.K), C.c_int64(A.nnz), D._dp(A.indptr),
-                                           D._dp(A.indices), D._dp(A.values), D._dp(v), C.c_int64(v.numel()),
-                                           C.c_int(_lib.MX_DV_OPS["/"]), C.c_int(1), D._dp(out), D._stream()))
+    _lib.check(_lib.load().mxd_csr_by_dvec(A.m, A.K, A.nnz, D._dp(A.indptr), D._dp(A.indices), D._dp(A.values),
+                                           D._dp(v), v.numel(), _lib.MX_DV_OPS["/"], 1, D._dp(out), D._stream()))
     return out, A.indices.clone()
 
 

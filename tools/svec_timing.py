@@ -73,9 +73,8 @@ def pair(A, rows, dvec):
     """gather of the stored rows, then the values-only product of the gathered rows with their values"""
     g = D.csr_gather_rows(A, rows)
     out = torch.empty(max(g.nnz, 1), dtype=torch.float64, device=rows.device)
-    _lib.check(_lib.load().mxd_csr_by_dvec(C.c_int(g.m), C.c_int(g.K), C.c_int64(g.nnz), D._dp(g.indptr),
-                                           D._dp(g.indices), D._dp(g.values), D._dp(dvec), C.c_int64(dvec.numel()),
-                                           C.c_int(0), C.c_int(1), D._dp(out), D._stream()))
+    _lib.check(_lib.load().mxd_csr_by_dvec(g.m, g.K, g.nnz, D._dp(g.indptr), D._dp(g.indices), D._dp(g.values),
+                                           D._dp(dvec), dvec.numel(), 0, 1, D._dp(out), D._stream()))
     return g, out
 
 

@@ -46,9 +46,8 @@ def time_one(name, p, j, x, n, warmup, iters):
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def run():
-        _lib.check(lib.mxd_csr_transpose(C.c_int(m), C.c_int(n), C.c_void_p(A.indptr.data_ptr()),
-                                         C.c_void_p(A.indices.data_ptr()), C.c_void_p(A.values.data_ptr()),
-                                         C.c_int(_lib.MX_F64), C.c_int64(nnz), C.c_void_p(op.data_ptr()),
+        _lib.check(lib.mxd_csr_transpose(m, n, C.c_void_p(A.indptr.data_ptr()), C.c_void_p(A.indices.data_ptr()),
+                                         C.c_void_p(A.values.data_ptr()), _lib.MX_F64, nnz, C.c_void_p(op.data_ptr()),
                                          C.c_void_p(oj.data_ptr()), C.c_void_p(ox.data_ptr()),
                                          C.c_void_p(ws.data_ptr()), C.byref(out_nnz), stream))
 
