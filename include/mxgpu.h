@@ -303,6 +303,17 @@ size_t mxd_sort_vector_indices_workspace_bytes(int64_t n);
 int mxd_sort_vector_indices(int32_t *ii, void *xx, int64_t n, int value_dtype, void *workspace,
                             int *was_sorted_host, void *stream);
 
+/* sort_sparse_indices of a TsparseMatrix (sort_coo_indices<T>, src/misc.cpp:387-457): the triplets
+ * ii[nnz], jj[nnz] (non-negative, below INT32_MAX) and their values xx[nnz] (MX_F64, MX_LGL, or MX_NONE with xx NULL)
+ * sorted by (ii, jj) in place.  The sort is stable: entries of one cell stay adjacent and in input order, one of the
+ * orders the reference's std::sort may give.  One reduction first: *was_sorted = 1 and nothing else is launched or
+ * written when the triplets are already non-decreasing; a negative index fails with all three arrays untouched.
+ * Otherwise the transpose's radix passes run on jj and then on ii, carrying the entry index through both, and the
+ * values are gathered once.  One synchronise (after the reduction).  workspace: mxd_coo_sort_workspace_bytes(nnz). */
+size_t mxd_coo_sort_workspace_bytes(int64_t nnz);
+int mxd_coo_sort(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int value_dtype, void *workspace, int *was_sorted,
+                 void *stream);
+
 /* CSR (op) dense vector with R's recycling (multiply_csr_by_dvec_no_NAs<>, src/operators.cpp:1604-2140): a
  * values-only transform, out[k] = values[k] op dvec[(row + col*m) mod dvec_len] (`recyle_pos`, :1478; the reference's
  * four length branches :1640,1773,1870,2033 all reduce to it).  op: R's * ^ / %% %/% on f64 values with the sparse
@@ -801,6 +812,11 @@ int mx_sort_sparse_indices(const int32_t *indptr, int32_t *indices, void *values
 /* sort_vector_indices_{numeric,integer,logical,binary}  src/misc.cpp:460-527 (R/utils.R:126-155): a sparse vector's
  * ii (and xx; MX_NONE with NULL for an nsparseVector) in host memory, sorted in place; left alone when sorted. */
 int mx_sort_vector_indices(int32_t *ii, void *xx, int64_t n, int value_dtype);
+/* sort_coo_indices_{numeric,logical,binary}  src/misc.cpp:387-457 (R/utils.R:85-124): a TsparseMatrix's ii, jj (and
+ * xx: MX_F64, MX_LGL, or MX_NONE with NULL for an ngTMatrix) in host memory, sorted by (ii, jj) in place through
+ * mxd_coo_sort.  The caller's arrays are written only on success and only when they were not already sorted; more
+ * than INT32_MAX entries fail before anything is allocated. */
+int mx_sort_coo_indices(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int value_dtype);
 /* multiply_csr_by_svec_no_NAs (keep_NAs = 0) and multiply_csr_by_svec_keep_NAs  src/operators.cpp:3426-3697,
  * through mxd_csr_by_svec_count / _fill: a new indptr (nrows + 1), indices and f64 values.  ii_base1 sorted, xx NULL
  * for an nsparseVector, length dividing nrows.  A result above INT32_MAX entries (dense-filled rows) fails before

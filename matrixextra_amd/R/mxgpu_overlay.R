@@ -59,7 +59,9 @@
     ## sparse-vector branch of sort_sparse_indices (R/utils.R:126-155), which sorts its arguments in place
     "multiply_csr_by_svec_no_NAs", "multiply_csr_by_svec_keep_NAs",
     "sort_vector_indices_numeric", "sort_vector_indices_integer", "sort_vector_indices_logical",
-    "sort_vector_indices_binary"
+    "sort_vector_indices_binary",
+    ## the TsparseMatrix branch of sort_sparse_indices (R/utils.R:85-124), in place as well
+    "sort_coo_indices_numeric", "sort_coo_indices_logical", "sort_coo_indices_binary"
 )
 
 mxgpu_enable <- function(shim_path, min_nnz = 0L) {

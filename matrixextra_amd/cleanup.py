@@ -10,7 +10,7 @@ import numpy as np
 
 from . import exports
 from .matrices import (MatrixExtraError, RsparseMatrix, TsparseMatrix, check_valid_matrix, dgCMatrix,
-                       sort_sparse_indices, stop)
+                       options, sort_sparse_indices, stop)
 from .operators import _as_logical
 
 _SPARSE = (RsparseMatrix, TsparseMatrix, dgCMatrix)
@@ -104,14 +104,15 @@ def _sort_csc(X, copy):
 def check_sparse_matrix(X, sort=True, remove_zeros=True):
     """R/utils.R:439-489: check_valid_matrix, the device index validation (the reference's message of the first
     failing check), remove_sparse_zeros, then the per-row device sort with copy = (nothing was removed).  A CSC is
-    checked with its ncol + 1 pointers and its row indices against nrow.  Sorting a COO is not on the accelerated
-    path: sort=True raises for a TsparseMatrix before any device call."""
+    checked with its ncol + 1 pointers and its row indices against nrow.  A COO is sorted (the device COO sort,
+    DESIGN.md §4.13) only under options["mxgpu.coo_sort_route"]; without it sort=True raises for a TsparseMatrix
+    before any device call."""
     if not isinstance(X, _SPARSE):
         stop("Function is only applicable to sparse matrices and sparse vectors.")
     check_valid_matrix(X)
     nrow, ncol = X.Dim
     if isinstance(X, TsparseMatrix):
-        if sort:
+        if sort and not options.get("mxgpu.coo_sort_route", False):
             stop(_COO_SORT)
         res = exports.check_valid_coo_matrix(X.i, X.j, nrow, ncol)
     elif isinstance(X, RsparseMatrix):
@@ -128,5 +129,5 @@ def check_sparse_matrix(X, sort=True, remove_zeros=True):
         X = remove_sparse_zeros(X)
     if sort:
         copy = nnz_before == nnz_of(X)
-        X = sort_sparse_indices(X, copy=copy) if isinstance(X, RsparseMatrix) else _sort_csc(X, copy)
+        X = _sort_csc(X, copy) if isinstance(X, dgCMatrix) else sort_sparse_indices(X, copy=copy)
     return X

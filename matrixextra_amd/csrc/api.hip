@@ -1487,4 +1487,31 @@ int mx_sort_vector_indices(int32_t *ii, void *xx, int64_t n, int value_dtype)
     return 0;
 }
 
+// sort_coo_indices_{numeric,logical,binary}  src/misc.cpp:387-457: sorts ii, jj (and xx) in place by (ii, jj)
+int mx_sort_coo_indices(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int value_dtype)
+{
+    MX_REQUIRE(nnz >= 0, "mx_sort_coo_indices: negative size");
+    MX_REQUIRE(nnz <= INT_MAX, "mx_sort_coo_indices: %lld entries exceed R's int32 index range", (long long)nnz);
+    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
+               "mx_sort_coo_indices: unsupported value dtype %d", value_dtype);
+    if (nnz == 0) return 0;
+    const size_t vb = value_dtype == MX_NONE ? 0 : dtype_bytes(value_dtype);
+    MX_REQUIRE(ii && jj && (!vb || xx), "mx_sort_coo_indices: bad arguments");
+    DevBuf di, dj, dx, ws;
+    if (di.upload(ii, sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (dj.upload(jj, sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (vb && dx.upload(xx, vb * (size_t)nnz)) return 1;
+    if (ws.alloc(mxd_coo_sort_workspace_bytes(nnz))) return 1;
+    int was_sorted = 1;
+    if (mxd_coo_sort(di.as<int32_t>(), dj.as<int32_t>(), vb ? dx.p : nullptr, nnz, value_dtype, ws.p, &was_sorted,
+                     nullptr))
+        return 1;
+    if (was_sorted) return 0;                  // nothing to do, inputs untouched
+    MX_HIP(hipStreamSynchronize(nullptr));     // a failed sort shows here, before any of the caller's arrays is written
+    if (mx::xfer_d2h(ii, di.p, sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (mx::xfer_d2h(jj, dj.p, sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (vb && mx::xfer_d2h(xx, dx.p, vb * (size_t)nnz)) return 1;
+    return 0;
+}
+
 }  // extern "C"

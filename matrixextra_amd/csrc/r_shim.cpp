@@ -834,6 +834,23 @@ SEXP _MatrixExtra_sort_vector_indices_integer(SEXP ii, SEXP xx) { return sort_sv
 SEXP _MatrixExtra_sort_vector_indices_logical(SEXP ii, SEXP xx) { return sort_svec(ii, xx, LGLSXP, MX_LGL); }
 SEXP _MatrixExtra_sort_vector_indices_binary(SEXP ii) { return sort_svec(ii, R_NilValue, NILSXP, MX_NONE); }
 
+// sort_coo_indices_*  (src/misc.cpp:430-457): the caller's triplets are sorted where they are, so no coercion
+static SEXP sort_coo(SEXP ii, SEXP jj, SEXP xx, int xtype, int dtype)
+{
+    if (TYPEOF(ii) != INTSXP || TYPEOF(jj) != INTSXP) Rf_error("sort_coo_indices: indices must be integer vectors");
+    if (XLENGTH(jj) != XLENGTH(ii)) Rf_error("sort_coo_indices: indices do not match");
+    void *xv = nullptr;
+    if (dtype != MX_NONE) {
+        if (TYPEOF(xx) != xtype || XLENGTH(xx) != XLENGTH(ii)) Rf_error("sort_coo_indices: values do not match");
+        xv = xtype == REALSXP ? (void *)REAL(xx) : (void *)LOGICAL(xx);
+    }
+    if (mx_sort_coo_indices(INTEGER(ii), INTEGER(jj), xv, (int64_t)XLENGTH(ii), dtype)) fail();
+    return R_NilValue;
+}
+SEXP _MatrixExtra_sort_coo_indices_numeric(SEXP ii, SEXP jj, SEXP xx) { return sort_coo(ii, jj, xx, REALSXP, MX_F64); }
+SEXP _MatrixExtra_sort_coo_indices_logical(SEXP ii, SEXP jj, SEXP xx) { return sort_coo(ii, jj, xx, LGLSXP, MX_LGL); }
+SEXP _MatrixExtra_sort_coo_indices_binary(SEXP ii, SEXP jj) { return sort_coo(ii, jj, R_NilValue, NILSXP, MX_NONE); }
+
 #define MX_ENTRY(name, n) {"_MatrixExtra_" #name, (DL_FUNC)&_MatrixExtra_##name, n}
 static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(matmul_dense_csc_numeric, 5), MX_ENTRY(matmul_dense_csc_float32, 5),
@@ -872,6 +889,7 @@ static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(multiply_csr_by_svec_no_NAs, 6), MX_ENTRY(multiply_csr_by_svec_keep_NAs, 7),
     MX_ENTRY(sort_vector_indices_numeric, 2), MX_ENTRY(sort_vector_indices_integer, 2),
     MX_ENTRY(sort_vector_indices_logical, 2), MX_ENTRY(sort_vector_indices_binary, 1),
+    MX_ENTRY(sort_coo_indices_numeric, 3), MX_ENTRY(sort_coo_indices_logical, 3), MX_ENTRY(sort_coo_indices_binary, 2),
     {"mxgpu_csr_transpose", (DL_FUNC)&mxgpu_csr_transpose, 4},
     {"mxgpu_coo_to_csr", (DL_FUNC)&mxgpu_coo_to_csr, 5},
     {NULL, NULL, 0}

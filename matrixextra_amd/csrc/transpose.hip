@@ -32,7 +32,8 @@
 //
 // COO -> CSR (mxd_coo_to_csr, at the end of this file) runs the same passes twice: pass 0 can take the source
 // rows from the caller instead of an indptr search (TP_SRC_ROWS).  The sort of a sparse vector
-// (mxd_sort_vector_indices, after it) runs them once, on one key.
+// (mxd_sort_vector_indices, after it) runs them once, on one key.  The sort of COO triplets (mxd_coo_sort, last)
+// runs them on both keys, the second run taking up the first run's permutation, and gathers the values once.
 #include "mx_common.h"
 
 namespace mx {
@@ -51,6 +52,10 @@ constexpr size_t TP_FLAG_BYTES = 256;
 constexpr int TP_SV_PASS_FLAGS = 8;      // [8..11] the radix passes' flags (bad key, duplicates, bad row)
 constexpr int TP_SV_WORDS = 16;          // [16..18] the sortedness reduction: descents, largest index, negative index
 static_assert((TP_SV_WORDS + 3) * sizeof(int32_t) <= TP_FLAG_BYTES, "the sort's words lie inside the flag block");
+// the COO sort's words: [24..26] its passes' flags, [32..35] descents, largest row, negative index, largest column
+constexpr int TP_COO_PASS_FLAGS = 24;
+constexpr int TP_COO_WORDS = 32;
+static_assert((TP_COO_WORDS + 4) * sizeof(int32_t) <= TP_FLAG_BYTES, "the COO sort's words lie inside the flag block");
 
 // last row r in [lo, m) with indptr[r] <= k (indptr[lo] <= k holds for every caller)
 __device__ __forceinline__ int tp_row_of(const int32_t *__restrict__ indptr, int lo, int m, int64_t k)
@@ -369,8 +374,13 @@ static unsigned grid_for(int64_t n, int block, int64_t cap = (int64_t)1 << 20)
 // The LSD radix passes shared by the CSR transpose and the COO sort: a stable sort of nnz entries by key
 // (keys in [0, n), checked in pass 0), carrying the entry index and the source row (src0 says where pass 0 finds
 // it).  *fin receives the buffer index of the sorted keys / perm / rows in L.
+// A run that continues an earlier one (src0 == TP_SRC_SORTED) takes that run's permutation in perm0 instead of
+// starting from the identity, so the entry index it carries is still the caller's.  Its keys0 / perm0 / rows0 may be
+// the earlier run's buffers L.*[b]: with buf0 = b ^ 1 pass 0 writes the other set.  Its keys are not checked: they
+// are what an earlier pass wrote.
 static int tp_sort_passes(int src0, const int32_t *keys0, const int32_t *rows0, const int32_t *indptr, int m, int n,
-                          int64_t nnz, const TpLayout &L, int32_t *flags, int *fin, hipStream_t st)
+                          int64_t nnz, const TpLayout &L, int32_t *flags, int *fin, hipStream_t st,
+                          const int32_t *perm0 = nullptr, int buf0 = 0)
 {
     const int key_bits = bits_of(n > 0 ? n - 1 : 0);
     const int npasses = n <= TP_RADIX ? 1 : (key_bits + 7) / 8;
@@ -379,11 +389,13 @@ static int tp_sort_passes(int src0, const int32_t *keys0, const int32_t *rows0, 
     for (int pass = 0; pass < npasses; pass++) {
         const int shift = 8 * pass;
         const int nbits = key_bits - shift < 8 ? (key_bits - shift > 0 ? key_bits - shift : 0) : 8;
-        const int32_t *kin = pass == 0 ? keys0 : L.keys[(pass - 1) & 1];
-        const int32_t *pin = pass == 0 ? nullptr : L.perm[(pass - 1) & 1];
-        const int32_t *rin = pass == 0 ? rows0 : L.rows[(pass - 1) & 1];
-        int32_t *kout = L.keys[pass & 1], *pout = L.perm[pass & 1], *rout = L.rows[pass & 1];
-        if (pass == 0)
+        const int in = (pass - 1 + buf0) & 1, out = (pass + buf0) & 1;
+        const int32_t *kin = pass == 0 ? keys0 : L.keys[in];
+        const int32_t *pin = pass == 0 ? perm0 : L.perm[in];
+        const int32_t *rin = pass == 0 ? rows0 : L.rows[in];
+        int32_t *kout = L.keys[out], *pout = L.perm[out], *rout = L.rows[out];
+        const bool first = pass == 0 && src0 != TP_SRC_SORTED;
+        if (first)
             hipLaunchKernelGGL(tp_count_kernel<true>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, nnz, n, shift, nbits,
                                ntiles, L.table, flags);
         else
@@ -391,7 +403,7 @@ static int tp_sort_passes(int src0, const int32_t *keys0, const int32_t *rows0, 
                                ntiles, L.table, flags);
         MX_LAUNCH_CHECK();
         if (exclusive_scan_i32(L.table, T, L.offsets, nullptr, L.scan_ws, st)) return 1;
-        if (pass > 0)
+        if (!first)
             hipLaunchKernelGGL(tp_scatter_kernel<TP_SRC_SORTED>, dim3(ntiles), dim3(TP_BLOCK), 0, st, kin, pin, rin,
                                indptr, m, nnz, n, shift, nbits, ntiles, L.offsets, kout, pout, rout, flags);
         else if (src0 == TP_SRC_INDPTR)
@@ -402,7 +414,7 @@ static int tp_sort_passes(int src0, const int32_t *keys0, const int32_t *rows0, 
                                indptr, m, nnz, n, shift, nbits, ntiles, L.offsets, kout, pout, rout, flags);
         MX_LAUNCH_CHECK();
     }
-    *fin = (npasses - 1) & 1;
+    *fin = (npasses - 1 + buf0) & 1;
     return 0;
 }
 
@@ -643,7 +655,147 @@ static int sort_vector(int32_t *ii, void *xx, int64_t n, int value_dtype, void *
     return 0;
 }
 
+// ---- COO triplets sorted by (row, column) in place, values carried -----------------------------------------
+// sort_coo_indices<T> (src/misc.cpp:387-457) argsorts the triplets by (indices1, indices2) with std::sort and
+// permutes all three arrays.  Here one reduction over both index arrays finds out whether anything is out of order,
+// whether an index is negative, and the two largest indices, which size the radix passes (words[0] descents,
+// words[1] largest ii, words[2] a negative index, words[3] largest jj).  The maxima go through one slot per block and
+// a one-block second step: no global atomics.  Only unsorted triplets go further: a stable sort by jj (the run of
+// mxd_coo_to_csr's stage 1, carrying ii as its "row"), then a stable sort by ii that takes up that permutation
+// (carrying jj), so the entry index that arrives is the caller's and the values are gathered once, by the composed
+// permutation.  Equal cells stay in input order, one of the orders std::sort may give.
+constexpr int COO_SORTED_BLOCKS = 2048;
+
+__global__ __launch_bounds__(256)
+void coo_sorted_kernel(const int32_t *__restrict__ ii, const int32_t *__restrict__ jj, int64_t n,
+                       int32_t *__restrict__ words, int32_t *__restrict__ part_i, int32_t *__restrict__ part_j)
+{
+    __shared__ int32_t wave_max[2][256 / MX_WAVE];
+    bool desc = false, neg = false;
+    int mx_i = 0, mx_j = 0;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        const int i = ii[k], j = jj[k];
+        if (k > 0) {
+            const int pi = ii[k - 1];
+            desc |= i < pi || (i == pi && j < jj[k - 1]);
+        }
+        neg |= (i | j) < 0;
+        mx_i = i > mx_i ? i : mx_i;
+        mx_j = j > mx_j ? j : mx_j;
+    }
+#pragma unroll
+    for (int off = MX_WAVE / 2; off > 0; off >>= 1) {
+        const int oi = __shfl_down(mx_i, off, MX_WAVE), oj = __shfl_down(mx_j, off, MX_WAVE);
+        mx_i = oi > mx_i ? oi : mx_i;
+        mx_j = oj > mx_j ? oj : mx_j;
+    }
+    const bool any_desc = __ballot(desc) != 0ULL, any_neg = __ballot(neg) != 0ULL;
+    const int wave = threadIdx.x / MX_WAVE;
+    if (lane_id() == 0) {
+        if (any_desc) words[0] = 1;
+        if (any_neg) words[2] = 1;
+        wave_max[0][wave] = mx_i;
+        wave_max[1][wave] = mx_j;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 256 / MX_WAVE; w++) {
+            mx_i = wave_max[0][w] > mx_i ? wave_max[0][w] : mx_i;
+            mx_j = wave_max[1][w] > mx_j ? wave_max[1][w] : mx_j;
+        }
+        part_i[blockIdx.x] = mx_i;
+        part_j[blockIdx.x] = mx_j;
+    }
+}
+
+// one wave: words[1] / words[3] = the largest of the per-block maxima
+__global__ __launch_bounds__(MX_WAVE)
+void coo_max_kernel(const int32_t *__restrict__ part_i, const int32_t *__restrict__ part_j, int nparts,
+                    int32_t *__restrict__ words)
+{
+    int mx_i = 0, mx_j = 0;
+    for (int b = threadIdx.x; b < nparts; b += MX_WAVE) {
+        mx_i = part_i[b] > mx_i ? part_i[b] : mx_i;
+        mx_j = part_j[b] > mx_j ? part_j[b] : mx_j;
+    }
+#pragma unroll
+    for (int off = MX_WAVE / 2; off > 0; off >>= 1) {
+        const int oi = __shfl_down(mx_i, off, MX_WAVE), oj = __shfl_down(mx_j, off, MX_WAVE);
+        mx_i = oi > mx_i ? oi : mx_i;
+        mx_j = oj > mx_j ? oj : mx_j;
+    }
+    if (threadIdx.x == 0) { words[1] = mx_i; words[3] = mx_j; }
+}
+
+static int coo_sort(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int value_dtype, void *workspace,
+                    int *was_sorted_host, hipStream_t st)
+{
+    MX_REQUIRE(nnz >= 0, "mxd_coo_sort: negative size");
+    MX_REQUIRE(nnz <= INT_MAX, "mxd_coo_sort: %lld entries exceed R's int32 index range", (long long)nnz);
+    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
+               "mxd_coo_sort: unsupported value dtype %d", value_dtype);
+    MX_REQUIRE(was_sorted_host, "mxd_coo_sort: null pointer");
+    *was_sorted_host = 1;
+    if (nnz == 0) return 0;
+    const bool has_values = value_dtype != MX_NONE;
+    MX_REQUIRE(ii && jj && workspace && (!has_values || xx), "mxd_coo_sort: null pointer");
+    TpLayout L(workspace, nnz);
+    void *tmp_values = (char *)workspace + L.bytes;
+    // the passes' own flags (F[0] bad key, F[2] bad row) cannot fire once the reduction below has passed, and the
+    // gather's duplicate flag F[1] means nothing here: none is read back
+    int32_t *F = L.flags + TP_COO_PASS_FLAGS, *words = L.flags + TP_COO_WORDS;
+    MX_HIP(hipMemsetAsync(L.flags, 0, TP_FLAG_BYTES, st));
+    // the per-block maxima lie where the first pass will write, at most nnz of them
+    const unsigned nparts = grid_for(nnz, 256, COO_SORTED_BLOCKS);
+    hipLaunchKernelGGL(coo_sorted_kernel, dim3(nparts), dim3(256), 0, st, ii, jj, nnz, words, L.keys[0], L.perm[0]);
+    MX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(coo_max_kernel, dim3(1), dim3(MX_WAVE), 0, st, L.keys[0], L.perm[0], (int)nparts, words);
+    MX_LAUNCH_CHECK();
+    int32_t w[4] = {0, 0, 0, 0};
+    MX_HIP(hipMemcpyAsync(w, words, sizeof(w), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipStreamSynchronize(st));
+    MX_REQUIRE(!w[2], "mxd_coo_sort: negative index");
+    if (!w[0]) return 0;                                    // already sorted: nothing is touched
+    *was_sorted_host = 0;
+    MX_REQUIRE(w[1] < INT_MAX && w[3] < INT_MAX, "mxd_coo_sort: index outside [0, %d)", INT_MAX);
+    const int nrow_keys = w[1] + 1, ncol_keys = w[3] + 1;
+
+    // by column, carrying the row; then by row, carrying the column and the first run's permutation
+    int fin = 0;
+    if (tp_sort_passes(TP_SRC_ROWS, jj, ii, nullptr, nrow_keys, ncol_keys, nnz, L, F, &fin, st)) return 1;
+    if (tp_sort_passes(TP_SRC_SORTED, L.rows[fin], L.keys[fin], nullptr, ncol_keys, nrow_keys, nnz, L, F, &fin, st,
+                       L.perm[fin], fin ^ 1))
+        return 1;
+    // the sorted rows, columns and permutation are all in the workspace: nothing below reads what it overwrites,
+    // except the values, which go through tmp_values
+    const int32_t *srows = L.keys[fin], *sperm = L.perm[fin], *scols = L.rows[fin];
+    const unsigned gq = (unsigned)ceil_div(nnz, 256);
+    if (value_dtype == MX_F64)
+        hipLaunchKernelGGL((tp_gather_kernel<double, true>), dim3(gq), dim3(256), 0, st, srows, sperm, nnz, scols,
+                           (const double *)xx, jj, (double *)tmp_values, F);
+    else if (has_values)
+        hipLaunchKernelGGL((tp_gather_kernel<int32_t, true>), dim3(gq), dim3(256), 0, st, srows, sperm, nnz, scols,
+                           (const int32_t *)xx, jj, (int32_t *)tmp_values, F);
+    else
+        hipLaunchKernelGGL((tp_gather_kernel<int32_t, false>), dim3(gq), dim3(256), 0, st, srows, sperm, nnz, scols,
+                           nullptr, jj, nullptr, F);
+    MX_LAUNCH_CHECK();
+    MX_HIP(hipMemcpyAsync(ii, srows, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToDevice, st));
+    if (has_values)
+        MX_HIP(hipMemcpyAsync(xx, tmp_values, (value_dtype == MX_F64 ? 8 : 4) * (size_t)nnz, hipMemcpyDeviceToDevice,
+                              st));
+    return 0;
+}
+
 }  // namespace mx
+
+extern "C" size_t mxd_coo_sort_workspace_bytes(int64_t nnz) { return mx::sv_sort_ws_bytes(nnz > 0 ? nnz : 0); }
+
+extern "C" int mxd_coo_sort(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int value_dtype, void *workspace,
+                            int *was_sorted, void *stream)
+{
+    return mx::coo_sort(ii, jj, xx, nnz, value_dtype, workspace, was_sorted, mx::as_stream(stream));
+}
 
 extern "C" size_t mxd_sort_vector_indices_workspace_bytes(int64_t n) { return mx::sv_sort_ws_bytes(n > 0 ? n : 0); }
 

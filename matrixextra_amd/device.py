@@ -256,6 +256,26 @@ def csr_to_coo(A: DeviceCSR):
     return rows[:A.nnz], A.indices, A.values
 
 
+def coo_sort(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor | None, byrow: bool = True) -> bool:
+    """Sorts COO triplets held in HBM (int32 0-based, non-negative) in place through mxd_coo_sort: by (i, j), or by
+    (j, i) with byrow=False; x (f64, int32 R logicals, or None) follows.  Entries of one cell keep their input order.
+    Returns whether the triplets were already sorted, in which case nothing was written."""
+    lib = _lib.load()
+    nnz = int(i.numel())
+    if int(j.numel()) != nnz or (x is not None and int(x.numel()) != nnz):
+        raise ValueError("i, j and x must have the same length")
+    if i.dtype != torch.int32 or j.dtype != torch.int32 or not (i.is_contiguous() and j.is_contiguous()):
+        raise ValueError("i and j must be contiguous int32 tensors")
+    if x is not None and not x.is_contiguous():
+        raise ValueError("x must be a contiguous tensor")
+    vd = _value_dtype(x)
+    ws = torch.empty(max(lib.mxd_coo_sort_workspace_bytes(nnz), 16), dtype=torch.uint8, device=i.device)
+    first, second = (i, j) if byrow else (j, i)
+    was_sorted = C.c_int(1)
+    check(lib.mxd_coo_sort(_dp(first), _dp(second), _dp(x), nnz, vd, _dp(ws), C.byref(was_sorted), _stream()))
+    return bool(was_sorted.value)
+
+
 CooAxis = _lib.CooAxis      # mx_coo_axis, as include/mxgpu.h declares it
 
 

@@ -604,6 +604,36 @@ def sort_vector_indices_binary(ii):
     _sort_vector(ii, None, MX_NONE, None)
 
 
+def _sort_coo(ii, jj, xx, vd, vdt):
+    for name, a in (("indices1", ii), ("indices2", jj)):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous):
+            raise TypeError(f"{name} must be a contiguous int32 numpy array (sorted in place)")
+    if jj.size != ii.size:
+        raise ValueError("indices1 and indices2 have different lengths")
+    if vdt is not None:
+        if not (isinstance(xx, np.ndarray) and xx.dtype == vdt and xx.flags.c_contiguous):
+            raise TypeError(f"values must be a contiguous {np.dtype(vdt).name} numpy array (sorted in place)")
+        if xx.size != ii.size:
+            raise ValueError("indices1 and values have different lengths")
+    check(_lib.load().mx_sort_coo_indices(ptr(ii), ptr(jj), None if vdt is None else ptr(xx), ii.size, vd))
+
+
+def sort_coo_indices_numeric(indices1, indices2, values):
+    """src/misc.cpp:430-438: sorts a TsparseMatrix's triplets IN PLACE by (indices1, indices2), stably (entries of
+    one cell keep their input order); left alone when sorted."""
+    _sort_coo(indices1, indices2, values, MX_F64, np.float64)
+
+
+def sort_coo_indices_logical(indices1, indices2, values):
+    """src/misc.cpp:440-448."""
+    _sort_coo(indices1, indices2, values, MX_LGL, np.int32)
+
+
+def sort_coo_indices_binary(indices1, indices2):
+    """src/misc.cpp:450-457."""
+    _sort_coo(indices1, indices2, None, MX_NONE, None)
+
+
 def _csr_by_svec(indptr, indices, values, ii_base1, xx, ncols, length, keep_NAs):
     p, j, x, vi = _i32(indptr), _i32(indices), _f64(values), _i32(ii_base1)
     vx = None if xx is None or (np.asarray(xx).size == 0 and vi.size != 0) else _f64(xx)

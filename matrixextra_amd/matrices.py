@@ -886,11 +886,28 @@ def check_valid_matrix(X):
         stop("Matrix is invalid ('p' has bad start/end.)")
 
 
-def sort_sparse_indices(X, copy=False):
+def sort_sparse_indices(X, copy=False, byrow=True):
     """sort_sparse_indices (R/utils.R:22-161) for RsparseMatrix: per-row index sort on the
     device (src/misc.cpp:261-298).  copy=TRUE sorts deep copies of @j/@x and returns a new object.
-    A sparseVector (:126-155) is sorted by @i, @x carried, by the device radix sort (src/misc.cpp:460-527)."""
+    A sparseVector (:126-155) is sorted by @i, @x carried, by the device radix sort (src/misc.cpp:460-527).
+    A TsparseMatrix (:85-124) has its triplets sorted by (i, j), or by (j, i) with byrow=False (the reference sorts
+    the t_shallow of X and turns it back), by the device COO sort (src/misc.cpp:387-457): in place
+    and returning X itself, or with copy=TRUE in deep copies of @i / @j / @x held by a new object.  Entries of one
+    cell keep their input order.  `byrow` matters to a TsparseMatrix only."""
     from . import exports
+    if isinstance(X, TsparseMatrix):
+        check_valid_matrix(X)
+        kind = {dgTMatrix: "numeric", lgTMatrix: "logical", ngTMatrix: "binary"}.get(type(X))
+        if kind is None:
+            stop("Method is only applicable to sparse matrices in CSR, CSC, and COO formats, and to sparse vectors.")
+        if copy:
+            X = X.copy()
+        first, second = (X.i, X.j) if byrow else (X.j, X.i)
+        if kind == "binary":
+            exports.sort_coo_indices_binary(first, second)
+        else:
+            getattr(exports, "sort_coo_indices_" + kind)(first, second, X.x)
+        return X
     if isinstance(X, sparseVector):
         if copy:
             X = X.copy()
