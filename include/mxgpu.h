@@ -295,6 +295,45 @@ int mxd_csr_by_svec_fill(int m, int ncol, int64_t nnz, const int32_t *indptr, co
                          int keep_na, const void *workspace, const int32_t *out_indptr, int32_t *out_indices,
                          double *out_values, void *stream);
 
+/* The outer products of `%*%` with a one-column CSR, and the float32 row vector x CSC product (outer.hip; DESIGN.md
+ * §4.14).  X is the CSR triple of a one-column matrix with m rows: row r is non-empty when indptr[r] < indptr[r+1]
+ * and its value is values[indptr[r]], the first stored entry; the column indices are never read.
+ * Dense outer (matmul_colvec_by_scolvecascsr{,_f32}, src/matmul.cpp:686-781): a CSR with m rows, every non-empty row
+ *   holding columns 0..dim-1 with value * colvec[c].  colvec_dtype MX_F64: 0.0 + a*v, the product rounded on its own
+ *   (daxpy into a zeroed slot: a product of -0 comes out as +0; a == 0 leaves the zeros).  MX_F32: a narrowed to float
+ *   (:53-57), 0.0f + a*v in float, widened for the output.  count: out_indptr[m+1], *nnz_out_host = output entries
+ *   (64-bit; above INT32_MAX the call fails); one synchronise.  workspace: mxd_csr_outer_dense_workspace_bytes(m).
+ * Sparse outer (matmul_spcolvec_by_scolvecascsr_*, :783-938): a CSC with y_length columns; column
+ *   y_indices_base1[k]-1 holds every non-empty row of X, ascending, with value y_values[k] * a (value_dtype MX_F64;
+ *   MX_I32 / MX_LGL: NA gives NA_real_, other values multiply as ints promoted to double; MX_NONE: a copied, y_values
+ *   NULL); every other column is empty.  y's positions sorted and unique; those outside [1, y_length] are skipped.
+ *   count: compacts the non-empty rows into the workspace (*nonempty_host of them) and scans out_indptr[y_length+1];
+ *   *nnz_out_host = nonempty * ny, refused above INT32_MAX; two synchronises.  fill: out_indices / out_values of that
+ *   many entries.  workspace: mxd_csr_outer_svec_workspace_bytes(m, y_length), shared by both passes.
+ * Deviations from the reference: (1) its output arrays have length(indices) * dim entries, which leaves a zero tail
+ *   when a row stores more than one entry; here they have out_indptr[m] entries.  (2) The entry count is checked
+ *   against INT32_MAX, which the reference does not check.  (3) Known defect, not copied: :808 reads y_values[col]
+ *   where it means y_values[ix], an out-of-bounds read whenever y stores fewer positions than its length;
+ *   y_values[k] is used here.
+ * Row vector (matmul_rowvec_by_csc / _cscbin, :643-684): out[col] = sum of values[ix] * rowvec[indices[ix]] over the
+ *   compressed column, each product in double, accumulated into a float (SpMV's float32 kind on the CSC arrays; the
+ *   lane-group reduction reorders the float sum).  values NULL: the sum of rowvec[indices[ix]]. */
+size_t mxd_csr_outer_dense_workspace_bytes(int m);
+int mxd_csr_outer_dense_count(int m, int dim, const int32_t *indptr, void *workspace, int32_t *out_indptr,
+                              int64_t *nnz_out_host, void *stream);
+int mxd_csr_outer_dense_fill(int m, int dim, int64_t nnz, const int32_t *indptr, const double *values,
+                             const void *colvec, int colvec_dtype, const int32_t *out_indptr, int32_t *out_indices,
+                             double *out_values, void *stream);
+size_t mxd_csr_outer_svec_workspace_bytes(int m, int y_length);
+int mxd_csr_outer_svec_count(int m, int64_t nnz, const int32_t *indptr, const double *values,
+                             const int32_t *y_indices_base1, int64_t ny, int y_length, void *workspace,
+                             int32_t *out_indptr, int64_t *nonempty_host, int64_t *nnz_out_host, void *stream);
+int mxd_csr_outer_svec_fill(int m, const int32_t *y_indices_base1, int64_t ny, const void *y_values, int value_dtype,
+                            int y_length, int64_t nonempty, const void *workspace, const int32_t *out_indptr,
+                            int32_t *out_indices, double *out_values, void *stream);
+int mxd_rowvec_by_csc(int ncols, int64_t nnz, const int32_t *indptr, const int32_t *indices, const double *values,
+                      const float *rowvec, float *out, void *stream);
+
 /* sort_sparse_indices of a sparse vector (sort_vector_indices_*, src/misc.cpp:460-527): ii[n] (non-negative) and
  * its values xx[n] (MX_F64, MX_I32 / MX_LGL, or MX_NONE with xx NULL) sorted by ii in place, stably, by the LSD
  * radix passes of the transpose.  One reduction first: *was_sorted_host = 1 and nothing is
@@ -824,6 +863,27 @@ int mx_sort_coo_indices(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int val
 int mx_multiply_csr_by_svec_begin(const int32_t *indptr, int nrows, const int32_t *indices, const double *values,
                                   const int32_t *ii_base1, const double *xx, int64_t nnz_v, int ncols, int length,
                                   int keep_NAs, mx_result **res, mx_result_info *info);
+
+/* matmul_colvec_by_scolvecascsr (colvec_dtype MX_F64) / _f32 (MX_F32, the float32@Data bits)  src/matmul.cpp:686-781,
+ * through mxd_csr_outer_dense_count / _fill: a CSR of nrows rows (indptr nrows + 1), indices and f64 values of
+ * out_indptr[nrows] entries (the reference pads to length(indices) * dim).  `indices` is not read.  (non-empty rows) *
+ * dim above INT32_MAX fails before anything is allocated; the reference does not check. */
+int mx_matmul_colvec_by_scolvecascsr_begin(const void *colvec, int colvec_dtype, int dim, const int32_t *indptr,
+                                           int nrows, const int32_t *indices, const double *values,
+                                           mx_result **res, mx_result_info *info);
+/* matmul_spcolvec_by_scolvecascsr_{numeric,integer,logical,binary}  src/matmul.cpp:783-938 (value_dtype MX_F64 /
+ * MX_I32 / MX_LGL / MX_NONE with y_values NULL), through mxd_csr_outer_svec_count / _fill: a CSC of y_length columns
+ * (indptr y_length + 1), row indices and f64 values.  Uses y_values[k] where the reference reads y_values[col]
+ * (:808, out of bounds for a vector that stores fewer positions than its length).  (non-empty rows) * nnz_y above
+ * INT32_MAX fails before anything is allocated. */
+int mx_matmul_spcolvec_by_scolvecascsr_begin(const int32_t *X_indptr, int nrows, const int32_t *X_indices,
+                                             const double *X_values, const int32_t *y_indices_base1,
+                                             const void *y_values, int value_dtype, int64_t nnz_y, int y_length,
+                                             mx_result **res, mx_result_info *info);
+/* matmul_rowvec_by_csc / matmul_rowvec_by_cscbin (values NULL)  src/matmul.cpp:643-684: out[ncols] float32; every
+ * index must lie in [0, len_rowvec), which is checked here and not in the reference */
+int mx_matmul_rowvec_by_csc(const float *rowvec, int64_t len_rowvec, const int32_t *indptr, int ncols,
+                            const int32_t *indices, const double *values, float *out);
 
 #ifdef __cplusplus
 }

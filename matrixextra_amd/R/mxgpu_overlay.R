@@ -61,7 +61,13 @@
     "sort_vector_indices_numeric", "sort_vector_indices_integer", "sort_vector_indices_logical",
     "sort_vector_indices_binary",
     ## the TsparseMatrix branch of sort_sparse_indices (R/utils.R:85-124), in place as well
-    "sort_coo_indices_numeric", "sort_coo_indices_logical", "sort_coo_indices_binary"
+    "sort_coo_indices_numeric", "sort_coo_indices_logical", "sort_coo_indices_binary",
+    ## the outer products of a one-column RsparseMatrix (outerprod_csrsinglecol_by_dvec, R/matmul.R:659-751) and the
+    ## float32 vector forms of `%*%` / tcrossprod / crossprod (R/matmul.R:220-262, 327-367, 405-427, 480-500)
+    "matmul_colvec_by_scolvecascsr", "matmul_colvec_by_scolvecascsr_f32",
+    "matmul_spcolvec_by_scolvecascsr_numeric", "matmul_spcolvec_by_scolvecascsr_integer",
+    "matmul_spcolvec_by_scolvecascsr_logical", "matmul_spcolvec_by_scolvecascsr_binary",
+    "matmul_rowvec_by_csc", "matmul_rowvec_by_cscbin"
 )
 
 mxgpu_enable <- function(shim_path, min_nnz = 0L) {

@@ -737,6 +737,108 @@ int mx_multiply_csr_by_svec_begin(const int32_t *indptr, int nrows, const int32_
     });
 }
 
+// ---- outer products with a one-column CSR, float32 row vector x CSC (outer.hip) ----------------
+// non-empty rows of a host indptr, and the refusal of an outer product beyond R's int32 index range before
+// anything is allocated for it (the reference does not check)
+static int outer_entries_ok(const char *what, const int32_t *indptr, int nrows, int64_t per_row)
+{
+    int64_t nonempty = 0;
+    for (int r = 0; r < nrows; r++) nonempty += indptr[r] < indptr[r + 1];
+    MX_REQUIRE(nonempty * per_row <= (int64_t)INT_MAX,
+               "%s: the outer product has %lld entries: exceeds R's int32 index range", what,
+               (long long)(nonempty * per_row));
+    return 0;
+}
+
+int mx_matmul_colvec_by_scolvecascsr_begin(const void *colvec, int colvec_dtype, int dim, const int32_t *indptr,
+                                           int nrows, const int32_t *indices, const double *values,
+                                           mx_result **res_out, mx_result_info *info)
+{
+    (void)indices;                                          // never read (matmul.cpp:722-731)
+    MX_REQUIRE(res_out && info && indptr && nrows >= 0 && dim >= 0 && (dim == 0 || colvec),
+               "mx_matmul_colvec_by_scolvecascsr_begin: bad arguments");
+    MX_REQUIRE(colvec_dtype == MX_F64 || colvec_dtype == MX_F32,
+               "mx_matmul_colvec_by_scolvecascsr_begin: unsupported dense dtype %d", colvec_dtype);
+    MX_REQUIRE(indptr[0] >= 0 && indptr[nrows] >= 0, "mx_matmul_colvec_by_scolvecascsr_begin: bad index pointer");
+    *res_out = nullptr;
+    if (outer_entries_ok("mx_matmul_colvec_by_scolvecascsr_begin", indptr, nrows, dim)) return 1;
+    const int64_t nnz = indptr[nrows];
+    return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
+        DevBuf p, x, v, ws;
+        if (p.upload(indptr, sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        if (x.upload(values, sizeof(double) * (size_t)nnz)) return 1;
+        if (v.upload(colvec, dtype_bytes(colvec_dtype) * (size_t)dim)) return 1;
+        if (ws.alloc(mxd_csr_outer_dense_workspace_bytes(nrows))) return 1;
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        int64_t total = 0;
+        if (mxd_csr_outer_dense_count(nrows, dim, p.as<int32_t>(), ws.p, res.indptr.as<int32_t>(), &total, nullptr))
+            return 1;
+        res.set_sizes((int64_t)nrows + 1, total, total);
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
+        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+        if (total == 0) return 0;
+        return mxd_csr_outer_dense_fill(nrows, dim, nnz, p.as<int32_t>(), x.as<double>(), v.p, colvec_dtype,
+                                        res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.as<double>(),
+                                        nullptr);
+    });
+}
+
+int mx_matmul_spcolvec_by_scolvecascsr_begin(const int32_t *X_indptr, int nrows, const int32_t *X_indices,
+                                             const double *X_values, const int32_t *y_indices_base1,
+                                             const void *y_values, int value_dtype, int64_t nnz_y, int y_length,
+                                             mx_result **res_out, mx_result_info *info)
+{
+    (void)X_indices;                                        // never read (matmul.cpp:811-833)
+    MX_REQUIRE(res_out && info && X_indptr && nrows >= 0 && nnz_y >= 0 && nnz_y <= INT_MAX && y_length >= 0,
+               "mx_matmul_spcolvec_by_scolvecascsr_begin: bad arguments");
+    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_I32 || value_dtype == MX_LGL || value_dtype == MX_NONE,
+               "mx_matmul_spcolvec_by_scolvecascsr_begin: unsupported value dtype %d", value_dtype);
+    MX_REQUIRE(nnz_y == 0 || (y_indices_base1 && (value_dtype == MX_NONE || y_values)),
+               "mx_matmul_spcolvec_by_scolvecascsr_begin: null pointer");
+    MX_REQUIRE(X_indptr[0] >= 0 && X_indptr[nrows] >= 0, "mx_matmul_spcolvec_by_scolvecascsr_begin: bad index pointer");
+    *res_out = nullptr;
+    if (outer_entries_ok("mx_matmul_spcolvec_by_scolvecascsr_begin", X_indptr, nrows, nnz_y)) return 1;
+    const int64_t nnz = X_indptr[nrows];
+    return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
+        DevBuf p, x, yi, yv, ws;
+        if (p.upload(X_indptr, sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        if (x.upload(X_values, sizeof(double) * (size_t)nnz)) return 1;
+        if (yi.upload(y_indices_base1, sizeof(int32_t) * (size_t)nnz_y)) return 1;
+        if (value_dtype != MX_NONE && yv.upload(y_values, dtype_bytes(value_dtype) * (size_t)nnz_y)) return 1;
+        if (ws.alloc(mxd_csr_outer_svec_workspace_bytes(nrows, y_length))) return 1;
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)y_length + 1))) return 1;
+        int64_t nonempty = 0, total = 0;
+        if (mxd_csr_outer_svec_count(nrows, nnz, p.as<int32_t>(), x.as<double>(), yi.as<int32_t>(), nnz_y, y_length,
+                                     ws.p, res.indptr.as<int32_t>(), &nonempty, &total, nullptr)) return 1;
+        res.set_sizes((int64_t)y_length + 1, total, total);
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
+        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+        if (total == 0) return 0;
+        return mxd_csr_outer_svec_fill(nrows, yi.as<int32_t>(), nnz_y, value_dtype != MX_NONE ? yv.p : nullptr,
+                                       value_dtype, y_length, nonempty, ws.p, res.indptr.as<int32_t>(),
+                                       res.indices.as<int32_t>(), res.values.as<double>(), nullptr);
+    });
+}
+
+int mx_matmul_rowvec_by_csc(const float *rowvec, int64_t len_rowvec, const int32_t *indptr, int ncols,
+                            const int32_t *indices, const double *values, float *out)
+{
+    MX_REQUIRE(ncols >= 0 && len_rowvec >= 0, "mx_matmul_rowvec_by_csc: negative size");
+    if (ncols == 0) return 0;
+    MX_REQUIRE(indptr && out, "mx_matmul_rowvec_by_csc: null pointer");
+    Csr A;
+    if (A.upload(indptr, indices, values, ncols, values ? sizeof(double) : 0)) return 1;
+    for (int64_t k = 0; k < A.nnz; k++)
+        MX_REQUIRE(indices[k] >= 0 && indices[k] < len_rowvec,
+                   "mx_matmul_rowvec_by_csc: row index %d outside the vector's length", indices[k]);
+    DevBuf v, o;
+    if (v.upload(rowvec, sizeof(float) * (size_t)len_rowvec)) return 1;
+    if (o.alloc(sizeof(float) * (size_t)ncols)) return 1;
+    if (mxd_rowvec_by_csc(ncols, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), values ? A.x.as<double>() : nullptr,
+                          v.as<float>(), o.as<float>(), nullptr)) return 1;
+    return mx::xfer_d2h(out, o.p, sizeof(float) * (size_t)ncols);
+}
+
 // ---- CSR (op) dense vector (§8f rank 4) ----------------------------------------------------------------------
 static int csr_by_dvec_export(const int32_t *indptr, const int32_t *indices, const void *values, int nrows,
                               const void *dvec, int64_t dvec_len, int ncols, int op, int lhs, void *values_out)

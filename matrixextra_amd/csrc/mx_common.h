@@ -58,7 +58,8 @@ int finish_count(int64_t n, void *workspace, int32_t *indptr, int64_t *nnz_out_h
 int xfer_h2d(void *dst_dev, const void *src_host, size_t bytes);
 int xfer_d2h(void *dst_host, const void *src_dev, size_t bytes);
 
-// spmv.hip
+// spmv.hip; v_dtype is an mx_dtype, or SPMV_F32_PATTERN: a float32 vector and a matrix without values (values unread)
+constexpr int SPMV_F32_PATTERN = 100;
 int spmv_launch(int m, int64_t nnz, const int32_t *indptr, const int32_t *indices, const double *values,
                 const void *v, int v_dtype, void *y, hipStream_t st);
 

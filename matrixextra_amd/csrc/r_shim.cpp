@@ -817,6 +817,72 @@ SEXP _MatrixExtra_multiply_csr_by_svec_keep_NAs(SEXP p_, SEXP j_, SEXP x_, SEXP 
     return csr_by_svec(1, p_, j_, x_, ii, xx, Rf_asInteger(ncols), length);
 }
 
+// outer products with a one-column CSR and float32 row vector x CSC  (src/matmul.cpp:643-938; outer.hip)
+static SEXP outer_dense(int dtype, SEXP colvec, SEXP p_, SEXP j_, SEXP x_)
+{
+    Protect p;
+    colvec = as_type(colvec, dtype == MX_F32 ? INTSXP : REALSXP, p);
+    p_ = as_type(p_, INTSXP, p); j_ = as_type(j_, INTSXP, p); x_ = as_type(x_, REALSXP, p);
+    if (XLENGTH(p_) < 1 || XLENGTH(x_) < INTEGER(p_)[XLENGTH(p_) - 1])
+        Rf_error("matmul_colvec_by_scolvecascsr: values shorter than the index pointer says");
+    mx_result *res = nullptr;
+    mx_result_info info;
+    if (mx_matmul_colvec_by_scolvecascsr_begin(dtype == MX_F32 ? (const void *)f32(colvec) : (const void *)REAL(colvec),
+                                               dtype, (int)XLENGTH(colvec), INTEGER(p_), (int)XLENGTH(p_) - 1,
+                                               INTEGER(j_), REAL(x_), &res, &info))
+        fail();
+    return finish_guarded(res, info, R_NilValue, R_NilValue);
+}
+SEXP _MatrixExtra_matmul_colvec_by_scolvecascsr(SEXP v, SEXP p_, SEXP j_, SEXP x_) { return outer_dense(MX_F64, v, p_, j_, x_); }
+SEXP _MatrixExtra_matmul_colvec_by_scolvecascsr_f32(SEXP v, SEXP p_, SEXP j_, SEXP x_) { return outer_dense(MX_F32, v, p_, j_, x_); }
+
+static SEXP outer_svec(int dtype, int ytype, SEXP p_, SEXP j_, SEXP x_, SEXP yi, SEXP yx, SEXP length)
+{
+    Protect p;
+    p_ = as_type(p_, INTSXP, p); j_ = as_type(j_, INTSXP, p); x_ = as_type(x_, REALSXP, p); yi = as_type(yi, INTSXP, p);
+    const void *yv = nullptr;
+    if (dtype != MX_NONE) {
+        yx = as_type(yx, ytype, p);
+        if (XLENGTH(yx) != XLENGTH(yi)) Rf_error("matmul_spcolvec_by_scolvecascsr: vector indices and values differ");
+        yv = ytype == REALSXP ? (const void *)REAL(yx) : ytype == LGLSXP ? (const void *)LOGICAL(yx) : (const void *)INTEGER(yx);
+    }
+    if (XLENGTH(p_) < 1 || XLENGTH(x_) < INTEGER(p_)[XLENGTH(p_) - 1])
+        Rf_error("matmul_spcolvec_by_scolvecascsr: values shorter than the index pointer says");
+    mx_result *res = nullptr;
+    mx_result_info info;
+    if (mx_matmul_spcolvec_by_scolvecascsr_begin(INTEGER(p_), (int)XLENGTH(p_) - 1, INTEGER(j_), REAL(x_), INTEGER(yi), yv,
+                                                 dtype, (int64_t)XLENGTH(yi), Rf_asInteger(length), &res, &info))
+        fail();
+    return finish_guarded(res, info, R_NilValue, R_NilValue);
+}
+SEXP _MatrixExtra_matmul_spcolvec_by_scolvecascsr_numeric(SEXP p_, SEXP j_, SEXP x_, SEXP yi, SEXP yx, SEXP n)
+{ return outer_svec(MX_F64, REALSXP, p_, j_, x_, yi, yx, n); }
+SEXP _MatrixExtra_matmul_spcolvec_by_scolvecascsr_integer(SEXP p_, SEXP j_, SEXP x_, SEXP yi, SEXP yx, SEXP n)
+{ return outer_svec(MX_I32, INTSXP, p_, j_, x_, yi, yx, n); }
+SEXP _MatrixExtra_matmul_spcolvec_by_scolvecascsr_logical(SEXP p_, SEXP j_, SEXP x_, SEXP yi, SEXP yx, SEXP n)
+{ return outer_svec(MX_LGL, LGLSXP, p_, j_, x_, yi, yx, n); }
+SEXP _MatrixExtra_matmul_spcolvec_by_scolvecascsr_binary(SEXP p_, SEXP j_, SEXP x_, SEXP yi, SEXP n)
+{ return outer_svec(MX_NONE, NILSXP, p_, j_, x_, yi, R_NilValue, n); }
+
+// a 1 x ncol integer matrix holding the float32 bits, as Rcpp::IntegerMatrix(1, ncols_Y)
+static SEXP rowvec_csc(SEXP v, SEXP p_, SEXP i_, SEXP x_)
+{
+    Protect p;
+    v = as_type(v, INTSXP, p); p_ = as_type(p_, INTSXP, p); i_ = as_type(i_, INTSXP, p);
+    const bool has = x_ != R_NilValue;
+    if (has) x_ = as_type(x_, REALSXP, p);
+    const int ncols = (int)XLENGTH(p_) - 1;
+    if (ncols < 0 || XLENGTH(i_) < INTEGER(p_)[ncols] || (has && XLENGTH(x_) < INTEGER(p_)[ncols]))
+        Rf_error("matmul_rowvec_by_csc: indices / values shorter than the index pointer says");
+    SEXP out = p(Rf_allocMatrix(INTSXP, 1, ncols));
+    if (mx_matmul_rowvec_by_csc(f32(v), (int64_t)XLENGTH(v), INTEGER(p_), ncols, INTEGER(i_), has ? REAL(x_) : nullptr,
+                                f32w(out)))
+        fail();
+    return out;
+}
+SEXP _MatrixExtra_matmul_rowvec_by_csc(SEXP v, SEXP p_, SEXP i_, SEXP x_) { return rowvec_csc(v, p_, i_, x_); }
+SEXP _MatrixExtra_matmul_rowvec_by_cscbin(SEXP v, SEXP p_, SEXP i_) { return rowvec_csc(v, p_, i_, R_NilValue); }
+
 // sort_vector_indices_*  (src/misc.cpp:489-527): the caller's vectors are sorted where they are, so no coercion
 static SEXP sort_svec(SEXP ii, SEXP xx, int xtype, int dtype)
 {
@@ -890,6 +956,10 @@ static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(sort_vector_indices_numeric, 2), MX_ENTRY(sort_vector_indices_integer, 2),
     MX_ENTRY(sort_vector_indices_logical, 2), MX_ENTRY(sort_vector_indices_binary, 1),
     MX_ENTRY(sort_coo_indices_numeric, 3), MX_ENTRY(sort_coo_indices_logical, 3), MX_ENTRY(sort_coo_indices_binary, 2),
+    MX_ENTRY(matmul_rowvec_by_csc, 4), MX_ENTRY(matmul_rowvec_by_cscbin, 3),
+    MX_ENTRY(matmul_colvec_by_scolvecascsr_f32, 4), MX_ENTRY(matmul_colvec_by_scolvecascsr, 4),
+    MX_ENTRY(matmul_spcolvec_by_scolvecascsr_numeric, 6), MX_ENTRY(matmul_spcolvec_by_scolvecascsr_integer, 6),
+    MX_ENTRY(matmul_spcolvec_by_scolvecascsr_logical, 6), MX_ENTRY(matmul_spcolvec_by_scolvecascsr_binary, 5),
     {"mxgpu_csr_transpose", (DL_FUNC)&mxgpu_csr_transpose, 4},
     {"mxgpu_coo_to_csr", (DL_FUNC)&mxgpu_coo_to_csr, 5},
     {NULL, NULL, 0}

@@ -3,6 +3,8 @@
 // Replaces matmul_csr_dvec<> (src/matmul.cpp:381-419; exports :421-483):
 //   numeric / integer / logical right-hand sides -> f64 result,
 //   float32 right-hand side -> f32 result with float accumulation (:403).
+// The float32 kind on a CSC's arrays is also matmul_rowvec_by_csc (:643-663, the same double product into a float
+// accumulator); SPMV_F32_PATTERN is its no-values twin matmul_rowvec_by_cscbin (:665-684), a float sum of v[j].
 // NA_INTEGER / NA_LOGICAL entries contribute NA_REAL (:406-411); a logical
 // entry counts as (bool)y (:411).
 //
@@ -31,6 +33,8 @@ __device__ __forceinline__ void spmv_term(double a, const void *__restrict__ v_,
     } else if constexpr (KIND == MX_LGL) {
         const int yv = ((const int32_t *)v_)[j];
         if (yv == MX_NA_INT) na = 1; else acc += a * (double)(yv != 0);
+    } else if constexpr (KIND == SPMV_F32_PATTERN) {
+        accf += ((const float *)v_)[j];
     } else {
         // float accumulator, double product: val += x * y with float val (matmul.cpp:403,413)
         accf = (float)((double)accf + a * (double)((const float *)v_)[j]);
@@ -61,7 +65,7 @@ void spmv_group_kernel(int m, const int32_t *__restrict__ indptr, const int32_t 
 #pragma unroll
         for (int r = 0; r < R; r++)
             if (lg == r % G && row0 + r < m) {
-                if constexpr (KIND == MX_F32) ((float *)y_)[row0 + r] = 0.0f; else ((double *)y_)[row0 + r] = 0.0;
+                if constexpr (KIND == MX_F32 || KIND == SPMV_F32_PATTERN) ((float *)y_)[row0 + r] = 0.0f; else ((double *)y_)[row0 + r] = 0.0;
             }
         return;
     }
@@ -77,7 +81,8 @@ void spmv_group_kernel(int m, const int32_t *__restrict__ indptr, const int32_t 
         const bool ok = k < e[r];
         const int ks = ok ? k : 0;                // unconditional (clamped) loads, selected afterwards
         const int jl = indices[ks];
-        const double al = values[ks];
+        double al = 1.0;
+        if constexpr (KIND != SPMV_F32_PATTERN) al = values[ks];
         j0[r] = ok ? jl : -1;
         a0[r] = al;
     }
@@ -96,13 +101,16 @@ void spmv_group_kernel(int m, const int32_t *__restrict__ indptr, const int32_t 
     }
 #pragma unroll
     for (int r = 0; r < R; r++)                   // rows longer than one group width
-        for (int k = s[r] + G + lg; k < e[r]; k += G)
-            spmv_term<KIND>(values[k], v_, indices[k], acc[r], accf[r], na[r]);
+        for (int k = s[r] + G + lg; k < e[r]; k += G) {
+            double a = 1.0;
+            if constexpr (KIND != SPMV_F32_PATTERN) a = values[k];
+            spmv_term<KIND>(a, v_, indices[k], acc[r], accf[r], na[r]);
+        }
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
-            if constexpr (KIND == MX_F32) accf[r] += __shfl_xor(accf[r], off, G);
+            if constexpr (KIND == MX_F32 || KIND == SPMV_F32_PATTERN) accf[r] += __shfl_xor(accf[r], off, G);
             else {
                 acc[r] += __shfl_xor(acc[r], off, G);
                 if constexpr (KIND == MX_I32 || KIND == MX_LGL) na[r] |= __shfl_xor(na[r], off, G);
@@ -112,7 +120,7 @@ void spmv_group_kernel(int m, const int32_t *__restrict__ indptr, const int32_t 
 #pragma unroll
     for (int r = 0; r < R; r++) {
         if (lg == r % G && row0 + r < m) {
-            if constexpr (KIND == MX_F32) ((float *)y_)[row0 + r] = accf[r];
+            if constexpr (KIND == MX_F32 || KIND == SPMV_F32_PATTERN) ((float *)y_)[row0 + r] = accf[r];
             else ((double *)y_)[row0 + r] = na[r] ? na_real() : acc[r];
         }
     }
@@ -123,7 +131,7 @@ int spmv_launch(int m, int64_t nnz, const int32_t *indptr, const int32_t *indice
                 const void *v, int v_dtype, void *y, hipStream_t st)
 {
     const int G = nnz < 0 ? 32 : pick_group((double)nnz / (double)(m > 0 ? m : 1));
-    return dispatch_int(int_list<MX_F64, MX_I32, MX_LGL, MX_F32>{}, "spmv", "vector dtype", v_dtype, [&](auto kind) {
+    return dispatch_int(int_list<MX_F64, MX_I32, MX_LGL, MX_F32, SPMV_F32_PATTERN>{}, "spmv", "vector dtype", v_dtype, [&](auto kind) {
         return launch_rows(lane_groups{}, "spmv", G, m, SPMV_BLOCK, [&](auto g, dim3 grid, dim3 block) {
             hipLaunchKernelGGL((spmv_group_kernel<g(), kind()>), grid, block, 0, st, m, indptr, indices, values, v, y);
         }, SPMV_ROWS);

@@ -514,3 +514,84 @@ def csr_filter(A: DeviceCSR, mask: torch.Tensor) -> DeviceCSR:
     if mask.dtype != torch.int32 or mask.numel() != A.nnz or mask.device != A.indptr.device:
         raise ValueError(f"mask must be {A.nnz} bool / int32 entries on {A.indptr.device}")
     return _csr_compact(A, _lib.MX_KEEP_MASK, mask.contiguous())
+
+
+def _one_column(A: DeviceCSR, what: str):
+    if A.K != 1:
+        raise ValueError(f"{what}: X must have one column")
+    if A.values is None or A.values.dtype != torch.float64:
+        raise ValueError(f"{what}: X needs float64 values")
+
+
+def csr_outer_dense(A: DeviceCSR, v: torch.Tensor):
+    """X %*% v for a device-resident one-column CSR X (f64 values) and a dense f64 or f32 vector, as
+    the (p, j, x) tensors of a CSR with A.m rows and v.numel() columns: every non-empty row of X times v, through the
+    row's first stored value.  An f32 v gives the float product, widened."""
+    lib = _lib.load()
+    dev = A.indptr.device
+    _one_column(A, "csr_outer_dense")
+    if v.dtype not in (torch.float64, torch.float32) or v.dim() != 1 or v.device != dev:
+        raise ValueError(f"csr_outer_dense: v must be a 1-d float64 or float32 tensor on {dev}")
+    v = v.contiguous()
+    dim = int(v.numel())
+    ws = torch.empty(max(lib.mxd_csr_outer_dense_workspace_bytes(A.m), 16), dtype=torch.uint8, device=dev)
+    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
+    total = C.c_int64(0)
+    check(lib.mxd_csr_outer_dense_count(A.m, dim, _dp(A.indptr), _dp(ws), _dp(out_p), C.byref(total), _stream()))
+    k = int(total.value)
+    out_j = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
+    if k:
+        check(lib.mxd_csr_outer_dense_fill(A.m, dim, A.nnz, _dp(A.indptr), _dp(A.values), _dp(v),
+                                           MX_F64 if v.dtype == torch.float64 else MX_F32, _dp(out_p), _dp(out_j),
+                                           _dp(out_x), _stream()))
+    return out_p, out_j[:k], out_x[:k]
+
+
+def csr_outer_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, length: int, v_dtype=None):
+    """X %*% v for a device-resident one-column CSR X and a sparse vector, as the (p, i, x) tensors
+    of a CSC with A.m rows and `length` columns: column vi[k] - 1 holds every non-empty row of X, ascending, times
+    vx[k].  vi: sorted, unique 1-based int32 positions; vx: f64 values, int32 values (v_dtype MX_I32, the default, or
+    MX_LGL; NA gives NA_real_), or None for an nsparseVector."""
+    lib = _lib.load()
+    dev = A.indptr.device
+    _one_column(A, "csr_outer_svec")
+    if vi.dtype != torch.int32 or vi.dim() != 1 or vi.device != dev:
+        raise ValueError(f"csr_outer_svec: vi must be a 1-d int32 tensor on {dev}")
+    if vx is not None and (vx.dtype not in (torch.float64, torch.int32) or vx.shape != vi.shape or vx.device != dev):
+        raise ValueError("csr_outer_svec: vx must be float64 or int32, of vi's shape and on its device")
+    if v_dtype is None:
+        v_dtype = MX_NONE if vx is None else MX_F64 if vx.dtype == torch.float64 else _lib.MX_I32
+    length, nv = int(length), int(vi.numel())
+    if length < 0 or nv > length:
+        raise ValueError("csr_outer_svec: more stored positions than the vector's length")
+    vi = vi.contiguous()
+    vx = None if vx is None else vx.contiguous()
+    ws = torch.empty(max(lib.mxd_csr_outer_svec_workspace_bytes(A.m, length), 16), dtype=torch.uint8, device=dev)
+    out_p = torch.empty(length + 1, dtype=torch.int32, device=dev)
+    nonempty, total = C.c_int64(0), C.c_int64(0)
+    check(lib.mxd_csr_outer_svec_count(A.m, A.nnz, _dp(A.indptr), _dp(A.values), _dp(vi), nv, length, _dp(ws),
+                                       _dp(out_p), C.byref(nonempty), C.byref(total), _stream()))
+    k = int(total.value)
+    out_i = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
+    if k:
+        check(lib.mxd_csr_outer_svec_fill(A.m, _dp(vi), nv, _dp(vx), v_dtype, length, nonempty.value, _dp(ws),
+                                          _dp(out_p), _dp(out_i), _dp(out_x), _stream()))
+    return out_p, out_i[:k], out_x[:k]
+
+
+def rowvec_by_csc(v: torch.Tensor, A: DeviceCSR):
+    """v %*% Y for a float32 row vector and a device-resident CSC Y held as DeviceCSR(p, i, x): A.m compressed columns
+    over A.K rows, f64 values or None.  Returns float32[A.m]: per column the sum of x * v[i], each
+    product in double, accumulated in float.  The row ids must lie below v.numel()."""
+    lib = _lib.load()
+    dev = A.indptr.device
+    if v.dtype != torch.float32 or v.dim() != 1 or v.device != dev or int(v.numel()) != A.K:
+        raise ValueError(f"rowvec_by_csc: v must be a 1-d float32 tensor of Y's {A.K} rows on {dev}")
+    if A.values is not None and A.values.dtype != torch.float64:
+        raise ValueError("rowvec_by_csc: Y needs float64 values or none")
+    out = torch.empty(A.m, dtype=torch.float32, device=dev)
+    check(lib.mxd_rowvec_by_csc(A.m, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v.contiguous()), _dp(out),
+                                _stream()))
+    return out

@@ -362,6 +362,90 @@ def matmul_csr_svec_float32(X_csr_indptr, X_csr_indices, X_csr_values, y_indices
     return _svec(4, X_csr_indptr, X_csr_indices, X_csr_values, y_indices_base1, y_values, nthreads)
 
 
+# ----------------------------------------------------------------------------- outer products, row vector x CSC (outer.hip)
+def _as_f32(a):
+    """float32 values; an int32 array is the float32@Data bits, as the R side passes them"""
+    a = np.asarray(a)
+    if a.dtype == np.int32:
+        a = a.view(np.float32)
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+
+
+def _rowvec(rowvec_, indptr, indices, values):
+    v, p, i = _as_f32(rowvec_), _i32(indptr), _i32(indices)
+    x = None if values is None else _f64(values)
+    if i.size < p[-1] or (x is not None and x.size < p[-1]):
+        raise ValueError("indices / values shorter than the index pointer says")
+    out = np.empty((1, p.size - 1), dtype=np.float32, order="F")
+    check(_lib.load().mx_matmul_rowvec_by_csc(ptr(v), v.size, ptr(p), p.size - 1, ptr(i), ptr(x), ptr(out)))
+    return out
+
+
+def matmul_rowvec_by_csc(rowvec_, indptr, indices, values):
+    """src/matmul.cpp:643-663: a 1 x ncol float32 matrix (the reference's IntegerMatrix of float bits)."""
+    return _rowvec(rowvec_, indptr, indices, values)
+
+
+def matmul_rowvec_by_cscbin(rowvec_, indptr, indices):
+    """src/matmul.cpp:665-684."""
+    return _rowvec(rowvec_, indptr, indices, None)
+
+
+def _outer_dense(colvec, dtype, indptr, indices, values_):
+    p, j, x = _i32(indptr), _i32(indices), _f64(values_)
+    if x.size < p[-1]:
+        raise ValueError("values shorter than the index pointer says")
+    return _begin(_lib.load().mx_matmul_colvec_by_scolvecascsr_begin, ptr(colvec), dtype, colvec.size, ptr(p),
+                  p.size - 1, ptr(j), ptr(x))[0]
+
+
+def matmul_colvec_by_scolvecascsr_f32(colvec_, indptr, indices, values_):
+    """src/matmul.cpp:747-762.  The arrays have out_indptr[-1] entries; the reference pads them with zeros to
+    length(indices) * length(colvec) when a row stores more than one entry."""
+    return _outer_dense(_as_f32(colvec_), _lib.MX_F32, indptr, indices, values_)
+
+
+def matmul_colvec_by_scolvecascsr(colvec_, indptr, indices, values_):
+    """src/matmul.cpp:766-781."""
+    return _outer_dense(_f64(colvec_).reshape(-1), MX_F64, indptr, indices, values_)
+
+
+def _outer_svec(value_dtype, X_csr_indptr, X_csr_indices, X_csr_values, y_indices_base1, y_values, y_length):
+    p, j, x, yi = _i32(X_csr_indptr), _i32(X_csr_indices), _f64(X_csr_values), _i32(y_indices_base1)
+    yv = None
+    if value_dtype == MX_F64:
+        yv = _f64(y_values)
+    elif value_dtype != MX_NONE:
+        yv = _i32(y_values)
+    if x.size < p[-1] or (yv is not None and yv.size != yi.size):
+        raise ValueError("values and index vectors have different lengths")
+    return _begin(_lib.load().mx_matmul_spcolvec_by_scolvecascsr_begin, ptr(p), p.size - 1, ptr(j), ptr(x), ptr(yi),
+                  ptr(yv), value_dtype, yi.size, int(y_length))[0]
+
+
+def matmul_spcolvec_by_scolvecascsr_numeric(X_csr_indptr, X_csr_indices, X_csr_values, y_indices_base1, y_values,
+                                            y_length):
+    """src/matmul.cpp:857-876 (with y_values[k] where :808 reads y_values[col])."""
+    return _outer_svec(MX_F64, X_csr_indptr, X_csr_indices, X_csr_values, y_indices_base1, y_values, y_length)
+
+
+def matmul_spcolvec_by_scolvecascsr_integer(X_csr_indptr, X_csr_indices, X_csr_values, y_indices_base1, y_values,
+                                            y_length):
+    """src/matmul.cpp:878-897."""
+    return _outer_svec(_lib.MX_I32, X_csr_indptr, X_csr_indices, X_csr_values, y_indices_base1, y_values, y_length)
+
+
+def matmul_spcolvec_by_scolvecascsr_logical(X_csr_indptr, X_csr_indices, X_csr_values, y_indices_base1, y_values,
+                                            y_length):
+    """src/matmul.cpp:899-918."""
+    return _outer_svec(MX_LGL, X_csr_indptr, X_csr_indices, X_csr_values, y_indices_base1, y_values, y_length)
+
+
+def matmul_spcolvec_by_scolvecascsr_binary(X_csr_indptr, X_csr_indices, X_csr_values, y_indices_base1, y_length):
+    """src/matmul.cpp:920-938."""
+    return _outer_svec(MX_NONE, X_csr_indptr, X_csr_indices, X_csr_values, y_indices_base1, None, y_length)
+
+
 def _csr_by_dense(kind, indptr, indices, values, dense_mat):
     p, j = _i32(indptr), _i32(indices)
     ddt = {0: np.float64, 1: np.float32, 2: np.int32, 3: np.int32, 4: np.int32}[kind]

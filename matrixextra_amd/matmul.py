@@ -9,9 +9,9 @@ from __future__ import annotations
 import numpy as np
 
 from . import exports
-from .matrices import (DenseMatrix, RsparseMatrix, as_csr_matrix, check_valid_matrix, dgCMatrix, dgRMatrix,
-                       dimnames_of, dsparseVector, float32, isparseVector, lsparseVector, nsparseVector, options,
-                       sort_sparse_indices, sparseVector, stop)
+from .matrices import (NA_INTEGER, NA_REAL, DenseMatrix, RsparseMatrix, as_csr_matrix, as_sparse_vector,
+                       check_valid_matrix, dgCMatrix, dgRMatrix, dimnames_of, dsparseVector, float32, isparseVector,
+                       lsparseVector, nsparseVector, options, sort_sparse_indices, sparseVector, stop)
 
 
 def _nthreads():
@@ -182,6 +182,7 @@ def gemv_csr_vec(x, y):
 
 _SVEC_OUTER = ("A one-column RsparseMatrix times a sparseVector is the reference's outer product "
                "(outerprod_csrsinglecol_by_dvec, R/matmul.R:659-752), which is not on the accelerated path.")
+# (taken on the device under options["mxgpu.outer_route"]: outerprod_csrsinglecol_by_dvec below)
 
 
 def _gemv_csr_svec(x, y):
@@ -210,6 +211,122 @@ def _gemv_csr_svec(x, y):
     return DenseMatrix(res.reshape(-1, 1), [dimnames_of(x)[0], None])
 
 
+# ---- outer products and float32 vector forms (outer.hip) ------------------------------------------
+def _outer_route():
+    """The routes below are taken only under options["mxgpu.outer_route"]; without it every refusal stays."""
+    return bool(options.get("mxgpu.outer_route", False))
+
+
+def _names(v):
+    """names(v) of a vector operand: its `names` attribute when it carries one"""
+    return getattr(v, "names", None)
+
+
+def _outer_csr(res, Dim, Dimnames):
+    return dgRMatrix(res["indptr"], res["indices"], res["values"], Dim, Dimnames)
+
+
+def _outer_csc(res, Dim, Dimnames):
+    return dgCMatrix(res["indptr"], res["indices"], res["values"], Dim, Dimnames)
+
+
+def outerprod_csrsinglecol_by_dvec(x, y):
+    """A one-column RsparseMatrix %*% vector or sparseVector — R/matmul.R:659-744: a dgCMatrix of nrow(x) x length(y)
+    for a sparse y, a dgRMatrix for a dense one."""
+    if x.Dim[1] != 1:
+        stop("Internal error. Please open an issue in GitHub describing what you were doing.")
+    x = as_csr_matrix(x)                                              # :663-668: anything but a plain dgRMatrix
+    check_valid_matrix(x)
+    rn = dimnames_of(x)[0]
+    if isinstance(y, sparseVector):
+        inplace_sort = bool(options.get("MatrixExtra.inplace_sort", False))
+        if type(y) not in (dsparseVector, isparseVector, lsparseVector, nsparseVector):
+            return outerprod_csrsinglecol_by_dvec(x, as_sparse_vector(y))        # as(y, "dsparseVector"), :710-713
+        y = sort_sparse_indices(y, copy=not inplace_sort)
+        if isinstance(y, dsparseVector):
+            res = exports.matmul_spcolvec_by_scolvecascsr_numeric(x.p, x.j, x.x, y.i, y.x, y.length)
+        elif isinstance(y, isparseVector):
+            res = exports.matmul_spcolvec_by_scolvecascsr_integer(x.p, x.j, x.x, y.i, y.x, y.length)
+        elif isinstance(y, lsparseVector):
+            res = exports.matmul_spcolvec_by_scolvecascsr_logical(x.p, x.j, x.x, y.i, y.x, y.length)
+        else:
+            res = exports.matmul_spcolvec_by_scolvecascsr_binary(x.p, x.j, x.x, y.i, y.length)
+        return _outer_csc(res, (x.Dim[0], y.length), [rn, None])     # :714-720
+    names = _names(y)
+    yv = np.asarray(y)
+    if yv.ndim != 1:
+        stop("Matrix-vector dimensions do not match.")
+    if yv.dtype != np.float64:                                        # mode(y) <- "double", :723-724
+        yv = np.where(yv == NA_INTEGER, NA_REAL, yv.astype(np.float64)) if yv.dtype == np.int32 \
+            else yv.astype(np.float64)
+    res = exports.matmul_colvec_by_scolvecascsr(yv, x.p, x.j, x.x)
+    return _outer_csr(res, (x.Dim[0], yv.size), [rn, names])         # :732-741
+
+
+def matmul_csr_vec(x, y):
+    """RsparseMatrix %*% numeric / logical / integer / sparseVector — R/matmul.R:746-767."""
+    if x.Dim[1] == 1:
+        return outerprod_csrsinglecol_by_dvec(x, y)
+    return gemv_csr_vec(x, y)
+
+
+def _gemm_csr_f32_vec(x, y):
+    """The vector branch of gemm_csr_f32, R/matmul.R:478-505."""
+    if x.Dim[1] != 1:
+        return gemv_csr_vec(x, y)
+    x = as_csr_matrix(x)
+    check_valid_matrix(x)
+    res = exports.matmul_colvec_by_scolvecascsr_f32(y.Data, x.p, x.j, x.x)
+    return _outer_csr(res, (x.Dim[0], y.Data.size), [dimnames_of(x)[0], _names(y)])
+
+
+def _f32_outer_csc(x, res, ncol, y):
+    """R/matmul.R:232-241 / :339-348: a dgCMatrix of length(x) x ncol that takes y's column names, or names(x) when
+    x carries some (the reference sets them as the column names)."""
+    names = _names(x)
+    return _outer_csc(res, (x.Data.size, ncol), [None, names if names is not None else dimnames_of(y)[1]])
+
+
+def _rowvec_by_sparse(x, p, idx, values):
+    if values is not None:
+        return float32(exports.matmul_rowvec_by_csc(x.Data, p, idx, values))
+    return float32(exports.matmul_rowvec_by_cscbin(x.Data, p, idx))
+
+
+def _gemm_f32vec_csc(x, y):
+    """The vector branch of gemm_f32_csc, R/matmul.R:209-262: to match base R, x is [n, 1] when y has one row and
+    [1, n] otherwise."""
+    check_valid_matrix(y)
+    if y.Dim[0] == 1:
+        res = exports.matmul_colvec_by_scolvecascsr_f32(x.Data, y.p, y.i, y.x)
+        return _f32_outer_csc(x, res, y.Dim[1], y)
+    if y.Dim[0] != x.Data.size:
+        stop("(row) vector-Matrix multiplication dimensions do not match.")
+    return _rowvec_by_sparse(x, y.p, y.i, y.x)
+
+
+def _tcrossprod_f32vec_csr(x, y):
+    """The vector branch of tcrossprod_f32_csr, R/matmul.R:316-367: x is [n, 1] when y has one column, else [1, n]
+    (no dimension check in the reference; the export refuses an index outside the vector)."""
+    if y.x is not None and not isinstance(y, dgRMatrix):
+        y = as_csr_matrix(y)
+    check_valid_matrix(y)
+    if y.Dim[1] == 1:
+        y = as_csr_matrix(y)
+        check_valid_matrix(y)
+        res = exports.matmul_colvec_by_scolvecascsr_f32(x.Data, y.p, y.j, y.x)
+        return _f32_outer_csc(x, res, y.Dim[0], y)
+    return _rowvec_by_sparse(x, y.p, y.j, y.x)
+
+
+def crossprod_f32_csc(x, y):
+    """crossprod(float32 vector, CsparseMatrix) — R/matmul.R:395-430."""
+    if x.Data.size != y.Dim[0]:
+        stop("(column) vector-Matrix crossprod dimensions do not match.")
+    check_valid_matrix(y)
+    return _rowvec_by_sparse(x, y.p, y.i, y.x)
+
+
 class RLogical(np.ndarray):
     """An int32 vector tagged as an R logical ({0,1,NA_LOGICAL}) so `%*%` picks the logical kernel."""
     r_logical = True
@@ -222,17 +339,24 @@ class RLogical(np.ndarray):
 def matmul(x, y):
     """`%*%` for the signatures the hot path registers (R/matmul.R:200,281,469,512,755-767)."""
     if isinstance(x, RsparseMatrix):
+        outer = _outer_route()
         if isinstance(y, float32):
-            return gemv_csr_vec(x, y) if y.is_vector else gemm_csr_f32(x, y)
+            if y.is_vector:
+                return _gemm_csr_f32_vec(x, y) if outer else gemv_csr_vec(x, y)
+            return gemm_csr_f32(x, y)
         if isinstance(y, sparseVector):               # R/matmul.R:755-767: one column -> the outer product
             if x.Dim[1] == 1:
+                if outer:
+                    return outerprod_csrsinglecol_by_dvec(x, y)
                 stop(_SVEC_OUTER)
             return gemv_csr_vec(x, y)
         y_arr = np.asarray(y)
         if y_arr.ndim == 1:
-            return gemv_csr_vec(x, y)
+            return matmul_csr_vec(x, y) if outer else gemv_csr_vec(x, y)
         return gemm_csr_dense(x, y)
     if isinstance(y, dgCMatrix):
+        if isinstance(x, float32) and x.is_vector and _outer_route():
+            return _gemm_f32vec_csc(x, y)
         return gemm_f32_csc(x, y) if isinstance(x, float32) else gemm_dense_csc(x, y)
     stop("Unsupported operand types for %*% in the MI355X hot path.")
 
@@ -242,12 +366,17 @@ def tcrossprod(x, y):
     if isinstance(x, RsparseMatrix):
         return tcrossprod_csr_f32(x, y) if isinstance(y, float32) else tcrossprod_csr_dense(x, y)
     if isinstance(y, RsparseMatrix):
+        if isinstance(x, float32) and x.is_vector and _outer_route():
+            return _tcrossprod_f32vec_csr(x, y)
         return tcrossprod_f32_csr(x, y) if isinstance(x, float32) else tcrossprod_dense_csr(x, y)
     stop("Unsupported operand types for tcrossprod in the MI355X hot path.")
 
 
 def crossprod(x, y):
-    """crossprod(matrix, CsparseMatrix) — R/matmul.R:393."""
+    """crossprod(matrix, CsparseMatrix) — R/matmul.R:393; (float32 vector, CsparseMatrix) — :434, under
+    options["mxgpu.outer_route"]."""
+    if isinstance(y, dgCMatrix) and isinstance(x, float32) and x.is_vector and _outer_route():
+        return crossprod_f32_csc(x, y)
     if isinstance(y, dgCMatrix) and not isinstance(x, float32):
         return crossprod_dense_csc(x, y)
     stop("Unsupported operand types for crossprod in the MI355X hot path.")
