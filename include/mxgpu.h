@@ -295,6 +295,40 @@ int mxd_csr_by_svec_fill(int m, int ncol, int64_t nnz, const int32_t *indptr, co
                          int keep_na, const void *workspace, const int32_t *out_indptr, int32_t *out_indices,
                          double *out_values, void *stream);
 
+/* Dense matrix * sparse vector (multiply_elemwise_dense_by_svec_template<>, src/operators.cpp:3699-4303; densevec.hip;
+ * DESIGN.md §4.15).  X is nrows x ncols, column-major, of dense_kind 0 double, 1 float32, 2 R integer, 3 R logical;
+ * the vector is vi_base1[nv] (1-based positions), vx[nv] f64 values and its length.  A stored cell holds X * value
+ * (float32 widened per cell; NA_INTEGER gives C's NAN, and NA_real_ on the CSR route with length == nrows and
+ * keep_na == 0, :3803).  A position outside 1..length is ignored here; the export level refuses it.
+ * mxd_dense_by_svec_dense (routes A and D, :3720-3763 and :4235-4300): out_colmajor[nrows * ncols], the vector
+ *   recycled over the flat column-major cell index; cells it does not cover hold 0, or under keep_na the fill of a
+ *   special cell (an f64 NaN unchanged; an f64 +-Inf or a float32 NaN / +-Inf as C's NAN; NA_INTEGER as NA_real_).  Of a
+ *   repeated position the last entry rules.  Cell indices >= nrows * ncols are never written (:4273 writes one).
+ * mxd_dense_by_svec_count / _fill (routes B and C, :3765-4233): a CSR result, length dividing nrows, the vector
+ *   recycled down the rows.  A row whose position is stored is a full row of products; the others are empty, or
+ *   under keep_na hold their special cells in column order with the fill above (NA_real_ also where :4113-4120
+ *   pushes (double)NA_INTEGER).  Of a repeated position the first entry rules.  With length < nrows, an f64 X and
+ *   keep_na == 0 the product is daxpy's: +0.0 for a value of 0, else 0.0 + value * X (:4005-4015).
+ *   count: out_indptr[nrows+1], *nnz_out_host = entries (64-bit; above INT32_MAX the call fails; one synchronise).
+ *   fill: out_indices / out_values of that many entries.  workspace: mxd_dense_by_svec_workspace_bytes(nrows,
+ *   length); the count leaves the position map there for the fill.  _dense takes the same workspace (nrows may be 0). */
+size_t mxd_dense_by_svec_workspace_bytes(int nrows, int length);
+int mxd_dense_by_svec_dense(int nrows, int ncols, const void *dense_colmajor, int dense_kind,
+                            const int32_t *vi_base1, int64_t nv, const double *vx, int length, int keep_na,
+                            void *workspace, double *out_colmajor, void *stream);
+int mxd_dense_by_svec_count(int nrows, int ncols, const void *dense_colmajor, int dense_kind,
+                            const int32_t *vi_base1, int64_t nv, int length, int keep_na, void *workspace,
+                            int32_t *out_indptr, int64_t *nnz_out_host, void *stream);
+int mxd_dense_by_svec_fill(int nrows, int ncols, const void *dense_colmajor, int dense_kind, const double *vx,
+                           int length, int keep_na, const void *workspace, const int32_t *out_indptr,
+                           int32_t *out_indices, double *out_values, void *stream);
+/* COO * dense matrix, values only (multiply_coo_by_dense<>, src/operators.cpp:721-770; densevec.hip): out[k] =
+ * xx[k] * dense[ii[k] + jj[k] * nrows] for kind 0 double, 1 float32, 2 R integer, 3 R logical (read as bool), with
+ * NA_INTEGER / NA_LOGICAL giving NA_real_; kind 4: xx, dense and out are R logicals, R's three-valued and.  An entry
+ * outside the matrix reads nothing and gives NA here; the export level refuses it. */
+int mxd_coo_by_dense(int64_t nnz, const int32_t *ii, const int32_t *jj, const void *xx, const void *dense_colmajor,
+                     int nrows, int ncols, int kind, void *out, void *stream);
+
 /* The outer products of `%*%` with a one-column CSR, and the float32 row vector x CSC product (outer.hip; DESIGN.md
  * §4.14).  X is the CSR triple of a one-column matrix with m rows: row r is non-empty when indptr[r] < indptr[r+1]
  * and its value is values[indptr[r]], the first stored entry; the column indices are never read.
@@ -884,6 +918,43 @@ int mx_matmul_spcolvec_by_scolvecascsr_begin(const int32_t *X_indptr, int nrows,
  * index must lie in [0, len_rowvec), which is checked here and not in the reference */
 int mx_matmul_rowvec_by_csc(const float *rowvec, int64_t len_rowvec, const int32_t *indptr, int ncols,
                             const int32_t *indices, const double *values, float *out);
+
+/* multiply_elemwise_dense_by_svec_{numeric,float32,integer,logical}  src/operators.cpp:3699-4379 (kind 0, 1, 2, 3 as
+ * for the csc (.) dense entries; X_colmajor holds nrows * ncols doubles, float32 values or R integers / logicals).
+ * mx_dense_by_svec_route is the reference's choice of route (:3720, :3765, :3984, :4235), taken in that order:
+ *   MX_DSV_ROUTE_A  length == nrows * ncols                    dense result
+ *   MX_DSV_ROUTE_B  length == nrows                            CSR result
+ *   MX_DSV_ROUTE_C  length < nrows and nrows % length == 0     CSR result, the vector recycled down the rows
+ *   MX_DSV_ROUTE_D  anything else                              dense result, the vector recycled over the cells
+ * or -1 for a negative argument, or a vector without length next to a matrix with cells.
+ * _begin serves routes B and C through mxd_dense_by_svec_count / _fill: a new indptr (nrows + 1), indices and f64
+ * values; _dense serves routes A and D through mxd_dense_by_svec_dense and writes out_colmajor[nrows * ncols].  Either
+ * fails on the other's routes.  Refused before any launch, where the reference checks nothing: a position outside
+ * 1..length, nnz_v > length, and (through the count) a CSR result above INT32_MAX entries.  ii_base1 sorted when
+ * keep_NAs is set, as the R side makes it. */
+typedef enum { MX_DSV_ROUTE_A = 0, MX_DSV_ROUTE_B = 1, MX_DSV_ROUTE_C = 2, MX_DSV_ROUTE_D = 3 } mx_dsv_route;
+int mx_dense_by_svec_route(int nrows, int ncols, int length);
+int mx_multiply_elemwise_dense_by_svec_begin(const void *X_colmajor, int kind, int nrows, int ncols,
+                                             const int32_t *ii_base1, const double *xx, int64_t nnz_v, int length,
+                                             int keep_NAs, mx_result **res, mx_result_info *info);
+int mx_multiply_elemwise_dense_by_svec_dense(const void *X_colmajor, int kind, int nrows, int ncols,
+                                             const int32_t *ii_base1, const double *xx, int64_t nnz_v, int length,
+                                             int keep_NAs, double *out_colmajor);
+/* multiply_coo_by_dense_{numeric,integer,logical,float32}  src/operators.cpp:772-838, and
+ * logicaland_coo_by_dense_logical  :840-855, through mxd_coo_by_dense: values_out[nnz] (f64; R logicals for the
+ * and); the row and column vectors of the result are the caller's (the reference copies them, :763-769).  X_colmajor
+ * is nrows x ncols.  An entry with ii outside [0, nrows) or jj outside [0, ncols) is refused before any launch; the
+ * reference does not check. */
+int mx_multiply_coo_by_dense_numeric(const double *X_colmajor, int nrows, int ncols, const int32_t *ii,
+                                     const int32_t *jj, const double *xx, int64_t nnz, double *values_out);
+int mx_multiply_coo_by_dense_integer(const int32_t *X_colmajor, int nrows, int ncols, const int32_t *ii,
+                                     const int32_t *jj, const double *xx, int64_t nnz, double *values_out);
+int mx_multiply_coo_by_dense_logical(const int32_t *X_colmajor, int nrows, int ncols, const int32_t *ii,
+                                     const int32_t *jj, const double *xx, int64_t nnz, double *values_out);
+int mx_multiply_coo_by_dense_float32(const float *X_colmajor, int nrows, int ncols, const int32_t *ii,
+                                     const int32_t *jj, const double *xx, int64_t nnz, double *values_out);
+int mx_logicaland_coo_by_dense_logical(const int32_t *X_colmajor, int nrows, int ncols, const int32_t *ii,
+                                       const int32_t *jj, const int32_t *xx, int64_t nnz, int32_t *values_out);
 
 #ifdef __cplusplus
 }

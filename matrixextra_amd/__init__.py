@@ -21,7 +21,8 @@ from .matrices import (as_sparse_vector, dsparseVector, isparseVector, lsparseVe
                        sparseVector)
 from .matmul import RLogical, crossprod, tcrossprod  # noqa: F401  (`%*%` is the @ operator)
 from .operators import (add_csr_matrices, logicalor_csr_matrices, multiply_csr_by_coo,  # noqa: F401
-                        multiply_csr_by_csr, multiply_csr_by_svec_elemwise, xor_csr_matrices)
+                        multiply_csr_by_csr, multiply_csr_by_svec_elemwise, multiply_elemwise_dense_by_svec,
+                        xor_csr_matrices)
 from .slice import subset_coo, subset_csr  # noqa: F401
 from .cleanup import check_sparse_matrix, filterSparse, remove_sparse_zeros  # noqa: F401
 

@@ -737,6 +737,144 @@ int mx_multiply_csr_by_svec_begin(const int32_t *indptr, int nrows, const int32_
     });
 }
 
+// ---- dense matrix * sparse vector, COO * dense matrix (densevec.hip) ---------------------------
+// the route of multiply_elemwise_dense_by_svec_template<> (operators.cpp:3720, :3765, :3984, :4235)
+int mx_dense_by_svec_route(int nrows, int ncols, int length)
+{
+    if (nrows < 0 || ncols < 0 || length < 0 || (length == 0 && (int64_t)nrows * ncols != 0)) {
+        set_error("mx_dense_by_svec_route: bad arguments");
+        return -1;
+    }
+    if ((int64_t)length == (int64_t)nrows * (int64_t)ncols) return MX_DSV_ROUTE_A;
+    if (length == nrows) return MX_DSV_ROUTE_B;
+    if (length < nrows && nrows % length == 0) return MX_DSV_ROUTE_C;
+    return MX_DSV_ROUTE_D;
+}
+
+// what the reference does not check (operators.cpp:3709-3712): the vector against its own length
+static int dense_by_svec_check(const char *what, const void *X, int kind, int nrows, int ncols, const int32_t *ii,
+                               const double *xx, int64_t nnz_v, int length)
+{
+    MX_REQUIRE(kind >= 0 && kind <= 3 && nnz_v >= 0 && mx_dense_by_svec_route(nrows, ncols, length) >= 0,
+               "%s: bad arguments", what);
+    MX_REQUIRE(((int64_t)nrows * ncols == 0 || X) && (nnz_v == 0 || (ii && xx)), "%s: null pointer", what);
+    MX_REQUIRE(nnz_v <= (int64_t)length, "%s: the vector stores %lld positions, more than its length %d", what,
+               (long long)nnz_v, length);
+    for (int64_t k = 0; k < nnz_v; k++)
+        MX_REQUIRE(ii[k] >= 1 && ii[k] <= length, "%s: position %d lies outside 1..%d", what, ii[k], length);
+    return 0;
+}
+
+// multiply_elemwise_dense_by_svec_{numeric,float32,integer,logical}, routes B and C  src/operators.cpp:3765-4233
+int mx_multiply_elemwise_dense_by_svec_begin(const void *X_colmajor, int kind, int nrows, int ncols,
+                                             const int32_t *ii_base1, const double *xx, int64_t nnz_v, int length,
+                                             int keep_NAs, mx_result **res_out, mx_result_info *info)
+{
+    const char *what = "mx_multiply_elemwise_dense_by_svec_begin";
+    MX_REQUIRE(res_out && info, "%s: null output pointer", what);
+    *res_out = nullptr;
+    if (dense_by_svec_check(what, X_colmajor, kind, nrows, ncols, ii_base1, xx, nnz_v, length)) return 1;
+    const int route = mx_dense_by_svec_route(nrows, ncols, length);
+    MX_REQUIRE(route == MX_DSV_ROUTE_B || route == MX_DSV_ROUTE_C,
+               "%s: a vector of length %d against %d x %d gives a dense result", what, length, nrows, ncols);
+    const size_t cell = kind == 0 ? 8 : 4;
+    return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
+        DevBuf X, vi, vx, ws;
+        if (X.upload(X_colmajor, cell * (size_t)nrows * (size_t)ncols)) return 1;
+        if (vi.upload(ii_base1, sizeof(int32_t) * (size_t)nnz_v)) return 1;
+        if (vx.upload(xx, sizeof(double) * (size_t)nnz_v)) return 1;
+        if (ws.alloc(mxd_dense_by_svec_workspace_bytes(nrows, length))) return 1;
+        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        int64_t total = 0;
+        if (mxd_dense_by_svec_count(nrows, ncols, X.p, kind, vi.as<int32_t>(), nnz_v, length, keep_NAs, ws.p,
+                                    res.indptr.as<int32_t>(), &total, nullptr)) return 1;
+        res.set_sizes((int64_t)nrows + 1, total, total);
+        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
+        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+        if (total == 0) return 0;
+        return mxd_dense_by_svec_fill(nrows, ncols, X.p, kind, vx.as<double>(), length, keep_NAs, ws.p,
+                                      res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.as<double>(),
+                                      nullptr);
+    });
+}
+
+// multiply_elemwise_dense_by_svec_{numeric,float32,integer,logical}, routes A and D  :3720-3763, :4235-4300
+int mx_multiply_elemwise_dense_by_svec_dense(const void *X_colmajor, int kind, int nrows, int ncols,
+                                             const int32_t *ii_base1, const double *xx, int64_t nnz_v, int length,
+                                             int keep_NAs, double *out_colmajor)
+{
+    const char *what = "mx_multiply_elemwise_dense_by_svec_dense";
+    if (dense_by_svec_check(what, X_colmajor, kind, nrows, ncols, ii_base1, xx, nnz_v, length)) return 1;
+    const int route = mx_dense_by_svec_route(nrows, ncols, length);
+    MX_REQUIRE(route == MX_DSV_ROUTE_A || route == MX_DSV_ROUTE_D,
+               "%s: a vector of length %d against %d x %d gives a CSR result", what, length, nrows, ncols);
+    const size_t cells = (size_t)nrows * (size_t)ncols;
+    if (cells == 0) return 0;
+    MX_REQUIRE(out_colmajor, "%s: null pointer", what);
+    DevBuf X, vi, vx, ws, out;
+    if (X.upload(X_colmajor, (kind == 0 ? 8 : 4) * cells)) return 1;
+    if (vi.upload(ii_base1, sizeof(int32_t) * (size_t)nnz_v)) return 1;
+    if (vx.upload(xx, sizeof(double) * (size_t)nnz_v)) return 1;
+    if (ws.alloc(mxd_dense_by_svec_workspace_bytes(0, length))) return 1;
+    if (out.alloc(sizeof(double) * cells)) return 1;
+    if (mxd_dense_by_svec_dense(nrows, ncols, X.p, kind, vi.as<int32_t>(), nnz_v, vx.as<double>(), length, keep_NAs,
+                                ws.p, out.as<double>(), nullptr)) return 1;
+    return mx::xfer_d2h(out_colmajor, out.p, sizeof(double) * cells);
+}
+
+// multiply_coo_by_dense<> (operators.cpp:721-770): values only; kind 4 is the logical and
+static int coo_by_dense(const char *what, const void *X, int nrows, int ncols, const int32_t *ii, const int32_t *jj,
+                        const void *xx, int64_t nnz, int kind, void *values_out)
+{
+    MX_REQUIRE(nrows >= 0 && ncols >= 0 && nnz >= 0 && nnz <= (int64_t)INT_MAX, "%s: bad arguments", what);
+    if (nnz == 0) return 0;
+    MX_REQUIRE(ii && jj && xx && values_out, "%s: null pointer", what);
+    for (int64_t k = 0; k < nnz; k++)             // the reference reads X wherever the entry points (:740)
+        MX_REQUIRE(ii[k] >= 0 && ii[k] < nrows && jj[k] >= 0 && jj[k] < ncols,
+                   "%s: entry %lld (%d, %d) lies outside the %d x %d matrix", what, (long long)k, ii[k], jj[k], nrows,
+                   ncols);
+    MX_REQUIRE(X, "%s: null pointer", what);
+    const size_t vb = kind == 4 ? 4 : 8;
+    DevBuf D, i, j, x, o;
+    if (D.upload(X, (kind == 0 ? 8 : 4) * (size_t)nrows * (size_t)ncols)) return 1;
+    if (i.upload(ii, sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (j.upload(jj, sizeof(int32_t) * (size_t)nnz)) return 1;
+    if (x.upload(xx, vb * (size_t)nnz)) return 1;
+    if (o.alloc(vb * (size_t)nnz)) return 1;
+    if (mxd_coo_by_dense(nnz, i.as<int32_t>(), j.as<int32_t>(), x.p, D.p, nrows, ncols, kind, o.p, nullptr)) return 1;
+    return mx::xfer_d2h(values_out, o.p, vb * (size_t)nnz);
+}
+// multiply_coo_by_dense_numeric  src/operators.cpp:772-787
+int mx_multiply_coo_by_dense_numeric(const double *X_colmajor, int nrows, int ncols, const int32_t *ii,
+                                     const int32_t *jj, const double *xx, int64_t nnz, double *values_out)
+{
+    return coo_by_dense("mx_multiply_coo_by_dense_numeric", X_colmajor, nrows, ncols, ii, jj, xx, nnz, 0, values_out);
+}
+// multiply_coo_by_dense_integer  :789-804
+int mx_multiply_coo_by_dense_integer(const int32_t *X_colmajor, int nrows, int ncols, const int32_t *ii,
+                                     const int32_t *jj, const double *xx, int64_t nnz, double *values_out)
+{
+    return coo_by_dense("mx_multiply_coo_by_dense_integer", X_colmajor, nrows, ncols, ii, jj, xx, nnz, 2, values_out);
+}
+// multiply_coo_by_dense_logical  :806-821
+int mx_multiply_coo_by_dense_logical(const int32_t *X_colmajor, int nrows, int ncols, const int32_t *ii,
+                                     const int32_t *jj, const double *xx, int64_t nnz, double *values_out)
+{
+    return coo_by_dense("mx_multiply_coo_by_dense_logical", X_colmajor, nrows, ncols, ii, jj, xx, nnz, 3, values_out);
+}
+// multiply_coo_by_dense_float32  :823-838 (float32@Data bit patterns)
+int mx_multiply_coo_by_dense_float32(const float *X_colmajor, int nrows, int ncols, const int32_t *ii,
+                                     const int32_t *jj, const double *xx, int64_t nnz, double *values_out)
+{
+    return coo_by_dense("mx_multiply_coo_by_dense_float32", X_colmajor, nrows, ncols, ii, jj, xx, nnz, 1, values_out);
+}
+// logicaland_coo_by_dense_logical  :840-855
+int mx_logicaland_coo_by_dense_logical(const int32_t *X_colmajor, int nrows, int ncols, const int32_t *ii,
+                                       const int32_t *jj, const int32_t *xx, int64_t nnz, int32_t *values_out)
+{
+    return coo_by_dense("mx_logicaland_coo_by_dense_logical", X_colmajor, nrows, ncols, ii, jj, xx, nnz, 4, values_out);
+}
+
 // ---- outer products with a one-column CSR, float32 row vector x CSC (outer.hip) ----------------
 // non-empty rows of a host indptr, and the refusal of an outer product beyond R's int32 index range before
 // anything is allocated for it (the reference does not check)

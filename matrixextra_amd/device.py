@@ -441,6 +441,61 @@ def csr_by_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, length:
     return out_p, out_j[:k], out_x[:k]
 
 
+def dense_by_svec(X: torch.Tensor, vi: torch.Tensor, vx: torch.Tensor, length: int, keep_na: bool = True,
+                  logical: bool = False):
+    """X * v for a device-resident dense matrix X and a sparse vector.  X: 2-d float64, float32,
+    int32 (R integer; R logical with logical=True) or bool, any strides; vi: 1-based int32 positions inside
+    1..length (sorted when keep_na is set); vx: their f64 values.  A length equal to the number of cells, or one that
+    does not divide the number of rows, gives a float64 tensor of X's shape (column-major storage, the vector
+    recycled over the cells); a length that divides the number of rows gives the CSR (p, j, x) of full rows.
+    keep_na=True keeps the NA / NaN / Inf cells that the vector does not cover, as NA / NaN."""
+    lib = _lib.load()
+    dev = X.device
+    if X.dim() != 2:
+        raise ValueError("dense_by_svec: X must be a matrix")
+    if X.dtype == torch.bool:
+        X, kind = X.to(torch.int32), 3
+    elif X.dtype == torch.int32:
+        kind = 3 if logical else 2
+    elif X.dtype in (torch.float64, torch.float32):
+        kind = 0 if X.dtype == torch.float64 else 1
+    else:
+        raise ValueError(f"dense_by_svec: unsupported dense dtype {X.dtype}")
+    if vi.dtype != torch.int32 or vi.dim() != 1 or vi.device != dev:
+        raise ValueError(f"dense_by_svec: vi must be a 1-d int32 tensor on {dev}")
+    if vx.dtype != torch.float64 or vx.shape != vi.shape or vx.device != dev:
+        raise ValueError("dense_by_svec: vx must be float64, of vi's shape and on its device")
+    nrows, ncols = int(X.shape[0]), int(X.shape[1])
+    length, nv = int(length), int(vi.numel())
+    route = lib.mx_dense_by_svec_route(nrows, ncols, length)
+    if route < 0:
+        check(1)
+    if nv > length:
+        raise ValueError("dense_by_svec: the vector stores more positions than its length")
+    if nv and (int(vi.min()) < 1 or int(vi.max()) > length):
+        raise ValueError(f"dense_by_svec: positions must lie inside 1..{length}")
+    Xc = X.t().contiguous()                         # row-major X^T = column-major X
+    vi, vx, keep = vi.contiguous(), vx.contiguous(), int(bool(keep_na))
+    if route in (_lib.MX_DSV_ROUTE_A, _lib.MX_DSV_ROUTE_D):
+        ws = torch.empty(max(lib.mxd_dense_by_svec_workspace_bytes(0, length), 16), dtype=torch.uint8, device=dev)
+        out = torch.empty((ncols, nrows), dtype=torch.float64, device=dev)
+        check(lib.mxd_dense_by_svec_dense(nrows, ncols, _dp(Xc), kind, _dp(vi), nv, _dp(vx), length, keep, _dp(ws),
+                                          _dp(out), _stream()))
+        return out.t()
+    ws = torch.empty(max(lib.mxd_dense_by_svec_workspace_bytes(nrows, length), 16), dtype=torch.uint8, device=dev)
+    out_p = torch.empty(nrows + 1, dtype=torch.int32, device=dev)
+    total = C.c_int64(0)
+    check(lib.mxd_dense_by_svec_count(nrows, ncols, _dp(Xc), kind, _dp(vi), nv, length, keep, _dp(ws), _dp(out_p),
+                                      C.byref(total), _stream()))
+    k = int(total.value)
+    out_j = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
+    if k:
+        check(lib.mxd_dense_by_svec_fill(nrows, ncols, _dp(Xc), kind, _dp(vx), length, keep, _dp(ws), _dp(out_p),
+                                         _dp(out_j), _dp(out_x), _stream()))
+    return out_p, out_j[:k], out_x[:k]
+
+
 def csr_by_dvec_keep_na(A: DeviceCSR, v: torch.Tensor, op: str = "*"):
     """X op v (op one of * ^ / %% %/%) for a device-resident CSR X (f64 values, sorted rows) and a dense f64 vector
     recycled over the matrix, keeping the cells that R makes NA / NaN / 1 / Inf outside X's pattern,

@@ -1121,3 +1121,82 @@ def check_valid_svec(ii, nrows):
     e = C.c_char_p()
     check(_lib.load().mx_check_valid_svec(ptr(i), i.size, int(nrows), C.byref(e)))
     return _err(e)
+
+
+# ----------------------------------------------------------------------------- dense matrix * sparse vector, COO * dense matrix (densevec.hip)
+def dense_by_svec_route(nrows, ncols, length) -> int:
+    """mx_dense_by_svec_route: MX_DSV_ROUTE_A / _D (dense result) or _B / _C (CSR result), src/operators.cpp:3720-4235."""
+    route = _lib.load().mx_dense_by_svec_route(int(nrows), int(ncols), int(length))
+    if route < 0:
+        check(1)
+    return route
+
+
+def _dense_by_svec(kind, X_, ii, xx, length, keep_NAs):
+    X, vi, vx = _dense(X_, _CSC_DENSE_DT[kind]), _i32(ii), _f64(xx)
+    if vx.size != vi.size:
+        raise ValueError("ii and xx have different lengths")
+    lib = _lib.load()
+    args = (ptr(X), kind, X.shape[0], X.shape[1], ptr(vi), ptr(vx), vi.size, int(length), int(bool(keep_NAs)))
+    if dense_by_svec_route(X.shape[0], X.shape[1], length) in (_lib.MX_DSV_ROUTE_B, _lib.MX_DSV_ROUTE_C):
+        return _begin(lib.mx_multiply_elemwise_dense_by_svec_begin, *args)[0]
+    out = np.empty(X.shape, dtype=np.float64, order="F")
+    check(lib.mx_multiply_elemwise_dense_by_svec_dense(*args, ptr(out)))
+    return dict(X_dense=out)
+
+
+def multiply_elemwise_dense_by_svec_numeric(X_, ii, xx, length, keep_NAs):
+    """src/operators.cpp:4305-4322: dict(X_dense=...) (F-order f64) when the vector covers the cells, or recycles over
+    them unevenly; dict(indptr, indices, values), a CSR of full rows, when its length divides the number of rows.  `ii`
+    holds 1-based positions, sorted when keep_NAs is set."""
+    return _dense_by_svec(0, X_, ii, xx, length, keep_NAs)
+
+
+def multiply_elemwise_dense_by_svec_integer(X_, ii, xx, length, keep_NAs):
+    """src/operators.cpp:4324-4341 (NA cells: NA_INTEGER)."""
+    return _dense_by_svec(2, X_, ii, xx, length, keep_NAs)
+
+
+def multiply_elemwise_dense_by_svec_logical(X_, ii, xx, length, keep_NAs):
+    """src/operators.cpp:4343-4360: R logical X (int32 or bool), read as integers."""
+    return _dense_by_svec(3, X_, ii, xx, length, keep_NAs)
+
+
+def multiply_elemwise_dense_by_svec_float32(X_, ii, xx, length, keep_NAs):
+    """src/operators.cpp:4362-4379: X_ holds the float32 values (float32@Data), widened to f64 per cell."""
+    return _dense_by_svec(1, X_, ii, xx, length, keep_NAs)
+
+
+def _coo_by_dense(fn, kind, X_, Y_coo_row, Y_coo_col, Y_coo_val):
+    X, i, j = _dense(X_, _CSC_DENSE_DT[kind]), _i32(Y_coo_row), _i32(Y_coo_col)
+    xv = np.ascontiguousarray(Y_coo_val, dtype=np.int32 if kind == 4 else np.float64)
+    if not i.size == j.size == xv.size:
+        raise ValueError("row, col and val have different lengths")
+    out = np.empty(xv.size, dtype=xv.dtype)
+    check(fn(ptr(X), X.shape[0], X.shape[1], ptr(i), ptr(j), ptr(xv), xv.size, ptr(out)))
+    return dict(row=i.copy(), col=j.copy(), val=out)         # new row / col vectors, as :763-769
+
+
+def multiply_coo_by_dense_numeric(X_, Y_coo_row, Y_coo_col, Y_coo_val):
+    """src/operators.cpp:772-787: dict(row, col, val) with val[k] = Y_coo_val[k] * X_[row[k], col[k]]."""
+    return _coo_by_dense(_lib.load().mx_multiply_coo_by_dense_numeric, 0, X_, Y_coo_row, Y_coo_col, Y_coo_val)
+
+
+def multiply_coo_by_dense_integer(X_, Y_coo_row, Y_coo_col, Y_coo_val):
+    """src/operators.cpp:789-804: an NA_INTEGER cell gives NA_real_."""
+    return _coo_by_dense(_lib.load().mx_multiply_coo_by_dense_integer, 2, X_, Y_coo_row, Y_coo_col, Y_coo_val)
+
+
+def multiply_coo_by_dense_logical(X_, Y_coo_row, Y_coo_col, Y_coo_val):
+    """src/operators.cpp:806-821: R logical X_ (int32 or bool) read as bool; NA gives NA_real_."""
+    return _coo_by_dense(_lib.load().mx_multiply_coo_by_dense_logical, 3, X_, Y_coo_row, Y_coo_col, Y_coo_val)
+
+
+def multiply_coo_by_dense_float32(X_, Y_coo_row, Y_coo_col, Y_coo_val):
+    """src/operators.cpp:823-838: X_ holds the float32 values (float32@Data)."""
+    return _coo_by_dense(_lib.load().mx_multiply_coo_by_dense_float32, 1, X_, Y_coo_row, Y_coo_col, Y_coo_val)
+
+
+def logicaland_coo_by_dense_logical(X_, Y_coo_row, Y_coo_col, Y_coo_val):
+    """src/operators.cpp:840-855: R logicals in and out, R's three-valued AND."""
+    return _coo_by_dense(_lib.load().mx_logicaland_coo_by_dense_logical, 4, X_, Y_coo_row, Y_coo_col, Y_coo_val)

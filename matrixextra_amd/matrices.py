@@ -297,10 +297,14 @@ class TsparseMatrix:
             return t_shallow(operators.multiply_csr_by_coo(t_shallow(other), t_shallow(self), logical=False))
         if isinstance(other, TsparseMatrix):
             return NotImplemented
+        if _coo_dense_route(other):                   # :495-515
+            return operators.multiply_coo_by_dense(self, other)
         return operators.csr_op_vector(self, other, "*")
 
     def __rmul__(self, other):
         from . import operators
+        if _coo_dense_route(other):                   # :519-539
+            return operators.multiply_coo_by_dense(self, other)
         return operators.csr_op_vector(self, other, "*")
 
     def __and__(self, other):                         # :194-215 (CSR), :1405-1430 (vector)
@@ -311,10 +315,14 @@ class TsparseMatrix:
             return t_shallow(operators.multiply_csr_by_coo(t_shallow(other), t_shallow(self), logical=True))
         if isinstance(other, TsparseMatrix):
             return NotImplemented
+        if _coo_dense_route(other):                   # :544-552
+            return operators.logicaland_coo_by_dense(self, other)
         return operators.csr_op_vector(self, other, "&")
 
     def __rand__(self, other):
         from . import operators
+        if _coo_dense_route(other):                   # :556-564
+            return operators.logicaland_coo_by_dense(self, other)
         return operators.csr_op_vector(self, other, "&")
 
     def __or__(self, other):                          # sparseMatrix | RsparseMatrix, :903-906
@@ -501,6 +509,18 @@ class sparseVector:
         from . import matmul
         return matmul.matmul(other, self)
 
+    def __mul__(self, other):                         # sparseVector * matrix / float32, R/operators.R:1697, :1705
+        from . import operators
+        if isinstance(other, float32) or (isinstance(other, np.ndarray) and other.ndim == 2):
+            return operators.multiply_elemwise_dense_by_svec(self, other)
+        return NotImplemented
+
+    def __rmul__(self, other):                        # matrix / float32 * sparseVector, :1693, :1701
+        from . import operators
+        if isinstance(other, float32) or (isinstance(other, np.ndarray) and other.ndim == 2):
+            return operators.multiply_elemwise_dense_by_svec(other, self)
+        return NotImplemented
+
     def __repr__(self):
         return f"<{self.r_class} of length {self.length}, {self.i.size} entries>"
 
@@ -559,6 +579,13 @@ class DenseMatrix(np.ndarray):
 
     def __array_finalize__(self, obj):
         self.Dimnames = getattr(obj, "Dimnames", [None, None])
+
+
+def _coo_dense_route(x):
+    """Whether `TsparseMatrix (op) x` takes multiply_coo_by_dense_internal (R/operators.R:400-483): only under
+    options["mxgpu.coo_dense_route"] (off unless set), and only for a dense matrix or a float32."""
+    return bool(options.get("mxgpu.coo_dense_route", False)) and (
+        isinstance(x, float32) or (isinstance(x, np.ndarray) and x.ndim == 2))
 
 
 def _dense_operand(x):
