@@ -12,14 +12,17 @@ struct mx_spmm_plan {
     int32_t *step_off = nullptr; size_t step_off_cap = 0;
     int32_t *pcol = nullptr;     size_t pcol_cap = 0;
     double *pval = nullptr;      size_t pval_cap = 0;
-    void *scratch = nullptr;     size_t scratch_cap = 0;       // steps + oct_off + read-back + scan workspace (build only)
+    void *scratch = nullptr;     size_t scratch_cap = 0;       // steps + read-back block (build only)
     bool ready = false;                                            // false: sized but not filled (rejected by AUTO)
-    // a build between plan_begin and plan_end: the CSR it reads, device-side sizes / go flag, the capacity the fill saw
+    // a build between plan_begin and plan_end: the CSR it reads, what the sizing pass wrote (steps per octet, the sum
+    // of every tile of tile_octs octets, nnz), the go flag, the capacity the fill saw
     bool pending = false;
     const int32_t *indptr = nullptr, *indices = nullptr;
     const double *values = nullptr;
-    const int32_t *oct_off = nullptr;
-    const long long *sizes = nullptr;
+    const int32_t *steps = nullptr;
+    const unsigned *tile_sums = nullptr;
+    int ntiles = 0, tile_octs = 0;
+    const long long *nnz_dev = nullptr;
     int *go = nullptr;
     long long fill_cap = 0;
     int pad_rule = 0;

@@ -38,17 +38,27 @@ constexpr int PLAN_ROW_SHIFT = 27;                 // col < 2^27
 
 // Plan construction.
 // Sizing: an octet is as long as its longest bundle rounded up to whole chunks, and a bundle's length is
-// indptr[r0 + 8] - indptr[r0], so the sizes (and the AUTO pad-ratio rule) come from indptr alone.  The scan of the
-// octet lengths gives oct_off[] and the step total; the total and nnz go back to the host in one pinned copy.
+// indptr[r0 + 8] - indptr[r0], so the sizes (and the AUTO pad-ratio rule) come from indptr alone.  The sizing pass
+// writes steps[oct] and, per tile of T octets (one workgroup), the sum of the tile's steps; the tile sums (at most
+// PLAN_MAX_TILES of them) and nnz go back to the host in one pinned copy.  There is no scan: a fill workgroup adds up
+// the tile sums in front of its tile and the steps in front of its octet inside the tile, and all tile sums for the
+// step total.  Everything a kernel reads was written by an earlier kernel on the stream.
 // Fill: one 512-thread workgroup per octet, one wavefront per bundle.  The wavefront reads its bundle's entries once
-// (coalesced, 64 per load, PLAN_LD loads in flight), counts them per panel, takes the prefix over the panels (the
-// bundle's panel offsets) and places every entry at (panel offset + rank inside its panel, in CSR order).  Ranks come
-// from a multisplit: ceil(log2 P) ballots of the panel's bits give each lane the mask of its peers, so the cost does
-// not grow with P.  Octets of up to PLAN_STAGE_STEPS steps are assembled in LDS in their final slot order and
-// written out with 16-byte stores; longer ones are scattered straight to global memory.
+// (coalesced, 64 per load, PLAN_LD loads in flight) and classifies each 64-entry chunk once: the entry's panel, its
+// rank among the chunk's entries of the same panel, and (lane q) the chunk's count of panel q.  The prefix over the
+// panel counts gives the bundle's panel offsets, and every entry goes to (panel offset + entries of its panel in
+// earlier chunks + rank), i.e. CSR order inside a panel.  Ranks come from a multisplit: NBITS = ceil(log2 P) ballots
+// of the panel's bits give each lane the mask of its peers, so the cost does not grow with P; NBITS is a template
+// parameter, the bit loops unroll exactly.  Octets of up to PLAN_STAGE_STEPS steps are assembled in LDS in their final
+// slot order and written out with 16-byte stores; longer ones are scattered straight to global memory.
 constexpr int PLAN_LD = 4;
 constexpr int PLAN_STAGE_STEPS = 384;              // 384 x 64 slots x 12 B = 36 KiB of LDS: four workgroups per CU
 constexpr int PLAN_PAD_NUM = 7, PLAN_PAD_DEN = 4;  // AUTO's pad rule: reject a plan of more than 1.75 x nnz + 65536 slots
+constexpr int PLAN_MAX_TILES = 4096;               // tile sums per build: 16 KiB read back, 8 loads per fill thread
+constexpr int PLAN_RB_HEAD = 16;                   // read-back block: [nnz : int64][go flag : int32][pad], then the tile sums
+
+// octets per sizing tile: 32 (the 256 bundles of one sizing workgroup) until that would make more than PLAN_MAX_TILES
+inline int plan_tile_octs(int noct) { return 32 * (int)ceil_div(noct > 0 ? noct : 1, 32 * PLAN_MAX_TILES); }
 
 // Accept the plan: it fits buffers of cap_slots slots and (pad_rule) is not padded beyond PLAN_PAD_NUM/DEN x nnz.
 // The fill kernel takes this decision from the device-side total, the host repeats it from the read-back copy.
@@ -68,72 +78,126 @@ __device__ __forceinline__ int panel_of(int col, int panel_cols, float inv_pc, i
     return q < npanels ? q : npanels - 1;
 }
 
-// steps[oct] = longest bundle of the octet rounded up to whole chunks; one thread per bundle, 8 per octet
+// steps[oct] = longest bundle of the octet rounded up to whole chunks; one thread per bundle, 8 per octet.  One
+// workgroup per tile of tile_octs octets (a multiple of 32: whole passes of 256 bundles); tile_sums[tile] = the sum of
+// its steps (unsigned: at most nnz + 31 per octet).
 __global__ __launch_bounds__(256)
-void plan_size_kernel(int m, int noct, const int32_t *__restrict__ indptr, int32_t *__restrict__ steps,
-                      long long *__restrict__ nnz_out)
+void plan_size_kernel(int m, int noct, int tile_octs, const int32_t *__restrict__ indptr, int32_t *__restrict__ steps,
+                      unsigned *__restrict__ tile_sums, long long *__restrict__ nnz_out)
 {
-    const int b = blockIdx.x * 256 + threadIdx.x;                    // bundle; noct * 8 threads are live
-    if (b == 0) *nnz_out = indptr[m];                                // rides back with the step total (one copy)
-    int len = 0;
-    if (b < noct * 8) {
-        const int r0 = min(b * PLAN_RB, m), r1 = min(b * PLAN_RB + PLAN_RB, m);
-        len = indptr[r1] - indptr[r0];
+    __shared__ unsigned s_part[4];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *nnz_out = indptr[m];   // rides back with the tile sums (one copy)
+    unsigned sum = 0;
+    for (int o = 0; o < tile_octs; o += 32) {
+        const long long bl = ((long long)blockIdx.x * tile_octs + o) * 8 + threadIdx.x;    // bundle
+        const bool live = bl < (long long)noct * 8;
+        const int b = live ? (int)bl : 0;
+        int len = 0;
+        if (live) {
+            const int r0 = (int)min((long long)b * PLAN_RB, (long long)m), r1 = (int)min((long long)b * PLAN_RB + PLAN_RB, (long long)m);
+            len = indptr[r1] - indptr[r0];
+        }
+        len = max(len, __shfl_xor(len, 1, 8));
+        len = max(len, __shfl_xor(len, 2, 8));
+        len = max(len, __shfl_xor(len, 4, 8));
+        if (live && (b & 7) == 0) {
+            const int st = (len + 8 * PLAN_CHUNK - 1) & ~(8 * PLAN_CHUNK - 1);             // whole chunks of 4 batches of 8 steps
+            steps[b >> 3] = st;
+            sum += (unsigned)st;
+        }
     }
-    len = max(len, __shfl_xor(len, 1, 8));
-    len = max(len, __shfl_xor(len, 2, 8));
-    len = max(len, __shfl_xor(len, 4, 8));
-    if (b < noct * 8 && (b & 7) == 0)
-        steps[b >> 3] = (len + 8 * PLAN_CHUNK - 1) & ~(8 * PLAN_CHUNK - 1);    // whole chunks of 4 batches of 8 steps
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
 }
 
-// lanes whose key agrees with `key` on the low nbits bits, among the lanes in `valid` (bal[b] = ballot of key bit b)
-__device__ __forceinline__ unsigned long long multisplit_peers(int key, const unsigned long long (&bal)[6], int nbits,
+// sum of v over the wavefront (wave-uniform): butterfly inside each row of 16 lanes by DPP (quad_perm [1,0,3,2] and
+// [2,3,0,1], row_half_mirror, row_mirror), then the four rows' sums as scalars
+__device__ __forceinline__ int wave_sum(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);
+    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
+           __builtin_amdgcn_readlane(v, 48);
+}
+
+// lanes whose key agrees with `key` on the low NBITS bits, among the lanes in `valid` (bal[b] = ballot of key bit b)
+template <int NBITS>
+__device__ __forceinline__ unsigned long long multisplit_peers(int key, const unsigned long long (&bal)[6],
                                                                 unsigned long long valid)
 {
     unsigned long long peers = valid;
 #pragma unroll
-    for (int b = 0; b < 6; b++)
-        if (b < nbits) peers &= ((key >> b) & 1) ? bal[b] : ~bal[b];
+    for (int b = 0; b < NBITS; b++) peers &= ((key >> b) & 1) ? bal[b] : ~bal[b];
     return peers;
 }
 
 // Slot layout inside a batch of 8 steps: [bundle g][step u] — lane 8g+u of the sweep's reading wavefront holds bundle
 // g's entry for step u, i.e. inside g's own lane group (intra-group DPP broadcast).  Step t of bundle g of an octet
 // lands in slot (t & ~7) * 8 + g * 8 + (t & 7) of the octet.
+// NBITS = ceil(log2 npanels), 0 for one panel.
+template <int NBITS>
 __global__ __launch_bounds__(512, 8)
 void plan_fill_kernel(int m, int npanels, int panel_cols, const int32_t *__restrict__ indptr,
                       const int32_t *__restrict__ indices, const double *__restrict__ values,
-                      const int32_t *__restrict__ oct_off, int32_t *__restrict__ pcol, double *__restrict__ pval,
+                      const int32_t *__restrict__ steps, const unsigned *__restrict__ tile_sums, int ntiles, int tile_octs,
+                      int32_t *__restrict__ pcol, double *__restrict__ pval,
                       int noct, int pad_col, int32_t *__restrict__ step_off,
-                      const long long *__restrict__ sizes, long long cap_slots, int pad_rule, int *__restrict__ go)
+                      const long long *__restrict__ nnz_dev, long long cap_slots, int pad_rule, int *__restrict__ go)
 {
     __shared__ int32_t s_col[PLAN_STAGE_STEPS * 8];
     __shared__ double s_val[PLAN_STAGE_STEPS * 8];
     __shared__ int s_bpo[8][PLAN_MAXP];
-
-    // sizes = [step total, nnz] from the sizing pass; a plan that does not fit (or that AUTO rejects) is not written
-    // at all, and the repack of B behind this kernel is skipped with it
-    const bool ok = plan_accept(sizes[0], sizes[1], cap_slots, pad_rule);
-    if (blockIdx.x == 0 && threadIdx.x == 0) *go = ok ? 1 : 0;
-    if (!ok) return;
+    __shared__ long long s_tot[8];
+    __shared__ int s_front[8];
 
     const int g = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int oct = blockIdx.x;
+
+    // Where the octet starts and how long the whole plan is, from the sizing pass alone: this thread's share of the
+    // tile sums (all of them: the step total; those in front of the octet's tile: its base) and of the steps in front
+    // of the octet inside its tile.  These loads go out together with the row pointers; the entries are read once
+    // the plan is accepted.
+    const int tile = oct / tile_octs, oct0 = tile * tile_octs;
+    int part_lo = 0, part_hi = 0, part_front = 0;                   // the total in 16-bit halves: 4096 of each fit an int
+    for (int i = threadIdx.x; i < ntiles; i += 512) {
+        const unsigned v = tile_sums[i];
+        part_lo += (int)(v & 0xffffu);
+        part_hi += (int)(v >> 16);
+        part_front += i < tile ? (int)v : 0;
+    }
+    for (int i = oct0 + threadIdx.x; i < oct; i += 512) part_front += steps[i];
+    const int steps_oct = steps[oct];
+    const long long nnz = *nnz_dev;
+
     const int row0 = oct * PLAN_OCT_ROWS + g * PLAN_RB;
     int rp[PLAN_RB + 1];                                             // the bundle's row pointers (wave-uniform)
 #pragma unroll
     for (int r = 0; r <= PLAN_RB; r++) rp[r] = uniform(indptr[min(row0 + r, m)]);
     const int s = rp[0], e = rp[PLAN_RB];
-    const int base = oct_off[oct];
-    const int steps_oct = oct_off[oct + 1] - base;
     const bool stage = steps_oct <= PLAN_STAGE_STEPS;                // workgroup-uniform
     const float inv_pc = 1.0f / (float)panel_cols;
-    const int nbits = npanels > 1 ? 32 - __clz(npanels - 1) : 0;
-    const unsigned long long below = (1ULL << lane) - 1ULL;
 
-    // The first PLAN_LD x 64 entries (all of a cfg2 bundle) stay in registers between the two passes; longer bundles
-    // read the rest again in pass 2 (from L2: the workgroup read it moments before).
+    const int wave_lo = wave_sum(part_lo), wave_hi = wave_sum(part_hi), wave_front = wave_sum(part_front);
+    if (lane == 0) { s_tot[g] = ((long long)wave_hi << 16) + wave_lo; s_front[g] = wave_front; }
+    __syncthreads();
+    long long total = 0;
+    int base = 0;
+#pragma unroll
+    for (int w = 0; w < 8; w++) { total += s_tot[w]; base += s_front[w]; }
+
+    // a plan that does not fit (or that AUTO rejects) is not written at all, and the repack of B behind this kernel
+    // is skipped with it
+    const bool ok = plan_accept(total, nnz, cap_slots, pad_rule);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *go = ok ? 1 : 0;
+    if (!ok) return;
+
+    // The first PLAN_LD x 64 entries (all of a cfg2 bundle) stay in registers; longer bundles read the rest twice
+    // (the second time from L2: the workgroup read it moments before).  A rejected plan does not read A at all.
     int col0[PLAN_LD];
     double val0[PLAN_LD];
 #pragma unroll
@@ -142,37 +206,50 @@ void plan_fill_kernel(int m, int npanels, int panel_cols, const int32_t *__restr
         col0[c] = -1; val0[c] = 0.0;
         if (k < e) { col0[c] = indices[k]; val0[c] = values[k]; }
     }
+
     // ballots of the panel bits of one 64-entry chunk (pan < 0: no entry)
     auto split = [&](int pan, unsigned long long (&bal)[6]) -> unsigned long long {
 #pragma unroll
-        for (int b = 0; b < 6; b++)
-            bal[b] = b < nbits ? __ballot(pan >= 0 && ((pan >> b) & 1)) : 0ULL;
+        for (int b = 0; b < NBITS; b++) bal[b] = __ballot(pan >= 0 && ((pan >> b) & 1));
         return __ballot(pan >= 0);
     };
+    // one chunk, classified: the entry's rank among the chunk's entries of its panel; lane q: the chunk's count of panel q
+    auto classify = [&](int pan, int &rank, int &cnt) {
+        unsigned long long bal[6];
+        const unsigned long long valid = split(pan, bal);
+        const unsigned long long peers = multisplit_peers<NBITS>(pan, bal, valid);
+        rank = __builtin_amdgcn_mbcnt_hi((unsigned)(peers >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)peers, 0u));
+        cnt = lane < npanels ? __popcll(multisplit_peers<NBITS>(lane, bal, valid)) : 0;
+    };
 
-    // pass 1: lane q counts the bundle's entries in panel q
-    int mine = 0;
-    for (int k0 = s; k0 < e; k0 += 64 * PLAN_LD) {
-        int colv[PLAN_LD];
+    // classification of the register-resident chunks, once; kept in one register per chunk:
+    // panel (signed byte, -1: no entry) | rank << 8 | count << 16
+    int cls0[PLAN_LD];
+    int mine = 0;                                                    // lane q: the bundle's entries in panel q
 #pragma unroll
-        for (int c = 0; c < PLAN_LD; c++) {
-            const int k = k0 + 64 * c + lane;
-            colv[c] = col0[c];
-            if (k0 != s) colv[c] = k < e ? indices[k] : -1;
-        }
-#pragma unroll
-        for (int c = 0; c < PLAN_LD; c++) {
-            if (k0 + 64 * c >= e) break;                             // uniform
-            const int pan = colv[c] >= 0 ? panel_of(colv[c], panel_cols, inv_pc, npanels) : -1;
-            unsigned long long bal[6];
-            const unsigned long long valid = split(pan, bal);
-            if (lane < npanels) mine += __popcll(multisplit_peers(lane, bal, nbits, valid));
+    for (int c = 0; c < PLAN_LD; c++) {
+        cls0[c] = 0xff;
+        if (s + 64 * c < e) {                                        // uniform
+            const int pan = col0[c] >= 0 ? panel_of(col0[c], panel_cols, inv_pc, npanels) : -1;
+            int rank, cnt;
+            classify(pan, rank, cnt);
+            cls0[c] = (pan & 0xff) | (rank << 8) | (cnt << 16);
+            mine += cnt;
         }
     }
+    // the part of a long bundle that does not fit in registers: counted here, read again for the placement
+    for (int k0 = s + 64 * PLAN_LD; k0 < e; k0 += 64) {
+        const int k = k0 + lane;
+        const int pan = k < e ? panel_of(indices[k], panel_cols, inv_pc, npanels) : -1;
+        int rank, cnt;
+        classify(pan, rank, cnt);
+        mine += cnt;
+    }
     // exclusive prefix over the panels (lanes 0..npanels-1): where panel q starts in the bundle's stream
-    int incl = lane < npanels ? mine : 0;
+    // (panels live in lanes 0..2^NBITS-1: NBITS steps; what the lanes above them hold is never used)
+    int incl = mine;
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
+    for (int off = 1; off < (1 << NBITS); off <<= 1) {
         const int up = __shfl_up(incl, off, 64);
         if (lane >= off) incl += up;
     }
@@ -184,46 +261,39 @@ void plan_fill_kernel(int m, int npanels, int panel_cols, const int32_t *__restr
         if (stage) { s_col[slot] = word; s_val[slot] = v; }
         else { pcol[(size_t)base * 8 + slot] = word; pval[(size_t)base * 8 + slot] = v; }
     };
+    auto local_row = [&](int k) {
+        int lrow = 0;
+#pragma unroll
+        for (int r = 1; r < PLAN_RB; r++) lrow += k >= rp[r];
+        return lrow;
+    };
 
-    // pass 2: place every entry at its panel's next step + its rank among the chunk's entries of that panel
-    for (int k0 = s; k0 < e; k0 += 64 * PLAN_LD) {
-        int colv[PLAN_LD];
-        double av[PLAN_LD];
+    // placement: every entry at its panel's next step + its rank among the chunk's entries of that panel
 #pragma unroll
-        for (int c = 0; c < PLAN_LD; c++) {
-            const int k = k0 + 64 * c + lane;
-            colv[c] = col0[c]; av[c] = val0[c];
-            if (k0 != s) {
-                colv[c] = -1; av[c] = 0.0;
-                if (k < e) { colv[c] = indices[k]; av[c] = values[k]; }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < PLAN_LD; c++) {
-            if (k0 + 64 * c >= e) break;                             // uniform
-            const int k = k0 + 64 * c + lane;
-            const int col = colv[c];
-            int pan = -1, lrow = 0;
-            if (col >= 0) {
-                pan = panel_of(col, panel_cols, inv_pc, npanels);
-#pragma unroll
-                for (int r = 1; r < PLAN_RB; r++) lrow += k >= rp[r];
-            }
-            unsigned long long bal[6];
-            const unsigned long long valid = split(pan, bal);
+    for (int c = 0; c < PLAN_LD; c++) {
+        if (s + 64 * c < e) {                                        // uniform
+            const int pan = (int)(signed char)cls0[c], rank = (cls0[c] >> 8) & 0xff, cnt = cls0[c] >> 16;
             const int start = __shfl(nextstep, pan < 0 ? 0 : pan, 64);
-            if (pan >= 0) put(start + __popcll(multisplit_peers(pan, bal, nbits, valid) & below), col | (lrow << PLAN_ROW_SHIFT), av[c]);
-            if (lane < npanels) nextstep += __popcll(multisplit_peers(lane, bal, nbits, valid));
+            if (pan >= 0) put(start + rank, col0[c] | (local_row(s + 64 * c + lane) << PLAN_ROW_SHIFT), val0[c]);
+            nextstep += cnt;
         }
+    }
+    for (int k0 = s + 64 * PLAN_LD; k0 < e; k0 += 64) {
+        const int k = k0 + lane;
+        int col = -1;
+        double av = 0.0;
+        if (k < e) { col = indices[k]; av = values[k]; }
+        const int pan = col >= 0 ? panel_of(col, panel_cols, inv_pc, npanels) : -1;
+        int rank, cnt;
+        classify(pan, rank, cnt);
+        const int start = __shfl(nextstep, pan < 0 ? 0 : pan, 64);
+        if (pan >= 0) put(start + rank, col | (local_row(k) << PLAN_ROW_SHIFT), av);
+        nextstep += cnt;
     }
     // Padding up to the octet's length: a no-op entry — value 0, column `pad_col` (the all-zero extra row of the
     // packed B), row = the bundle's last entry's row so that it does not even trigger a row switch.  0 * 0 added to
     // an accumulator that is never -0.0 leaves it unchanged bit for bit.
-    int last_lrow = 0;
-    if (e > s) {
-#pragma unroll
-        for (int r = 1; r < PLAN_RB; r++) last_lrow += (e - 1) >= rp[r];
-    }
+    const int last_lrow = e > s ? local_row(e - 1) : 0;
     for (int t = (e - s) + lane; t < steps_oct; t += 64) put(t, pad_col | (last_lrow << PLAN_ROW_SHIFT), 0.0);
 
     __syncthreads();
@@ -233,7 +303,7 @@ void plan_fill_kernel(int m, int npanels, int panel_cols, const int32_t *__restr
 #pragma unroll
         for (int gg = 0; gg < 8; gg++) sum += s_bpo[gg][lane];
         step_off[(size_t)oct * npanels + lane] = base + (lane == 0 ? 0 : sum / 8);
-        if (oct == noct - 1 && lane == 0) step_off[(size_t)noct * npanels] = oct_off[noct];
+        if (oct == noct - 1 && lane == 0) step_off[(size_t)noct * npanels] = (int32_t)total;
     }
     if (stage) {
         // the octet's image is contiguous: slots [base * 8, (base + steps_oct) * 8), a multiple of 256 slots
@@ -250,7 +320,7 @@ void plan_fill_kernel(int m, int npanels, int panel_cols, const int32_t *__restr
     // PLAN_TAIL_SLOTS padding slots behind the last octet: the kernel's read-ahead runs two batches past an octet
     if (oct == noct - 1) {
         static_assert(PLAN_TAIL_SLOTS == 512, "one slot per thread of the last block");
-        const size_t dst = (size_t)oct_off[noct] * 8 + threadIdx.x;
+        const size_t dst = (size_t)total * 8 + threadIdx.x;
         pcol[dst] = pad_col;
         pval[dst] = 0.0;
     }
@@ -532,24 +602,38 @@ static int grow(void **p, size_t *cap, size_t bytes)
 
 // pinned landing zone + event for the one host read-back of a plan build
 struct PlanReadback {
-    long long *host = nullptr;                                      // [0] total steps, [1] nnz (int32 in the low half)
+    char *host = nullptr;                                           // PLAN_RB_HEAD bytes ([0] nnz : int64), then the tile sums
     hipEvent_t ev = nullptr;
 };
+constexpr size_t PLAN_RB_BYTES = PLAN_RB_HEAD + PLAN_MAX_TILES * sizeof(unsigned);
 static PlanReadback *plan_readback()
 {
     static thread_local PlanReadback rb;
     if (!rb.host) {
-        if (hipHostMalloc((void **)&rb.host, 2 * sizeof(long long), hipHostMallocDefault) != hipSuccess) { rb.host = nullptr; return nullptr; }
+        if (hipHostMalloc((void **)&rb.host, PLAN_RB_BYTES, hipHostMallocDefault) != hipSuccess) { rb.host = nullptr; return nullptr; }
         if (hipEventCreateWithFlags(&rb.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(rb.host); rb.host = nullptr; return nullptr; }
     }
     return &rb;
 }
 
+static int launch_fill(const mx_spmm_plan *pl, hipStream_t st)
+{
+    const int nbits = pl->npanels > 1 ? 32 - __builtin_clz((unsigned)(pl->npanels - 1)) : 0;
+    return dispatch_int(int_list<0, 1, 2, 3, 4, 5, 6>{}, "spmm plan", "panel bits", nbits, [&](auto nb) {
+        hipLaunchKernelGGL((plan_fill_kernel<nb()>), dim3((unsigned)pl->noct), dim3(512), 0, st, pl->m, pl->npanels,
+                           pl->panel_cols, pl->indptr, pl->indices, pl->values, pl->steps, pl->tile_sums, pl->ntiles,
+                           pl->tile_octs, pl->pcol, pl->pval, pl->noct, pl->K, pl->step_off, pl->nnz_dev, pl->fill_cap,
+                           pl->pad_rule, pl->go);
+        MX_LAUNCH_CHECK();
+        return 0;
+    });
+}
+
 // Building a plan is split in two so that the GPU never waits for the host.  plan_begin enqueues the sizing pass, the
-// scan, the one read-back of [step total, nnz] and the fill, which decides on the device-side total whether the plan
-// fits the current (grow-only) buffers; the caller may enqueue more work behind it (AUTO packs B).  plan_end waits for
-// the read-back, takes the same decision on the host and, when the buffers were too small (typically the first call),
-// grows them and fills again (*refilled = true).
+// one read-back of [nnz, tile sums] and the fill, which decides on the device-side total whether the plan fits the
+// current (grow-only) buffers; the caller may enqueue more work behind it (AUTO packs B).  plan_end waits for the
+// read-back, adds the tile sums up to the step total, takes the same decision on the host and, when the buffers were
+// too small (typically the first call), grows them and fills again (*refilled = true).
 // pad_rule: AUTO's rejection of plans that would hold more than 1.75 x nnz slots (rows of very uneven length pad the
 // 8-way interleave: an octet is as long as its longest bundle) — pl->ready then stays false and nothing is written.
 int plan_begin(mx_spmm_plan *pl, int m, int K, const int32_t *indptr, const int32_t *indices, const double *values,
@@ -570,30 +654,26 @@ int plan_begin(mx_spmm_plan *pl, int m, int K, const int32_t *indptr, const int3
     const size_t nop = (size_t)pl->noct * npanels;
     const size_t al = 255;
     const size_t steps_b = (((size_t)pl->noct * 4) + al) & ~al;
-    const size_t octoff_b = ((((size_t)pl->noct + 1) * 4) + al) & ~al;
-    const size_t rb_b = 256;                                        // [total steps][nnz][go flag], read back in one copy
-    if (grow(&pl->scratch, &pl->scratch_cap, steps_b + octoff_b + rb_b + scan_workspace_bytes((int64_t)pl->noct))) return 1;
+    pl->tile_octs = plan_tile_octs(pl->noct);
+    pl->ntiles = (int)ceil_div(pl->noct, pl->tile_octs);
+    if (grow(&pl->scratch, &pl->scratch_cap, steps_b + PLAN_RB_BYTES)) return 1;
     if (grow((void **)&pl->step_off, &pl->step_off_cap, (nop + 1) * 4)) return 1;
     int32_t *steps = (int32_t *)pl->scratch;
-    int32_t *oct_off = (int32_t *)((char *)steps + steps_b);
-    long long *rb_dev = (long long *)((char *)oct_off + octoff_b);
-    void *scan_ws = (char *)rb_dev + rb_b;
-    const unsigned sblocks = (unsigned)ceil_div((long long)pl->noct * 8, 256);
-    hipLaunchKernelGGL(plan_size_kernel, dim3(sblocks), dim3(256), 0, st, m, pl->noct, indptr, steps, rb_dev + 1);
+    char *rb_dev = (char *)steps + steps_b;                          // [nnz][go flag][tile sums]: read back in one copy
+    pl->steps = steps;
+    pl->nnz_dev = (long long *)rb_dev; pl->go = (int *)(rb_dev + 8);
+    pl->tile_sums = (unsigned *)(rb_dev + PLAN_RB_HEAD);
+    hipLaunchKernelGGL(plan_size_kernel, dim3((unsigned)pl->ntiles), dim3(256), 0, st, m, pl->noct, pl->tile_octs, indptr,
+                       steps, (unsigned *)(rb_dev + PLAN_RB_HEAD), (long long *)rb_dev);
     MX_LAUNCH_CHECK();
-    if (exclusive_scan_i32(steps, (int64_t)pl->noct, oct_off, (int64_t *)rb_dev, scan_ws, st)) return 1;
     PlanReadback *rb = plan_readback();
     MX_REQUIRE(rb, "spmm plan: cannot allocate the pinned read-back buffer");
-    MX_HIP(hipMemcpyAsync(rb->host, rb_dev, 2 * sizeof(long long), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipMemcpyAsync(rb->host, rb_dev, PLAN_RB_HEAD + (size_t)pl->ntiles * sizeof(unsigned), hipMemcpyDeviceToHost, st));
     MX_HIP(hipEventRecord(rb->ev, st));
     pl->indptr = indptr; pl->indices = indices; pl->values = values;
-    pl->oct_off = oct_off; pl->sizes = rb_dev; pl->go = (int *)(rb_dev + 2);
     pl->pad_rule = pad_rule;
     pl->fill_cap = (long long)std::min(pl->pcol_cap / 4, pl->pval_cap / 8);
-    hipLaunchKernelGGL(plan_fill_kernel, dim3((unsigned)pl->noct), dim3(512), 0, st, m, npanels, pl->panel_cols, indptr,
-                       indices, values, oct_off, pl->pcol, pl->pval, pl->noct, K, pl->step_off, pl->sizes, pl->fill_cap,
-                       pad_rule, pl->go);
-    MX_LAUNCH_CHECK();
+    if (launch_fill(pl, st)) return 1;
     pl->pending = true;
     return 0;
 }
@@ -605,8 +685,11 @@ int plan_end(mx_spmm_plan *pl, hipStream_t st, bool *refilled)
     pl->pending = false;
     PlanReadback *rb = plan_readback();
     MX_HIP(hipEventSynchronize(rb->ev));
-    const long long total = rb->host[0];
-    pl->nnz = (int32_t)rb->host[1];
+    const long long nnz = *(const long long *)rb->host;           // hipHostMalloc'ed: aligned
+    long long total = 0;
+    const unsigned *sums = (const unsigned *)(rb->host + PLAN_RB_HEAD);
+    for (int i = 0; i < pl->ntiles; i++) total += sums[i];
+    pl->nnz = (int32_t)nnz;
     MX_REQUIRE(total >= 0 && total * 8 <= (long long)INT_MAX * 4LL, "spmm plan: too many steps (%lld)", total);
     MX_REQUIRE(total <= (long long)INT_MAX, "spmm plan: step offsets exceed int32");
     pl->total_steps = total;
@@ -616,10 +699,7 @@ int plan_end(mx_spmm_plan *pl, hipStream_t st, bool *refilled)
     if (grow((void **)&pl->pcol, &pl->pcol_cap, slots * 4)) return 1;
     if (grow((void **)&pl->pval, &pl->pval_cap, slots * 8)) return 1;
     pl->fill_cap = (long long)std::min(pl->pcol_cap / 4, pl->pval_cap / 8);
-    hipLaunchKernelGGL(plan_fill_kernel, dim3((unsigned)pl->noct), dim3(512), 0, st, pl->m, pl->npanels, pl->panel_cols,
-                       pl->indptr, pl->indices, pl->values, pl->oct_off, pl->pcol, pl->pval, pl->noct, pl->K, pl->step_off,
-                       pl->sizes, pl->fill_cap, pl->pad_rule, pl->go);
-    MX_LAUNCH_CHECK();
+    if (launch_fill(pl, st)) return 1;
     pl->ready = true;
     if (refilled) *refilled = true;
     return 0;
