@@ -13,6 +13,7 @@
 // ascending) instead of the reference's hash map; rows are re-ordered by new column id afterwards unless
 // cols_take is non-decreasing, as the reference does.
 #include "mx_dispatch.h"
+#include "mx_workspace.h"
 
 namespace mx {
 
@@ -195,7 +196,7 @@ extern "C" int mxd_csr_colrange_count(int r, const int32_t *indptr, const int32_
 {
     MX_REQUIRE(r >= 0 && new_indptr && workspace, "mxd_csr_colrange_count: bad arguments");
     hipStream_t st = mx::as_stream(stream);
-    int32_t *lens = (int32_t *)workspace;
+    int32_t *lens = mx::CountLayout(workspace, r).counts;
     if (r > 0) {
         const int G = mx::pick_group(avg_row_len);
         const int rc = mx::launch_rows(mx::lane_groups{}, "mxd_csr_colrange_count", G, r, mx::CS_BLOCK,
@@ -227,31 +228,37 @@ extern "C" int mxd_csr_colrange_fill(int r, const int32_t *indptr, const int32_t
     });
 }
 
-extern "C" size_t mxd_colmap_workspace_bytes(int ncol_map)
-{
-    // [cursor int32[ncol_map]][counts int32[ncol_map]][scan workspace]
-    return 2 * mx::padded_i32_bytes(ncol_map) + mx::scan_workspace_bytes(ncol_map);
-}
+namespace mx {
+// cursor and counts are adjacent: one memset clears both
+struct ColmapLayout {
+    WsCursor c;
+    int ncol_map;
+    int32_t *cursor = c.take_i32(ncol_map), *counts = c.take_i32(ncol_map);
+    void *scan_ws = c.take(scan_workspace_bytes(ncol_map));
+    size_t bytes = c.bytes();
+    ColmapLayout(const void *ws, int ncol_map_) : c(ws), ncol_map(ncol_map_) {}
+};
+}  // namespace mx
+
+extern "C" size_t mxd_colmap_workspace_bytes(int ncol_map) { return mx::ColmapLayout(nullptr, ncol_map).bytes; }
 
 extern "C" int mxd_colmap_build(const int32_t *cols_take, int64_t n, int ncol_map, int32_t *start, int32_t *pos,
                                 void *workspace, void *stream)
 {
     MX_REQUIRE(n >= 0 && ncol_map >= 0 && start && workspace, "mxd_colmap_build: bad arguments");
     hipStream_t st = mx::as_stream(stream);
-    const size_t seg = mx::padded_i32_bytes(ncol_map);
-    int32_t *cursor = (int32_t *)workspace;
-    int32_t *cnt = (int32_t *)((char *)workspace + seg);
-    void *scan_ws = (char *)workspace + 2 * seg;
-    MX_HIP(hipMemsetAsync(workspace, 0, 2 * seg, st));
-    const unsigned grid = (unsigned)(mx::ceil_div(n > 0 ? n : 1, 256) < 1024 ? mx::ceil_div(n > 0 ? n : 1, 256) : 1024);
+    const mx::ColmapLayout L(workspace, ncol_map);
+    MX_HIP(hipMemsetAsync(L.cursor, 0, 2 * mx::padded_i32_bytes(ncol_map), st));
+    const unsigned grid = mx::grid_for(n, 256, 1024);
     if (n > 0) {
-        hipLaunchKernelGGL(mx::colmap_count_kernel, dim3(grid), dim3(256), 0, st, cols_take, n, ncol_map, cnt);
+        hipLaunchKernelGGL(mx::colmap_count_kernel, dim3(grid), dim3(256), 0, st, cols_take, n, ncol_map, L.counts);
         MX_LAUNCH_CHECK();
     }
-    const int rc = mx::exclusive_scan_i32(cnt, ncol_map, start, nullptr, scan_ws, st);
+    const int rc = mx::exclusive_scan_i32(L.counts, ncol_map, start, nullptr, L.scan_ws, st);
     if (rc) return rc;
     if (n > 0) {
-        hipLaunchKernelGGL(mx::colmap_place_kernel, dim3(grid), dim3(256), 0, st, cols_take, n, ncol_map, start, cursor, pos);
+        hipLaunchKernelGGL(mx::colmap_place_kernel, dim3(grid), dim3(256), 0, st, cols_take, n, ncol_map, start,
+                           L.cursor, pos);
         MX_LAUNCH_CHECK();
         const unsigned g2 = (unsigned)(mx::ceil_div(ncol_map, 256) < 2048 ? mx::ceil_div(ncol_map, 256) : 2048);
         hipLaunchKernelGGL(mx::colmap_order_kernel, dim3(g2), dim3(256), 0, st, ncol_map, start, pos);
@@ -266,7 +273,7 @@ extern "C" int mxd_csr_colmap_count(int r, const int32_t *indptr, const int32_t 
 {
     MX_REQUIRE(r >= 0 && new_indptr && workspace, "mxd_csr_colmap_count: bad arguments");
     hipStream_t st = mx::as_stream(stream);
-    int32_t *lens = (int32_t *)workspace;
+    int32_t *lens = mx::CountLayout(workspace, r).counts;
     if (r > 0) {
         const int G = mx::pick_group(avg_row_len);
         const int rc = mx::launch_rows(mx::lane_groups{}, "mxd_csr_colmap_count", G, r, mx::CS_BLOCK,

@@ -20,7 +20,7 @@
 // fall into rows: a 1 M-entry row is 256 tiles like any other 1 M entries.
 // Loads of a tile are issued together ahead of their first use, in blocks hoisted out of any per-element condition
 // (a wave-uniform condition per element still makes hipcc wait for each load in turn).
-#include "mx_common.h"
+#include "mx_workspace.h"
 
 namespace mx {
 
@@ -220,11 +220,10 @@ void validate_kernel(const int32_t *__restrict__ idx, int64_t n, int bound, cons
 }
 
 static int64_t compact_ntiles(int64_t n) { return ceil_div(n > 0 ? n : 0, CP_TILE); }
-// workspace: [count workspace of ntiles][tile offsets ntiles + 1]
-static int32_t *compact_offsets(void *workspace, int64_t ntiles)
-{
-    return (int32_t *)((char *)workspace + count_workspace_bytes(ntiles));
-}
+// per tile: its count, then its offset in the output
+struct CompactLayout : CountOffsetsLayout {
+    CompactLayout(const void *ws, int64_t n) : CountOffsetsLayout(ws, compact_ntiles(n)) {}
+};
 
 static bool rule_ok(int rule, int value_dtype, const void *values, const int32_t *mask)
 {
@@ -241,11 +240,7 @@ static int value_bytes(int value_dtype)
 
 }  // namespace mx
 
-extern "C" size_t mxd_compact_workspace_bytes(int64_t n)
-{
-    const int64_t t = mx::compact_ntiles(n);
-    return mx::count_workspace_bytes(t) + mx::padded_i32_bytes(t + 1);
-}
+extern "C" size_t mxd_compact_workspace_bytes(int64_t n) { return mx::CompactLayout(nullptr, n).bytes; }
 
 extern "C" int mxd_compact_count(int64_t n, const void *values, int value_dtype, int rule, const int32_t *mask,
                                  void *workspace, int64_t *kept_host, void *stream)
@@ -258,7 +253,8 @@ extern "C" int mxd_compact_count(int64_t n, const void *values, int value_dtype,
     MX_REQUIRE(workspace && mx::rule_ok(rule, value_dtype, values, mask), "mxd_compact_count: bad rule or null pointer");
     hipStream_t st = mx::as_stream(stream);
     const int64_t t = mx::compact_ntiles(n);
-    int32_t *counts = (int32_t *)workspace;
+    const mx::CompactLayout L(workspace, n);
+    int32_t *counts = L.counts;
     if (vb == 8)
         hipLaunchKernelGGL(mx::compact_count_kernel<8>, dim3((unsigned)t), dim3(mx::CP_BLOCK), 0, st, n, values, rule,
                            mask, counts);
@@ -269,7 +265,7 @@ extern "C" int mxd_compact_count(int64_t n, const void *values, int value_dtype,
         hipLaunchKernelGGL(mx::compact_count_kernel<0>, dim3((unsigned)t), dim3(mx::CP_BLOCK), 0, st, n, values, rule,
                            mask, counts);
     MX_LAUNCH_CHECK();
-    return mx::finish_count(t, workspace, mx::compact_offsets(workspace, t), kept_host, st);
+    return mx::finish_count(t, L.counts, L.offsets, kept_host, st);
 }
 
 extern "C" int mxd_compact_fill(int64_t n, const void *values, int value_dtype, int rule, const int32_t *mask,
@@ -289,7 +285,7 @@ extern "C" int mxd_compact_fill(int64_t n, const void *values, int value_dtype, 
     }
     MX_REQUIRE(workspace && mx::rule_ok(rule, value_dtype, values, mask), "mxd_compact_fill: bad rule or null pointer");
     const int64_t t = mx::compact_ntiles(n);
-    const int32_t *off = mx::compact_offsets(const_cast<void *>(workspace), t);
+    const int32_t *off = mx::CompactLayout(workspace, n).offsets;
     void *ov = vb ? out_values : nullptr;
     if (vb == 8)
         hipLaunchKernelGGL(mx::compact_fill_kernel<8>, dim3((unsigned)t), dim3(mx::CP_BLOCK), 0, st, n, t, values, rule,

@@ -11,7 +11,7 @@
 // by count -> scan -> fill, so a duplicated COO entry gives one output entry per occurrence.
 // The reference tests only `row < nrow(X)` and `col < ncol(X)`; a negative index is skipped here as well, so no
 // index is used to read outside X.
-#include "mx_common.h"
+#include "mx_workspace.h"
 
 namespace mx {
 
@@ -78,19 +78,11 @@ void csr_by_coo_fill_kernel(int m, int ncol, const int32_t *__restrict__ indptr,
     else ((double *)out_vals)[q] = xd * ((const double *)yvals)[k];
 }
 
-// workspace: [count workspace of nnz_y][pos nnz_y + 1]
-static int32_t *cb_pos(void *workspace, int64_t nnz_y)
-{
-    return (int32_t *)((char *)workspace + count_workspace_bytes(nnz_y));
-}
+using CbLayout = CountOffsetsLayout;         // per entry of y: its count, then its position in the output
 
 }  // namespace mx
 
-extern "C" size_t mxd_csr_by_coo_workspace_bytes(int64_t nnz_y)
-{
-    const int64_t n = nnz_y > 0 ? nnz_y : 0;
-    return mx::count_workspace_bytes(n) + mx::padded_i32_bytes(n + 1);
-}
+extern "C" size_t mxd_csr_by_coo_workspace_bytes(int64_t nnz_y) { return mx::CbLayout(nullptr, nnz_y).bytes; }
 
 extern "C" int mxd_csr_by_coo_count(int logical, int m, int ncol, const int32_t *indptr, const int32_t *indices,
                                     const void *x_values, const int32_t *y_rows, const int32_t *y_cols,
@@ -103,7 +95,8 @@ extern "C" int mxd_csr_by_coo_count(int logical, int m, int ncol, const int32_t 
     MX_REQUIRE(m == 0 || indptr, "mxd_csr_by_coo_count: null pointer");
     if (nnz_y == 0) { *nnz_out_host = 0; return 0; }
     hipStream_t st = mx::as_stream(stream);
-    int32_t *counts = (int32_t *)workspace;
+    const mx::CbLayout L(workspace, nnz_y);
+    int32_t *counts = L.counts;
     const unsigned g = (unsigned)mx::ceil_div(nnz_y, mx::CB_BLOCK);
     if (logical)
         hipLaunchKernelGGL(mx::csr_by_coo_count_kernel<true>, dim3(g), dim3(mx::CB_BLOCK), 0, st, m, ncol, indptr,
@@ -112,7 +105,7 @@ extern "C" int mxd_csr_by_coo_count(int logical, int m, int ncol, const int32_t 
         hipLaunchKernelGGL(mx::csr_by_coo_count_kernel<false>, dim3(g), dim3(mx::CB_BLOCK), 0, st, m, ncol, indptr,
                            indices, x_values, y_rows, y_cols, y_values, nnz_y, counts);
     MX_LAUNCH_CHECK();
-    return mx::finish_count(nnz_y, workspace, mx::cb_pos(workspace, nnz_y), nnz_out_host, st);
+    return mx::finish_count(nnz_y, L.counts, L.offsets, nnz_out_host, st);
 }
 
 extern "C" int mxd_csr_by_coo_fill(int logical, int m, int ncol, const int32_t *indptr, const int32_t *indices,
@@ -124,7 +117,7 @@ extern "C" int mxd_csr_by_coo_fill(int logical, int m, int ncol, const int32_t *
     if (nnz_y == 0) return 0;
     MX_REQUIRE(y_rows && y_cols && y_values && workspace, "mxd_csr_by_coo_fill: null pointer");
     hipStream_t st = mx::as_stream(stream);
-    const int32_t *pos = mx::cb_pos(const_cast<void *>(workspace), nnz_y);
+    const int32_t *pos = mx::CbLayout(workspace, nnz_y).offsets;
     const unsigned g = (unsigned)mx::ceil_div(nnz_y, mx::CB_BLOCK);
     if (logical)
         hipLaunchKernelGGL(mx::csr_by_coo_fill_kernel<true>, dim3(g), dim3(mx::CB_BLOCK), 0, st, m, ncol, indptr,

@@ -26,6 +26,7 @@
 // single: smallest k with (rows[k], cols[k]) == (r, c) by a per-block minimum and one final block; the final block
 //        also reads the value, so the host reads back 16 bytes.
 #include "mx_dispatch.h"
+#include "mx_workspace.h"
 
 #include <cstring>
 
@@ -214,15 +215,22 @@ void coo_single_final_kernel(const long long *__restrict__ partial, int nblocks,
     }
 }
 
-// workspace: [count workspace of nnz][offsets nnz + 1][flags 16 B]
-static int32_t *csl_offsets(void *workspace, int64_t nnz)
-{
-    return (int32_t *)((char *)workspace + count_workspace_bytes(nnz));
-}
-static int32_t *csl_flags(void *workspace, int64_t nnz)
-{
-    return (int32_t *)((char *)csl_offsets(workspace, nnz) + padded_i32_bytes(nnz + 1));
-}
+struct CslLayout {
+    WsCursor c;
+    int64_t nnz;
+    int32_t *counts = c.take_counts(nnz), *offsets = c.take_i32(nnz + 1), *flags = c.take<int32_t>(16);
+    size_t bytes = c.bytes();
+    CslLayout(const void *ws, int64_t nnz_) : c(ws), nnz(nnz_ > 0 ? nnz_ : 0) {}
+};
+
+// the single-cell lookup: {entry index, value bits}, then one partial per block
+struct CssLayout {
+    WsCursor c;
+    long long *out = c.take<long long>(2 * sizeof(long long));
+    long long *partial = c.take<long long>(CSS_MAX_BLOCKS * sizeof(long long));
+    size_t bytes = c.bytes();
+    explicit CssLayout(const void *ws) : c(ws) {}
+};
 
 static int csl_check_axis(const mx_coo_axis *a, int n, const char *what)
 {
@@ -253,11 +261,7 @@ static int csl_dispatch_axes(const mx_coo_axis *axis_i, const mx_coo_axis *axis_
 
 }  // namespace mx
 
-extern "C" size_t mxd_coo_slice_workspace_bytes(int64_t nnz)
-{
-    const int64_t n = nnz > 0 ? nnz : 0;
-    return mx::count_workspace_bytes(n) + mx::padded_i32_bytes(n + 1) + 16;
-}
+extern "C" size_t mxd_coo_slice_workspace_bytes(int64_t nnz) { return mx::CslLayout(nullptr, nnz).bytes; }
 
 extern "C" int mxd_coo_slice_count(int nrow, int ncol, const int32_t *rows, const int32_t *cols, int64_t nnz,
                                    const mx_coo_axis *axis_i, const mx_coo_axis *axis_j, void *workspace,
@@ -268,16 +272,17 @@ extern "C" int mxd_coo_slice_count(int nrow, int ncol, const int32_t *rows, cons
     if (mx::csl_check_axis(axis_i, nrow, "row") || mx::csl_check_axis(axis_j, ncol, "column")) return 1;
     if (nnz == 0) { *nnz_out_host = 0; return 0; }
     hipStream_t st = mx::as_stream(stream);
-    int32_t *flags = mx::csl_flags(workspace, nnz);
+    const mx::CslLayout L(workspace, nnz);
+    int32_t *flags = L.flags;
     MX_HIP(hipMemsetAsync(flags, 0, 16, st));
     const mx::CslAxis ai = mx::csl_axis(*axis_i), aj = mx::csl_axis(*axis_j);
     const unsigned g = (unsigned)mx::ceil_div(nnz, mx::CSL_BLOCK);
     const int lrc = mx::csl_dispatch_axes(axis_i, axis_j, [&](auto mi, auto mj) {
         hipLaunchKernelGGL((mx::coo_slice_count_kernel<mi(), mj()>), dim3(g), dim3(mx::CSL_BLOCK), 0, st, nrow, ncol,
-                           rows, cols, nnz, ai, aj, (int32_t *)workspace, flags);
+                           rows, cols, nnz, ai, aj, L.counts, flags);
     });
     if (lrc) return lrc;
-    const int rc = mx::finish_count(nnz, workspace, mx::csl_offsets(workspace, nnz), nnz_out_host, st);
+    const int rc = mx::finish_count(nnz, L.counts, L.offsets, nnz_out_host, st);
     int32_t hf[4] = {0, 0, 0, 0};
     MX_HIP(hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, st));
     MX_HIP(hipStreamSynchronize(st));
@@ -299,7 +304,7 @@ extern "C" int mxd_coo_slice_fill(int nrow, int ncol, const int32_t *rows, const
     MX_REQUIRE(rows && cols && workspace && out_rows && out_cols, "mxd_coo_slice_fill: null pointer");
     MX_REQUIRE(value_dtype == MX_NONE || (values && out_values), "mxd_coo_slice_fill: null values");
     hipStream_t st = mx::as_stream(stream);
-    const int32_t *off = mx::csl_offsets(const_cast<void *>(workspace), nnz);
+    const int32_t *off = mx::CslLayout(workspace, nnz).offsets;
     const mx::CslAxis ai = mx::csl_axis(*axis_i), aj = mx::csl_axis(*axis_j);
     const unsigned g = (unsigned)mx::ceil_div(nnz, mx::CSL_BLOCK);
     using kinds = mx::int_list<MX_F64, MX_LGL, MX_NONE>;
@@ -311,10 +316,7 @@ extern "C" int mxd_coo_slice_fill(int nrow, int ncol, const int32_t *rows, const
     });
 }
 
-extern "C" size_t mxd_coo_single_workspace_bytes(void)
-{
-    return sizeof(long long) * (2 + mx::CSS_MAX_BLOCKS);
-}
+extern "C" size_t mxd_coo_single_workspace_bytes(void) { return mx::CssLayout(nullptr).bytes; }
 
 extern "C" int mxd_coo_single(const int32_t *rows, const int32_t *cols, const void *values, int value_dtype,
                               int64_t nnz, int r, int c, void *workspace, int64_t *k_host, void *value_host,
@@ -327,7 +329,8 @@ extern "C" int mxd_coo_single(const int32_t *rows, const int32_t *cols, const vo
     *k_host = -1;
     if (nnz == 0) return 0;
     hipStream_t st = mx::as_stream(stream);
-    long long *out = (long long *)workspace, *partial = out + 2;
+    const mx::CssLayout L(workspace);
+    long long *out = L.out, *partial = L.partial;
     const int64_t want = mx::ceil_div(nnz, mx::CSL_BLOCK);
     const int nb = (int)(want < mx::CSS_MAX_BLOCKS ? want : mx::CSS_MAX_BLOCKS);
     hipLaunchKernelGGL(mx::coo_single_partial_kernel, dim3(nb), dim3(mx::CSL_BLOCK), 0, st, rows, cols, nnz, r, c,

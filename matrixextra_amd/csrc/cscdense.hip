@@ -22,6 +22,7 @@
 // and an entry whose cell falls outside its tile (an index outside [0, m)) is ignored in both, so that nothing is
 // written or read out of bounds whatever the input.
 #include "mx_dispatch.h"
+#include "mx_workspace.h"
 
 namespace mx {
 
@@ -62,9 +63,8 @@ __device__ __forceinline__ int64_t cd_first_at(int64_t f, int64_t m, int n, cons
 {
     const int64_t c = f / m;
     if (c >= n) return nnz;
-    int64_t s = indptr[c], e = indptr[c + 1];
-    s = s < 0 ? 0 : s > nnz ? nnz : s;
-    e = e < s ? s : e > nnz ? nnz : e;
+    const RowBounds b = row_bounds(indptr[c], indptr[c + 1], nnz);
+    int64_t s = b.start, e = b.start + b.len;
     const int key = (int)(f - c * m);
     while (e > s) {                                       // the answer lies in [s, e]
         const int64_t step = (e - s + MX_WAVE - 1) / MX_WAVE;
@@ -257,26 +257,22 @@ void cd_fill_kernel(int64_t m, int n, int64_t F, int64_t ntiles, const int32_t *
 
 static int64_t cd_ntiles(int m, int n) { return ceil_div((int64_t)m * (int64_t)n, CD_TILE); }
 
-// workspace: [count workspace of ntiles][tile offsets ntiles + 1][NA-outside flag, 16 B][NA mask, 64 words a tile]
-//            [first entry of each tile, ntiles]
-static int32_t *cd_offsets(void *ws, int64_t t) { return (int32_t *)((char *)ws + count_workspace_bytes(t)); }
-static unsigned long long *cd_outside(void *ws, int64_t t)
-{
-    return (unsigned long long *)((char *)cd_offsets(ws, t) + padded_i32_bytes(t + 1));
-}
-static unsigned long long *cd_mask(void *ws, int64_t t) { return cd_outside(ws, t) + 2; }
-static int32_t *cd_first(void *ws, int64_t t) { return (int32_t *)(cd_mask(ws, t) + t * CD_WORDS); }
+struct CdLayout {
+    WsCursor c;
+    int64_t ntiles;
+    int32_t *counts = c.take_counts(ntiles), *offsets = c.take_i32(ntiles + 1);       // per tile; offsets one more
+    unsigned long long *na_outside = c.take<unsigned long long>(16);    // one word in 16 B: an NA outside the pattern
+    unsigned long long *na_mask = c.take<unsigned long long>(sizeof(unsigned long long) * (size_t)ntiles * CD_WORDS);
+    int32_t *first = c.take_i32(ntiles);                                // first entry of each tile
+    size_t bytes = c.bytes();
+    CdLayout(const void *ws, int m, int n) : c(ws), ntiles(m > 0 && n > 0 ? cd_ntiles(m, n) : 0) {}
+};
 
 using cd_kinds = int_list<0, 1, 2, 3>;
 
 }  // namespace mx
 
-extern "C" size_t mxd_csc_dense_na_workspace_bytes(int m, int n)
-{
-    const int64_t t = m > 0 && n > 0 ? mx::cd_ntiles(m, n) : 0;
-    return mx::count_workspace_bytes(t) + mx::padded_i32_bytes(t + 1) + 16 +
-           sizeof(unsigned long long) * (size_t)t * mx::CD_WORDS + mx::padded_i32_bytes(t);
-}
+extern "C" size_t mxd_csc_dense_na_workspace_bytes(int m, int n) { return mx::CdLayout(nullptr, m, n).bytes; }
 
 extern "C" int mxd_csc_dense_na_count(int m, int n, int64_t nnz, const int32_t *indptr, const int32_t *indices,
                                       const void *dense_colmajor, int dense_kind, void *workspace,
@@ -290,22 +286,22 @@ extern "C" int mxd_csc_dense_na_count(int m, int n, int64_t nnz, const int32_t *
     if (m == 0 || n == 0) return 0;
     MX_REQUIRE(workspace && indptr && dense_colmajor && (nnz == 0 || indices), "mxd_csc_dense_na_count: null pointer");
     hipStream_t st = mx::as_stream(stream);
-    const int64_t t = mx::cd_ntiles(m, n);
+    const mx::CdLayout L(workspace, m, n);
+    const int64_t t = L.ntiles;
     MX_REQUIRE(t <= (int64_t)UINT_MAX, "mxd_csc_dense_na_count: dense operand too large");
-    unsigned long long *outside = mx::cd_outside(workspace, t);
+    unsigned long long *outside = L.na_outside;
     MX_HIP(hipMemsetAsync(outside, 0, sizeof(unsigned long long), st));
     const int64_t F = (int64_t)m * (int64_t)n;
     const int rc = mx::dispatch_int(mx::cd_kinds{}, "mxd_csc_dense_na_count", "dense kind", dense_kind, [&](auto dk) {
         hipLaunchKernelGGL(mx::cd_count_kernel<dk()>, dim3((unsigned)t), dim3(mx::CD_BLOCK), 0, st, (int64_t)m, n, F,
-                           indptr, indices, nnz, dense_colmajor, mx::cd_mask(workspace, t), (int32_t *)workspace,
-                           mx::cd_first(workspace, t), outside);
+                           indptr, indices, nnz, dense_colmajor, L.na_mask, L.counts, L.first, outside);
         MX_LAUNCH_CHECK();
         return 0;
     });
     if (rc) return rc;
     MX_HIP(hipMemcpyAsync(na_outside_host, outside, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     // the 64-bit total is read back (one synchronise) and refused above INT_MAX before any output exists
-    return mx::finish_count(t, workspace, mx::cd_offsets(workspace, t), nnz_out_host, st);
+    return mx::finish_count(t, L.counts, L.offsets, nnz_out_host, st);
 }
 
 extern "C" int mxd_csc_dense_na_fill(int m, int n, int64_t nnz, const int32_t *indptr, const int32_t *indices,
@@ -323,13 +319,13 @@ extern "C" int mxd_csc_dense_na_fill(int m, int n, int64_t nnz, const int32_t *i
     }
     MX_REQUIRE(workspace && indptr && dense_colmajor && (nnz == 0 || (indices && values)) && out_indices && out_values,
                "mxd_csc_dense_na_fill: null pointer");
-    const int64_t t = mx::cd_ntiles(m, n);
-    void *ws = const_cast<void *>(workspace);
+    const mx::CdLayout L(workspace, m, n);
+    const int64_t t = L.ntiles;
     const int64_t F = (int64_t)m * (int64_t)n;
     return mx::dispatch_int(mx::cd_kinds{}, "mxd_csc_dense_na_fill", "dense kind", dense_kind, [&](auto dk) {
         hipLaunchKernelGGL(mx::cd_fill_kernel<dk()>, dim3((unsigned)t), dim3(mx::CD_BLOCK), 0, st, (int64_t)m, n, F, t,
-                           indptr, indices, nnz, values, dense_colmajor, mx::cd_mask(ws, t), mx::cd_offsets(ws, t),
-                           mx::cd_first(ws, t), out_indptr, out_indices, out_values);
+                           indptr, indices, nnz, values, dense_colmajor, L.na_mask, L.offsets, L.first, out_indptr,
+                           out_indices, out_values);
         MX_LAUNCH_CHECK();
         return 0;
     });

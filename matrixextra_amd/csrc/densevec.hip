@@ -24,6 +24,7 @@
 // Every write position comes from the scanned counts and every row / column / cell index is checked against its
 // bound, so that nothing is read or written out of bounds whatever the input.
 #include "mx_dispatch.h"
+#include "mx_workspace.h"
 
 namespace mx {
 
@@ -232,9 +233,12 @@ void coo_by_dense_kernel(int64_t nnz, const int32_t *__restrict__ ii, const int3
 using dsv_kinds = int_list<0, 1, 2, 3>;
 using coo_dense_kinds = int_list<0, 1, 2, 3, 4>;
 
-// workspace: [position map: length][count workspace of nrows]
-static int32_t *dsv_pos(void *ws) { return (int32_t *)ws; }
-static void *dsv_counts(void *ws, int64_t length) { return (char *)ws + padded_i32_bytes(length); }
+struct DsvLayout {
+    WsCursor c;
+    int32_t *pos, *counts;                  // position map: `length` entries; counts per row
+    size_t bytes = c.bytes();
+    DsvLayout(const void *ws, int nrows, int length) : c(ws), pos(c.take_i32(length)), counts(c.take_counts(nrows)) {}
+};
 
 static int dsv_check(const char *what, int nrows, int ncols, int64_t nv, int length, int kind)
 {
@@ -259,7 +263,7 @@ static int dsv_build_map(const int32_t *vi, int64_t nv, int length, bool first, 
 
 extern "C" size_t mxd_dense_by_svec_workspace_bytes(int nrows, int length)
 {
-    return mx::padded_i32_bytes(length > 0 ? length : 0) + mx::count_workspace_bytes(nrows > 0 ? nrows : 0);
+    return mx::DsvLayout(nullptr, nrows, length).bytes;
 }
 
 extern "C" int mxd_dense_by_svec_dense(int nrows, int ncols, const void *dense_colmajor, int dense_kind,
@@ -273,7 +277,7 @@ extern "C" int mxd_dense_by_svec_dense(int nrows, int ncols, const void *dense_c
                "mxd_dense_by_svec_dense: null pointer");
     MX_REQUIRE(mx::ceil_div(F, mx::DSV_BLOCK) <= (int64_t)UINT_MAX, "mxd_dense_by_svec_dense: dense operand too large");
     hipStream_t st = mx::as_stream(stream);
-    int32_t *pos = mx::dsv_pos(workspace);
+    int32_t *pos = mx::DsvLayout(workspace, nrows, length).pos;
     if (mx::dsv_build_map(vi_base1, nv, length, false, pos, st)) return 1;
     return mx::dispatch_int(mx::dsv_kinds{}, "mxd_dense_by_svec_dense", "dense kind", dense_kind, [&](auto dk) {
         hipLaunchKernelGGL(mx::dsv_dense_kernel<dk()>, dim3((unsigned)mx::ceil_div(F, mx::DSV_BLOCK)),
@@ -295,22 +299,22 @@ extern "C" int mxd_dense_by_svec_count(int nrows, int ncols, const void *dense_c
                "mxd_dense_by_svec_count: null pointer");
     hipStream_t st = mx::as_stream(stream);
     *nnz_out_host = 0;
-    void *counts = mx::dsv_counts(workspace, length > 0 ? length : 0);
+    const mx::DsvLayout L(workspace, nrows, length);
     if (nrows > 0) {
-        int32_t *pos = mx::dsv_pos(workspace);
+        int32_t *pos = L.pos;
         if (mx::dsv_build_map(vi_base1, nv, length, true, pos, st)) return 1;
         const int rc = mx::dispatch_int(mx::dsv_kinds{}, "mxd_dense_by_svec_count", "dense kind", dense_kind,
                                         [&](auto dk) {
             hipLaunchKernelGGL(mx::dsv_count_kernel<dk()>, dim3((unsigned)mx::ceil_div(nrows, mx::DSV_BLOCK)),
                                dim3(mx::DSV_BLOCK), 0, st, nrows, ncols, dense_colmajor, pos, length, keep_na,
-                               (int32_t *)counts);
+                               L.counts);
             MX_LAUNCH_CHECK();
             return 0;
         });
         if (rc) return rc;
     }
     // the 64-bit total is read back (one synchronise) and refused above INT_MAX before any output exists
-    return mx::finish_count(nrows, counts, out_indptr, nnz_out_host, st);
+    return mx::finish_count(nrows, L.counts, out_indptr, nnz_out_host, st);
 }
 
 extern "C" int mxd_dense_by_svec_fill(int nrows, int ncols, const void *dense_colmajor, int dense_kind,
@@ -325,7 +329,7 @@ extern "C" int mxd_dense_by_svec_fill(int nrows, int ncols, const void *dense_co
     MX_REQUIRE(workspace && dense_colmajor && out_indptr && out_indices && out_values,
                "mxd_dense_by_svec_fill: null pointer");
     hipStream_t st = mx::as_stream(stream);
-    const int32_t *pos = mx::dsv_pos(const_cast<void *>(workspace));
+    const int32_t *pos = mx::DsvLayout(workspace, nrows, length).pos;
     const int col_tiles = (int)mx::ceil_div(ncols, mx::DSV_T);
     const int64_t tiles = mx::ceil_div(nrows, mx::DSV_T) * col_tiles;
     MX_REQUIRE(tiles <= (int64_t)UINT_MAX, "mxd_dense_by_svec_fill: dense operand too large");

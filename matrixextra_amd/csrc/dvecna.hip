@@ -30,6 +30,7 @@
 // Row bounds are clamped into [0, nnz], every write position comes from a scanned count, and the candidate count is
 // refused at INT_MAX before anything is allocated for it.
 #include "mx_dispatch.h"
+#include "mx_workspace.h"
 #include "mx_rarith.h"
 #include "mx_dense_row.h"
 
@@ -80,11 +81,9 @@ __device__ __forceinline__ DnRow dn_row(long long r, int64_t nnz, const int32_t 
                                         const double *__restrict__ dvec, int L, int op)
 {
     DnRow w;
-    int64_t s = indptr[r], e = indptr[r + 1];
-    s = s < 0 ? 0 : s > nnz ? nnz : s;
-    e = e < s ? s : e > nnz ? nnz : e;
-    w.s = (int)s;
-    w.len = (int)(e - s);
+    const RowBounds b = row_bounds(indptr[r], indptr[r + 1], nnz);
+    w.s = (int)b.start;
+    w.len = (int)b.len;
     w.val = dvec[r % L];
     w.filled = dn_row_filled(op, w.val);
     return w;
@@ -186,10 +185,9 @@ __device__ __forceinline__ bool dn_pair_cell(const DnPairs &pp, long long t, con
 __device__ __forceinline__ bool dn_cell_is_new(int row, int col, int64_t nnz, const int32_t *__restrict__ indptr,
                                                const int32_t *__restrict__ indices)
 {
-    int64_t s = indptr[row], e = indptr[row + 1];
-    s = s < 0 ? 0 : s > nnz ? nnz : s;
-    e = e < s ? s : e > nnz ? nnz : e;
-    const int len = (int)(e - s);
+    const RowBounds b = row_bounds(indptr[row], indptr[row + 1], nnz);
+    const int64_t s = b.start;
+    const int len = (int)b.len;
     if (len == 0) return true;
     const int lb = lower_bound_dev(indices + s, len, col);
     return lb >= len || indices[s + lb] != col;
@@ -232,16 +230,16 @@ void dn_indptr_sum_kernel(int m, const int32_t *__restrict__ p1, const int32_t *
 }
 
 static inline bool dn_op_known(int op) { return op >= MX_DV_MULTIPLY && op <= MX_DV_INTDIV; }
-static inline unsigned dn_grid(int64_t n) { return (unsigned)ceil_div(n > 0 ? n : 1, DN_BLOCK); }
 
-// special workspace: [count workspace of L][offsets: L + 1][special positions: L]
-static int32_t *dn_special_offsets(const void *ws, int64_t L) { return (int32_t *)((char *)ws + count_workspace_bytes(L)); }
-static int32_t *dn_special_list(const void *ws, int64_t L)
-{
-    return (int32_t *)((char *)dn_special_offsets(ws, L) + padded_i32_bytes(L + 1));
-}
-// cells workspace: [count workspace of the candidates][offsets: candidates + 1]
-static int32_t *dn_cells_offsets(const void *ws, int64_t c) { return (int32_t *)((char *)ws + count_workspace_bytes(c)); }
+// the special positions of the vector: a flag per position, the scanned flags, the positions compacted
+struct DnSpecialLayout {
+    WsCursor c;
+    int64_t L;
+    int32_t *counts = c.take_counts(L), *offsets = c.take_i32(L + 1), *list = c.take_i32(L);
+    size_t bytes = c.bytes();
+    DnSpecialLayout(const void *ws, int64_t L_) : c(ws), L(L_ > 0 ? L_ : 0) {}
+};
+using DnCellsLayout = CountOffsetsLayout;   // per candidate cell: is it new, then its position among the new ones
 
 static const char *const DN_OVERFLOW =
     "Error: the resulting matrix would have too many entries for a sparse CSR representation (int overflow).";
@@ -262,7 +260,7 @@ static int dn_pairs(const char *what, int m, int ncols, int64_t dvec_len, int64_
 
 }  // namespace mx
 
-extern "C" size_t mxd_csr_by_dvec_na_rows_workspace_bytes(int m) { return mx::count_workspace_bytes(m > 0 ? m : 0); }
+extern "C" size_t mxd_csr_by_dvec_na_rows_workspace_bytes(int m) { return mx::CountLayout(nullptr, m).bytes; }
 
 static int dn_rows_check(const char *what, int m, int ncols, int64_t nnz, int64_t dvec_len, int op)
 {
@@ -283,8 +281,8 @@ extern "C" int mxd_csr_by_dvec_na_rows_count(int m, int ncols, int64_t nnz, cons
     hipStream_t st = mx::as_stream(stream);
     *nnz_out_host = 0;
     if (m > 0) {
-        hipLaunchKernelGGL(mx::dn_rows_count_kernel, dim3(mx::dn_grid(m)), dim3(mx::DN_BLOCK), 0, st, m, ncols, nnz,
-                           indptr, dvec, (int)dvec_len, op, (int32_t *)workspace);
+        hipLaunchKernelGGL(mx::dn_rows_count_kernel, dim3(mx::grid_for(m, mx::DN_BLOCK)), dim3(mx::DN_BLOCK), 0, st, m,
+                           ncols, nnz, indptr, dvec, (int)dvec_len, op, mx::CountLayout(workspace, m).counts);
         MX_LAUNCH_CHECK();
     }
     // the 64-bit total is read back (one synchronise) and refused above INT_MAX before any output exists
@@ -309,11 +307,7 @@ extern "C" int mxd_csr_by_dvec_na_rows_fill(int m, int ncols, int64_t nnz, const
     });
 }
 
-extern "C" size_t mxd_dvec_na_special_workspace_bytes(int64_t dvec_len)
-{
-    const int64_t L = dvec_len > 0 ? dvec_len : 0;
-    return mx::count_workspace_bytes(L) + mx::padded_i32_bytes(L + 1) + mx::padded_i32_bytes(L);
-}
+extern "C" size_t mxd_dvec_na_special_workspace_bytes(int64_t L) { return mx::DnSpecialLayout(nullptr, L).bytes; }
 
 extern "C" int mxd_dvec_na_special(int m, int ncols, const double *dvec, int64_t dvec_len, int op, void *special_ws,
                                    int64_t *nspecial_host, int64_t *candidates_host, void *stream)
@@ -327,14 +321,15 @@ extern "C" int mxd_dvec_na_special(int m, int ncols, const double *dvec, int64_t
     MX_REQUIRE(L <= N, "mxd_dvec_na_special: the vector has more entries than the matrix");
     hipStream_t st = mx::as_stream(stream);
     *nspecial_host = *candidates_host = 0;
-    int32_t *offsets = mx::dn_special_offsets(special_ws, L);
-    hipLaunchKernelGGL(mx::dn_special_flag_kernel, dim3(mx::dn_grid(L)), dim3(mx::DN_BLOCK), 0, st, dvec, (int)L, op,
-                       (int32_t *)special_ws);
+    const mx::DnSpecialLayout S(special_ws, L);
+    int32_t *offsets = S.offsets;
+    hipLaunchKernelGGL(mx::dn_special_flag_kernel, dim3(mx::grid_for(L, mx::DN_BLOCK)), dim3(mx::DN_BLOCK), 0, st, dvec,
+                       (int)L, op, S.counts);
     MX_LAUNCH_CHECK();
-    if (mx::finish_count(L, special_ws, offsets, nspecial_host, st)) return 1;
+    if (mx::finish_count(L, S.counts, offsets, nspecial_host, st)) return 1;
     if (*nspecial_host == 0) return 0;
-    hipLaunchKernelGGL(mx::dn_special_scatter_kernel, dim3(mx::dn_grid(L)), dim3(mx::DN_BLOCK), 0, st, (int)L, offsets,
-                       mx::dn_special_list(special_ws, L));
+    hipLaunchKernelGGL(mx::dn_special_scatter_kernel, dim3(mx::grid_for(L, mx::DN_BLOCK)), dim3(mx::DN_BLOCK), 0, st,
+                       (int)L, offsets, S.list);
     MX_LAUNCH_CHECK();
     // sum over the special positions of ceil((N - ix) / L): R for those below cut, R - 1 for the others
     const long long R = (N + L - 1) / L, cut = N - (R - 1) * L;             // 0 < cut <= L
@@ -347,11 +342,7 @@ extern "C" int mxd_dvec_na_special(int m, int ncols, const double *dvec, int64_t
     return 0;
 }
 
-extern "C" size_t mxd_dvec_na_cells_workspace_bytes(int64_t candidates)
-{
-    const int64_t c = candidates > 0 ? candidates : 0;
-    return mx::count_workspace_bytes(c) + mx::padded_i32_bytes(c + 1);
-}
+extern "C" size_t mxd_dvec_na_cells_workspace_bytes(int64_t n) { return mx::DnCellsLayout(nullptr, n).bytes; }
 
 extern "C" int mxd_dvec_na_cells_count(int m, int ncols, int64_t nnz, const int32_t *indptr, const int32_t *indices,
                                        int64_t dvec_len, const void *special_ws, int64_t nspecial, int64_t candidates,
@@ -363,12 +354,14 @@ extern "C" int mxd_dvec_na_cells_count(int m, int ncols, int64_t nnz, const int3
                "mxd_dvec_na_cells_count: bad arguments");
     hipStream_t st = mx::as_stream(stream);
     *new_host = 0;
+    const mx::DnCellsLayout cells(cells_ws, candidates);
     if (candidates > 0) {
-        hipLaunchKernelGGL(mx::dn_cells_count_kernel, dim3(mx::dn_grid(candidates)), dim3(mx::DN_BLOCK), 0, st, pp, nnz,
-                           indptr, indices, mx::dn_special_list(special_ws, dvec_len), (int32_t *)cells_ws);
+        hipLaunchKernelGGL(mx::dn_cells_count_kernel, dim3(mx::grid_for(candidates, mx::DN_BLOCK)), dim3(mx::DN_BLOCK),
+                           0, st, pp, nnz, indptr, indices, mx::DnSpecialLayout(special_ws, dvec_len).list,
+                           cells.counts);
         MX_LAUNCH_CHECK();
     }
-    if (mx::finish_count(candidates, cells_ws, mx::dn_cells_offsets(cells_ws, candidates), new_host, st)) return 1;
+    if (mx::finish_count(candidates, cells.counts, cells.offsets, new_host, st)) return 1;
     MX_REQUIRE(*new_host == 0 || *new_host + nnz < (int64_t)INT_MAX, "%s", mx::DN_OVERFLOW);   // :2654-2660
     return 0;
 }
@@ -384,9 +377,9 @@ extern "C" int mxd_dvec_na_cells_fill(int m, int ncols, const double *dvec, int6
     if (candidates == 0) return 0;
     MX_REQUIRE(dvec && special_ws && cells_ws && out_rows && out_cols && out_values,
                "mxd_dvec_na_cells_fill: null pointer");
-    hipLaunchKernelGGL(mx::dn_cells_fill_kernel, dim3(mx::dn_grid(candidates)), dim3(mx::DN_BLOCK), 0,
-                       mx::as_stream(stream), pp, dvec, op, mx::dn_special_list(special_ws, dvec_len),
-                       mx::dn_cells_offsets(cells_ws, candidates), out_rows, out_cols, out_values);
+    hipLaunchKernelGGL(mx::dn_cells_fill_kernel, dim3(mx::grid_for(candidates, mx::DN_BLOCK)), dim3(mx::DN_BLOCK), 0,
+                       mx::as_stream(stream), pp, dvec, op, mx::DnSpecialLayout(special_ws, dvec_len).list,
+                       mx::DnCellsLayout(cells_ws, candidates).offsets, out_rows, out_cols, out_values);
     MX_LAUNCH_CHECK();
     return 0;
 }
@@ -398,8 +391,8 @@ extern "C" int mxd_csr_join_disjoint(int m, const int32_t *indptr1, const int32_
 {
     MX_REQUIRE(m >= 0 && nnz1 >= 0 && nnz2 >= 0 && nnz1 + nnz2 <= INT_MAX, "mxd_csr_join_disjoint: bad arguments");
     MX_REQUIRE(indptr1 && indptr2 && out_indptr, "mxd_csr_join_disjoint: null pointer");
-    hipLaunchKernelGGL(mx::dn_indptr_sum_kernel, dim3(mx::dn_grid((int64_t)m + 1)), dim3(mx::DN_BLOCK), 0,
-                       mx::as_stream(stream), m, indptr1, indptr2, out_indptr);
+    hipLaunchKernelGGL(mx::dn_indptr_sum_kernel, dim3(mx::grid_for((int64_t)m + 1, mx::DN_BLOCK)), dim3(mx::DN_BLOCK),
+                       0, mx::as_stream(stream), m, indptr1, indptr2, out_indptr);
     MX_LAUNCH_CHECK();
     if (m == 0 || nnz1 + nnz2 == 0) return 0;
     MX_REQUIRE(out_indices && out_values, "mxd_csr_join_disjoint: null pointer");

@@ -10,6 +10,7 @@
 // indices and values (contiguous source and destination segments, so both
 // sides are coalesced inside a row).  HBM-bound: 4r + 8r + 4(r+1) + 2*12*nnz_out bytes.
 #include "mx_dispatch.h"
+#include "mx_workspace.h"
 
 namespace mx {
 
@@ -115,7 +116,7 @@ static int run_flag_check(int32_t *flag_dev, int *flag_host, hipStream_t st, F &
 
 }  // namespace mx
 
-extern "C" size_t mxd_gather_workspace_bytes(int r) { return mx::count_workspace_bytes(r); }
+extern "C" size_t mxd_gather_workspace_bytes(int r) { return mx::CountLayout(nullptr, r).bytes; }
 
 extern "C" int mxd_csr_gather_count(int r, const int32_t *indptr, const int32_t *rows_take, int32_t *new_indptr,
                                     void *workspace, int64_t *nnz_out_host, void *stream)
@@ -125,7 +126,7 @@ extern "C" int mxd_csr_gather_count(int r, const int32_t *indptr, const int32_t 
     hipStream_t st = mx::as_stream(stream);
     if (r > 0) {
         hipLaunchKernelGGL(mx::gather_lengths_kernel, dim3((unsigned)mx::ceil_div(r, mx::GATHER_BLOCK)),
-                           dim3(mx::GATHER_BLOCK), 0, st, r, indptr, rows_take, (int32_t *)workspace);
+                           dim3(mx::GATHER_BLOCK), 0, st, r, indptr, rows_take, mx::CountLayout(workspace, r).counts);
         MX_LAUNCH_CHECK();
     }
     return mx::finish_count(r, workspace, new_indptr, nnz_out_host, st);

@@ -27,6 +27,7 @@
 // Roofline: HBM-bound; algorithmic bytes = 2*(12 nnz + 4(m+1)) read + 12 nnz_out + 4(m+1)
 // written; the count pass re-reads the indices (8 nnz) on top of that.
 #include "mx_dispatch.h"
+#include "mx_workspace.h"
 
 namespace mx {
 
@@ -267,7 +268,7 @@ int merge_fill_launch(int op, int G, int m, const int32_t *p1, const int32_t *j1
 
 }  // namespace mx
 
-extern "C" size_t mxd_merge_workspace_bytes(int m) { return mx::count_workspace_bytes(m); }
+extern "C" size_t mxd_merge_workspace_bytes(int m) { return mx::CountLayout(nullptr, m).bytes; }
 
 extern "C" int mxd_csr_merge_count(int op, int m, const int32_t *indptr1, const int32_t *indices1, int64_t nnz1,
                                    const int32_t *indptr2, const int32_t *indices2, int64_t nnz2,
@@ -278,7 +279,7 @@ extern "C" int mxd_csr_merge_count(int op, int m, const int32_t *indptr1, const 
     hipStream_t st = mx::as_stream(stream);
     if (m > 0) {
         const int rc = mx::merge_count_launch(op, mx::merge_group(m, nnz1, nnz2), m, indptr1, indices1, indptr2, indices2,
-                                              (int32_t *)workspace, st);
+                                              mx::CountLayout(workspace, m).counts, st);
         if (rc) return rc;
     }
     return mx::finish_count(m, workspace, out_indptr, nnz_out_host, st);

@@ -38,6 +38,13 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// blocks of `block` threads for n items (at least one), at most cap
+inline unsigned grid_for(int64_t n, int block, int64_t cap = UINT_MAX)
+{
+    const int64_t g = ceil_div(n > 0 ? n : 1, block);
+    return (unsigned)(g < cap ? g : cap);
+}
+
 // scan.hip: exclusive scan of counts[0..n) into out[0..n]; the int64 total goes to *total_dev (the workspace's
 // first word when null)
 size_t scan_workspace_bytes(int64_t n);
@@ -118,6 +125,17 @@ __device__ __forceinline__ int r_logical_xor(int x, int y)
 {
     if (x == MX_NA_INT || y == MX_NA_INT) return MX_NA_INT;
     return (x != 0) != (y != 0);
+}
+
+// a row's [indptr[r], indptr[r + 1]) clamped into [0, nnz], whatever the two words hold (they are taken as loaded,
+// int32, so that the compiler knows their range as it did when the clamp was written out in each kernel)
+struct RowBounds { int64_t start, len; };
+__device__ __forceinline__ RowBounds row_bounds(int32_t first, int32_t next, int64_t nnz)
+{
+    int64_t s = first, e = next;
+    s = s < 0 ? 0 : s > nnz ? nnz : s;
+    e = e < s ? s : e > nnz ? nnz : e;
+    return {s, e - s};
 }
 
 // first position in [first, first+count) whose value is >= key

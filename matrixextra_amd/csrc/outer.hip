@@ -29,6 +29,7 @@
 // Every write position comes from the scanned counts and is bounded by them again in the fill, positions of y
 // outside [1, y_length] are skipped in both passes, and a row start outside [0, nnz) reads nothing.
 #include "mx_dispatch.h"
+#include "mx_workspace.h"
 
 namespace mx {
 
@@ -133,28 +134,25 @@ void outer_svec_fill_kernel(int64_t items, int64_t chunks, const int32_t *__rest
     }
 }
 
-// workspace of the sparse outer product:
-// [compaction workspace of m][flags m][ids m][rows m][firsts m f64][compacted firsts m f64][count workspace of y_length]
-struct OuterWs {
-    char *base;
-    size_t i32, f64, cp;
-    OuterWs(const void *ws, int m)
-        : base((char *)const_cast<void *>(ws)), i32(padded_i32_bytes(m)), f64(2 * padded_i32_bytes(m)),
-          cp((mxd_compact_workspace_bytes(m) + 15) & ~(size_t)15) {}
-    int32_t *flags() const { return (int32_t *)(base + cp); }
-    int32_t *ids() const { return (int32_t *)(base + cp + i32); }
-    int32_t *rows() const { return (int32_t *)(base + cp + 2 * i32); }
-    double *firsts() const { return (double *)(base + cp + 3 * i32); }
-    double *kept_firsts() const { return (double *)(base + cp + 3 * i32 + f64); }
-    void *cols() const { return base + cp + 3 * i32 + 2 * f64; }
-    size_t bytes(int y_length) const { return cp + 3 * i32 + 2 * f64 + count_workspace_bytes(y_length); }
+// workspace of the sparse outer product
+struct OuterLayout {
+    WsCursor c;
+    int m, y_length;
+    void *compact = c.take((mxd_compact_workspace_bytes(m) + 15) & ~(size_t)15);   // mxd_compact_* over the m rows
+    int32_t *flags = c.take_i32(m), *ids = c.take_i32(m);              // per row: non-empty, its own id
+    int32_t *rows = c.take_i32(m);                                      // the non-empty rows, compacted
+    double *firsts = c.take<double>(2 * padded_i32_bytes(m));           // per row: its first value
+    double *kept_firsts = c.take<double>(2 * padded_i32_bytes(m));      // the same, compacted
+    int32_t *col_counts = c.take_counts(y_length);                      // per column of the result
+    size_t bytes = c.bytes();
+    OuterLayout(const void *ws, int m_, int y_length_) : c(ws), m(m_), y_length(y_length_) {}
 };
 
 static const char *const OUTER_OVERFLOW = "%s: the outer product has %lld entries: exceeds R's int32 index range";
 
 }  // namespace mx
 
-extern "C" size_t mxd_csr_outer_dense_workspace_bytes(int m) { return mx::count_workspace_bytes(m > 0 ? m : 0); }
+extern "C" size_t mxd_csr_outer_dense_workspace_bytes(int m) { return mx::CountLayout(nullptr, m).bytes; }
 
 extern "C" int mxd_csr_outer_dense_count(int m, int dim, const int32_t *indptr, void *workspace, int32_t *out_indptr,
                                          int64_t *nnz_out_host, void *stream)
@@ -165,7 +163,7 @@ extern "C" int mxd_csr_outer_dense_count(int m, int dim, const int32_t *indptr, 
     *nnz_out_host = 0;
     if (m > 0) {
         hipLaunchKernelGGL(mx::outer_mark_kernel, dim3((unsigned)mx::ceil_div(m, mx::OP_BLOCK)), dim3(mx::OP_BLOCK), 0,
-                           st, m, dim, indptr, (int32_t *)workspace);
+                           st, m, dim, indptr, mx::CountLayout(workspace, m).counts);
         MX_LAUNCH_CHECK();
     }
     return mx::finish_count(m, workspace, out_indptr, nnz_out_host, st);
@@ -192,7 +190,7 @@ extern "C" int mxd_csr_outer_dense_fill(int m, int dim, int64_t nnz, const int32
 
 extern "C" size_t mxd_csr_outer_svec_workspace_bytes(int m, int y_length)
 {
-    return mx::OuterWs(nullptr, m > 0 ? m : 0).bytes(y_length > 0 ? y_length : 0);
+    return mx::OuterLayout(nullptr, m, y_length).bytes;
 }
 
 extern "C" int mxd_csr_outer_svec_count(int m, int64_t nnz, const int32_t *indptr, const double *values,
@@ -205,27 +203,27 @@ extern "C" int mxd_csr_outer_svec_count(int m, int64_t nnz, const int32_t *indpt
     MX_REQUIRE(workspace && out_indptr && nonempty_host && nnz_out_host && (m == 0 || indptr) &&
                (nnz == 0 || values) && (ny == 0 || y_indices_base1), "mxd_csr_outer_svec_count: null pointer");
     hipStream_t st = mx::as_stream(stream);
-    const mx::OuterWs ws(workspace, m);
+    const mx::OuterLayout ws(workspace, m, y_length);
     *nonempty_host = 0;
     *nnz_out_host = 0;
     if (m > 0) {
         hipLaunchKernelGGL(mx::outer_rows_kernel, dim3((unsigned)mx::ceil_div(m, mx::OP_BLOCK)), dim3(mx::OP_BLOCK), 0,
-                           st, m, nnz, indptr, values, ws.flags(), ws.ids(), ws.firsts());
+                           st, m, nnz, indptr, values, ws.flags, ws.ids, ws.firsts);
         MX_LAUNCH_CHECK();
-        if (mxd_compact_count(m, ws.firsts(), MX_F64, MX_KEEP_MASK, ws.flags(), workspace, nonempty_host, stream))
+        if (mxd_compact_count(m, ws.firsts, MX_F64, MX_KEEP_MASK, ws.flags, ws.compact, nonempty_host, stream))
             return 1;
-        if (mxd_compact_fill(m, ws.firsts(), MX_F64, MX_KEEP_MASK, ws.flags(), ws.ids(), nullptr, 0, nullptr,
-                             workspace, ws.rows(), nullptr, ws.kept_firsts(), nullptr, stream)) return 1;
+        if (mxd_compact_fill(m, ws.firsts, MX_F64, MX_KEEP_MASK, ws.flags, ws.ids, nullptr, 0, nullptr,
+                             ws.compact, ws.rows, nullptr, ws.kept_firsts, nullptr, stream)) return 1;
     }
     MX_REQUIRE(*nonempty_host * ny <= (int64_t)INT_MAX, mx::OUTER_OVERFLOW, "mxd_csr_outer_svec_count",
                (long long)(*nonempty_host * ny));
-    MX_HIP(hipMemsetAsync(ws.cols(), 0, sizeof(int32_t) * (size_t)(y_length > 0 ? y_length : 1), st));
+    MX_HIP(hipMemsetAsync(ws.col_counts, 0, sizeof(int32_t) * (size_t)(y_length > 0 ? y_length : 1), st));
     if (ny > 0 && y_length > 0) {
         hipLaunchKernelGGL(mx::outer_cols_kernel, dim3((unsigned)mx::ceil_div(ny, mx::OP_BLOCK)), dim3(mx::OP_BLOCK), 0,
-                           st, ny, y_indices_base1, y_length, (int)*nonempty_host, (int32_t *)ws.cols());
+                           st, ny, y_indices_base1, y_length, (int)*nonempty_host, ws.col_counts);
         MX_LAUNCH_CHECK();
     }
-    return mx::finish_count(y_length, ws.cols(), out_indptr, nnz_out_host, st);
+    return mx::finish_count(y_length, ws.col_counts, out_indptr, nnz_out_host, st);
 }
 
 extern "C" int mxd_csr_outer_svec_fill(int m, const int32_t *y_indices_base1, int64_t ny, const void *y_values,
@@ -239,7 +237,7 @@ extern "C" int mxd_csr_outer_svec_fill(int m, const int32_t *y_indices_base1, in
     MX_REQUIRE(workspace && y_indices_base1 && out_indptr && out_indices && out_values &&
                (value_dtype == MX_NONE || y_values), "mxd_csr_outer_svec_fill: null pointer");
     hipStream_t st = mx::as_stream(stream);
-    const mx::OuterWs ws(workspace, m);
+    const mx::OuterLayout ws(workspace, m, y_length);
     const int64_t chunks = mx::ceil_div(nonempty, mx::OP_CHUNK), items = ny * chunks;
     const int G = mx::pick_group((double)(nonempty < mx::OP_CHUNK ? nonempty : mx::OP_CHUNK));
     return mx::dispatch_values("mxd_csr_outer_svec_fill", value_dtype, [&](auto kind) {
@@ -247,8 +245,8 @@ extern "C" int mxd_csr_outer_svec_fill(int m, const int32_t *y_indices_base1, in
         return mx::launch_rows(mx::lane_groups{}, "mxd_csr_outer_svec_fill", G, items, mx::OP_BLOCK,
                                [&](auto g, dim3 grid, dim3 block) {
             hipLaunchKernelGGL((mx::outer_svec_fill_kernel<g(), typename K::VT, K::has_values>), grid, block, 0, st,
-                               items, chunks, y_indices_base1, (const typename K::VT *)y_values, y_length, ws.rows(),
-                               ws.kept_firsts(), (int)nonempty, out_indptr, out_indices, out_values);
+                               items, chunks, y_indices_base1, (const typename K::VT *)y_values, y_length, ws.rows,
+                               ws.kept_firsts, (int)nonempty, out_indptr, out_indices, out_values);
         });
     });
 }

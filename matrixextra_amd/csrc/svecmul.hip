@@ -27,6 +27,7 @@
 // Row bounds are clamped into [0, nnz] in both passes and every write position comes from the scanned counts, so
 // nothing is read or written out of bounds whatever the input.
 #include "mx_dispatch.h"
+#include "mx_workspace.h"
 #include "mx_dense_row.h"
 
 namespace mx {
@@ -67,11 +68,9 @@ __device__ __forceinline__ SvRow sv_row(long long r, int64_t nnz, const int32_t 
                                         const double *__restrict__ vx, bool keep_na)
 {
     SvRow w{0, 0, pos >= 0, false, 1.0};
-    int64_t s = indptr[r], e = indptr[r + 1];
-    s = s < 0 ? 0 : s > nnz ? nnz : s;
-    e = e < s ? s : e > nnz ? nnz : e;
-    w.s = (int)s;
-    w.len = (int)(e - s);
+    const RowBounds b = row_bounds(indptr[r], indptr[r + 1], nnz);
+    w.s = (int)b.start;
+    w.len = (int)b.len;
     if (w.stored && vx) {
         w.val = vx[pos];
         w.dense = keep_na && sv_nonfinite(w.val);
@@ -156,9 +155,15 @@ void sv_fill_kernel(int m, int ncol, int64_t nnz, const int32_t *__restrict__ in
                      SvDenseRule{});
 }
 
-// workspace: [count workspace of m][NA flag, 16 B][position in v of each row, or -1: m]
-static unsigned long long *sv_flag(void *ws, int m) { return (unsigned long long *)((char *)ws + count_workspace_bytes(m)); }
-static int32_t *sv_pos(void *ws, int m) { return (int32_t *)(sv_flag(ws, m) + 2); }
+struct SvLayout {
+    WsCursor c;
+    int m;
+    int32_t *counts = c.take_counts(m);
+    unsigned long long *na_flag = c.take<unsigned long long>(16);      // one word in 16 B
+    int32_t *pos = c.take_i32(m);                                       // position in v of each row, or -1
+    size_t bytes = c.bytes();
+    SvLayout(const void *ws, int m_) : c(ws), m(m_ > 0 ? m_ : 0) {}
+};
 
 static int sv_check(const char *what, int m, int ncol, int64_t nnz, int64_t nv, int length)
 {
@@ -170,10 +175,7 @@ static int sv_check(const char *what, int m, int ncol, int64_t nnz, int64_t nv, 
 
 }  // namespace mx
 
-extern "C" size_t mxd_csr_by_svec_workspace_bytes(int m)
-{
-    return mx::count_workspace_bytes(m > 0 ? m : 0) + 16 + mx::padded_i32_bytes(m);
-}
+extern "C" size_t mxd_csr_by_svec_workspace_bytes(int m) { return mx::SvLayout(nullptr, m).bytes; }
 
 extern "C" int mxd_csr_by_svec_count(int m, int ncol, int64_t nnz, const int32_t *indptr, const double *values,
                                      const int32_t *vi_base1, int64_t nv, const double *vx, int length, int keep_na,
@@ -187,20 +189,21 @@ extern "C" int mxd_csr_by_svec_count(int m, int ncol, int64_t nnz, const int32_t
     hipStream_t st = mx::as_stream(stream);
     *nnz_out_host = 0;
     *x_na_host = 0;
-    unsigned long long *flag = mx::sv_flag(workspace, m > 0 ? m : 0);
+    const mx::SvLayout L(workspace, m);
+    unsigned long long *flag = L.na_flag;
     MX_HIP(hipMemsetAsync(flag, 0, sizeof(unsigned long long), st));
     if (m > 0) {
         const int G = mx::pick_group((double)nnz / (double)m);
         const int rc = mx::launch_rows(mx::lane_groups{}, "mxd_csr_by_svec_count", G, m, mx::SV_BLOCK,
                                        [&](auto g, dim3 grid, dim3 block) {
             hipLaunchKernelGGL(mx::sv_count_kernel<g()>, grid, block, 0, st, m, ncol, nnz, indptr, values, vi_base1,
-                               (int)nv, vx, length, keep_na, (int32_t *)workspace, mx::sv_pos(workspace, m), flag);
+                               (int)nv, vx, length, keep_na, L.counts, L.pos, flag);
         });
         if (rc) return rc;
     }
     MX_HIP(hipMemcpyAsync(x_na_host, flag, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     // the 64-bit total is read back (one synchronise) and refused above INT_MAX before any output exists
-    return mx::finish_count(m, workspace, out_indptr, nnz_out_host, st);
+    return mx::finish_count(m, L.counts, out_indptr, nnz_out_host, st);
 }
 
 extern "C" int mxd_csr_by_svec_fill(int m, int ncol, int64_t nnz, const int32_t *indptr, const int32_t *indices,
@@ -217,6 +220,6 @@ extern "C" int mxd_csr_by_svec_fill(int m, int ncol, int64_t nnz, const int32_t 
     return mx::launch_rows(mx::lane_groups{}, "mxd_csr_by_svec_fill", G, m, mx::SV_BLOCK,
                            [&](auto g, dim3 grid, dim3 block) {
         hipLaunchKernelGGL(mx::sv_fill_kernel<g()>, grid, block, 0, st, m, ncol, nnz, indptr, indices, values, vx,
-                           keep_na, mx::sv_pos(const_cast<void *>(workspace), m), out_indptr, out_indices, out_values);
+                           keep_na, mx::SvLayout(workspace, m).pos, out_indptr, out_indices, out_values);
     });
 }

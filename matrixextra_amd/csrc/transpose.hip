@@ -34,7 +34,8 @@
 // rows from the caller instead of an indptr search (TP_SRC_ROWS).  The sort of a sparse vector
 // (mxd_sort_vector_indices, after it) runs them once, on one key.  The sort of COO triplets (mxd_coo_sort, last)
 // runs them on both keys, the second run taking up the first run's permutation, and gathers the values once.
-#include "mx_common.h"
+#include "mx_dispatch.h"
+#include "mx_workspace.h"
 
 namespace mx {
 
@@ -333,29 +334,52 @@ static size_t tp_scan_ws_bytes(int64_t nnz)
     return ((a > b ? a : b) + 15) & ~(size_t)15;
 }
 
-// workspace: [flags][keys0 nnz+1][perm0 nnz][keys1 nnz+1][perm1 nnz][rows0 nnz+1][rows1 nnz+1][table T]
-// [offsets T+1][scan].  Each keys/perm pair is contiguous, so a free pair also holds nnz doubles during compaction.
+// nnz values of 8 bytes, padded to 16 B
+static size_t tp_f64_bytes(int64_t nnz) { return ((size_t)8 * (size_t)(nnz > 0 ? nnz : 1) + 15) & ~(size_t)15; }
+
+// The radix passes' workspace.  Each keys/perm pair is contiguous, so a free pair also holds nnz doubles during
+// compaction.
 struct TpLayout {
-    int32_t *flags, *keys[2], *perm[2], *rows[2], *table, *offsets;
+    WsCursor c;
+    int64_t nnz;
+    int32_t *flags = c.take<int32_t>(TP_FLAG_BYTES);
+    int32_t *keys[2], *perm[2], *rows[2];   // double-buffered: keys and rows nnz + 1, perm nnz
+    int32_t *table, *offsets;               // digit counts per tile (T = TP_RADIX * tiles), scanned into T + 1
     void *scan_ws;
     size_t bytes;
-    TpLayout(void *ws, int64_t nnz)
+    TpLayout(const void *ws, int64_t nnz_) : c(ws), nnz(nnz_ > 0 ? nnz_ : 0)
     {
-        char *p = (char *)ws;
         const int64_t T = TP_RADIX * tp_ntiles(nnz);
-        flags = (int32_t *)p;            p += TP_FLAG_BYTES;
         for (int b = 0; b < 2; b++) {
-            keys[b] = (int32_t *)p;      p += padded_i32_bytes(nnz + 1);
-            perm[b] = (int32_t *)p;      p += padded_i32_bytes(nnz);
+            keys[b] = c.take_i32(nnz + 1);
+            perm[b] = c.take_i32(nnz);
         }
-        for (int b = 0; b < 2; b++) {
-            rows[b] = (int32_t *)p;      p += padded_i32_bytes(nnz + 1);
-        }
-        table = (int32_t *)p;            p += padded_i32_bytes(T);
-        offsets = (int32_t *)p;          p += padded_i32_bytes(T + 1);
-        scan_ws = p;                     p += tp_scan_ws_bytes(nnz);
-        bytes = (size_t)(p - (char *)ws);
+        for (int b = 0; b < 2; b++) rows[b] = c.take_i32(nnz + 1);
+        table = c.take_i32(T);
+        offsets = c.take_i32(T + 1);
+        scan_ws = c.take(tp_scan_ws_bytes(nnz));
+        bytes = c.bytes();
     }
+};
+
+// COO -> CSR: the passes' workspace (used by both stages), then stage 1's CSC
+struct CooLayout {
+    TpLayout tp;
+    int64_t n;
+    WsCursor c = tp.c;
+    int32_t *csc_indptr = c.take_i32(n + 1), *csc_rows = c.take_i32(tp.nnz);
+    void *csc_values = c.take(tp_f64_bytes(tp.nnz));                    // 8 bytes an entry
+    size_t bytes = c.bytes();
+    CooLayout(const void *ws, int64_t nnz, int n_) : tp(ws, nnz), n(n_ > 0 ? n_ : 0) {}
+};
+
+// the sorts of a sparse vector and of COO triplets: the passes' workspace, then the gathered values on their way back
+struct SortLayout {
+    TpLayout tp;
+    WsCursor c = tp.c;
+    void *tmp_values = c.take(tp_f64_bytes(tp.nnz));                    // 8 bytes an entry
+    size_t bytes = c.bytes();
+    SortLayout(const void *ws, int64_t n) : tp(ws, n) {}
 };
 
 static int bits_of(int64_t v)   // bits needed to hold v >= 0
@@ -365,10 +389,22 @@ static int bits_of(int64_t v)   // bits needed to hold v >= 0
     return b;
 }
 
-static unsigned grid_for(int64_t n, int block, int64_t cap = (int64_t)1 << 20)
+constexpr int64_t TP_GRID_CAP = (int64_t)1 << 20;      // the per-column kernels stride over what is left
+
+// out_rows[q] = rows[q] and out_values[q] = values[perm[q]] over the sorted entries, by value kind
+static int tp_gather(const char *what, int value_dtype, const int32_t *keys, const int32_t *perm, int64_t nnz,
+                     const int32_t *rows, const void *values, int32_t *out_rows, void *out_values, int32_t *flags,
+                     hipStream_t st)
 {
-    int64_t g = ceil_div(n > 0 ? n : 1, block);
-    return (unsigned)(g < cap ? g : cap);
+    return dispatch_values(what, value_dtype, [&](auto kind) {
+        using K = decltype(kind);
+        using VT = typename K::VT;
+        hipLaunchKernelGGL((tp_gather_kernel<VT, K::has_values>), dim3((unsigned)ceil_div(nnz, 256)), dim3(256), 0, st,
+                           keys, perm, nnz, rows, K::has_values ? (const VT *)values : nullptr, out_rows,
+                           K::has_values ? (VT *)out_values : nullptr, flags);
+        MX_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 // The LSD radix passes shared by the CSR transpose and the COO sort: a stable sort of nnz entries by key
@@ -441,19 +477,11 @@ static int csr_transpose(int m, int n, const int32_t *indptr, const int32_t *ind
     int fin = 0;
     if (tp_sort_passes(TP_SRC_INDPTR, indices, nullptr, indptr, m, n, nnz, L, L.flags, &fin, st)) return 1;
     const int32_t *skeys = L.keys[fin], *sperm = L.perm[fin], *srows = L.rows[fin];
-    const unsigned gq = (unsigned)ceil_div(nnz, 256);
-    if (value_dtype == MX_F64)
-        hipLaunchKernelGGL((tp_gather_kernel<double, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz, srows,
-                           (const double *)values, out_indices, (double *)out_values, L.flags);
-    else if (value_dtype == MX_LGL)
-        hipLaunchKernelGGL((tp_gather_kernel<int32_t, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz, srows,
-                           (const int32_t *)values, out_indices, (int32_t *)out_values, L.flags);
-    else
-        hipLaunchKernelGGL((tp_gather_kernel<int32_t, false>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz,
-                           srows, nullptr, out_indices, nullptr, L.flags);
-    MX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tp_indptr_kernel, dim3(grid_for((int64_t)n + 1, 256)), dim3(256), 0, st, skeys, nnz, (int64_t)n,
-                       out_indptr);
+    if (tp_gather("mxd_csr_transpose", value_dtype, skeys, sperm, nnz, srows, values, out_indices, out_values,
+                  L.flags, st))
+        return 1;
+    hipLaunchKernelGGL(tp_indptr_kernel, dim3(grid_for((int64_t)n + 1, 256, TP_GRID_CAP)), dim3(256), 0, st, skeys, nnz,
+                       (int64_t)n, out_indptr);
     MX_LAUNCH_CHECK();
 
     int32_t flags[2] = {0, 0};
@@ -466,6 +494,7 @@ static int csr_transpose(int m, int n, const int32_t *indptr, const int32_t *ind
     int32_t *heads = L.perm[fin], *newpos = L.rows[fin ^ 1];
     int32_t *merged_rows = L.perm[fin];                          // heads are consumed by the scan before the merge
     void *merged_vals = L.keys[fin ^ 1];                         // keys + perm of the free pair: >= 8 * nnz bytes
+    const unsigned gq = (unsigned)ceil_div(nnz, 256);
     hipLaunchKernelGGL(tp_heads_kernel, dim3(gq), dim3(256), 0, st, skeys, out_indices, nnz, heads);
     MX_LAUNCH_CHECK();
     int64_t *total_dev = (int64_t *)L.scan_ws;
@@ -480,8 +509,8 @@ static int csr_transpose(int m, int n, const int32_t *indptr, const int32_t *ind
         hipLaunchKernelGGL(tp_merge_kernel<2>, dim3(gq), dim3(256), 0, st, skeys, out_indices, out_values, nnz, newpos,
                            merged_rows, merged_vals);
     MX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tp_remap_indptr_kernel, dim3(grid_for((int64_t)n + 1, 256)), dim3(256), 0, st, (int64_t)n,
-                       newpos, out_indptr);
+    hipLaunchKernelGGL(tp_remap_indptr_kernel, dim3(grid_for((int64_t)n + 1, 256, TP_GRID_CAP)), dim3(256), 0, st,
+                       (int64_t)n, newpos, out_indptr);
     MX_LAUNCH_CHECK();
     int64_t total = 0;
     MX_HIP(hipMemcpyAsync(&total, total_dev, sizeof(total), hipMemcpyDeviceToHost, st));
@@ -500,15 +529,9 @@ static int csr_transpose(int m, int n, const int32_t *indptr, const int32_t *ind
 // rows in input order.  Stage 2 is csr_transpose of that CSC: its stable sort by row gives each CSR row its
 // columns in ascending order with repeated (row, col) pairs adjacent and in input order, and its compaction
 // merges them by Matrix's triplet rules.
-// workspace: [TpLayout(nnz)][csc indptr n+1][csc rows nnz][csc values 8 * nnz]; stage 2 re-uses the TpLayout part.
-// Stage 1's flags sit at L.flags[4..7] ([4] column out of range, [5] the gather's duplicate flag, unused,
-// [6] row out of range), out of the way of stage 2's flags[0..1].
-static size_t coo_ws_bytes(int64_t nnz, int n)
-{
-    return TpLayout(nullptr, nnz).bytes + padded_i32_bytes((int64_t)n + 1) + padded_i32_bytes(nnz) +
-           (((size_t)8 * (size_t)(nnz > 0 ? nnz : 1) + 15) & ~(size_t)15);
-}
-
+// Stage 2 re-uses the passes' part of the workspace (CooLayout).  Stage 1's flags sit at L.flags[4..7] ([4] column
+// out of range, [5] the gather's duplicate flag, unused, [6] row out of range), out of the way of stage 2's
+// flags[0..1].
 static int coo_to_csr(int m, int n, const int32_t *rows, const int32_t *cols, const void *values, int value_dtype,
                       int64_t nnz, int32_t *out_indptr, int32_t *out_indices, void *out_values, void *workspace,
                       int64_t *nnz_out_host, hipStream_t st)
@@ -528,34 +551,22 @@ static int coo_to_csr(int m, int n, const int32_t *rows, const int32_t *cols, co
     }
     MX_REQUIRE(m > 0 && n > 0, "mxd_coo_to_csr: %lld entries in a %d x %d matrix: index outside the matrix",
                (long long)nnz, m, n);
-    TpLayout L(workspace, nnz);
-    char *p = (char *)workspace + L.bytes;
-    int32_t *csc_indptr = (int32_t *)p;  p += padded_i32_bytes((int64_t)n + 1);
-    int32_t *csc_rows = (int32_t *)p;    p += padded_i32_bytes(nnz);
-    void *csc_values = p;
+    const CooLayout C(workspace, nnz, n);
+    const TpLayout &L = C.tp;
     int32_t *F = L.flags + 4;
     MX_HIP(hipMemsetAsync(F, 0, 4 * sizeof(int32_t), st));
 
     int fin = 0;
     if (tp_sort_passes(TP_SRC_ROWS, cols, rows, nullptr, m, n, nnz, L, F, &fin, st)) return 1;
     const int32_t *skeys = L.keys[fin], *sperm = L.perm[fin], *srows = L.rows[fin];
-    const unsigned gq = (unsigned)ceil_div(nnz, 256);
-    if (value_dtype == MX_F64)
-        hipLaunchKernelGGL((tp_gather_kernel<double, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz, srows,
-                           (const double *)values, csc_rows, (double *)csc_values, F);
-    else if (value_dtype == MX_LGL)
-        hipLaunchKernelGGL((tp_gather_kernel<int32_t, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz, srows,
-                           (const int32_t *)values, csc_rows, (int32_t *)csc_values, F);
-    else
-        hipLaunchKernelGGL((tp_gather_kernel<int32_t, false>), dim3(gq), dim3(256), 0, st, skeys, sperm, nnz,
-                           srows, nullptr, csc_rows, nullptr, F);
-    MX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tp_indptr_kernel, dim3(grid_for((int64_t)n + 1, 256)), dim3(256), 0, st, skeys, nnz, (int64_t)n,
-                       csc_indptr);
+    if (tp_gather("mxd_coo_to_csr", value_dtype, skeys, sperm, nnz, srows, values, C.csc_rows, C.csc_values, F, st))
+        return 1;
+    hipLaunchKernelGGL(tp_indptr_kernel, dim3(grid_for((int64_t)n + 1, 256, TP_GRID_CAP)), dim3(256), 0, st, skeys, nnz,
+                       (int64_t)n, C.csc_indptr);
     MX_LAUNCH_CHECK();
 
     // stage 2 ends with the stream synchronised; bad indices were clamped to 0, so it runs safely either way
-    if (csr_transpose(n, m, csc_indptr, csc_rows, has_values ? csc_values : nullptr, value_dtype, nnz, out_indptr,
+    if (csr_transpose(n, m, C.csc_indptr, C.csc_rows, has_values ? C.csc_values : nullptr, value_dtype, nnz, out_indptr,
                       out_indices, out_values, workspace, nnz_out_host, st))
         return 1;
     int32_t flags[4] = {0, 0, 0, 0};
@@ -603,11 +614,6 @@ void sv_sorted_kernel(const int32_t *__restrict__ ii, int64_t n, int32_t *__rest
     }
 }
 
-static size_t sv_sort_ws_bytes(int64_t n)
-{
-    return TpLayout(nullptr, n).bytes + (((size_t)8 * (size_t)(n > 0 ? n : 1) + 15) & ~(size_t)15);
-}
-
 static int sort_vector(int32_t *ii, void *xx, int64_t n, int value_dtype, void *workspace, int *was_sorted_host,
                        hipStream_t st)
 {
@@ -619,8 +625,9 @@ static int sort_vector(int32_t *ii, void *xx, int64_t n, int value_dtype, void *
     if (n < 2) return 0;
     const bool has_values = value_dtype != MX_NONE;
     MX_REQUIRE(ii && workspace && (!has_values || xx), "mxd_sort_vector_indices: null pointer");
-    TpLayout L(workspace, n);
-    void *tmp_values = (char *)workspace + L.bytes;
+    const SortLayout S(workspace, n);
+    const TpLayout &L = S.tp;
+    void *tmp_values = S.tmp_values;
     // the passes' own flags (F[0] bad key, F[2] bad row) cannot fire once the reduction below has passed (no
     // negative index, keys < nkeys), and the gather's duplicate flag F[1] means nothing here: none is read back
     int32_t *F = L.flags + TP_SV_PASS_FLAGS, *words = L.flags + TP_SV_WORDS;
@@ -638,17 +645,7 @@ static int sort_vector(int32_t *ii, void *xx, int64_t n, int value_dtype, void *
     int fin = 0;
     if (tp_sort_passes(TP_SRC_ROWS, ii, ii, nullptr, nkeys, nkeys, n, L, F, &fin, st)) return 1;
     const int32_t *skeys = L.keys[fin], *sperm = L.perm[fin], *srows = L.rows[fin];
-    const unsigned gq = (unsigned)ceil_div(n, 256);
-    if (value_dtype == MX_F64)
-        hipLaunchKernelGGL((tp_gather_kernel<double, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, n, srows,
-                           (const double *)xx, ii, (double *)tmp_values, F);
-    else if (has_values)
-        hipLaunchKernelGGL((tp_gather_kernel<int32_t, true>), dim3(gq), dim3(256), 0, st, skeys, sperm, n, srows,
-                           (const int32_t *)xx, ii, (int32_t *)tmp_values, F);
-    else
-        hipLaunchKernelGGL((tp_gather_kernel<int32_t, false>), dim3(gq), dim3(256), 0, st, skeys, sperm, n, srows,
-                           nullptr, ii, nullptr, F);
-    MX_LAUNCH_CHECK();
+    if (tp_gather("mxd_sort_vector_indices", value_dtype, skeys, sperm, n, srows, xx, ii, tmp_values, F, st)) return 1;
     if (has_values)
         MX_HIP(hipMemcpyAsync(xx, tmp_values, (value_dtype == MX_F64 ? 8 : 4) * (size_t)n, hipMemcpyDeviceToDevice,
                               st));
@@ -739,8 +736,9 @@ static int coo_sort(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int value_d
     if (nnz == 0) return 0;
     const bool has_values = value_dtype != MX_NONE;
     MX_REQUIRE(ii && jj && workspace && (!has_values || xx), "mxd_coo_sort: null pointer");
-    TpLayout L(workspace, nnz);
-    void *tmp_values = (char *)workspace + L.bytes;
+    const SortLayout S(workspace, nnz);
+    const TpLayout &L = S.tp;
+    void *tmp_values = S.tmp_values;
     // the passes' own flags (F[0] bad key, F[2] bad row) cannot fire once the reduction below has passed, and the
     // gather's duplicate flag F[1] means nothing here: none is read back
     int32_t *F = L.flags + TP_COO_PASS_FLAGS, *words = L.flags + TP_COO_WORDS;
@@ -769,17 +767,7 @@ static int coo_sort(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int value_d
     // the sorted rows, columns and permutation are all in the workspace: nothing below reads what it overwrites,
     // except the values, which go through tmp_values
     const int32_t *srows = L.keys[fin], *sperm = L.perm[fin], *scols = L.rows[fin];
-    const unsigned gq = (unsigned)ceil_div(nnz, 256);
-    if (value_dtype == MX_F64)
-        hipLaunchKernelGGL((tp_gather_kernel<double, true>), dim3(gq), dim3(256), 0, st, srows, sperm, nnz, scols,
-                           (const double *)xx, jj, (double *)tmp_values, F);
-    else if (has_values)
-        hipLaunchKernelGGL((tp_gather_kernel<int32_t, true>), dim3(gq), dim3(256), 0, st, srows, sperm, nnz, scols,
-                           (const int32_t *)xx, jj, (int32_t *)tmp_values, F);
-    else
-        hipLaunchKernelGGL((tp_gather_kernel<int32_t, false>), dim3(gq), dim3(256), 0, st, srows, sperm, nnz, scols,
-                           nullptr, jj, nullptr, F);
-    MX_LAUNCH_CHECK();
+    if (tp_gather("mxd_coo_sort", value_dtype, srows, sperm, nnz, scols, xx, jj, tmp_values, F, st)) return 1;
     MX_HIP(hipMemcpyAsync(ii, srows, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToDevice, st));
     if (has_values)
         MX_HIP(hipMemcpyAsync(xx, tmp_values, (value_dtype == MX_F64 ? 8 : 4) * (size_t)nnz, hipMemcpyDeviceToDevice,
@@ -789,7 +777,7 @@ static int coo_sort(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int value_d
 
 }  // namespace mx
 
-extern "C" size_t mxd_coo_sort_workspace_bytes(int64_t nnz) { return mx::sv_sort_ws_bytes(nnz > 0 ? nnz : 0); }
+extern "C" size_t mxd_coo_sort_workspace_bytes(int64_t nnz) { return mx::SortLayout(nullptr, nnz).bytes; }
 
 extern "C" int mxd_coo_sort(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int value_dtype, void *workspace,
                             int *was_sorted, void *stream)
@@ -797,7 +785,7 @@ extern "C" int mxd_coo_sort(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int
     return mx::coo_sort(ii, jj, xx, nnz, value_dtype, workspace, was_sorted, mx::as_stream(stream));
 }
 
-extern "C" size_t mxd_sort_vector_indices_workspace_bytes(int64_t n) { return mx::sv_sort_ws_bytes(n > 0 ? n : 0); }
+extern "C" size_t mxd_sort_vector_indices_workspace_bytes(int64_t n) { return mx::SortLayout(nullptr, n).bytes; }
 
 extern "C" int mxd_sort_vector_indices(int32_t *ii, void *xx, int64_t n, int value_dtype, void *workspace,
                                        int *was_sorted_host, void *stream)
@@ -805,10 +793,7 @@ extern "C" int mxd_sort_vector_indices(int32_t *ii, void *xx, int64_t n, int val
     return mx::sort_vector(ii, xx, n, value_dtype, workspace, was_sorted_host, mx::as_stream(stream));
 }
 
-extern "C" size_t mxd_coo_to_csr_workspace_bytes(int64_t nnz, int n)
-{
-    return mx::coo_ws_bytes(nnz > 0 ? nnz : 0, n > 0 ? n : 0);
-}
+extern "C" size_t mxd_coo_to_csr_workspace_bytes(int64_t nnz, int n) { return mx::CooLayout(nullptr, nnz, n).bytes; }
 
 extern "C" int mxd_coo_to_csr(int m, int n, const int32_t *rows, const int32_t *cols, const void *values,
                               int value_dtype, int64_t nnz, int32_t *out_indptr, int32_t *out_indices,
@@ -830,10 +815,7 @@ extern "C" int mxd_csr_to_coo(int m, int64_t nnz, const int32_t *indptr, int32_t
     return 0;
 }
 
-extern "C" size_t mxd_csr_transpose_workspace_bytes(int64_t nnz)
-{
-    return mx::TpLayout(nullptr, nnz > 0 ? nnz : 0).bytes;
-}
+extern "C" size_t mxd_csr_transpose_workspace_bytes(int64_t nnz) { return mx::TpLayout(nullptr, nnz).bytes; }
 
 extern "C" int mxd_csr_transpose(int m, int n, const int32_t *indptr, const int32_t *indices, const void *values,
                                  int value_dtype, int64_t nnz, int32_t *out_indptr, int32_t *out_indices,

@@ -502,3 +502,300 @@ def dev_scan(counts):
     gc.assert_untouched()
     gws._download()
     return gout.result(), int(gtotal.result()[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The two-pass families with a workspace of several segments (csrc/mx_workspace.h): every operand, every output and
+# the workspace, exactly mxd_*_workspace_bytes long, between guards.  A segment that the library places past the size
+# it publishes lands in the back guard.
+def _ws(nbytes):
+    return GuardedVec(np.uint8, n=nbytes)
+
+
+def _entries(nout, *dtypes):
+    return [None if dt is None else GuardedVec(dt, n=nout + SLACK) for dt in dtypes]
+
+
+def _vec(a, dtype=None):
+    return None if a is None else GuardedVec(np.asarray(a).dtype if dtype is None else dtype, data=a)
+
+
+def _ptr(g):
+    return None if g is None else g.ptr
+
+
+def value_dtype_of(x):
+    """MX_F64 for f64 values, MX_LGL for int32 ones, MX_NONE for none"""
+    return _lib.MX_NONE if x is None else _lib.MX_F64 if np.asarray(x).dtype == np.float64 else _lib.MX_LGL
+
+
+def dev_csc_dense_na(p, i, x, D, kind):
+    """mxd_csc_dense_na_count + _fill of an m x n column-major D (dense kind 0..3): (indptr, indices, values)"""
+    lib = _lib.load()
+    m, n = D.shape
+    A, gd = GCsr(p, i, x), GuardedVec(D.dtype, data=np.asarray(D).reshape(-1, order="F"))
+    gws = _ws(lib.mxd_csc_dense_na_workspace_bytes(m, n))
+    total, outside = C.c_int64(-1), C.c_int64(-1)
+    check(lib.mxd_csc_dense_na_count(m, n, A.nnz, A.p.ptr, A.j.ptr, gd.ptr, kind, gws.ptr, C.byref(total),
+                                     C.byref(outside), None))
+    gws._download()
+    nout = int(total.value)
+    gp = GuardedVec(np.int32, n=n + 1)
+    gj, gx = _entries(nout, np.int32, np.float64)
+    check(lib.mxd_csc_dense_na_fill(m, n, A.nnz, A.p.ptr, A.j.ptr, A.xptr, gd.ptr, kind, gws.ptr, gp.ptr, gj.ptr, gx.ptr,
+                                    None))
+    _sync()
+    _untouched(A, gd)
+    gws._download()
+    return gp.result(), gj.result(nout), gx.result(nout)
+
+
+def dev_dvec_na_rows(p, j, x, ncols, v, op):
+    """mxd_csr_by_dvec_na_rows_count + _fill (the vector's length divides the rows): dict(indptr, indices, values)"""
+    lib = _lib.load()
+    A, gv, m, code = GCsr(p, j, x), GuardedVec(np.float64, data=v), int(p.size - 1), _lib.MX_DV_OPS[op]
+    gws, gp, total = _ws(lib.mxd_csr_by_dvec_na_rows_workspace_bytes(m)), GuardedVec(np.int32, n=m + 1), C.c_int64(-1)
+    check(lib.mxd_csr_by_dvec_na_rows_count(m, ncols, A.nnz, A.p.ptr, gv.ptr, gv.n, code, gws.ptr, gp.ptr,
+                                            C.byref(total), None))
+    gws._download()
+    nout = int(total.value)
+    gj, gx = _entries(nout, np.int32, np.float64)
+    check(lib.mxd_csr_by_dvec_na_rows_fill(m, ncols, A.nnz, A.p.ptr, A.j.ptr, A.xptr, gv.ptr, gv.n, code, gp.ptr, gj.ptr,
+                                           gx.ptr, None))
+    _sync()
+    _untouched(A, gv)
+    return dict(indptr=gp.result(), indices=gj.result(nout), values=gx.result(nout))
+
+
+def dev_dvec_na_flat(p, j, x, ncols, v, op):
+    """The flat route of the NA-keeping CSR (op) dense vector, step by step as device.csr_by_dvec_keep_na takes it:
+    mxd_dvec_na_special, mxd_dvec_na_cells_count / _fill, the new cells through mxd_coo_to_csr, mxd_csr_join_disjoint.
+    Returns (dict(indptr, indices, values), special positions, candidate cells, new cells)."""
+    lib = _lib.load()
+    A, gv, m, code = GCsr(p, j, x), GuardedVec(np.float64, data=v), int(p.size - 1), _lib.MX_DV_OPS[op]
+    L = gv.n
+    sws = _ws(lib.mxd_dvec_na_special_workspace_bytes(L))
+    nsp, cand, new = C.c_int64(-1), C.c_int64(-1), C.c_int64(-1)
+    check(lib.mxd_dvec_na_special(m, ncols, gv.ptr, L, code, sws.ptr, C.byref(nsp), C.byref(cand), None))
+    sws._download()
+    assert cand.value > 0, "the case has no candidate cell"
+    cws = _ws(lib.mxd_dvec_na_cells_workspace_bytes(cand.value))
+    check(lib.mxd_dvec_na_cells_count(m, ncols, A.nnz, A.p.ptr, A.j.ptr, L, sws.ptr, nsp.value, cand.value, cws.ptr,
+                                      C.byref(new), None))
+    cws._download()
+    n_new = int(new.value)
+    assert n_new > 0, "the case adds no cell"
+    gax = GuardedVec(np.float64, n=A.nnz + SLACK)
+    check(lib.mxd_csr_by_dvec(m, ncols, A.nnz, A.p.ptr, A.j.ptr, A.xptr, gv.ptr, L, code, 1, gax.ptr, None))
+    gi, gj, gx = _entries(n_new, np.int32, np.int32, np.float64)
+    check(lib.mxd_dvec_na_cells_fill(m, ncols, gv.ptr, L, code, sws.ptr, nsp.value, cand.value, cws.ptr, gi.ptr, gj.ptr,
+                                     gx.ptr, None))
+    _sync()
+    sws._download()
+    cws._download()
+    bp, bj, bx = dev_coo_to_csr(gi.result(n_new), gj.result(n_new), gx.result(n_new), m, ncols)
+    assert bj.size == n_new, "the new cells are not distinct"
+    B = GCsr(bp, bj, bx)
+    nout = A.nnz + n_new
+    gp = GuardedVec(np.int32, n=m + 1)
+    oj, ox = _entries(nout, np.int32, np.float64)
+    check(lib.mxd_csr_join_disjoint(m, A.p.ptr, A.j.ptr, gax.ptr, A.nnz, B.p.ptr, B.j.ptr, B.xptr, n_new, gp.ptr, oj.ptr,
+                                    ox.ptr, None))
+    _sync()
+    _untouched(A, B, gv)
+    gax.result(A.nnz)
+    return (dict(indptr=gp.result(), indices=oj.result(nout), values=ox.result(nout)), int(nsp.value), int(cand.value),
+            n_new)
+
+
+def dev_dense_by_svec(X, kind, vi_base1, vx, length, keep_na):
+    """mxd_dense_by_svec_dense (the routes with a dense result: dict(X_dense)) or mxd_dense_by_svec_count + _fill
+    (dict(indptr, indices, values)), as mx_dense_by_svec_route chooses; X column-major, dense kind 0..3"""
+    lib = _lib.load()
+    nrows, ncols = X.shape
+    gX = GuardedVec(X.dtype, data=np.asarray(X).reshape(-1, order="F"))
+    gvi, gvx = GuardedVec(np.int32, data=vi_base1), GuardedVec(np.float64, data=vx)
+    nv, keep = gvi.n, int(bool(keep_na))
+    route = lib.mx_dense_by_svec_route(nrows, ncols, length)
+    assert route >= 0
+    if route in (_lib.MX_DSV_ROUTE_A, _lib.MX_DSV_ROUTE_D):
+        gws, gout = _ws(lib.mxd_dense_by_svec_workspace_bytes(0, length)), GuardedVec(np.float64, n=nrows * ncols)
+        check(lib.mxd_dense_by_svec_dense(nrows, ncols, gX.ptr, kind, gvi.ptr, nv, gvx.ptr, length, keep, gws.ptr,
+                                          gout.ptr, None))
+        _sync()
+        _untouched(gX, gvi, gvx)
+        gws._download()
+        return dict(X_dense=gout.result().reshape((nrows, ncols), order="F"))
+    gws, gp, total = _ws(lib.mxd_dense_by_svec_workspace_bytes(nrows, length)), GuardedVec(np.int32, n=nrows + 1), C.c_int64(-1)
+    check(lib.mxd_dense_by_svec_count(nrows, ncols, gX.ptr, kind, gvi.ptr, nv, length, keep, gws.ptr, gp.ptr,
+                                      C.byref(total), None))
+    gws._download()
+    nout = int(total.value)
+    gj, gx = _entries(nout, np.int32, np.float64)
+    check(lib.mxd_dense_by_svec_fill(nrows, ncols, gX.ptr, kind, gvx.ptr, length, keep, gws.ptr, gp.ptr, gj.ptr, gx.ptr,
+                                     None))
+    _sync()
+    _untouched(gX, gvi, gvx)
+    gws._download()
+    return dict(indptr=gp.result(), indices=gj.result(nout), values=gx.result(nout))
+
+
+def dev_outer_dense(p, x, colvec):
+    """mxd_csr_outer_dense_count + _fill of a one-column CSR (p, x) and an f64 / f32 vector: dict(indptr, indices, values)"""
+    lib = _lib.load()
+    m, dim = int(p.size - 1), int(colvec.size)
+    gp_in, gx_in, gv = GuardedVec(np.int32, data=p), GuardedVec(np.float64, data=x), GuardedVec(colvec.dtype, data=colvec)
+    gws, gp, total = _ws(lib.mxd_csr_outer_dense_workspace_bytes(m)), GuardedVec(np.int32, n=m + 1), C.c_int64(-1)
+    check(lib.mxd_csr_outer_dense_count(m, dim, gp_in.ptr, gws.ptr, gp.ptr, C.byref(total), None))
+    gws._download()
+    nout = int(total.value)
+    gj, gx = _entries(nout, np.int32, np.float64)
+    check(lib.mxd_csr_outer_dense_fill(m, dim, gx_in.n, gp_in.ptr, gx_in.ptr, gv.ptr,
+                                       _lib.MX_F64 if colvec.dtype == np.float64 else _lib.MX_F32, gp.ptr, gj.ptr, gx.ptr,
+                                       None))
+    _sync()
+    _untouched(gp_in, gx_in, gv)
+    return dict(indptr=gp.result(), indices=gj.result(nout), values=gx.result(nout))
+
+
+def dev_outer_svec(p, x, yi_base1, yv, v_dtype, length):
+    """mxd_csr_outer_svec_count + _fill of a one-column CSR (p, x) and a sparse vector: dict(indptr, indices, values)"""
+    lib = _lib.load()
+    m = int(p.size - 1)
+    gp_in, gx_in = GuardedVec(np.int32, data=p), GuardedVec(np.float64, data=x)
+    gyi, gyv = GuardedVec(np.int32, data=yi_base1), _vec(yv)
+    gws, gp = _ws(lib.mxd_csr_outer_svec_workspace_bytes(m, length)), GuardedVec(np.int32, n=length + 1)
+    nonempty, total = C.c_int64(-1), C.c_int64(-1)
+    check(lib.mxd_csr_outer_svec_count(m, gx_in.n, gp_in.ptr, gx_in.ptr, gyi.ptr, gyi.n, length, gws.ptr, gp.ptr,
+                                       C.byref(nonempty), C.byref(total), None))
+    gws._download()
+    nout = int(total.value)
+    gi, gx = _entries(nout, np.int32, np.float64)
+    check(lib.mxd_csr_outer_svec_fill(m, gyi.ptr, gyi.n, _ptr(gyv), v_dtype, length, nonempty.value, gws.ptr, gp.ptr,
+                                      gi.ptr, gx.ptr, None))
+    _sync()
+    _untouched(gp_in, gx_in, gyi, gyv)
+    gws._download()
+    return dict(indptr=gp.result(), indices=gi.result(nout), values=gx.result(nout))
+
+
+def dev_coo_slice(i, j, x, m, n, rows_take_base1, col_lo, col_hi):
+    """mxd_coo_slice_count + _fill with a map on the rows (mxd_colmap_build of the 1-based selector, repeats allowed)
+    and the columns col_lo..col_hi: (rows, cols, values or None) of the slice"""
+    lib = _lib.load()
+    gi, gj, gx = GuardedVec(np.int32, data=i), GuardedVec(np.int32, data=j), _vec(x)
+    vd, nnz = value_dtype_of(x), gi.n
+    gtake = GuardedVec(np.int32, data=rows_take_base1)
+    nmap = int(np.max(rows_take_base1)) + 1
+    gstart, gpos = GuardedVec(np.int32, n=nmap + 1), GuardedVec(np.int32, n=gtake.n)
+    gmws = _ws(lib.mxd_colmap_workspace_bytes(nmap))
+    check(lib.mxd_colmap_build(gtake.ptr, gtake.n, nmap, gstart.ptr, gpos.ptr, gmws.ptr, None))
+    _sync()
+    gmws._download()
+    ai = _lib.CooAxis(1, 0, 0, 0, nmap, gstart.ptr.value, gpos.ptr.value)
+    aj = _lib.CooAxis(0, col_lo, col_hi, 0, 0, None, None)
+    gws, total = _ws(lib.mxd_coo_slice_workspace_bytes(nnz)), C.c_int64(-1)
+    check(lib.mxd_coo_slice_count(m, n, gi.ptr, gj.ptr, nnz, C.byref(ai), C.byref(aj), gws.ptr, C.byref(total), None))
+    gws._download()
+    nout = int(total.value)
+    oi, oj, ox = _entries(nout, np.int32, np.int32, None if x is None else x.dtype)
+    check(lib.mxd_coo_slice_fill(m, n, gi.ptr, gj.ptr, _ptr(gx), vd, nnz, C.byref(ai), C.byref(aj), gws.ptr, oi.ptr,
+                                 oj.ptr, _ptr(ox), None))
+    _sync()
+    _untouched(gi, gj, gx, gtake)
+    gws._download()
+    gstart.result(), gpos.result()
+    return oi.result(nout), oj.result(nout), None if ox is None else ox.result(nout)
+
+
+def dev_coo_single(i, j, x, r, c):
+    """mxd_coo_single: (index of the first triplet at (r, c) or -1, the 8 value bytes read back)"""
+    lib = _lib.load()
+    gi, gj, gx = GuardedVec(np.int32, data=i), GuardedVec(np.int32, data=j), _vec(x)
+    gws, k, value = _ws(lib.mxd_coo_single_workspace_bytes()), C.c_int64(-2), (C.c_uint8 * 8)()
+    check(lib.mxd_coo_single(gi.ptr, gj.ptr, _ptr(gx), value_dtype_of(x), gi.n, r, c, gws.ptr, C.byref(k), value, None))
+    _sync()
+    _untouched(gi, gj, gx)
+    gws._download()
+    return int(k.value), bytes(value)
+
+
+def dev_csr_by_coo(logical, p, j, x, ncol, yi, yj, yv):
+    """mxd_csr_by_coo_count + _fill: (rows, cols, values) in the order of y's entries"""
+    lib = _lib.load()
+    A, m = GCsr(p, j, x), int(p.size - 1)
+    gyi, gyj, gyv = GuardedVec(np.int32, data=yi), GuardedVec(np.int32, data=yj), _vec(yv)
+    gws, total = _ws(lib.mxd_csr_by_coo_workspace_bytes(gyi.n)), C.c_int64(-1)
+    check(lib.mxd_csr_by_coo_count(int(logical), m, ncol, A.p.ptr, A.j.ptr, A.xptr, gyi.ptr, gyj.ptr, gyv.ptr, gyi.n,
+                                   gws.ptr, C.byref(total), None))
+    gws._download()
+    nout = int(total.value)
+    oi, oj, ox = _entries(nout, np.int32, np.int32, gyv.dtype)
+    check(lib.mxd_csr_by_coo_fill(int(logical), m, ncol, A.p.ptr, A.j.ptr, A.xptr, gyi.ptr, gyj.ptr, gyv.ptr, gyi.n,
+                                  gws.ptr, oi.ptr, oj.ptr, ox.ptr, None))
+    _sync()
+    _untouched(A, gyi, gyj, gyv)
+    gws._download()
+    return oi.result(nout), oj.result(nout), ox.result(nout)
+
+
+def dev_compact(p, j, x, rule, mask=None):
+    """mxd_compact_count + _fill over the entries of a CSR: (indptr, indices, values, kept)"""
+    lib = _lib.load()
+    A, gmask, vd, m = GCsr(p, j, x), _vec(mask, np.int32), value_dtype_of(x), int(p.size - 1)
+    gws, kept = _ws(lib.mxd_compact_workspace_bytes(A.nnz)), C.c_int64(-1)
+    check(lib.mxd_compact_count(A.nnz, A.xptr, vd, rule, _ptr(gmask), gws.ptr, C.byref(kept), None))
+    gws._download()
+    nout = int(kept.value)
+    gp = GuardedVec(np.int32, n=m + 1)
+    oj, ox = _entries(nout, np.int32, A.x.dtype)
+    check(lib.mxd_compact_fill(A.nnz, A.xptr, vd, rule, _ptr(gmask), A.j.ptr, None, m, A.p.ptr, gws.ptr, oj.ptr, None,
+                               ox.ptr, gp.ptr, None))
+    _sync()
+    _untouched(A, gmask)
+    gws._download()
+    return gp.result(), oj.result(nout), ox.result(nout), nout
+
+
+def dev_csr_transpose(p, j, x, ncol):
+    """mxd_csr_transpose: (indptr, indices, values or None) of the transpose, repeated cells merged"""
+    lib = _lib.load()
+    A = GCsr(p, j, x)
+    gws, total = _ws(lib.mxd_csr_transpose_workspace_bytes(A.nnz)), C.c_int64(-1)
+    gp = GuardedVec(np.int32, n=ncol + 1)
+    oj, ox = _entries(A.nnz, np.int32, None if x is None else x.dtype)
+    check(lib.mxd_csr_transpose(A.m, ncol, A.p.ptr, A.j.ptr, A.xptr, value_dtype_of(x), A.nnz, gp.ptr, oj.ptr, _ptr(ox),
+                                gws.ptr, C.byref(total), None))
+    _sync()
+    _untouched(A)
+    gws._download()
+    nout = int(total.value)        # every entry is written before repeated cells are merged into the first nout
+    return gp.result(), oj.result(A.nnz)[:nout], None if ox is None else ox.result(A.nnz)[:nout]
+
+
+def dev_coo_to_csr(i, j, x, m, n):
+    """mxd_coo_to_csr: (indptr, indices, values or None), repeated cells merged"""
+    lib = _lib.load()
+    gi, gj, gx = GuardedVec(np.int32, data=i), GuardedVec(np.int32, data=j), _vec(x)
+    nnz = gi.n
+    gws, total = _ws(lib.mxd_coo_to_csr_workspace_bytes(nnz, n)), C.c_int64(-1)
+    gp = GuardedVec(np.int32, n=m + 1)
+    oj, ox = _entries(nnz, np.int32, None if x is None else x.dtype)
+    check(lib.mxd_coo_to_csr(m, n, gi.ptr, gj.ptr, _ptr(gx), value_dtype_of(x), nnz, gp.ptr, oj.ptr, _ptr(ox), gws.ptr,
+                             C.byref(total), None))
+    _sync()
+    _untouched(gi, gj, gx)
+    gws._download()
+    nout = int(total.value)        # every entry is written before repeated cells are merged into the first nout
+    return gp.result(), oj.result(nnz)[:nout], None if ox is None else ox.result(nnz)[:nout]
+
+
+def dev_sort_vector(ii, xx, value_dtype):
+    """mxd_sort_vector_indices, in place: (indices, values or None, was_sorted)"""
+    lib = _lib.load()
+    gi, gx = GuardedVec(np.int32, data=ii), _vec(xx)
+    gws, was = _ws(lib.mxd_sort_vector_indices_workspace_bytes(gi.n)), C.c_int(-1)
+    check(lib.mxd_sort_vector_indices(gi.ptr, _ptr(gx), gi.n, value_dtype, gws.ptr, C.byref(was), None))
+    _sync()
+    gws._download()
+    return gi.read(), None if gx is None else gx.read(), int(was.value)
