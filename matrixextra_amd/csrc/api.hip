@@ -3,8 +3,10 @@
 // device, running the HIP kernels and bringing the result back.  There is no
 // CPU fallback: without a usable GPU every call fails with an error.
 #include "mx_dispatch.h"
+#include "mx_export.h"
 
 #include <cstdlib>
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <memory>
@@ -53,68 +55,24 @@ struct Trace {
     }
 };
 
-// owning device buffer
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n)
-    {
-        bytes = n;
-        if (n == 0) n = 16;                  // keep pointers non-null and 16-B aligned
-        MX_HIP(hipMalloc(&p, n));
-        return 0;
-    }
-    int upload(const void *h, size_t n)
-    {
-        if (alloc(n)) return 1;
-        if (n && mx::xfer_h2d(p, h, n)) return 1;               // pipelined through pinned slots when large (xfer.hip)
-        return 0;
-    }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-static inline size_t dtype_bytes(int dt)
-{
-    switch (dt) { case MX_F64: return 8; case MX_F32: case MX_I32: case MX_LGL: return 4; default: return 0; }
-}
-
-struct Csr {
-    DevBuf p, j, x;
-    int64_t nnz = 0;
-    // uploads indptr[0..m], indices/values[0..indptr[m]); value_bytes 0 => no values
-    int upload(const int32_t *indptr, const int32_t *indices, const void *values, int m, size_t value_bytes)
-    {
-        MX_REQUIRE(m >= 0 && indptr, "CSR upload: bad arguments");
-        nnz = indptr[m];
-        MX_REQUIRE(nnz >= 0 && indptr[0] >= 0, "CSR upload: negative index pointer");
-        if (p.upload(indptr, sizeof(int32_t) * ((size_t)m + 1))) return 1;
-        if (j.upload(indices, sizeof(int32_t) * (size_t)nnz)) return 1;
-        if (value_bytes && x.upload(values, value_bytes * (size_t)nnz)) return 1;
-        return 0;
-    }
-};
-
 // C(m x n) = A(CSR, m rows) * B(row-major rows of length ldb); host in, host out
 template <typename real_t>
 static int spmm_host(int m, int n, int K_rows, const int32_t *indptr, const int32_t *indices, const double *values,
-                     const real_t *B_host, size_t ldb, real_t *C_host, size_t ldc, size_t c_elems, bool colmajor)
+                     const real_t *B_host, int ldb, real_t *C_host, int ldc, bool colmajor)
 {
     MX_REQUIRE(m >= 0 && n >= 0 && K_rows >= 0, "negative dimension");
+    const int64_t c_elems = (int64_t)m * n;
     if (c_elems == 0) return 0;
     // reference early-out (matmul.cpp:128-129,160-161): result stays the zero-initialised matrix
-    if (m == 0 || n == 0 || indptr[0] == indptr[m]) { memset(C_host, 0, c_elems * sizeof(real_t)); return 0; }
+    if (indptr[0] == indptr[m]) { std::fill_n(C_host, c_elems, real_t(0)); return 0; }
     Trace tr("spmm export");
     Csr A;
     if (A.upload(indptr, indices, values, m, sizeof(double))) return 1;
     tr.mark("H2D csr");
-    DevBuf B, C;
-    if (B.upload(B_host, sizeof(real_t) * (size_t)K_rows * ldb)) return 1;
+    Dev<real_t> B, C;
+    if (B.upload(B_host, (int64_t)K_rows * ldb)) return 1;
     tr.mark("H2D dense");
-    if (C.alloc(sizeof(real_t) * c_elems)) return 1;
+    if (C.alloc(c_elems)) return 1;
     tr.mark("alloc C");
     const int dt = sizeof(real_t) == 8 ? MX_F64 : MX_F32;
     // kernel choice: AUTO unless the MXGPU_SPMM_ALGO / MXGPU_SPMM_PANELS tuning knobs say otherwise
@@ -124,14 +82,14 @@ static int spmm_host(int m, int n, int K_rows, const int32_t *indptr, const int3
     int sorted = 0;
     if (algo == MX_SPMM_SLAB) {
         // column panels need rows sorted by column id: one pass over the indices on the device
-        DevBuf flag;
-        if (flag.alloc(16)) return 1;
-        if (mxd_csr_rows_sorted(m, A.p.as<int32_t>(), A.j.as<int32_t>(), flag.as<int32_t>(), &sorted, nullptr)) return 1;
+        Dev<int32_t> flag;
+        if (flag.alloc(4)) return 1;
+        if (mxd_csr_rows_sorted(m, A.p, A.j, flag, &sorted, nullptr)) return 1;
     }
-    if (mxd_spmm_csr_dense_ex(m, n, K_rows, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.as<double>(), B.p, ldb, C.p, ldc,
+    if (mxd_spmm_csr_dense_ex(m, n, K_rows, A.p, A.j, A.x, B, ldb, C, ldc,
                               dt, colmajor ? 1 : 0, algo, sorted, npanels, 0, nullptr)) return 1;
     if (tr.on) { MX_HIP(hipDeviceSynchronize()); tr.mark("kernels"); }
-    const int rc = mx::xfer_d2h(C_host, C.p, sizeof(real_t) * c_elems);
+    const int rc = C.download(C_host, c_elems);
     tr.mark("D2H C");
     return rc;
 }
@@ -144,28 +102,15 @@ static int spmv_host(int m, const int32_t *indptr, const int32_t *indices, const
     if (m == 0) return 0;
     Csr A;
     if (A.upload(indptr, indices, values, m, sizeof(double))) return 1;
-    DevBuf v, o;
-    if (v.upload(y, sizeof(vec_t) * (size_t)len_y)) return 1;
-    if (o.alloc(sizeof(out_t) * (size_t)m)) return 1;
-    if (spmv_launch(m, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.as<double>(), v.p, v_dtype, o.p, nullptr))
-        return 1;
-    if (mx::xfer_d2h(out, o.p, sizeof(out_t) * (size_t)m)) return 1;
-    return 0;
+    Dev<vec_t> v;
+    Dev<out_t> o;
+    if (v.upload(y, len_y)) return 1;
+    if (o.alloc(m)) return 1;
+    if (spmv_launch(m, A.nnz, A.p, A.j, A.x, v, v_dtype, o, nullptr)) return 1;
+    return o.download(out, m);
 }
 
 }  // namespace mx
-
-// variable-size result waiting on the device for the caller's vectors
-struct mx_result {
-    mx::DevBuf indptr, indices, values;
-    mx_result_info info;
-    void set_sizes(int64_t indptr_len, int64_t nnz, int64_t values_len)
-    {
-        info.indptr_len = indptr_len;
-        info.nnz = nnz;
-        info.values_len = values_len;
-    }
-};
 
 using namespace mx;
 
@@ -184,6 +129,17 @@ static int begin_result(mx_result **res_out, mx_result_info *info, int values_dt
     *info = res->info;
     *res_out = res.release();
     return 0;
+}
+
+// The values-only products end alike: one value of value_bytes for each of the sparse operand's n entries, which
+// `launch` fills from the operands already on the device, and which goes back to the caller.
+template <typename Launch>
+static int values_only(int64_t n, size_t value_bytes, void *values_out, Launch &&launch)
+{
+    DevBuf o;
+    if (o.alloc(n, value_bytes)) return 1;
+    if (launch(o)) return 1;
+    return o.download(values_out, n, value_bytes);
 }
 
 extern "C" {
@@ -243,16 +199,16 @@ int mx_tcrossprod_csr_dense_numeric(const int32_t *X_indptr, const int32_t *X_in
 {
     (void)nthreads;
     // gemm_csr_drm_as_dcm(m = nrow X, n = nrow Y, B = Y, ldb = nrow Y, C, ldc = m)   matmul.cpp:326-332
-    return spmm_host<double>(nrows_X, nrow_Y, ncol_Y, X_indptr, X_indices, X_values, Y_colmajor, (size_t)nrow_Y,
-                             out_colmajor, (size_t)nrows_X, (size_t)nrows_X * (size_t)nrow_Y, true);
+    return spmm_host<double>(nrows_X, nrow_Y, ncol_Y, X_indptr, X_indices, X_values, Y_colmajor, nrow_Y,
+                             out_colmajor, nrows_X, true);
 }
 int mx_tcrossprod_csr_dense_float32(const int32_t *X_indptr, const int32_t *X_indices, const double *X_values,
                                     int nrows_X, const float *Y_colmajor, int nrow_Y, int ncol_Y, int nthreads,
                                     float *out_colmajor)
 {
     (void)nthreads;
-    return spmm_host<float>(nrows_X, nrow_Y, ncol_Y, X_indptr, X_indices, X_values, Y_colmajor, (size_t)nrow_Y,
-                            out_colmajor, (size_t)nrows_X, (size_t)nrows_X * (size_t)nrow_Y, true);
+    return spmm_host<float>(nrows_X, nrow_Y, ncol_Y, X_indptr, X_indices, X_values, Y_colmajor, nrow_Y,
+                            out_colmajor, nrows_X, true);
 }
 int mx_matmul_dense_csc_numeric(const double *X_colmajor, int nrows_X, int ncols_X, const int32_t *Y_indptr,
                                 const int32_t *Y_indices, const double *Y_values, int ncols_Y, int nthreads,
@@ -260,16 +216,16 @@ int mx_matmul_dense_csc_numeric(const double *X_colmajor, int nrows_X, int ncols
 {
     (void)nthreads;
     // gemm_csr_drm_as_drm(m = ncol Y, n = nrow X, CSC-as-CSR, B = X, ldb = nrow X, C, ldc = nrow X)  matmul.cpp:201-208
-    return spmm_host<double>(ncols_Y, nrows_X, ncols_X, Y_indptr, Y_indices, Y_values, X_colmajor, (size_t)nrows_X,
-                             out_colmajor, (size_t)nrows_X, (size_t)nrows_X * (size_t)ncols_Y, false);
+    return spmm_host<double>(ncols_Y, nrows_X, ncols_X, Y_indptr, Y_indices, Y_values, X_colmajor, nrows_X,
+                             out_colmajor, nrows_X, false);
 }
 int mx_matmul_dense_csc_float32(const float *X_colmajor, int nrows_X, int ncols_X, const int32_t *Y_indptr,
                                 const int32_t *Y_indices, const double *Y_values, int ncols_Y, int nthreads,
                                 float *out_colmajor)
 {
     (void)nthreads;
-    return spmm_host<float>(ncols_Y, nrows_X, ncols_X, Y_indptr, Y_indices, Y_values, X_colmajor, (size_t)nrows_X,
-                            out_colmajor, (size_t)nrows_X, (size_t)nrows_X * (size_t)ncols_Y, false);
+    return spmm_host<float>(ncols_Y, nrows_X, ncols_X, Y_indptr, Y_indices, Y_values, X_colmajor, nrows_X,
+                            out_colmajor, nrows_X, false);
 }
 int mx_tcrossprod_dense_csr_numeric(const double *X_colmajor, int nrows_X, int ncols_X, const int32_t *Y_indptr,
                                     const int32_t *Y_indices, const double *Y_values, int nrows_Y, int nthreads,
@@ -277,16 +233,16 @@ int mx_tcrossprod_dense_csr_numeric(const double *X_colmajor, int nrows_X, int n
 {
     (void)nthreads; (void)ncols_Y;
     // gemm_csr_drm_as_drm(m = nrow Y, n = nrow X, Y, B = X, ldb = nrow X, C, ldc = nrow X)  matmul.cpp:263-270
-    return spmm_host<double>(nrows_Y, nrows_X, ncols_X, Y_indptr, Y_indices, Y_values, X_colmajor, (size_t)nrows_X,
-                             out_colmajor, (size_t)nrows_X, (size_t)nrows_X * (size_t)nrows_Y, false);
+    return spmm_host<double>(nrows_Y, nrows_X, ncols_X, Y_indptr, Y_indices, Y_values, X_colmajor, nrows_X,
+                             out_colmajor, nrows_X, false);
 }
 int mx_tcrossprod_dense_csr_float32(const float *X_colmajor, int nrows_X, int ncols_X, const int32_t *Y_indptr,
                                     const int32_t *Y_indices, const double *Y_values, int nrows_Y, int nthreads,
                                     int ncols_Y, float *out_colmajor)
 {
     (void)nthreads; (void)ncols_Y;
-    return spmm_host<float>(nrows_Y, nrows_X, ncols_X, Y_indptr, Y_indices, Y_values, X_colmajor, (size_t)nrows_X,
-                            out_colmajor, (size_t)nrows_X, (size_t)nrows_X * (size_t)nrows_Y, false);
+    return spmm_host<float>(nrows_Y, nrows_X, ncols_X, Y_indptr, Y_indices, Y_values, X_colmajor, nrows_X,
+                            out_colmajor, nrows_X, false);
 }
 
 // ---- SpMV exports ------------------------------------------------------------------------------
@@ -332,37 +288,28 @@ int mx_csr_elemwise_begin(int op, int nrows, const int32_t *indptr1, const int32
         if (nnz1 == nnz2 && indptr1 == indptr2 && indices1 == indices2) {
             if (op == MX_OP_SUB && values1 == values2) {
                 // operators.cpp:348-355: IntegerVector(indptr.size()) zeros, empty indices / values
-                res.set_sizes((int64_t)nrows + 1, 0, 0);
-                if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
-                MX_HIP(hipMemset(res.indptr.p, 0, sizeof(int32_t) * ((size_t)nrows + 1)));
-                return 0;
+                if (res.alloc_indptr((int64_t)nrows + 1)) return 1;
+                return res.indptr.zero((int64_t)nrows + 1);
             }
-            res.info.alias_structure = 1;
-            res.set_sizes((int64_t)nrows + 1, nnz1, nnz1);
+            res.alias(1, (int64_t)nrows + 1, nnz1);
             DevBuf a, b;
-            if (a.upload(values1, vb * (size_t)nnz1)) return 1;
-            if (b.upload(values2, vb * (size_t)nnz2)) return 1;
-            if (res.values.alloc(vb * (size_t)nnz1)) return 1;
-            return mxd_values_elemwise(op, nnz1, a.p, b.p, res.values.p, nullptr);
+            if (a.upload(values1, nnz1, vb)) return 1;
+            if (b.upload(values2, nnz2, vb)) return 1;
+            if (res.alloc_values(nnz1, vb)) return 1;
+            return mxd_values_elemwise(op, nnz1, a, b, res.values, nullptr);
         }
         Csr A, B;
         if (A.upload(indptr1, indices1, values1, nrows, vb)) return 1;
         if (B.upload(indptr2, indices2, values2, nrows, vb)) return 1;
         DevBuf ws;
-        if (ws.alloc(mxd_merge_workspace_bytes(nrows))) return 1;
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        if (ws.alloc_bytes(mxd_merge_workspace_bytes(nrows))) return 1;
+        if (res.alloc_indptr((int64_t)nrows + 1)) return 1;
         int64_t nnz_out = 0;
-        if (mxd_csr_merge_count(op, nrows, A.p.as<int32_t>(), A.j.as<int32_t>(), A.nnz, B.p.as<int32_t>(),
-                                B.j.as<int32_t>(), B.nnz, res.indptr.as<int32_t>(), ws.p, &nnz_out, nullptr))
+        if (mxd_csr_merge_count(op, nrows, A.p, A.j, A.nnz, B.p, B.j, B.nnz, res.indptr, ws, &nnz_out, nullptr))
             return 1;
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
-        if (res.values.alloc(vb * (size_t)nnz_out)) return 1;
-        if (mxd_csr_merge_fill(op, nrows, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, A.nnz, B.p.as<int32_t>(),
-                               B.j.as<int32_t>(), B.x.p, B.nnz, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
-                               res.values.p, nullptr))
-            return 1;
-        res.set_sizes((int64_t)nrows + 1, nnz_out, nnz_out);
-        return 0;
+        if (res.alloc_entries(nnz_out, vb)) return 1;
+        return mxd_csr_merge_fill(op, nrows, A.p, A.j, A.x, A.nnz, B.p, B.j, B.x, B.nnz, res.indptr, res.indices,
+                                  res.values, nullptr);
     });
 }
 
@@ -373,35 +320,27 @@ int mx_copy_csr_rows_begin(const int32_t *indptr, int nrows, const int32_t *indi
 {
     MX_REQUIRE(res_out && info, "mx_copy_csr_rows_begin: null output pointer");
     MX_REQUIRE(nrows >= 0 && n_take >= 0 && n_take <= INT_MAX, "mx_copy_csr_rows_begin: bad size");
-    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
-               "mx_copy_csr_rows_begin: unsupported value dtype %d", value_dtype);
+    if (admit_values("mx_copy_csr_rows_begin", value_dtype)) return 1;
     *res_out = nullptr;
-    const bool has_values = value_dtype != MX_NONE && n_values > 0;   // slice.cpp:246,257
-    const size_t vb = has_values ? dtype_bytes(value_dtype) : 0;
+    const Values vals(value_dtype, n_values);                         // slice.cpp:246,257
     return begin_result(res_out, info, value_dtype, [&](mx_result &res) {
         Csr A;
-        if (A.upload(indptr, indices, values, nrows, vb)) return 1;
-        DevBuf rows, ws;
-        if (rows.upload(rows_take, sizeof(int32_t) * (size_t)n_take)) return 1;
-        if (ws.alloc(mxd_gather_workspace_bytes((int)n_take))) return 1;
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)n_take + 1))) return 1;
+        if (A.upload(indptr, indices, values, nrows, vals.bytes)) return 1;
+        Dev<int32_t> rows;
+        DevBuf ws;
+        if (rows.upload(rows_take, n_take)) return 1;
+        if (ws.alloc_bytes(mxd_gather_workspace_bytes((int)n_take))) return 1;
+        if (res.alloc_indptr(n_take + 1)) return 1;
         int64_t nnz_out = 0;
-        if (mxd_csr_gather_count((int)n_take, A.p.as<int32_t>(), rows.as<int32_t>(), res.indptr.as<int32_t>(), ws.p,
-                                 &nnz_out, nullptr))
-            return 1;
+        if (mxd_csr_gather_count((int)n_take, A.p, rows, res.indptr, ws, &nnz_out, nullptr)) return 1;
         if (nnz_out == 0) {          // slice.cpp:236-240: three EMPTY vectors (even the indptr)
             res.set_sizes(0, 0, 0);
             return 0;
         }
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
-        if (has_values && res.values.alloc(vb * (size_t)nnz_out)) return 1;
-        if (mxd_csr_gather_fill((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, rows.as<int32_t>(),
-                                res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.p,
-                                has_values ? value_dtype : MX_NONE, nnz_out, nullptr))
-            return 1;
-        res.set_sizes(n_take + 1, nnz_out, has_values ? nnz_out : 0);
-        if (!has_values) res.info.values_dtype = MX_NONE;
-        return 0;
+        if (res.alloc_entries(nnz_out, vals.bytes)) return 1;
+        if (!vals) res.info.values_dtype = MX_NONE;
+        return mxd_csr_gather_fill((int)n_take, A.p, A.j, A.x, rows, res.indptr, res.indices, res.values, vals.dtype,
+                                   nnz_out, nullptr);
     });
 }
 
@@ -413,32 +352,28 @@ int mx_copy_csr_rows_col_seq_begin(const int32_t *indptr, int nrows, const int32
 {
     MX_REQUIRE(res_out && info, "mx_copy_csr_rows_col_seq_begin: null output pointer");
     MX_REQUIRE(nrows >= 0 && n_take >= 0 && n_take <= INT_MAX && n_cols_take > 0, "mx_copy_csr_rows_col_seq_begin: bad size");
-    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
-               "mx_copy_csr_rows_col_seq_begin: unsupported value dtype %d", value_dtype);
+    if (admit_values("mx_copy_csr_rows_col_seq_begin", value_dtype)) return 1;
     *res_out = nullptr;
     int min_col = cols_take[0], max_col = cols_take[0];                      // slice.cpp:337-338
     for (int64_t c = 1; c < n_cols_take; c++) { if (cols_take[c] < min_col) min_col = cols_take[c]; if (cols_take[c] > max_col) max_col = cols_take[c]; }
     min_col -= index1 ? 1 : 0; max_col -= index1 ? 1 : 0;
-    const bool has_values = value_dtype != MX_NONE && n_values > 0;
+    const Values vals(value_dtype, n_values);
     return begin_result(res_out, info, MX_F64, [&](mx_result &res) {   // always a NumericVector (slice.cpp:363)
         Csr A;
-        if (A.upload(indptr, indices, values, nrows, has_values ? dtype_bytes(value_dtype) : 0)) return 1;
-        DevBuf rows, ws;
-        if (rows.upload(rows_take, sizeof(int32_t) * (size_t)n_take)) return 1;
-        if (ws.alloc(mxd_gather_workspace_bytes((int)n_take))) return 1;
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)n_take + 1))) return 1;
+        if (A.upload(indptr, indices, values, nrows, vals.bytes)) return 1;
+        Dev<int32_t> rows;
+        DevBuf ws;
+        if (rows.upload(rows_take, n_take)) return 1;
+        if (ws.alloc_bytes(mxd_gather_workspace_bytes((int)n_take))) return 1;
+        if (res.alloc_indptr(n_take + 1)) return 1;                           // full-length indptr even when empty
         const double avg = nrows > 0 ? (double)A.nnz / nrows : 0.0;
         int64_t nnz_out = 0;
-        if (mxd_csr_colrange_count((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), rows.as<int32_t>(), min_col,
-                                   max_col, avg, res.indptr.as<int32_t>(), ws.p, &nnz_out, nullptr)) return 1;
-        res.set_sizes(n_take + 1, nnz_out, has_values ? nnz_out : 0);       // full-length indptr even when empty
+        if (mxd_csr_colrange_count((int)n_take, A.p, A.j, rows, min_col, max_col, avg, res.indptr, ws, &nnz_out,
+                                   nullptr)) return 1;
+        if (res.alloc_entries(nnz_out, vals ? sizeof(double) : 0)) return 1;
         if (nnz_out == 0) return 0;                                           // slice.cpp:355-359
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
-        if (has_values && res.values.alloc(sizeof(double) * (size_t)nnz_out)) return 1;
-        return mxd_csr_colrange_fill((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p,
-                                     has_values ? value_dtype : MX_NONE, rows.as<int32_t>(), min_col, max_col, avg,
-                                     res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.as<double>(),
-                                     nullptr);
+        return mxd_csr_colrange_fill((int)n_take, A.p, A.j, A.x, vals.dtype, rows, min_col, max_col, avg, res.indptr,
+                                     res.indices, res.values, nullptr);
     });
 }
 
@@ -450,11 +385,9 @@ int mx_copy_csr_arbitrary_begin(const int32_t *indptr, int nrows, const int32_t 
     MX_REQUIRE(res_out && info, "mx_copy_csr_arbitrary_begin: null output pointer");
     MX_REQUIRE(nrows >= 0 && n_take >= 0 && n_take <= INT_MAX && n_cols_take >= 0 && n_cols_take <= INT_MAX,
                "mx_copy_csr_arbitrary_begin: bad size");
-    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
-               "mx_copy_csr_arbitrary_begin: unsupported value dtype %d", value_dtype);
+    if (admit_values("mx_copy_csr_arbitrary_begin", value_dtype)) return 1;
     *res_out = nullptr;
-    const bool has_values = value_dtype != MX_NONE && n_values > 0;           // `if (values.size())`, slice.cpp:565
-    const size_t vb = has_values ? dtype_bytes(value_dtype) : 0;
+    const Values vals(value_dtype, n_values);                                 // `if (values.size())`, slice.cpp:565
     int max_j = -1;
     bool cols_sorted = true;                                                  // slice.cpp:487-493
     for (int64_t c = 0; c < n_cols_take; c++) {
@@ -463,37 +396,34 @@ int mx_copy_csr_arbitrary_begin(const int32_t *indptr, int nrows, const int32_t 
         if (c && cols_take[c] < cols_take[c - 1]) cols_sorted = false;
     }
     const int ncol_map = max_j + 1;
-    return begin_result(res_out, info, has_values ? value_dtype : MX_NONE, [&](mx_result &res) {
+    return begin_result(res_out, info, vals.dtype, [&](mx_result &res) {
         Csr A;
-        if (A.upload(indptr, indices, values, nrows, vb)) return 1;
-        DevBuf rows, cols, start, pos, ws, mws;
-        if (rows.upload(rows_take, sizeof(int32_t) * (size_t)n_take)) return 1;
-        if (cols.upload(cols_take, sizeof(int32_t) * (size_t)n_cols_take)) return 1;
-        if (start.alloc(sizeof(int32_t) * ((size_t)ncol_map + 1))) return 1;
-        if (pos.alloc(sizeof(int32_t) * (size_t)n_cols_take)) return 1;
-        if (mws.alloc(mxd_colmap_workspace_bytes(ncol_map))) return 1;
-        if (ws.alloc(mxd_gather_workspace_bytes((int)n_take))) return 1;
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)n_take + 1))) return 1;
-        if (mxd_colmap_build(cols.as<int32_t>(), n_cols_take, ncol_map, start.as<int32_t>(), pos.as<int32_t>(), mws.p,
-                             nullptr)) return 1;
+        if (A.upload(indptr, indices, values, nrows, vals.bytes)) return 1;
+        Dev<int32_t> rows, cols, start, pos;
+        DevBuf ws, mws;
+        if (rows.upload(rows_take, n_take)) return 1;
+        if (cols.upload(cols_take, n_cols_take)) return 1;
+        if (start.alloc((int64_t)ncol_map + 1)) return 1;
+        if (pos.alloc(n_cols_take)) return 1;
+        if (mws.alloc_bytes(mxd_colmap_workspace_bytes(ncol_map))) return 1;
+        if (ws.alloc_bytes(mxd_gather_workspace_bytes((int)n_take))) return 1;
+        if (res.alloc_indptr(n_take + 1)) return 1;
+        if (mxd_colmap_build(cols, n_cols_take, ncol_map, start, pos, mws, nullptr)) return 1;
         const double avg = nrows > 0 ? (double)A.nnz / nrows : 0.0;
         int64_t nnz_out = 0;
-        if (mxd_csr_colmap_count((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), rows.as<int32_t>(), ncol_map,
-                                 start.as<int32_t>(), avg, res.indptr.as<int32_t>(), ws.p, &nnz_out, nullptr)) return 1;
-        res.set_sizes(n_take + 1, nnz_out, has_values ? nnz_out : 0);
+        if (mxd_csr_colmap_count((int)n_take, A.p, A.j, rows, ncol_map, start, avg, res.indptr, ws, &nnz_out,
+                                 nullptr)) return 1;
+        if (res.alloc_entries(nnz_out, vals.bytes)) return 1;
         if (nnz_out == 0) return 0;
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
-        if (has_values && res.values.alloc(vb * (size_t)nnz_out)) return 1;
-        if (mxd_csr_colmap_fill((int)n_take, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p,
-                                has_values ? value_dtype : MX_NONE, rows.as<int32_t>(), ncol_map, start.as<int32_t>(),
-                                pos.as<int32_t>(), avg, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
-                                res.values.p, nullptr)) return 1;
+        if (mxd_csr_colmap_fill((int)n_take, A.p, A.j, A.x, vals.dtype, rows, ncol_map, start, pos, avg, res.indptr,
+                                res.indices, res.values, nullptr)) return 1;
         if (cols_sorted) return 0;
-        DevBuf tj, tx;                                                        // slice.cpp:540-560
-        if (tj.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
-        if (has_values && tx.alloc(vb * (size_t)nnz_out)) return 1;
-        return mxd_csr_sort_rows((int)n_take, nnz_out, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
-                                 res.values.p, has_values ? value_dtype : MX_NONE, tj.as<int32_t>(), tx.p, nullptr);
+        Dev<int32_t> tj;                                                      // slice.cpp:540-560
+        DevBuf tx;
+        if (tj.alloc(nnz_out)) return 1;
+        if (vals && tx.alloc(nnz_out, vals.bytes)) return 1;
+        return mxd_csr_sort_rows((int)n_take, nnz_out, res.indptr, res.indices, res.values, vals.dtype, tj, tx,
+                                 nullptr);
     });
 }
 
@@ -503,26 +433,22 @@ int mx_reverse_rows_begin(const int32_t *indptr, int nrows, const int32_t *indic
     MX_REQUIRE(res_out && info, "mx_reverse_rows_begin: null output pointer");
     MX_REQUIRE(nrows >= 0, "mx_reverse_rows_begin: negative size");
     *res_out = nullptr;
-    const bool has_values = value_dtype != MX_NONE && n_values > 0;           // slice.cpp:66
-    const size_t vb = has_values ? dtype_bytes(value_dtype) : 0;
-    return begin_result(res_out, info, has_values ? value_dtype : MX_NONE, [&](mx_result &res) {
+    const Values vals(value_dtype, n_values);                                 // slice.cpp:66
+    return begin_result(res_out, info, vals.dtype, [&](mx_result &res) {
         Csr A;
-        if (A.upload(indptr, indices, values, nrows, vb)) return 1;
-        DevBuf rows, ws;
-        if (rows.alloc(sizeof(int32_t) * (size_t)nrows)) return 1;
-        if (ws.alloc(mxd_gather_workspace_bytes(nrows))) return 1;
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
-        if (mxd_reversed_iota(nrows, rows.as<int32_t>(), nullptr)) return 1;
+        if (A.upload(indptr, indices, values, nrows, vals.bytes)) return 1;
+        Dev<int32_t> rows;
+        DevBuf ws;
+        if (rows.alloc(nrows)) return 1;
+        if (ws.alloc_bytes(mxd_gather_workspace_bytes(nrows))) return 1;
+        if (res.alloc_indptr((int64_t)nrows + 1)) return 1;                   // always full length (slice.cpp:57)
+        if (mxd_reversed_iota(nrows, rows, nullptr)) return 1;
         int64_t nnz_out = 0;
-        if (mxd_csr_gather_count(nrows, A.p.as<int32_t>(), rows.as<int32_t>(), res.indptr.as<int32_t>(), ws.p,
-                                 &nnz_out, nullptr)) return 1;
-        res.set_sizes((int64_t)nrows + 1, nnz_out, has_values ? nnz_out : 0);   // always full length (slice.cpp:57)
+        if (mxd_csr_gather_count(nrows, A.p, rows, res.indptr, ws, &nnz_out, nullptr)) return 1;
+        if (res.alloc_entries(nnz_out, vals.bytes)) return 1;
         if (nnz_out == 0) return 0;
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
-        if (has_values && res.values.alloc(vb * (size_t)nnz_out)) return 1;
-        return mxd_csr_gather_fill(nrows, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, rows.as<int32_t>(),
-                                   res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.p,
-                                   has_values ? value_dtype : MX_NONE, nnz_out, nullptr);
+        return mxd_csr_gather_fill(nrows, A.p, A.j, A.x, rows, res.indptr, res.indices, res.values, vals.dtype,
+                                   nnz_out, nullptr);
     });
 }
 
@@ -530,15 +456,13 @@ int mx_reverse_columns_inplace(const int32_t *indptr, int nrows, int32_t *indice
                                int64_t n_values, int ncol)
 {
     if (nrows <= 0) return 0;
-    const bool has_values = value_dtype != MX_NONE && n_values > 0 && values;
-    const size_t vb = has_values ? dtype_bytes(value_dtype) : 0;
+    const Values vals(value_dtype, values ? n_values : 0);
     Csr A;
-    if (A.upload(indptr, indices, values, nrows, vb)) return 1;
+    if (A.upload(indptr, indices, values, nrows, vals.bytes)) return 1;
     if (A.nnz == 0) return 0;
-    if (mxd_csr_reverse_columns(nrows, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p,
-                                has_values ? value_dtype : MX_NONE, ncol, nullptr)) return 1;
-    if (mx::xfer_d2h(indices, A.j.p, sizeof(int32_t) * (size_t)A.nnz)) return 1;
-    if (vb && mx::xfer_d2h(values, A.x.p, vb * (size_t)A.nnz)) return 1;
+    if (mxd_csr_reverse_columns(nrows, A.nnz, A.p, A.j, A.x, vals.dtype, ncol, nullptr)) return 1;
+    if (A.j.download(indices, A.nnz)) return 1;
+    if (vals && A.x.download(values, A.nnz, vals.bytes)) return 1;
     return 0;
 }
 
@@ -549,18 +473,18 @@ int mx_matmul_csr_svec(const int32_t *Xp, const int32_t *Xj, const double *Xx, i
     (void)nthreads;
     MX_REQUIRE(nrows >= 0 && ny >= 0 && ny <= INT_MAX && kind >= 0 && kind <= 4, "mx_matmul_csr_svec: bad arguments");
     if (nrows == 0) return 0;
-    if (ny == 0) { memset(out, 0, sizeof(double) * (size_t)nrows); return 0; }
+    if (ny == 0) { std::fill_n(out, nrows, 0.0); return 0; }
     Csr A;
     if (A.upload(Xp, Xj, Xx, nrows, sizeof(double))) return 1;
-    DevBuf di, dv, o;
-    if (di.upload(yi, sizeof(int32_t) * (size_t)ny)) return 1;
+    Dev<int32_t> di;
+    DevBuf dv;
+    Dev<double> o;
+    if (di.upload(yi, ny)) return 1;
     const size_t vb = kind == 0 ? 8 : kind == 3 ? 0 : 4;
-    if (vb && dv.upload(yv, vb * (size_t)ny)) return 1;
-    if (o.alloc(sizeof(double) * (size_t)nrows)) return 1;
-    if (mxd_spmv_csr_svec(nrows, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.as<double>(), di.as<int32_t>(), (int)ny,
-                          vb ? dv.p : nullptr, kind, o.as<double>(), nullptr)) return 1;
-    if (mx::xfer_d2h(out, o.p, sizeof(double) * (size_t)nrows)) return 1;
-    return 0;
+    if (vb && dv.upload(yv, ny, vb)) return 1;
+    if (o.alloc(nrows)) return 1;
+    if (mxd_spmv_csr_svec(nrows, A.nnz, A.p, A.j, A.x, di, (int)ny, dv, kind, o, nullptr)) return 1;
+    return o.download(out, nrows);
 }
 
 int mx_multiply_csr_by_dense_elemwise(const int32_t *indptr, const int32_t *indices, const void *values, int nrows,
@@ -572,12 +496,11 @@ int mx_multiply_csr_by_dense_elemwise(const int32_t *indptr, const int32_t *indi
     Csr A;
     if (A.upload(indptr, indices, values, nrows, vb)) return 1;
     if (A.nnz == 0) return 0;
-    DevBuf D, o;
-    if (D.upload(dense_mat, db * (size_t)nrows * (size_t)ncols)) return 1;
-    if (o.alloc(vb * (size_t)A.nnz)) return 1;
-    if (mxd_csr_by_dense_elemwise(nrows, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, D.p, kind, o.p, nullptr)) return 1;
-    if (mx::xfer_d2h(values_out, o.p, vb * (size_t)A.nnz)) return 1;
-    return 0;
+    DevBuf D;
+    if (D.upload(dense_mat, nrows * ncols, db)) return 1;
+    return values_only(A.nnz, vb, values_out, [&](DevBuf &o) {
+        return mxd_csr_by_dense_elemwise(nrows, A.nnz, A.p, A.j, A.x, D, kind, o, nullptr);
+    });
 }
 
 // ---- CSC (.) dense (svec.hip, cscdense.hip) -------------------------------------------------
@@ -592,12 +515,11 @@ static int csc_by_dense_ignore(const int32_t *indptr, int ncols, const int32_t *
     if (A.upload(indptr, indices, values, ncols, vb)) return 1;
     if (A.nnz == 0) return 0;
     MX_REQUIRE(nrows > 0 && dense && values_out, "csc (.) dense: entries in a matrix without rows");
-    DevBuf D, o;
-    if (D.upload(dense, db * (size_t)nrows * (size_t)ncols)) return 1;
-    if (o.alloc(vb * (size_t)A.nnz)) return 1;
-    if (mxd_csc_by_dense_elemwise(ncols, nrows, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, D.p, kind, o.p,
-                                  nullptr)) return 1;
-    return mx::xfer_d2h(values_out, o.p, vb * (size_t)A.nnz);
+    DevBuf D;
+    if (D.upload(dense, (int64_t)nrows * ncols, db)) return 1;
+    return values_only(A.nnz, vb, values_out, [&](DevBuf &o) {
+        return mxd_csc_by_dense_elemwise(ncols, nrows, A.nnz, A.p, A.j, A.x, D, kind, o, nullptr);
+    });
 }
 
 // NA-keeping (multiply_csc_by_dense_keep_NAs_template<>, operators.cpp:1207-1386): count -> scan -> read-back, then
@@ -613,26 +535,19 @@ static int csc_by_dense_keep(const int32_t *indptr, int ncols, const int32_t *in
         Csr A;
         if (A.upload(indptr, indices, values, ncols, sizeof(double))) return 1;
         DevBuf D, ws;
-        if (D.upload(dense, db * (size_t)nrows * (size_t)ncols)) return 1;
-        if (ws.alloc(mxd_csc_dense_na_workspace_bytes(nrows, ncols))) return 1;
+        if (D.upload(dense, (int64_t)nrows * ncols, db)) return 1;
+        if (ws.alloc_bytes(mxd_csc_dense_na_workspace_bytes(nrows, ncols))) return 1;
         int64_t total = 0, outside = 0;
-        if (mxd_csc_dense_na_count(nrows, ncols, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), D.p, kind, ws.p, &total,
-                                   &outside, nullptr)) return 1;
-        res.set_sizes((int64_t)ncols + 1, total, total);
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)ncols + 1))) return 1;
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
-        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+        if (mxd_csc_dense_na_count(nrows, ncols, A.nnz, A.p, A.j, D, kind, ws, &total, &outside, nullptr)) return 1;
+        if (res.alloc_indptr((int64_t)ncols + 1)) return 1;
+        if (res.alloc_entries(total, sizeof(double))) return 1;
         if (outside == 0 && total == A.nnz) {           // no NA cell outside the pattern, no repeated row
-            MX_HIP(hipMemcpyAsync(res.indptr.p, A.p.p, sizeof(int32_t) * ((size_t)ncols + 1), hipMemcpyDeviceToDevice,
-                                  nullptr));
-            MX_HIP(hipMemcpyAsync(res.indices.p, A.j.p, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToDevice,
-                                  nullptr));
-            return mxd_csc_by_dense_elemwise(ncols, nrows, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, D.p,
-                                             kind, res.values.p, nullptr);
+            if (res.indptr.copy_from(A.p, (int64_t)ncols + 1)) return 1;
+            if (res.indices.copy_from(A.j, total)) return 1;
+            return mxd_csc_by_dense_elemwise(ncols, nrows, A.nnz, A.p, A.j, A.x, D, kind, res.values, nullptr);
         }
-        return mxd_csc_dense_na_fill(nrows, ncols, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.as<double>(), D.p,
-                                     kind, ws.p, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
-                                     res.values.as<double>(), nullptr);
+        return mxd_csc_dense_na_fill(nrows, ncols, A.nnz, A.p, A.j, A.x, D, kind, ws, res.indptr, res.indices,
+                                     res.values, nullptr);
     });
 }
 
@@ -717,23 +632,20 @@ int mx_multiply_csr_by_svec_begin(const int32_t *indptr, int nrows, const int32_
     return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
         Csr A;
         if (A.upload(indptr, indices, values, nrows, sizeof(double))) return 1;
-        DevBuf vi, vx, ws;
-        if (vi.upload(ii_base1, sizeof(int32_t) * (size_t)nnz_v)) return 1;
-        if (xx && vx.upload(xx, sizeof(double) * (size_t)nnz_v)) return 1;
-        if (ws.alloc(mxd_csr_by_svec_workspace_bytes(nrows))) return 1;
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        Dev<int32_t> vi;
+        Dev<double> vx;                                   // stays null for an nsparseVector
+        DevBuf ws;
+        if (vi.upload(ii_base1, nnz_v)) return 1;
+        if (xx && vx.upload(xx, nnz_v)) return 1;
+        if (ws.alloc_bytes(mxd_csr_by_svec_workspace_bytes(nrows))) return 1;
+        if (res.alloc_indptr((int64_t)nrows + 1)) return 1;
         int64_t total = 0, x_na = 0;
-        if (mxd_csr_by_svec_count(nrows, ncols, A.nnz, A.p.as<int32_t>(), A.x.as<double>(), vi.as<int32_t>(), nnz_v,
-                                  xx ? vx.as<double>() : nullptr, length, keep_NAs, ws.p, res.indptr.as<int32_t>(),
+        if (mxd_csr_by_svec_count(nrows, ncols, A.nnz, A.p, A.x, vi, nnz_v, vx, length, keep_NAs, ws, res.indptr,
                                   &total, &x_na, nullptr)) return 1;
-        res.set_sizes((int64_t)nrows + 1, total, total);
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
-        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+        if (res.alloc_entries(total, sizeof(double))) return 1;
         if (total == 0) return 0;
-        return mxd_csr_by_svec_fill(nrows, ncols, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.as<double>(),
-                                    vi.as<int32_t>(), nnz_v, xx ? vx.as<double>() : nullptr, length, keep_NAs, ws.p,
-                                    res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.as<double>(),
-                                    nullptr);
+        return mxd_csr_by_svec_fill(nrows, ncols, A.nnz, A.p, A.j, A.x, vi, nnz_v, vx, length, keep_NAs, ws,
+                                    res.indptr, res.indices, res.values, nullptr);
     });
 }
 
@@ -779,22 +691,21 @@ int mx_multiply_elemwise_dense_by_svec_begin(const void *X_colmajor, int kind, i
                "%s: a vector of length %d against %d x %d gives a dense result", what, length, nrows, ncols);
     const size_t cell = kind == 0 ? 8 : 4;
     return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
-        DevBuf X, vi, vx, ws;
-        if (X.upload(X_colmajor, cell * (size_t)nrows * (size_t)ncols)) return 1;
-        if (vi.upload(ii_base1, sizeof(int32_t) * (size_t)nnz_v)) return 1;
-        if (vx.upload(xx, sizeof(double) * (size_t)nnz_v)) return 1;
-        if (ws.alloc(mxd_dense_by_svec_workspace_bytes(nrows, length))) return 1;
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        DevBuf X, ws;
+        Dev<int32_t> vi;
+        Dev<double> vx;
+        if (X.upload(X_colmajor, (int64_t)nrows * ncols, cell)) return 1;
+        if (vi.upload(ii_base1, nnz_v)) return 1;
+        if (vx.upload(xx, nnz_v)) return 1;
+        if (ws.alloc_bytes(mxd_dense_by_svec_workspace_bytes(nrows, length))) return 1;
+        if (res.alloc_indptr((int64_t)nrows + 1)) return 1;
         int64_t total = 0;
-        if (mxd_dense_by_svec_count(nrows, ncols, X.p, kind, vi.as<int32_t>(), nnz_v, length, keep_NAs, ws.p,
-                                    res.indptr.as<int32_t>(), &total, nullptr)) return 1;
-        res.set_sizes((int64_t)nrows + 1, total, total);
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
-        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+        if (mxd_dense_by_svec_count(nrows, ncols, X, kind, vi, nnz_v, length, keep_NAs, ws, res.indptr, &total,
+                                    nullptr)) return 1;
+        if (res.alloc_entries(total, sizeof(double))) return 1;
         if (total == 0) return 0;
-        return mxd_dense_by_svec_fill(nrows, ncols, X.p, kind, vx.as<double>(), length, keep_NAs, ws.p,
-                                      res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.as<double>(),
-                                      nullptr);
+        return mxd_dense_by_svec_fill(nrows, ncols, X, kind, vx, length, keep_NAs, ws, res.indptr, res.indices,
+                                      res.values, nullptr);
     });
 }
 
@@ -808,18 +719,19 @@ int mx_multiply_elemwise_dense_by_svec_dense(const void *X_colmajor, int kind, i
     const int route = mx_dense_by_svec_route(nrows, ncols, length);
     MX_REQUIRE(route == MX_DSV_ROUTE_A || route == MX_DSV_ROUTE_D,
                "%s: a vector of length %d against %d x %d gives a CSR result", what, length, nrows, ncols);
-    const size_t cells = (size_t)nrows * (size_t)ncols;
+    const int64_t cells = (int64_t)nrows * ncols;
     if (cells == 0) return 0;
     MX_REQUIRE(out_colmajor, "%s: null pointer", what);
-    DevBuf X, vi, vx, ws, out;
-    if (X.upload(X_colmajor, (kind == 0 ? 8 : 4) * cells)) return 1;
-    if (vi.upload(ii_base1, sizeof(int32_t) * (size_t)nnz_v)) return 1;
-    if (vx.upload(xx, sizeof(double) * (size_t)nnz_v)) return 1;
-    if (ws.alloc(mxd_dense_by_svec_workspace_bytes(0, length))) return 1;
-    if (out.alloc(sizeof(double) * cells)) return 1;
-    if (mxd_dense_by_svec_dense(nrows, ncols, X.p, kind, vi.as<int32_t>(), nnz_v, vx.as<double>(), length, keep_NAs,
-                                ws.p, out.as<double>(), nullptr)) return 1;
-    return mx::xfer_d2h(out_colmajor, out.p, sizeof(double) * cells);
+    DevBuf X, ws;
+    Dev<int32_t> vi;
+    Dev<double> vx, out;
+    if (X.upload(X_colmajor, cells, kind == 0 ? 8 : 4)) return 1;
+    if (vi.upload(ii_base1, nnz_v)) return 1;
+    if (vx.upload(xx, nnz_v)) return 1;
+    if (ws.alloc_bytes(mxd_dense_by_svec_workspace_bytes(0, length))) return 1;
+    if (out.alloc(cells)) return 1;
+    if (mxd_dense_by_svec_dense(nrows, ncols, X, kind, vi, nnz_v, vx, length, keep_NAs, ws, out, nullptr)) return 1;
+    return out.download(out_colmajor, cells);
 }
 
 // multiply_coo_by_dense<> (operators.cpp:721-770): values only; kind 4 is the logical and
@@ -835,14 +747,15 @@ static int coo_by_dense(const char *what, const void *X, int nrows, int ncols, c
                    ncols);
     MX_REQUIRE(X, "%s: null pointer", what);
     const size_t vb = kind == 4 ? 4 : 8;
-    DevBuf D, i, j, x, o;
-    if (D.upload(X, (kind == 0 ? 8 : 4) * (size_t)nrows * (size_t)ncols)) return 1;
-    if (i.upload(ii, sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (j.upload(jj, sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (x.upload(xx, vb * (size_t)nnz)) return 1;
-    if (o.alloc(vb * (size_t)nnz)) return 1;
-    if (mxd_coo_by_dense(nnz, i.as<int32_t>(), j.as<int32_t>(), x.p, D.p, nrows, ncols, kind, o.p, nullptr)) return 1;
-    return mx::xfer_d2h(values_out, o.p, vb * (size_t)nnz);
+    DevBuf D, x;
+    Dev<int32_t> i, j;
+    if (D.upload(X, (int64_t)nrows * ncols, kind == 0 ? 8 : 4)) return 1;
+    if (i.upload(ii, nnz)) return 1;
+    if (j.upload(jj, nnz)) return 1;
+    if (x.upload(xx, nnz, vb)) return 1;
+    return values_only(nnz, vb, values_out, [&](DevBuf &o) {
+        return mxd_coo_by_dense(nnz, i, j, x, D, nrows, ncols, kind, o, nullptr);
+    });
 }
 // multiply_coo_by_dense_numeric  src/operators.cpp:772-787
 int mx_multiply_coo_by_dense_numeric(const double *X_colmajor, int nrows, int ncols, const int32_t *ii,
@@ -902,21 +815,19 @@ int mx_matmul_colvec_by_scolvecascsr_begin(const void *colvec, int colvec_dtype,
     if (outer_entries_ok("mx_matmul_colvec_by_scolvecascsr_begin", indptr, nrows, dim)) return 1;
     const int64_t nnz = indptr[nrows];
     return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
-        DevBuf p, x, v, ws;
-        if (p.upload(indptr, sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
-        if (x.upload(values, sizeof(double) * (size_t)nnz)) return 1;
-        if (v.upload(colvec, dtype_bytes(colvec_dtype) * (size_t)dim)) return 1;
-        if (ws.alloc(mxd_csr_outer_dense_workspace_bytes(nrows))) return 1;
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
+        Dev<int32_t> p;
+        Dev<double> x;
+        DevBuf v, ws;
+        if (p.upload(indptr, (int64_t)nrows + 1)) return 1;
+        if (x.upload(values, nnz)) return 1;
+        if (v.upload(colvec, dim, dtype_bytes(colvec_dtype))) return 1;
+        if (ws.alloc_bytes(mxd_csr_outer_dense_workspace_bytes(nrows))) return 1;
+        if (res.alloc_indptr((int64_t)nrows + 1)) return 1;
         int64_t total = 0;
-        if (mxd_csr_outer_dense_count(nrows, dim, p.as<int32_t>(), ws.p, res.indptr.as<int32_t>(), &total, nullptr))
-            return 1;
-        res.set_sizes((int64_t)nrows + 1, total, total);
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
-        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+        if (mxd_csr_outer_dense_count(nrows, dim, p, ws, res.indptr, &total, nullptr)) return 1;
+        if (res.alloc_entries(total, sizeof(double))) return 1;
         if (total == 0) return 0;
-        return mxd_csr_outer_dense_fill(nrows, dim, nnz, p.as<int32_t>(), x.as<double>(), v.p, colvec_dtype,
-                                        res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.as<double>(),
+        return mxd_csr_outer_dense_fill(nrows, dim, nnz, p, x, v, colvec_dtype, res.indptr, res.indices, res.values,
                                         nullptr);
     });
 }
@@ -929,8 +840,8 @@ int mx_matmul_spcolvec_by_scolvecascsr_begin(const int32_t *X_indptr, int nrows,
     (void)X_indices;                                        // never read (matmul.cpp:811-833)
     MX_REQUIRE(res_out && info && X_indptr && nrows >= 0 && nnz_y >= 0 && nnz_y <= INT_MAX && y_length >= 0,
                "mx_matmul_spcolvec_by_scolvecascsr_begin: bad arguments");
-    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_I32 || value_dtype == MX_LGL || value_dtype == MX_NONE,
-               "mx_matmul_spcolvec_by_scolvecascsr_begin: unsupported value dtype %d", value_dtype);
+    if (admit_values("mx_matmul_spcolvec_by_scolvecascsr_begin", value_dtype, kNumeric | kInteger | kLogical | kPattern))
+        return 1;
     MX_REQUIRE(nnz_y == 0 || (y_indices_base1 && (value_dtype == MX_NONE || y_values)),
                "mx_matmul_spcolvec_by_scolvecascsr_begin: null pointer");
     MX_REQUIRE(X_indptr[0] >= 0 && X_indptr[nrows] >= 0, "mx_matmul_spcolvec_by_scolvecascsr_begin: bad index pointer");
@@ -938,23 +849,22 @@ int mx_matmul_spcolvec_by_scolvecascsr_begin(const int32_t *X_indptr, int nrows,
     if (outer_entries_ok("mx_matmul_spcolvec_by_scolvecascsr_begin", X_indptr, nrows, nnz_y)) return 1;
     const int64_t nnz = X_indptr[nrows];
     return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
-        DevBuf p, x, yi, yv, ws;
-        if (p.upload(X_indptr, sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
-        if (x.upload(X_values, sizeof(double) * (size_t)nnz)) return 1;
-        if (yi.upload(y_indices_base1, sizeof(int32_t) * (size_t)nnz_y)) return 1;
-        if (value_dtype != MX_NONE && yv.upload(y_values, dtype_bytes(value_dtype) * (size_t)nnz_y)) return 1;
-        if (ws.alloc(mxd_csr_outer_svec_workspace_bytes(nrows, y_length))) return 1;
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)y_length + 1))) return 1;
+        Dev<int32_t> p, yi;
+        Dev<double> x;
+        DevBuf yv, ws;                                    // yv stays null for an nsparseVector
+        if (p.upload(X_indptr, (int64_t)nrows + 1)) return 1;
+        if (x.upload(X_values, nnz)) return 1;
+        if (yi.upload(y_indices_base1, nnz_y)) return 1;
+        if (value_dtype != MX_NONE && yv.upload(y_values, nnz_y, dtype_bytes(value_dtype))) return 1;
+        if (ws.alloc_bytes(mxd_csr_outer_svec_workspace_bytes(nrows, y_length))) return 1;
+        if (res.alloc_indptr((int64_t)y_length + 1)) return 1;
         int64_t nonempty = 0, total = 0;
-        if (mxd_csr_outer_svec_count(nrows, nnz, p.as<int32_t>(), x.as<double>(), yi.as<int32_t>(), nnz_y, y_length,
-                                     ws.p, res.indptr.as<int32_t>(), &nonempty, &total, nullptr)) return 1;
-        res.set_sizes((int64_t)y_length + 1, total, total);
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
-        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+        if (mxd_csr_outer_svec_count(nrows, nnz, p, x, yi, nnz_y, y_length, ws, res.indptr, &nonempty, &total,
+                                     nullptr)) return 1;
+        if (res.alloc_entries(total, sizeof(double))) return 1;
         if (total == 0) return 0;
-        return mxd_csr_outer_svec_fill(nrows, yi.as<int32_t>(), nnz_y, value_dtype != MX_NONE ? yv.p : nullptr,
-                                       value_dtype, y_length, nonempty, ws.p, res.indptr.as<int32_t>(),
-                                       res.indices.as<int32_t>(), res.values.as<double>(), nullptr);
+        return mxd_csr_outer_svec_fill(nrows, yi, nnz_y, yv, value_dtype, y_length, nonempty, ws, res.indptr,
+                                       res.indices, res.values, nullptr);
     });
 }
 
@@ -969,12 +879,11 @@ int mx_matmul_rowvec_by_csc(const float *rowvec, int64_t len_rowvec, const int32
     for (int64_t k = 0; k < A.nnz; k++)
         MX_REQUIRE(indices[k] >= 0 && indices[k] < len_rowvec,
                    "mx_matmul_rowvec_by_csc: row index %d outside the vector's length", indices[k]);
-    DevBuf v, o;
-    if (v.upload(rowvec, sizeof(float) * (size_t)len_rowvec)) return 1;
-    if (o.alloc(sizeof(float) * (size_t)ncols)) return 1;
-    if (mxd_rowvec_by_csc(ncols, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), values ? A.x.as<double>() : nullptr,
-                          v.as<float>(), o.as<float>(), nullptr)) return 1;
-    return mx::xfer_d2h(out, o.p, sizeof(float) * (size_t)ncols);
+    Dev<float> v, o;
+    if (v.upload(rowvec, len_rowvec)) return 1;
+    if (o.alloc(ncols)) return 1;
+    if (mxd_rowvec_by_csc(ncols, A.nnz, A.p, A.j, A.x, v, o, nullptr)) return 1;      // A.x is null without values
+    return o.download(out, ncols);
 }
 
 // ---- CSR (op) dense vector (§8f rank 4) ----------------------------------------------------------------------
@@ -988,13 +897,11 @@ static int csr_by_dvec_export(const int32_t *indptr, const int32_t *indices, con
     if (A.upload(indptr, indices, values, nrows, eb)) return 1;
     if (A.nnz == 0) return 0;
     MX_REQUIRE(dvec_len > 0, "csr (op) vector: empty vector");
-    DevBuf D, o;
-    if (D.upload(dvec, eb * (size_t)dvec_len)) return 1;
-    if (o.alloc(eb * (size_t)A.nnz)) return 1;
-    if (mxd_csr_by_dvec(nrows, ncols, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p, D.p, dvec_len, op, lhs, o.p, nullptr))
-        return 1;
-    if (mx::xfer_d2h(values_out, o.p, eb * (size_t)A.nnz)) return 1;
-    return 0;
+    DevBuf D;
+    if (D.upload(dvec, dvec_len, eb)) return 1;
+    return values_only(A.nnz, eb, values_out, [&](DevBuf &o) {
+        return mxd_csr_by_dvec(nrows, ncols, A.nnz, A.p, A.j, A.x, D, dvec_len, op, lhs, o, nullptr);
+    });
 }
 
 int mx_multiply_csr_by_dvec_no_NAs_numeric(const int32_t *indptr, const int32_t *indices, const double *values,
@@ -1002,14 +909,8 @@ int mx_multiply_csr_by_dvec_no_NAs_numeric(const int32_t *indptr, const int32_t 
                                            int powerto, int divide, int divrest, int intdiv, int X_is_LHS,
                                            double *values_out)
 {
-    // same precedence as the reference's if/else chain (operators.cpp:1620-1632)
     int op;
-    if (multiply) op = MX_DV_MULTIPLY;
-    else if (powerto) op = MX_DV_POWERTO;
-    else if (divide) op = MX_DV_DIVIDE;
-    else if (divrest) op = MX_DV_DIVREST;
-    else if (intdiv) op = MX_DV_INTDIV;
-    else return set_error("Internal error. Please file an issue in GitHub.");        // throw_internal_err()
+    if (dvec_op_of(multiply, powerto, divide, divrest, intdiv, &op)) return 1;       // operators.cpp:1620-1632
     return csr_by_dvec_export(indptr, indices, values, nrows, dvec, dvec_len, ncols, op, X_is_LHS, values_out);
 }
 
@@ -1025,12 +926,7 @@ int mx_multiply_csr_by_dvec_with_NAs_begin(const int32_t *indptr, const int32_t 
     // :2275-2289
     if ((powerto || divide || divrest) && !X_is_LHS) return set_error("Internal error. Please file an issue in GitHub.");
     int op;
-    if (multiply) op = MX_DV_MULTIPLY;
-    else if (powerto) op = MX_DV_POWERTO;
-    else if (divide) op = MX_DV_DIVIDE;
-    else if (divrest) op = MX_DV_DIVREST;
-    else if (intdiv) op = MX_DV_INTDIV;
-    else return set_error("Internal error. Please file an issue in GitHub.");
+    if (dvec_op_of(multiply, powerto, divide, divrest, intdiv, &op)) return 1;
     MX_REQUIRE(indptr[0] == 0 && indptr[nrows] >= 0, "mx_multiply_csr_by_dvec_with_NAs_begin: bad index pointer");
     MX_REQUIRE(dvec_len >= 1, "mx_multiply_csr_by_dvec_with_NAs_begin: empty vector");   // R/operators.R:961-966
     const bool row_ruled = dvec_len <= nrows && nrows % dvec_len == 0;                    // :2314
@@ -1039,74 +935,62 @@ int mx_multiply_csr_by_dvec_with_NAs_begin(const int32_t *indptr, const int32_t 
     return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
         Csr A;
         if (A.upload(indptr, indices, values, nrows, sizeof(double))) return 1;
-        DevBuf D;
-        if (D.upload(dvec, sizeof(double) * (size_t)dvec_len)) return 1;
-        const int32_t *Ap = A.p.as<int32_t>(), *Aj = A.j.as<int32_t>();
-        const size_t pbytes = sizeof(int32_t) * ((size_t)nrows + 1);
+        Dev<double> D;
+        if (D.upload(dvec, dvec_len)) return 1;
         if (row_ruled) {
             DevBuf ws;
-            if (ws.alloc(mxd_csr_by_dvec_na_rows_workspace_bytes(nrows))) return 1;
-            if (res.indptr.alloc(pbytes)) return 1;
+            if (ws.alloc_bytes(mxd_csr_by_dvec_na_rows_workspace_bytes(nrows))) return 1;
+            if (res.alloc_indptr((int64_t)nrows + 1)) return 1;
             int64_t total = 0;
-            if (mxd_csr_by_dvec_na_rows_count(nrows, ncols, A.nnz, Ap, D.as<double>(), dvec_len, op, ws.p,
-                                              res.indptr.as<int32_t>(), &total, nullptr)) return 1;
-            res.set_sizes((int64_t)nrows + 1, total, total);
-            if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
-            if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
+            if (mxd_csr_by_dvec_na_rows_count(nrows, ncols, A.nnz, A.p, D, dvec_len, op, ws, res.indptr, &total,
+                                              nullptr)) return 1;
+            if (res.alloc_entries(total, sizeof(double))) return 1;
             if (total == 0) return 0;
-            return mxd_csr_by_dvec_na_rows_fill(nrows, ncols, A.nnz, Ap, Aj, A.x.as<double>(), D.as<double>(), dvec_len,
-                                                op, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
-                                                res.values.as<double>(), nullptr);
+            return mxd_csr_by_dvec_na_rows_fill(nrows, ncols, A.nnz, A.p, A.j, A.x, D, dvec_len, op, res.indptr,
+                                                res.indices, res.values, nullptr);
         }
         // the flat regime: the new cells first, as COO triplets
         int64_t nspecial = 0, candidates = 0, n_new = 0;
-        DevBuf nr, nc, nx;
+        Dev<int32_t> nr, nc;
+        Dev<double> nx;
         {
             DevBuf sws, cws;
-            if (sws.alloc(mxd_dvec_na_special_workspace_bytes(dvec_len))) return 1;
-            if (mxd_dvec_na_special(nrows, ncols, D.as<double>(), dvec_len, op, sws.p, &nspecial, &candidates, nullptr))
-                return 1;
+            if (sws.alloc_bytes(mxd_dvec_na_special_workspace_bytes(dvec_len))) return 1;
+            if (mxd_dvec_na_special(nrows, ncols, D, dvec_len, op, sws, &nspecial, &candidates, nullptr)) return 1;
             if (candidates > 0) {
-                if (cws.alloc(mxd_dvec_na_cells_workspace_bytes(candidates))) return 1;
-                if (mxd_dvec_na_cells_count(nrows, ncols, A.nnz, Ap, Aj, dvec_len, sws.p, nspecial, candidates, cws.p,
+                if (cws.alloc_bytes(mxd_dvec_na_cells_workspace_bytes(candidates))) return 1;
+                if (mxd_dvec_na_cells_count(nrows, ncols, A.nnz, A.p, A.j, dvec_len, sws, nspecial, candidates, cws,
                                             &n_new, nullptr)) return 1;
             }
             if (n_new > 0) {
-                if (nr.alloc(sizeof(int32_t) * (size_t)n_new) || nc.alloc(sizeof(int32_t) * (size_t)n_new) ||
-                    nx.alloc(sizeof(double) * (size_t)n_new)) return 1;
-                if (mxd_dvec_na_cells_fill(nrows, ncols, D.as<double>(), dvec_len, op, sws.p, nspecial, candidates, cws.p,
-                                           nr.as<int32_t>(), nc.as<int32_t>(), nx.as<double>(), nullptr)) return 1;
+                if (nr.alloc(n_new) || nc.alloc(n_new) || nx.alloc(n_new)) return 1;
+                if (mxd_dvec_na_cells_fill(nrows, ncols, D, dvec_len, op, sws, nspecial, candidates, cws, nr, nc, nx,
+                                           nullptr)) return 1;
             }
         }
         if (n_new == 0) {
             // :2643-2651: the input structure itself and the values-only product, with X on the side it was given
-            res.info.alias_structure = 1;
-            res.set_sizes((int64_t)nrows + 1, A.nnz, A.nnz);
-            if (res.values.alloc(sizeof(double) * (size_t)A.nnz)) return 1;
-            return mxd_csr_by_dvec(nrows, ncols, A.nnz, Ap, Aj, A.x.p, D.p, dvec_len, op, X_is_LHS, res.values.p, nullptr);
+            res.alias(1, (int64_t)nrows + 1, A.nnz);
+            if (res.alloc_values(A.nnz, sizeof(double))) return 1;
+            return mxd_csr_by_dvec(nrows, ncols, A.nnz, A.p, A.j, A.x, D, dvec_len, op, X_is_LHS, res.values, nullptr);
         }
-        DevBuf Bp, Bj, Bx, Ax;
+        Dev<int32_t> Bp, Bj;
+        Dev<double> Bx, Ax;
         {
             DevBuf ws;
-            if (ws.alloc(mxd_coo_to_csr_workspace_bytes(n_new, ncols))) return 1;
-            if (Bp.alloc(pbytes) || Bj.alloc(sizeof(int32_t) * (size_t)n_new) || Bx.alloc(sizeof(double) * (size_t)n_new))
-                return 1;
+            if (ws.alloc_bytes(mxd_coo_to_csr_workspace_bytes(n_new, ncols))) return 1;
+            if (Bp.alloc((int64_t)nrows + 1) || Bj.alloc(n_new) || Bx.alloc(n_new)) return 1;
             int64_t kept = 0;
-            if (mxd_coo_to_csr(nrows, ncols, nr.as<int32_t>(), nc.as<int32_t>(), nx.p, MX_F64, n_new, Bp.as<int32_t>(),
-                               Bj.as<int32_t>(), Bx.p, ws.p, &kept, nullptr)) return 1;
+            if (mxd_coo_to_csr(nrows, ncols, nr, nc, nx, MX_F64, n_new, Bp, Bj, Bx, ws, &kept, nullptr)) return 1;
             MX_REQUIRE(kept == n_new, "mx_multiply_csr_by_dvec_with_NAs_begin: repeated new cells");
         }
         // :2705-2743: the stored entries, always with X on the left
-        if (Ax.alloc(sizeof(double) * (size_t)A.nnz)) return 1;
-        if (mxd_csr_by_dvec(nrows, ncols, A.nnz, Ap, Aj, A.x.p, D.p, dvec_len, op, 1, Ax.p, nullptr)) return 1;
-        const int64_t total = A.nnz + n_new;
-        res.set_sizes((int64_t)nrows + 1, total, total);
-        if (res.indptr.alloc(pbytes)) return 1;
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)total)) return 1;
-        if (res.values.alloc(sizeof(double) * (size_t)total)) return 1;
-        return mxd_csr_join_disjoint(nrows, Ap, Aj, Ax.as<double>(), A.nnz, Bp.as<int32_t>(), Bj.as<int32_t>(),
-                                     Bx.as<double>(), n_new, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
-                                     res.values.as<double>(), nullptr);
+        if (Ax.alloc(A.nnz)) return 1;
+        if (mxd_csr_by_dvec(nrows, ncols, A.nnz, A.p, A.j, A.x, D, dvec_len, op, 1, Ax, nullptr)) return 1;
+        if (res.alloc_indptr((int64_t)nrows + 1)) return 1;
+        if (res.alloc_entries(A.nnz + n_new, sizeof(double))) return 1;
+        return mxd_csr_join_disjoint(nrows, A.p, A.j, Ax, A.nnz, Bp, Bj, Bx, n_new, res.indptr, res.indices,
+                                     res.values, nullptr);
     });
 }
 
@@ -1124,27 +1008,20 @@ int mx_cbind_csr_begin(const int32_t *Xp, int nX, const int32_t *Xj, const void 
 {
     MX_REQUIRE(res_out && info && nX >= 0 && nY >= 0, "mx_cbind_csr_begin: bad arguments");
     *res_out = nullptr;
-    const bool has_values = value_dtype != MX_NONE && (nvX > 0 || nvY > 0);           // cbind.cpp:19-20
-    const size_t vb = has_values ? dtype_bytes(value_dtype) : 0;
+    const Values vals(value_dtype, nvX > nvY ? nvX : nvY);            // either operand has values: cbind.cpp:19-20
     // binary: an empty NumericVector
     return begin_result(res_out, info, value_dtype == MX_NONE ? MX_F64 : value_dtype, [&](mx_result &res) {
         Csr X, Y;
-        if (X.upload(Xp, Xj, Xx, nX, vb)) return 1;
-        if (Y.upload(Yp, Yj, Yx, nY, vb)) return 1;
+        if (X.upload(Xp, Xj, Xx, nX, vals.bytes)) return 1;
+        if (Y.upload(Yp, Yj, Yx, nY, vals.bytes)) return 1;
         const int nrows = nX > nY ? nX : nY;
         const int64_t nnz = X.nnz + Y.nnz;
         MX_REQUIRE(nnz <= INT_MAX, "cbind result exceeds R's int32 index range");
-        res.set_sizes((int64_t)nrows + 1, nnz, has_values ? nnz : 0);
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
-        if (nnz == 0) {                                                               // cbind.cpp:22-29: zeros
-            MX_HIP(hipMemset(res.indptr.p, 0, sizeof(int32_t) * ((size_t)nrows + 1)));
-            return 0;
-        }
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz)) return 1;
-        if (has_values && res.values.alloc(vb * (size_t)nnz)) return 1;
-        return mxd_csr_cbind(nX, nY, X.p.as<int32_t>(), X.j.as<int32_t>(), X.x.p, Y.p.as<int32_t>(), Y.j.as<int32_t>(),
-                             Y.x.p, has_values ? value_dtype : MX_NONE, nnz, res.indptr.as<int32_t>(),
-                             res.indices.as<int32_t>(), res.values.p, nullptr);
+        if (res.alloc_indptr((int64_t)nrows + 1)) return 1;
+        if (nnz == 0) return res.indptr.zero((int64_t)nrows + 1);                      // cbind.cpp:22-29: zeros
+        if (res.alloc_entries(nnz, vals.bytes)) return 1;
+        return mxd_csr_cbind(nX, nY, X.p, X.j, X.x, Y.p, Y.j, Y.x, vals.dtype, nnz, res.indptr, res.indices,
+                             res.values, nullptr);
     });
 }
 
@@ -1162,24 +1039,22 @@ int mx_concat_csr_batch_begin(const mx_rbind_input *objs, int n_inputs, int out_
     MX_REQUIRE(nrows <= INT_MAX - 1 && nnz <= INT_MAX, "rbind result exceeds R's int32 index range");
     const size_t vb = out_kind == 0 ? 8 : out_kind == 1 ? 4 : 0;
     return begin_result(res_out, info, out_kind == 0 ? MX_F64 : out_kind == 1 ? MX_LGL : MX_NONE, [&](mx_result &res) {
-        res.set_sizes(nrows + 1, nnz, vb ? nnz : 0);
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz)) return 1;
-        if (vb && res.values.alloc(vb * (size_t)nnz)) return 1;
-        MX_HIP(hipMemset(res.indptr.p, 0, sizeof(int32_t)));
+        if (res.alloc_indptr(nrows + 1)) return 1;
+        if (res.alloc_entries(nnz, vb)) return 1;
+        if (res.indptr.zero(1)) return 1;
         int row = 0;
         int64_t pos = 0;
         for (int k = 0; k < n_inputs; k++) {
             const mx_rbind_input &o = objs[k];
             const bool vec = o.kind >= 3;
             const size_t ivb = (o.kind == 0 || o.kind == 3) ? 8 : (o.kind == 2 || o.kind == 6) ? 0 : 4;
-            DevBuf p, j, x;
-            if (!vec && p.upload(o.indptr, sizeof(int32_t) * ((size_t)o.nrows + 1))) return 1;
-            if (j.upload(o.indices, sizeof(int32_t) * (size_t)o.nnz)) return 1;
-            if (ivb && x.upload(o.values, ivb * (size_t)o.nnz)) return 1;
-            if (mxd_csr_rbind_append(o.kind, p.as<int32_t>(), j.as<int32_t>(), ivb ? x.p : nullptr, vec ? 1 : o.nrows,
-                                     o.nnz, out_kind, row, pos, res.indptr.as<int32_t>(), res.indices.as<int32_t>(),
-                                     res.values.p, nullptr)) return 1;
+            Dev<int32_t> p, j;                            // p stays null for a vector, x without values
+            DevBuf x;
+            if (!vec && p.upload(o.indptr, (int64_t)o.nrows + 1)) return 1;
+            if (j.upload(o.indices, o.nnz)) return 1;
+            if (ivb && x.upload(o.values, o.nnz, ivb)) return 1;
+            if (mxd_csr_rbind_append(o.kind, p, j, x, vec ? 1 : o.nrows, o.nnz, out_kind, row, pos, res.indptr,
+                                     res.indices, res.values, nullptr)) return 1;
             MX_HIP(hipStreamSynchronize(nullptr));
             row += vec ? 1 : o.nrows;
             pos += o.nnz;
@@ -1194,26 +1069,22 @@ int mx_csr_transpose_begin(const int32_t *indptr, int nrows, int ncols, const in
 {
     MX_REQUIRE(res_out && info && indptr, "mx_csr_transpose_begin: null pointer");
     MX_REQUIRE(nrows >= 0 && ncols >= 0, "mx_csr_transpose_begin: negative dimension");
-    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
-               "mx_csr_transpose_begin: unsupported value dtype %d", value_dtype);
+    if (admit_values("mx_csr_transpose_begin", value_dtype)) return 1;
     MX_REQUIRE(indptr[0] == 0 && indptr[nrows] >= 0, "mx_csr_transpose_begin: bad index pointer");
     *res_out = nullptr;
-    const bool has_values = value_dtype != MX_NONE && n_values > 0;
-    MX_REQUIRE(!has_values || n_values == indptr[nrows], "mx_csr_transpose_begin: lengths of indices and values differ");
-    const size_t vb = has_values ? dtype_bytes(value_dtype) : 0;
-    return begin_result(res_out, info, has_values ? value_dtype : MX_NONE, [&](mx_result &res) {
+    const Values vals(value_dtype, n_values);
+    MX_REQUIRE(!vals || n_values == indptr[nrows], "mx_csr_transpose_begin: lengths of indices and values differ");
+    return begin_result(res_out, info, vals.dtype, [&](mx_result &res) {
         Csr A;
-        if (A.upload(indptr, indices, values, nrows, vb)) return 1;
+        if (A.upload(indptr, indices, values, nrows, vals.bytes)) return 1;
         DevBuf ws;
-        if (ws.alloc(mxd_csr_transpose_workspace_bytes(A.nnz))) return 1;
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)ncols + 1))) return 1;
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)A.nnz)) return 1;
-        if (has_values && res.values.alloc(vb * (size_t)A.nnz)) return 1;
+        if (ws.alloc_bytes(mxd_csr_transpose_workspace_bytes(A.nnz))) return 1;
+        if (res.alloc_indptr((int64_t)ncols + 1)) return 1;
+        if (res.alloc_entries(A.nnz, vals.bytes)) return 1;
         int64_t nnz_out = 0;
-        if (mxd_csr_transpose(nrows, ncols, A.p.as<int32_t>(), A.j.as<int32_t>(), A.x.p,
-                              has_values ? value_dtype : MX_NONE, A.nnz, res.indptr.as<int32_t>(),
-                              res.indices.as<int32_t>(), res.values.p, ws.p, &nnz_out, nullptr)) return 1;
-        res.set_sizes((int64_t)ncols + 1, nnz_out, has_values ? nnz_out : 0);
+        if (mxd_csr_transpose(nrows, ncols, A.p, A.j, A.x, vals.dtype, A.nnz, res.indptr, res.indices, res.values, ws,
+                              &nnz_out, nullptr)) return 1;
+        res.set_sizes((int64_t)ncols + 1, nnz_out, vals ? nnz_out : 0);
         return 0;
     });
 }
@@ -1226,25 +1097,22 @@ int mx_coo_to_csr_begin(const int32_t *rows, const int32_t *cols, const void *va
     MX_REQUIRE(nrows >= 0 && ncols >= 0 && n_entries >= 0, "mx_coo_to_csr_begin: negative size");
     MX_REQUIRE(n_entries <= INT_MAX, "mx_coo_to_csr_begin: %lld entries exceed R's int32 index range",
                (long long)n_entries);
-    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
-               "mx_coo_to_csr_begin: unsupported value dtype %d", value_dtype);
+    if (admit_values("mx_coo_to_csr_begin", value_dtype)) return 1;
     *res_out = nullptr;
-    const bool has_values = value_dtype != MX_NONE;
-    const size_t vb = dtype_bytes(value_dtype);
+    const Values vals(value_dtype);
     return begin_result(res_out, info, value_dtype, [&](mx_result &res) {
-        DevBuf r, c, x, ws;
-        if (r.upload(rows, sizeof(int32_t) * (size_t)n_entries)) return 1;
-        if (c.upload(cols, sizeof(int32_t) * (size_t)n_entries)) return 1;
-        if (has_values && x.upload(values, vb * (size_t)n_entries)) return 1;
-        if (ws.alloc(mxd_coo_to_csr_workspace_bytes(n_entries, ncols))) return 1;
-        if (res.indptr.alloc(sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)n_entries)) return 1;
-        if (has_values && res.values.alloc(vb * (size_t)n_entries)) return 1;
+        Dev<int32_t> r, c;
+        DevBuf x, ws;
+        if (r.upload(rows, n_entries)) return 1;
+        if (c.upload(cols, n_entries)) return 1;
+        if (vals && x.upload(values, n_entries, vals.bytes)) return 1;
+        if (ws.alloc_bytes(mxd_coo_to_csr_workspace_bytes(n_entries, ncols))) return 1;
+        if (res.alloc_indptr((int64_t)nrows + 1)) return 1;
+        if (res.alloc_entries(n_entries, vals.bytes)) return 1;
         int64_t nnz_out = 0;
-        if (mxd_coo_to_csr(nrows, ncols, r.as<int32_t>(), c.as<int32_t>(), x.p, value_dtype, n_entries,
-                           res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.p, ws.p, &nnz_out,
-                           nullptr)) return 1;
-        res.set_sizes((int64_t)nrows + 1, nnz_out, has_values ? nnz_out : 0);
+        if (mxd_coo_to_csr(nrows, ncols, r, c, x, value_dtype, n_entries, res.indptr, res.indices, res.values, ws,
+                           &nnz_out, nullptr)) return 1;
+        res.set_sizes((int64_t)nrows + 1, nnz_out, vals ? nnz_out : 0);
         return 0;
     });
 }
@@ -1256,11 +1124,11 @@ int mx_csr_to_coo(const int32_t *indptr, int nrows, int32_t *out_rows)
     const int64_t nnz = indptr[nrows];
     if (nnz == 0) return 0;
     MX_REQUIRE(out_rows, "mx_csr_to_coo: null pointer");
-    DevBuf p, o;
-    if (p.upload(indptr, sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
-    if (o.alloc(sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (mxd_csr_to_coo(nrows, nnz, p.as<int32_t>(), o.as<int32_t>(), nullptr)) return 1;
-    return mx::xfer_d2h(out_rows, o.p, sizeof(int32_t) * (size_t)nnz);
+    Dev<int32_t> p, o;
+    if (p.upload(indptr, (int64_t)nrows + 1)) return 1;
+    if (o.alloc(nnz)) return 1;
+    if (mxd_csr_to_coo(nrows, nnz, p, o, nullptr)) return 1;
+    return o.download(out_rows, nnz);
 }
 
 int mx_multiply_csr_by_coo_begin(int logical, const int32_t *X_indptr, const int32_t *X_indices,
@@ -1277,22 +1145,20 @@ int mx_multiply_csr_by_coo_begin(int logical, const int32_t *X_indptr, const int
     return begin_result(res_out, info, logical ? MX_LGL : MX_F64, [&](mx_result &res) {
         Csr X;
         if (X.upload(X_indptr, X_indices, X_values, max_row_X, vb)) return 1;
-        DevBuf r, c, y, ws;
-        if (r.upload(Y_rows, sizeof(int32_t) * (size_t)nnz_Y)) return 1;
-        if (c.upload(Y_cols, sizeof(int32_t) * (size_t)nnz_Y)) return 1;
-        if (y.upload(Y_values, vb * (size_t)nnz_Y)) return 1;
-        if (ws.alloc(mxd_csr_by_coo_workspace_bytes(nnz_Y))) return 1;
+        Dev<int32_t> r, c;
+        DevBuf y, ws;
+        if (r.upload(Y_rows, nnz_Y)) return 1;
+        if (c.upload(Y_cols, nnz_Y)) return 1;
+        if (y.upload(Y_values, nnz_Y, vb)) return 1;
+        if (ws.alloc_bytes(mxd_csr_by_coo_workspace_bytes(nnz_Y))) return 1;
         int64_t nnz_out = 0;
-        if (mxd_csr_by_coo_count(logical, max_row_X, max_col_X, X.p.as<int32_t>(), X.j.as<int32_t>(), X.x.p,
-                                 r.as<int32_t>(), c.as<int32_t>(), y.p, nnz_Y, ws.p, &nnz_out, nullptr)) return 1;
-        res.set_sizes(nnz_out, nnz_out, nnz_out);                  // row ids travel in the indptr vector
-        if (res.indptr.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
-        if (res.values.alloc(vb * (size_t)nnz_out)) return 1;
+        if (mxd_csr_by_coo_count(logical, max_row_X, max_col_X, X.p, X.j, X.x, r, c, y, nnz_Y, ws, &nnz_out, nullptr))
+            return 1;
+        if (res.alloc_indptr(nnz_out)) return 1;                    // row ids travel in the indptr vector
+        if (res.alloc_entries(nnz_out, vb)) return 1;
         if (nnz_out == 0) return 0;
-        return mxd_csr_by_coo_fill(logical, max_row_X, max_col_X, X.p.as<int32_t>(), X.j.as<int32_t>(), X.x.p,
-                                   r.as<int32_t>(), c.as<int32_t>(), y.p, nnz_Y, ws.p, res.indptr.as<int32_t>(),
-                                   res.indices.as<int32_t>(), res.values.p, nullptr);
+        return mxd_csr_by_coo_fill(logical, max_row_X, max_col_X, X.p, X.j, X.x, r, c, y, nnz_Y, ws, res.indptr,
+                                   res.indices, res.values, nullptr);
     });
 }
 
@@ -1303,15 +1169,15 @@ static int coo_by_dvec_export(const int32_t *ii, const int32_t *jj, const void *
     if (nnz == 0) return 0;
     MX_REQUIRE(dvec_len > 0, "coo (op) vector: empty vector");
     const size_t eb = op == MX_DV_LOGICAL_AND ? 4 : 8;
-    DevBuf i, j, x, D, o;
-    if (i.upload(ii, sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (j.upload(jj, sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (x.upload(xx, eb * (size_t)nnz)) return 1;
-    if (D.upload(dvec, eb * (size_t)dvec_len)) return 1;
-    if (o.alloc(eb * (size_t)nnz)) return 1;
-    if (mxd_coo_by_dvec(nrows, ncols, nnz, i.as<int32_t>(), j.as<int32_t>(), x.p, D.p, dvec_len, op, lhs, o.p, nullptr))
-        return 1;
-    return mx::xfer_d2h(values_out, o.p, eb * (size_t)nnz);
+    Dev<int32_t> i, j;
+    DevBuf x, D;
+    if (i.upload(ii, nnz)) return 1;
+    if (j.upload(jj, nnz)) return 1;
+    if (x.upload(xx, nnz, eb)) return 1;
+    if (D.upload(dvec, dvec_len, eb)) return 1;
+    return values_only(nnz, eb, values_out, [&](DevBuf &o) {
+        return mxd_coo_by_dvec(nrows, ncols, nnz, i, j, x, D, dvec_len, op, lhs, o, nullptr);
+    });
 }
 
 int mx_multiply_coo_by_dense_ignore_NAs_numeric(const int32_t *ii, const int32_t *jj, const double *xx, int64_t nnz,
@@ -1319,14 +1185,8 @@ int mx_multiply_coo_by_dense_ignore_NAs_numeric(const int32_t *ii, const int32_t
                                                 int multiply, int powerto, int divide, int divrest, int intdiv,
                                                 int X_is_LHS, double *values_out)
 {
-    // same precedence as the reference's if/else chain (operators.cpp:2872-2883)
     int op;
-    if (multiply) op = MX_DV_MULTIPLY;
-    else if (powerto) op = MX_DV_POWERTO;
-    else if (divide) op = MX_DV_DIVIDE;
-    else if (divrest) op = MX_DV_DIVREST;
-    else if (intdiv) op = MX_DV_INTDIV;
-    else return set_error("Internal error. Please file an issue in GitHub.");        // throw_internal_err()
+    if (dvec_op_of(multiply, powerto, divide, divrest, intdiv, &op)) return 1;       // operators.cpp:2872-2883
     return coo_by_dvec_export(ii, jj, xx, nnz, dvec, dvec_len, nrows, ncols, op, X_is_LHS, values_out);
 }
 
@@ -1342,7 +1202,7 @@ int mx_multiply_coo_by_dense_ignore_NAs_logical(const int32_t *ii, const int32_t
 // (process_i_arbitrary, src/slice_coo.cpp:73-114, and post_process_seq, :120-150); anything else becomes the dense
 // map of the 1-based selector (the reference's robin_map + i_indices_rep), in mxd_colmap_build's layout.
 static int coo_axis_setup(const int32_t *take_base1, int64_t n_take, int all, int is_seq, int is_rev_seq, int n,
-                          const char *what, mx_coo_axis *ax, DevBuf &start, DevBuf &pos)
+                          const char *what, mx_coo_axis *ax, Dev<int32_t> &start, Dev<int32_t> &pos)
 {
     *ax = mx_coo_axis{MX_AXIS_AFFINE, 0, n - 1, 0, 0, nullptr, nullptr};
     if (all) return 0;
@@ -1366,18 +1226,17 @@ static int coo_axis_setup(const int32_t *take_base1, int64_t n_take, int all, in
     // mxd_colmap_build's layout, made here by a stable counting sort while the selector is checked anyway: its
     // device build orders repeated positions by an insertion sort in one lane per index, which is quadratic in the
     // repeats of one index (minutes for 50 000 repeats)
-    std::unique_ptr<int32_t[]> h_start(new (std::nothrow) int32_t[(size_t)nmap + 1]);
+    std::unique_ptr<int32_t[]> h_start(new (std::nothrow) int32_t[(size_t)nmap + 1]());      // zeros
     std::unique_ptr<int32_t[]> h_pos(new (std::nothrow) int32_t[(size_t)n_take]);
     MX_REQUIRE(h_start && h_pos, "out of host memory");
-    memset(h_start.get(), 0, sizeof(int32_t) * ((size_t)nmap + 1));
     for (int64_t t = 0; t < n_take; t++) h_start[take_base1[t] + 1]++;  // key v counted at v + 1 <= nmap
     for (int v = 1; v <= nmap; v++) h_start[v] += h_start[v - 1];            // start[v] = entries with key < v
     for (int64_t t = 0; t < n_take; t++) h_pos[h_start[take_base1[t]]++] = (int32_t)t;
     for (int v = nmap; v > 0; v--) h_start[v] = h_start[v - 1];             // undo the cursor shift
     h_start[0] = 0;
-    if (start.upload(h_start.get(), sizeof(int32_t) * ((size_t)nmap + 1))) return 1;
-    if (pos.upload(h_pos.get(), sizeof(int32_t) * (size_t)n_take)) return 1;
-    *ax = mx_coo_axis{MX_AXIS_MAP, 0, 0, 0, nmap, start.as<int32_t>(), pos.as<int32_t>()};
+    if (start.upload(h_start.get(), (int64_t)nmap + 1)) return 1;
+    if (pos.upload(h_pos.get(), n_take)) return 1;
+    *ax = mx_coo_axis{MX_AXIS_MAP, 0, 0, 0, nmap, start, pos};
     return 0;
 }
 
@@ -1392,37 +1251,33 @@ int mx_slice_coo_arbitrary_begin(const int32_t *ii, const int32_t *jj, const voi
                "mx_slice_coo_arbitrary_begin: negative size");
     MX_REQUIRE(nnz <= INT_MAX, "mx_slice_coo_arbitrary_begin: %lld entries exceed R's int32 index range",
                (long long)nnz);
-    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
-               "mx_slice_coo_arbitrary_begin: unsupported value dtype %d", value_dtype);
+    if (admit_values("mx_slice_coo_arbitrary_begin", value_dtype)) return 1;
     MX_REQUIRE((nnz == 0 || (ii && jj && (value_dtype == MX_NONE || xx))) && (n_rows_take == 0 || rows_take_base1) &&
                (n_cols_take == 0 || cols_take_base1), "mx_slice_coo_arbitrary_begin: null pointer");
     *res_out = nullptr;
-    const bool has_values = value_dtype != MX_NONE;
-    const size_t vb = dtype_bytes(value_dtype);
+    const Values vals(value_dtype);
     return begin_result(res_out, info, value_dtype, [&](mx_result &res) {
         // the reference reads rows_take_base1[0] unguarded; the R caller never passes an empty selector (:108-125)
-        if (nnz == 0 || n_rows_take == 0 || n_cols_take == 0) { res.set_sizes(0, 0, 0); return 0; }
-        DevBuf sti, psi, stj, psj;
+        if (nnz == 0 || n_rows_take == 0 || n_cols_take == 0) return 0;       // three empty vectors
+        Dev<int32_t> sti, psi, stj, psj;
         mx_coo_axis ai, aj;
         if (coo_axis_setup(rows_take_base1, n_rows_take, all_i, i_is_seq, i_is_rev_seq, nrows, "row", &ai, sti, psi))
             return 1;
         if (coo_axis_setup(cols_take_base1, n_cols_take, all_j, j_is_seq, j_is_rev_seq, ncols, "column", &aj, stj,
                            psj)) return 1;
-        DevBuf r, c, x, ws;
-        if (r.upload(ii, sizeof(int32_t) * (size_t)nnz)) return 1;
-        if (c.upload(jj, sizeof(int32_t) * (size_t)nnz)) return 1;
-        if (has_values && x.upload(xx, vb * (size_t)nnz)) return 1;
-        if (ws.alloc(mxd_coo_slice_workspace_bytes(nnz))) return 1;
+        Dev<int32_t> r, c;
+        DevBuf x, ws;
+        if (r.upload(ii, nnz)) return 1;
+        if (c.upload(jj, nnz)) return 1;
+        if (vals && x.upload(xx, nnz, vals.bytes)) return 1;
+        if (ws.alloc_bytes(mxd_coo_slice_workspace_bytes(nnz))) return 1;
         int64_t nnz_out = 0;
-        if (mxd_coo_slice_count(nrows, ncols, r.as<int32_t>(), c.as<int32_t>(), nnz, &ai, &aj, ws.p, &nnz_out,
-                                nullptr)) return 1;
-        res.set_sizes(nnz_out, nnz_out, has_values ? nnz_out : 0);     // row ids travel in the indptr vector
-        if (res.indptr.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)nnz_out)) return 1;
-        if (has_values && res.values.alloc(vb * (size_t)nnz_out)) return 1;
+        if (mxd_coo_slice_count(nrows, ncols, r, c, nnz, &ai, &aj, ws, &nnz_out, nullptr)) return 1;
+        if (res.alloc_indptr(nnz_out)) return 1;                      // row ids travel in the indptr vector
+        if (res.alloc_entries(nnz_out, vals.bytes)) return 1;
         if (nnz_out == 0) return 0;
-        return mxd_coo_slice_fill(nrows, ncols, r.as<int32_t>(), c.as<int32_t>(), x.p, value_dtype, nnz, &ai, &aj,
-                                  ws.p, res.indptr.as<int32_t>(), res.indices.as<int32_t>(), res.values.p, nullptr);
+        return mxd_coo_slice_fill(nrows, ncols, r, c, x, value_dtype, nnz, &ai, &aj, ws, res.indptr, res.indices,
+                                  res.values, nullptr);
     });
 }
 
@@ -1430,19 +1285,18 @@ int mx_slice_coo_single(const int32_t *ii, const int32_t *jj, const void *xx, in
                         int j, int *found, void *value_out)
 {
     MX_REQUIRE(found && nnz >= 0, "mx_slice_coo_single: bad arguments");
-    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
-               "mx_slice_coo_single: unsupported value dtype %d", value_dtype);
+    if (admit_values("mx_slice_coo_single", value_dtype)) return 1;
     *found = 0;
     if (nnz == 0) return 0;
     MX_REQUIRE(ii && jj && (value_dtype == MX_NONE || xx), "mx_slice_coo_single: null pointer");
-    DevBuf r, c, x, ws;
-    if (r.upload(ii, sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (c.upload(jj, sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (value_dtype != MX_NONE && x.upload(xx, dtype_bytes(value_dtype) * (size_t)nnz)) return 1;
-    if (ws.alloc(mxd_coo_single_workspace_bytes())) return 1;
+    Dev<int32_t> r, c;
+    DevBuf x, ws;
+    if (r.upload(ii, nnz)) return 1;
+    if (c.upload(jj, nnz)) return 1;
+    if (value_dtype != MX_NONE && x.upload(xx, nnz, dtype_bytes(value_dtype))) return 1;
+    if (ws.alloc_bytes(mxd_coo_single_workspace_bytes())) return 1;
     int64_t k = -1;
-    if (mxd_coo_single(r.as<int32_t>(), c.as<int32_t>(), x.p, value_dtype, nnz, i, j, ws.p, &k, value_out, nullptr))
-        return 1;
+    if (mxd_coo_single(r, c, x, value_dtype, nnz, i, j, ws, &k, value_out, nullptr)) return 1;
     *found = k >= 0;
     return 0;
 }
@@ -1457,8 +1311,7 @@ static int compact_begin(int layout, const int32_t *indptr, int nrows, const int
 {
     MX_REQUIRE(res_out && info, "compaction: null output pointer");
     MX_REQUIRE(layout >= 0 && layout <= 2 && nrows >= 0 && nrows < INT_MAX, "compaction: bad arguments");
-    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_I32,
-               "compaction: unsupported value dtype %d", value_dtype);
+    if (admit_values("compaction", value_dtype, kNumeric | kLogical | kInteger)) return 1;
     if (layout == 0) {
         MX_REQUIRE(indptr && indptr[0] == 0 && indptr[nrows] >= 0, "compaction: bad index pointer");
         nnz = indptr[nrows];
@@ -1469,31 +1322,27 @@ static int compact_begin(int layout, const int32_t *indptr, int nrows, const int
     *res_out = nullptr;
     const size_t vb = dtype_bytes(value_dtype);
     return begin_result(res_out, info, value_dtype, [&](mx_result &res) {
-        DevBuf x, mk, ws;
-        if (x.upload(values, vb * (size_t)nnz)) return 1;
-        if (rule == MX_KEEP_MASK && mk.upload(mask, sizeof(int32_t) * (size_t)nnz)) return 1;
-        if (ws.alloc(mxd_compact_workspace_bytes(nnz))) return 1;
+        DevBuf x, ws;
+        Dev<int32_t> mk;                                  // stays null without a mask
+        if (x.upload(values, nnz, vb)) return 1;
+        if (rule == MX_KEEP_MASK && mk.upload(mask, nnz)) return 1;
+        if (ws.alloc_bytes(mxd_compact_workspace_bytes(nnz))) return 1;
         int64_t kept = 0;
-        if (mxd_compact_count(nnz, x.p, value_dtype, rule, mk.as<int32_t>(), ws.p, &kept, nullptr)) return 1;
+        if (mxd_compact_count(nnz, x, value_dtype, rule, mk, ws, &kept, nullptr)) return 1;
         if (kept == nnz && rule != MX_KEEP_MASK) {                  // misc.cpp:586-590, :735-739, :864-867
-            res.info.alias_structure = MX_ALIAS_ALL;
-            res.set_sizes(layout == 0 ? (int64_t)nrows + 1 : layout == 1 ? nnz : 0, nnz, nnz);
+            res.alias(MX_ALIAS_ALL, layout == 0 ? (int64_t)nrows + 1 : layout == 1 ? nnz : 0, nnz);
             return 0;
         }
-        DevBuf p, i0, i1;
-        if (layout == 0 && p.upload(indptr, sizeof(int32_t) * ((size_t)nrows + 1))) return 1;
-        if (i0.upload(idx0, sizeof(int32_t) * (size_t)nnz)) return 1;
-        if (layout == 1 && i1.upload(idx1, sizeof(int32_t) * (size_t)nnz)) return 1;
-        res.set_sizes(layout == 0 ? (int64_t)nrows + 1 : layout == 1 ? kept : 0, kept, kept);
-        if (layout != 2 && res.indptr.alloc(sizeof(int32_t) * (size_t)res.info.indptr_len)) return 1;
-        if (res.indices.alloc(sizeof(int32_t) * (size_t)kept)) return 1;
-        if (res.values.alloc(vb * (size_t)kept)) return 1;
-        int32_t *o0 = layout == 1 ? res.indptr.as<int32_t>() : res.indices.as<int32_t>();
-        int32_t *o1 = layout == 1 ? res.indices.as<int32_t>() : nullptr;
-        return mxd_compact_fill(nnz, x.p, value_dtype, rule, mk.as<int32_t>(), i0.as<int32_t>(),
-                                layout == 1 ? i1.as<int32_t>() : nullptr, layout == 0 ? nrows : 0,
-                                layout == 0 ? p.as<int32_t>() : nullptr, ws.p, o0, o1, res.values.p,
-                                layout == 0 ? res.indptr.as<int32_t>() : nullptr, nullptr);
+        Dev<int32_t> p, i0, i1;                           // p: layout 0 only, i1: layout 1 only, else null
+        if (layout == 0 && p.upload(indptr, (int64_t)nrows + 1)) return 1;
+        if (i0.upload(idx0, nnz)) return 1;
+        if (layout == 1 && i1.upload(idx1, nnz)) return 1;
+        if (layout != 2 && res.alloc_indptr(layout == 0 ? (int64_t)nrows + 1 : kept)) return 1;
+        if (res.alloc_entries(kept, vb)) return 1;
+        int32_t *const rp = res.indptr, *const rj = res.indices;
+        return mxd_compact_fill(nnz, x, value_dtype, rule, mk, i0, i1, layout == 0 ? nrows : 0, p, ws,
+                                layout == 1 ? rp : rj, layout == 1 ? rj : nullptr, res.values,
+                                layout == 0 ? rp : nullptr, nullptr);
     });
 }
 
@@ -1564,17 +1413,18 @@ int mx_rebuild_indptr_after_filter(const int32_t *indptr, int64_t indptr_len, co
     MX_REQUIRE(indptr[0] == 0 && indptr[m] >= 0, "rebuild_indptr_after_filter: bad index pointer");
     const int64_t nnz = indptr[m];
     MX_REQUIRE(nnz == 0 || filter, "rebuild_indptr_after_filter: null pointer");
-    DevBuf p, f, ws, o;
-    if (p.upload(indptr, sizeof(int32_t) * (size_t)indptr_len)) return 1;
-    if (f.upload(filter, sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (ws.alloc(mxd_compact_workspace_bytes(nnz))) return 1;
-    if (o.alloc(sizeof(int32_t) * (size_t)indptr_len)) return 1;
+    Dev<int32_t> p, f, o;
+    DevBuf ws;
+    if (p.upload(indptr, indptr_len)) return 1;
+    if (f.upload(filter, nnz)) return 1;
+    if (ws.alloc_bytes(mxd_compact_workspace_bytes(nnz))) return 1;
+    if (o.alloc(indptr_len)) return 1;
     int64_t kept = 0;
-    if (mxd_compact_count(nnz, nullptr, MX_NONE, MX_KEEP_MASK, f.as<int32_t>(), ws.p, &kept, nullptr)) return 1;
-    if (mxd_compact_fill(nnz, nullptr, MX_NONE, MX_KEEP_MASK, f.as<int32_t>(), nullptr, nullptr, m, p.as<int32_t>(),
-                         ws.p, nullptr, nullptr, nullptr, o.as<int32_t>(), nullptr)) return 1;
+    if (mxd_compact_count(nnz, nullptr, MX_NONE, MX_KEEP_MASK, f, ws, &kept, nullptr)) return 1;
+    if (mxd_compact_fill(nnz, nullptr, MX_NONE, MX_KEEP_MASK, f, nullptr, nullptr, m, p, ws, nullptr, nullptr, nullptr,
+                         o, nullptr)) return 1;
     MX_HIP(hipStreamSynchronize(nullptr));
-    return mx::xfer_d2h(out_indptr, o.p, sizeof(int32_t) * (size_t)indptr_len);
+    return o.download(out_indptr, indptr_len);
 }
 
 // check_valid_*: the first failing check in the reference's order, with its message (misc.cpp:978-1013)
@@ -1591,12 +1441,11 @@ static const char *first_failure(int f)
 static int validate_host(const int32_t *idx, int64_t n, int bound, const int32_t *indptr, int64_t n_ptr,
                          int64_t n_mono, int *flags)
 {
-    DevBuf d, p, ws;
-    if (d.upload(idx, sizeof(int32_t) * (size_t)n)) return 1;
-    if (p.upload(indptr, sizeof(int32_t) * (size_t)n_ptr)) return 1;
-    if (ws.alloc(16)) return 1;
-    return mxd_validate_indices(d.as<int32_t>(), n, bound, p.as<int32_t>(), n_ptr, n_mono, ws.as<int32_t>(), flags,
-                                nullptr);
+    Dev<int32_t> d, p, ws;
+    if (d.upload(idx, n)) return 1;
+    if (p.upload(indptr, n_ptr)) return 1;
+    if (ws.alloc(4)) return 1;
+    return mxd_validate_indices(d, n, bound, p, n_ptr, n_mono, ws, flags, nullptr);
 }
 
 int mx_check_valid_csr_matrix(const int32_t *indptr, int64_t indptr_len, const int32_t *indices, int64_t nnz,
@@ -1642,16 +1491,14 @@ int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, 
     const std::unique_ptr<mx_result> owned(res);
     const mx_result_info &inf = res->info;
     if (!inf.alias_structure) {
-        if (inf.indptr_len > 0 && out_indptr &&
-            mx::xfer_d2h(out_indptr, res->indptr.p, sizeof(int32_t) * (size_t)inf.indptr_len) != 0)
+        if (inf.indptr_len > 0 && out_indptr && res->indptr.download(out_indptr, inf.indptr_len) != 0)
             return set_error("D2H copy of indptr failed");
-        if (inf.nnz > 0 && out_indices &&
-            mx::xfer_d2h(out_indices, res->indices.p, sizeof(int32_t) * (size_t)inf.nnz) != 0)
+        if (inf.nnz > 0 && out_indices && res->indices.download(out_indices, inf.nnz) != 0)
             return set_error("D2H copy of indices failed");
     }
     const size_t vb = dtype_bytes(inf.values_dtype);
     if (vb && inf.values_len > 0 && out_values && res->values.p &&
-        mx::xfer_d2h(out_values, res->values.p, vb * (size_t)inf.values_len) != 0)
+        res->values.download(out_values, inf.values_len, vb) != 0)
         return set_error("D2H copy of values failed");
     return 0;
 }
@@ -1666,10 +1513,10 @@ static int check_seq_host(const int32_t *indices, int64_t n, int reversed, int *
     // slice.cpp:28,40: end-point test first — avoids the transfer for the common negative
     const int64_t span = reversed ? (int64_t)indices[0] - indices[n - 1] : (int64_t)indices[n - 1] - indices[0];
     if (span != n - 1) { *result = 0; return 0; }
-    DevBuf d, flag;
-    if (d.upload(indices, sizeof(int32_t) * (size_t)n)) return 1;
-    if (flag.alloc(16)) return 1;
-    return mxd_check_is_seq(d.as<int32_t>(), n, reversed, flag.as<int32_t>(), result, nullptr);
+    Dev<int32_t> d, flag;
+    if (d.upload(indices, n)) return 1;
+    if (flag.alloc(4)) return 1;
+    return mxd_check_is_seq(d, n, reversed, flag, result, nullptr);
 }
 int mx_check_is_seq(const int32_t *indices, int64_t n, int *result) { return check_seq_host(indices, n, 0, result); }
 int mx_check_is_rev_seq(const int32_t *indices, int64_t n, int *result) { return check_seq_host(indices, n, 1, result); }
@@ -1681,9 +1528,9 @@ int mx_check_indices_are_sorted(const int32_t *indptr, const int32_t *indices, i
     if (nrows <= 0) { *result = 1; return 0; }
     Csr A;
     if (A.upload(indptr, indices, nullptr, nrows, 0)) return 1;
-    DevBuf flag;
-    if (flag.alloc(16)) return 1;
-    return mxd_csr_rows_sorted(nrows, A.p.as<int32_t>(), A.j.as<int32_t>(), flag.as<int32_t>(), result, nullptr);
+    Dev<int32_t> flag;
+    if (flag.alloc(4)) return 1;
+    return mxd_csr_rows_sorted(nrows, A.p, A.j, flag, result, nullptr);
 }
 
 int mx_sort_sparse_indices(const int32_t *indptr, int32_t *indices, void *values, int value_dtype, int nrows)
@@ -1693,17 +1540,17 @@ int mx_sort_sparse_indices(const int32_t *indptr, int32_t *indices, void *values
     Csr A;
     if (A.upload(indptr, indices, values, nrows, vb)) return 1;
     if (A.nnz < 2) return 0;
-    DevBuf flag, tj, tx;
-    if (flag.alloc(16)) return 1;
+    Dev<int32_t> flag, tj;
+    DevBuf tx;
+    if (flag.alloc(4)) return 1;
     int sorted = 0;
-    if (mxd_csr_rows_sorted(nrows, A.p.as<int32_t>(), A.j.as<int32_t>(), flag.as<int32_t>(), &sorted, nullptr)) return 1;
+    if (mxd_csr_rows_sorted(nrows, A.p, A.j, flag, &sorted, nullptr)) return 1;
     if (sorted) return 0;                      // nothing to do, inputs untouched
-    if (tj.alloc(sizeof(int32_t) * (size_t)A.nnz)) return 1;
-    if (vb && tx.alloc(vb * (size_t)A.nnz)) return 1;
-    if (mxd_csr_sort_rows(nrows, A.nnz, A.p.as<int32_t>(), A.j.as<int32_t>(), vb ? A.x.p : nullptr,
-                          vb ? value_dtype : MX_NONE, tj.as<int32_t>(), tx.p, nullptr)) return 1;
-    if (mx::xfer_d2h(indices, A.j.p, sizeof(int32_t) * (size_t)A.nnz)) return 1;
-    if (vb && mx::xfer_d2h(values, A.x.p, vb * (size_t)A.nnz)) return 1;
+    if (tj.alloc(A.nnz)) return 1;
+    if (vb && tx.alloc(A.nnz, vb)) return 1;
+    if (mxd_csr_sort_rows(nrows, A.nnz, A.p, A.j, A.x, vb ? value_dtype : MX_NONE, tj, tx, nullptr)) return 1;
+    if (A.j.download(indices, A.nnz)) return 1;
+    if (vb && A.x.download(values, A.nnz, vb)) return 1;
     return 0;
 }
 
@@ -1714,16 +1561,16 @@ int mx_sort_vector_indices(int32_t *ii, void *xx, int64_t n, int value_dtype)
     if (n < 2) return 0;
     const size_t vb = value_dtype == MX_NONE ? 0 : dtype_bytes(value_dtype);
     MX_REQUIRE(ii && (vb || value_dtype == MX_NONE) && (!vb || xx), "mx_sort_vector_indices: bad arguments");
-    DevBuf di, dx, ws;
-    if (di.upload(ii, sizeof(int32_t) * (size_t)n)) return 1;
-    if (vb && dx.upload(xx, vb * (size_t)n)) return 1;
-    if (ws.alloc(mxd_sort_vector_indices_workspace_bytes(n))) return 1;
+    Dev<int32_t> di;
+    DevBuf dx, ws;                             // dx stays null without values
+    if (di.upload(ii, n)) return 1;
+    if (vb && dx.upload(xx, n, vb)) return 1;
+    if (ws.alloc_bytes(mxd_sort_vector_indices_workspace_bytes(n))) return 1;
     int was_sorted = 1;
-    if (mxd_sort_vector_indices(di.as<int32_t>(), vb ? dx.p : nullptr, n, value_dtype, ws.p, &was_sorted, nullptr))
-        return 1;
+    if (mxd_sort_vector_indices(di, dx, n, value_dtype, ws, &was_sorted, nullptr)) return 1;
     if (was_sorted) return 0;                  // nothing to do, inputs untouched
-    if (mx::xfer_d2h(ii, di.p, sizeof(int32_t) * (size_t)n)) return 1;
-    if (vb && mx::xfer_d2h(xx, dx.p, vb * (size_t)n)) return 1;
+    if (di.download(ii, n)) return 1;
+    if (vb && dx.download(xx, n, vb)) return 1;
     return 0;
 }
 
@@ -1732,25 +1579,23 @@ int mx_sort_coo_indices(int32_t *ii, int32_t *jj, void *xx, int64_t nnz, int val
 {
     MX_REQUIRE(nnz >= 0, "mx_sort_coo_indices: negative size");
     MX_REQUIRE(nnz <= INT_MAX, "mx_sort_coo_indices: %lld entries exceed R's int32 index range", (long long)nnz);
-    MX_REQUIRE(value_dtype == MX_F64 || value_dtype == MX_LGL || value_dtype == MX_NONE,
-               "mx_sort_coo_indices: unsupported value dtype %d", value_dtype);
+    if (admit_values("mx_sort_coo_indices", value_dtype)) return 1;
     if (nnz == 0) return 0;
     const size_t vb = value_dtype == MX_NONE ? 0 : dtype_bytes(value_dtype);
     MX_REQUIRE(ii && jj && (!vb || xx), "mx_sort_coo_indices: bad arguments");
-    DevBuf di, dj, dx, ws;
-    if (di.upload(ii, sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (dj.upload(jj, sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (vb && dx.upload(xx, vb * (size_t)nnz)) return 1;
-    if (ws.alloc(mxd_coo_sort_workspace_bytes(nnz))) return 1;
+    Dev<int32_t> di, dj;
+    DevBuf dx, ws;                             // dx stays null without values
+    if (di.upload(ii, nnz)) return 1;
+    if (dj.upload(jj, nnz)) return 1;
+    if (vb && dx.upload(xx, nnz, vb)) return 1;
+    if (ws.alloc_bytes(mxd_coo_sort_workspace_bytes(nnz))) return 1;
     int was_sorted = 1;
-    if (mxd_coo_sort(di.as<int32_t>(), dj.as<int32_t>(), vb ? dx.p : nullptr, nnz, value_dtype, ws.p, &was_sorted,
-                     nullptr))
-        return 1;
+    if (mxd_coo_sort(di, dj, dx, nnz, value_dtype, ws, &was_sorted, nullptr)) return 1;
     if (was_sorted) return 0;                  // nothing to do, inputs untouched
     MX_HIP(hipStreamSynchronize(nullptr));     // a failed sort shows here, before any of the caller's arrays is written
-    if (mx::xfer_d2h(ii, di.p, sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (mx::xfer_d2h(jj, dj.p, sizeof(int32_t) * (size_t)nnz)) return 1;
-    if (vb && mx::xfer_d2h(xx, dx.p, vb * (size_t)nnz)) return 1;
+    if (di.download(ii, nnz)) return 1;
+    if (dj.download(jj, nnz)) return 1;
+    if (vb && dx.download(xx, nnz, vb)) return 1;
     return 0;
 }
 
