@@ -559,6 +559,37 @@ size_t mxd_coo_single_workspace_bytes(void);
 int mxd_coo_single(const int32_t *rows, const int32_t *cols, const void *values, int value_dtype, int64_t nnz,
                    int r, int c, void *workspace, int64_t *k_host, void *value_host, void *stream);
 
+/* X[i, j] <- scalar and X[i, ] <- CSR of a CSR with f64 values (assign.hip): count -> scan -> fill
+ * with one lane group per row, chosen from avg_row_len as for mxd_csr_colrange_*.  Both selectors are mx_coo_axis
+ * values without duplicates (MX_AXIS_MAP as mxd_colmap_build makes it of the 1-based selector); nsel_i / nsel_j are
+ * their lengths.  workspace: mxd_gather_workspace_bytes(nrows).
+ *   scalar, is_const = 0: a selected row drops the entries whose column is selected, in order
+ *   scalar, is_const = 1: a selected row becomes the ascending merge of its kept entries and one (col, value) per
+ *                         selected column; rows must be sorted and free of duplicates; `value` is written bit for bit
+ *   count:  new_indptr[nrows + 1], *nnz_out_host = the 64-bit total, *hits_out_host = the selected cells the matrix
+ *           stores; one host read-back.  A total above INT32_MAX fails with the reference's message
+ *           (src/assignment.cpp:380-382) and nothing has been written but the workspace and new_indptr.  When the
+ *           column axis is all columns, indices is not read.
+ *   fill:   cols_sorted[nsel_j] = the selected columns ascending, read only for an MX_AXIS_MAP column axis on the
+ *           const route; new_indices may be NULL when the structure does not change (total = nnz on the const route)
+ *   replace_rows: selected row r becomes row k of the value CSR (nvalue_rows rows), k = r's position in the selector;
+ *           every other row is copied */
+int mxd_csr_assign_count(int nrows, int ncols, const int32_t *indptr, const int32_t *indices, int64_t nnz,
+                         const mx_coo_axis *axis_i, const mx_coo_axis *axis_j, int64_t nsel_i, int64_t nsel_j,
+                         int is_const, double avg_row_len, int32_t *new_indptr, void *workspace,
+                         int64_t *nnz_out_host, int64_t *hits_out_host, void *stream);
+int mxd_csr_assign_fill(int nrows, int ncols, const int32_t *indptr, const int32_t *indices, const double *values,
+                        const mx_coo_axis *axis_i, const mx_coo_axis *axis_j, const int32_t *cols_sorted,
+                        int64_t nsel_j, int is_const, double value, double avg_row_len, const int32_t *new_indptr,
+                        int32_t *new_indices, double *new_values, void *stream);
+int mxd_csr_replace_rows_count(int nrows, const int32_t *indptr, const mx_coo_axis *axis_i, int nvalue_rows,
+                               const int32_t *v_indptr, int32_t *new_indptr, void *workspace, int64_t *nnz_out_host,
+                               void *stream);
+int mxd_csr_replace_rows_fill(int nrows, const int32_t *indptr, const int32_t *indices, const double *values,
+                              const mx_coo_axis *axis_i, int nvalue_rows, const int32_t *v_indptr,
+                              const int32_t *v_indices, const double *v_values, double avg_row_len,
+                              const int32_t *new_indptr, int32_t *new_indices, double *new_values, void *stream);
+
 /* Stable compaction of sparse entries (compact.hip), the core of remove_sparse_zeros and filterSparse
  * (remove_zero_valued_{csr,coo,svec}_*, src/misc.cpp:553-968; rebuild_indptr_after_filter, :1099-1116).
  * Entry k of n is kept by `rule`, evaluated on values[k] (value_dtype MX_F64, MX_LGL or MX_I32) or on mask[k]:
@@ -870,6 +901,27 @@ int mx_check_valid_coo_matrix(const int32_t *ii, const int32_t *jj, int64_t nnz,
                               const char **err);
 /* check_valid_svec  src/misc.cpp:1069-1097: ii against nrows (the R caller passes 1-based ii and the length) */
 int mx_check_valid_svec(const int32_t *ii, int64_t nnz, int nrows, const char **err);
+/* `[<-` of a dgRMatrix (R/assignment.R:37-513; api_assign.hip, through mxd_csr_assign_* / mxd_csr_replace_rows_*).
+ * A selector is a kind and 0-based indices: MX_SEL_ALL, MX_SEL_SINGLE (lo), MX_SEL_RANGE (lo..hi) or
+ * MX_SEL_ARBITRARY (set[0..n_set), any order, no duplicates).  info.alias_structure follows the reference export by
+ * export: MX_ALIAS_ALL where it returns the input vectors themselves (nothing to remove), 1 where it returns the
+ * input indptr / indices with new values (the diff == 0 branches of the const routes), else 0. */
+typedef enum { MX_SEL_ALL = 0, MX_SEL_SINGLE = 1, MX_SEL_RANGE = 2, MX_SEL_ARBITRARY = 3 } mx_sel_kind;
+/* X[i, j] <- value: the twenty set_*_to_zero / set_*_to_const exports of src/assignment.cpp:384-769 (single row /
+ * col / val), :1135-1364 (rowseq, colseq), :1366-1793 (arbitrary rows, arbitrary cols) and :1795-2476 (arbitrary rows
+ * x single col, single row x arbitrary cols, arbitrary x arbitrary).  The zero route is value == 0 (-0.0 included);
+ * anything else, NaN and NA included, is the const route, whose rows must be sorted. */
+int mx_assign_csr_scalar_begin(const int32_t *indptr, int nrows, const int32_t *indices, const double *values,
+                               int ncols, int i_kind, int i_lo, int i_hi, const int32_t *rows_set, int64_t n_rows_set,
+                               int j_kind, int j_lo, int j_hi, const int32_t *cols_set, int64_t n_cols_set,
+                               double value, mx_result **res, mx_result_info *info);
+/* X[i, ] <- value, value a CSR of v_nrows = length(i) rows: set_rowseq_to_smat and set_arbitrary_rows_to_smat,
+ * src/assignment.cpp:2478-2598, without the latter's tail defect (:2554) and in any order of the selector: row
+ * set[k] (or lo + k) becomes row k of the value. */
+int mx_assign_csr_rows_begin(const int32_t *indptr, int nrows, const int32_t *indices, const double *values,
+                             int i_kind, int i_lo, int i_hi, const int32_t *rows_set, int64_t n_rows_set,
+                             const int32_t *v_indptr, int64_t v_nrows, const int32_t *v_indices,
+                             const double *v_values, mx_result **res, mx_result_info *info);
 int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, void *out_values);
 int mx_result_discard(mx_result *res);
 

@@ -2,7 +2,7 @@
 ###
 ### The S4 method registrations of the reference (R/matmul.R, R/operators.R, R/slice.R) and its R glue stay
 ### exactly as they are: `%*%`, `tcrossprod`, `+`, `-`, `*`, `&`, `|`, `[` on dgRMatrix objects dispatch
-### unchanged.  The glue reaches native code only through the one-line wrappers of R/RcppExports.R
+### unchanged, and so does `[<-` on a dgRMatrix.  The glue reaches native code only through the one-line wrappers of R/RcppExports.R
 ### (e.g. :148-150 `tcrossprod_csr_dense_numeric <- function(...) .Call(`_MatrixExtra_tcrossprod_csr_dense_numeric`, ...)`).
 ### This overlay rebinds those 19 wrappers inside the MatrixExtra namespace so that they `.Call` the routines of
 ### the same names registered by mxgpu_r.so (matrixextra_amd/csrc/r_shim.cpp), which forward to libmxgpu.so.
@@ -67,7 +67,18 @@
     "matmul_colvec_by_scolvecascsr", "matmul_colvec_by_scolvecascsr_f32",
     "matmul_spcolvec_by_scolvecascsr_numeric", "matmul_spcolvec_by_scolvecascsr_integer",
     "matmul_spcolvec_by_scolvecascsr_logical", "matmul_spcolvec_by_scolvecascsr_binary",
-    "matmul_rowvec_by_csc", "matmul_rowvec_by_cscbin"
+    "matmul_rowvec_by_csc", "matmul_rowvec_by_cscbin",
+    ## `[<-` of a dgRMatrix (assign_csr_internal, R/assignment.R:37-513): scalar values and whole-row replacement;
+    ## the vector-valued routines (set_single_*_to_rowvec / _colvec / _svec) stay on the CPU
+    "set_single_row_to_zero", "set_single_col_to_zero", "set_single_val_to_zero",
+    "set_rowseq_to_zero", "set_colseq_to_zero", "set_arbitrary_rows_to_zero", "set_arbitrary_cols_to_zero",
+    "set_arbitrary_rows_single_col_to_zero", "set_single_row_arbitrary_cols_to_zero",
+    "set_arbitrary_rows_arbitrary_cols_to_zero",
+    "set_single_row_to_const", "set_single_col_to_const", "set_single_val_to_const",
+    "set_rowseq_to_const", "set_colseq_to_const", "set_arbitrary_rows_to_const", "set_arbitrary_cols_to_const",
+    "set_arbitrary_rows_single_col_to_const", "set_single_row_arbitrary_cols_to_const",
+    "set_arbitrary_rows_arbitrary_cols_to_const",
+    "set_rowseq_to_smat", "set_arbitrary_rows_to_smat"
 )
 
 mxgpu_enable <- function(shim_path, min_nnz = 0L) {

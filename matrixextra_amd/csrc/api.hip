@@ -114,23 +114,6 @@ static int spmv_host(int m, const int32_t *indptr, const int32_t *indices, const
 
 using namespace mx;
 
-// The one owner of an mx_result under construction: `body` fills it and returns 0, or fails and the result is
-// freed.  Every success ends with the null stream synchronised, which mx_result_finish's transfers rely on
-// (device buffers the body frees on its way out are safe: hipFree synchronises the device).
-template <typename Body>
-static int begin_result(mx_result **res_out, mx_result_info *info, int values_dtype, Body &&body)
-{
-    std::unique_ptr<mx_result> res(new (std::nothrow) mx_result());
-    MX_REQUIRE(res, "out of host memory");
-    res->info.values_dtype = values_dtype;
-    res->info.alias_structure = 0;
-    if (const int rc = body(*res)) return rc;
-    MX_HIP(hipStreamSynchronize(nullptr));
-    *info = res->info;
-    *res_out = res.release();
-    return 0;
-}
-
 // The values-only products end alike: one value of value_bytes for each of the sparse operand's n entries, which
 // `launch` fills from the operands already on the device, and which goes back to the caller.
 template <typename Launch>

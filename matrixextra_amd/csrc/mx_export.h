@@ -1,9 +1,12 @@
-// mx_export.h — what the export level (api.hip, and nothing else) keeps its arrays and results in: owning device
-// arrays that know their element size, the caller's values as one description, and the result under construction.
-// Host-only: no kernel unit includes it.  Byte counts and pointer casts live here and nowhere in api.hip.
+// mx_export.h — what the export level (the export-level units: api.hip, api_assign.hip) keeps its arrays and results
+// in: owning device arrays that know their element size, the caller's values as one description, and the result under
+// construction.  Host-only: no kernel unit includes it.  Byte counts and pointer casts live here and nowhere in those
+// units.
 #pragma once
 #include "mx_common.h"
-#pragma GCC visibility push(hidden)     // helpers of one translation unit: none of this joins the dynamic symbols
+#include <memory>
+#include <new>
+#pragma GCC visibility push(hidden)     // helpers of the unit that includes it: none of this joins the dynamic symbols
 namespace mx {
 
 static inline size_t dtype_bytes(int dt)
@@ -147,4 +150,21 @@ struct mx_result {
     // how = 1: the structure stays the caller's and only values come back; MX_ALIAS_ALL: all three vectors do
     void alias(int how, int64_t indptr_len, int64_t nnz) { info.alias_structure = how; set_sizes(indptr_len, nnz, nnz); }
 };
+
+// The one owner of an mx_result under construction: `body` fills it and returns 0, or fails and the result is
+// freed.  Every success ends with the null stream synchronised, which mx_result_finish's transfers rely on
+// (device buffers the body frees on its way out are safe: hipFree synchronises the device).
+template <typename Body>
+static int begin_result(mx_result **res_out, mx_result_info *info, int values_dtype, Body &&body)
+{
+    std::unique_ptr<mx_result> res(new (std::nothrow) mx_result());
+    MX_REQUIRE(res, "out of host memory");
+    res->info.values_dtype = values_dtype;
+    res->info.alias_structure = 0;
+    if (const int rc = body(*res)) return rc;
+    MX_HIP(hipStreamSynchronize(nullptr));
+    *info = res->info;
+    *res_out = res.release();
+    return 0;
+}
 #pragma GCC visibility pop

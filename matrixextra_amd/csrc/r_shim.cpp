@@ -917,6 +917,111 @@ SEXP _MatrixExtra_sort_coo_indices_numeric(SEXP ii, SEXP jj, SEXP xx) { return s
 SEXP _MatrixExtra_sort_coo_indices_logical(SEXP ii, SEXP jj, SEXP xx) { return sort_coo(ii, jj, xx, LGLSXP, MX_LGL); }
 SEXP _MatrixExtra_sort_coo_indices_binary(SEXP ii, SEXP jj) { return sort_coo(ii, jj, R_NilValue, NILSXP, MX_NONE); }
 
+// `[<-` of a dgRMatrix: the set_* routines of src/assignment.cpp (glue: src/RcppExports.cpp, one CallEntries line
+// each) over mx_assign_csr_scalar_begin / mx_assign_csr_rows_begin.  A selector is (kind, lo, hi, set); where the
+// reference returns its input vectors (MX_ALIAS_ALL) or its input indptr / indices with new values (alias 1), so
+// does this.  The zero-route routines of the reference receive no ncol; INT_MAX stands for "not needed".
+struct Sel { int kind, lo, hi; SEXP set; };
+static Sel sel_all() { return Sel{MX_SEL_ALL, 0, 0, R_NilValue}; }
+static Sel sel_one(SEXP k) { const int v = Rf_asInteger(k); return Sel{MX_SEL_SINGLE, v, v, R_NilValue}; }
+static Sel sel_seq(SEXP a, SEXP b) { return Sel{MX_SEL_RANGE, Rf_asInteger(a), Rf_asInteger(b), R_NilValue}; }
+static Sel sel_set(SEXP v) { return Sel{MX_SEL_ARBITRARY, 0, 0, v}; }
+
+static SEXP assigned(mx_result *res, const mx_result_info &info, SEXP p_, SEXP j_, SEXP x_)
+{
+    if (info.alias_structure == MX_ALIAS_ALL) {
+        mx_result_discard(res);
+        Protect p;
+        return named_list3(p_, j_, x_, p);
+    }
+    return finish_guarded(res, info, p_, j_);
+}
+
+static SEXP assign_scalar(SEXP p_, SEXP j_, SEXP x_, int ncols, Sel si, Sel sj, double value)
+{
+    Protect p;
+    p_ = as_type(p_, INTSXP, p); j_ = as_type(j_, INTSXP, p); x_ = as_type(x_, REALSXP, p);
+    if (XLENGTH(x_) != XLENGTH(j_)) Rf_error("assignment: indices and values have different length");
+    if (si.kind == MX_SEL_ARBITRARY) si.set = as_type(si.set, INTSXP, p);
+    if (sj.kind == MX_SEL_ARBITRARY) sj.set = as_type(sj.set, INTSXP, p);
+    mx_result *res = nullptr;
+    mx_result_info info;
+    if (mx_assign_csr_scalar_begin(INTEGER(p_), (int)XLENGTH(p_) - 1, INTEGER(j_), REAL(x_), ncols,
+                                   si.kind, si.lo, si.hi, si.kind == MX_SEL_ARBITRARY ? INTEGER(si.set) : nullptr,
+                                   si.kind == MX_SEL_ARBITRARY ? (int64_t)XLENGTH(si.set) : 0,
+                                   sj.kind, sj.lo, sj.hi, sj.kind == MX_SEL_ARBITRARY ? INTEGER(sj.set) : nullptr,
+                                   sj.kind == MX_SEL_ARBITRARY ? (int64_t)XLENGTH(sj.set) : 0, value, &res, &info))
+        fail();
+    return assigned(res, info, p_, j_, x_);
+}
+
+static SEXP assign_rows(SEXP p_, SEXP j_, SEXP x_, Sel si, SEXP vp, SEXP vj, SEXP vx)
+{
+    Protect p;
+    p_ = as_type(p_, INTSXP, p); j_ = as_type(j_, INTSXP, p); x_ = as_type(x_, REALSXP, p);
+    vp = as_type(vp, INTSXP, p); vj = as_type(vj, INTSXP, p); vx = as_type(vx, REALSXP, p);
+    if (XLENGTH(x_) != XLENGTH(j_) || XLENGTH(vx) != XLENGTH(vj) || XLENGTH(vp) < 1)
+        Rf_error("assignment: indices and values have different length");
+    if (si.kind == MX_SEL_ARBITRARY) si.set = as_type(si.set, INTSXP, p);
+    mx_result *res = nullptr;
+    mx_result_info info;
+    if (mx_assign_csr_rows_begin(INTEGER(p_), (int)XLENGTH(p_) - 1, INTEGER(j_), REAL(x_), si.kind, si.lo, si.hi,
+                                 si.kind == MX_SEL_ARBITRARY ? INTEGER(si.set) : nullptr,
+                                 si.kind == MX_SEL_ARBITRARY ? (int64_t)XLENGTH(si.set) : 0, INTEGER(vp),
+                                 (int64_t)XLENGTH(vp) - 1, INTEGER(vj), REAL(vx), &res, &info))
+        fail();
+    return assigned(res, info, p_, j_, x_);
+}
+
+#define MX_NCOL_UNKNOWN 2147483647
+SEXP _MatrixExtra_set_single_row_to_zero(SEXP p, SEXP j, SEXP x, SEXP row)
+{ return assign_scalar(p, j, x, MX_NCOL_UNKNOWN, sel_one(row), sel_all(), 0.0); }
+SEXP _MatrixExtra_set_single_col_to_zero(SEXP p, SEXP j, SEXP x, SEXP col)
+{ return assign_scalar(p, j, x, MX_NCOL_UNKNOWN, sel_all(), sel_one(col), 0.0); }
+SEXP _MatrixExtra_set_single_row_to_const(SEXP p, SEXP j, SEXP x, SEXP ncols, SEXP row, SEXP val)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_one(row), sel_all(), Rf_asReal(val)); }
+SEXP _MatrixExtra_set_single_col_to_const(SEXP p, SEXP j, SEXP x, SEXP ncols, SEXP col, SEXP val)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_all(), sel_one(col), Rf_asReal(val)); }
+SEXP _MatrixExtra_set_single_val_to_zero(SEXP p, SEXP j, SEXP x, SEXP row, SEXP col)
+{ return assign_scalar(p, j, x, MX_NCOL_UNKNOWN, sel_one(row), sel_one(col), 0.0); }
+SEXP _MatrixExtra_set_single_val_to_const(SEXP p, SEXP j, SEXP x, SEXP ncols, SEXP row, SEXP col, SEXP val)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_one(row), sel_one(col), Rf_asReal(val)); }
+SEXP _MatrixExtra_set_rowseq_to_zero(SEXP p, SEXP j, SEXP x, SEXP st, SEXP end)
+{ return assign_scalar(p, j, x, MX_NCOL_UNKNOWN, sel_seq(st, end), sel_all(), 0.0); }
+SEXP _MatrixExtra_set_rowseq_to_const(SEXP p, SEXP j, SEXP x, SEXP st, SEXP end, SEXP ncols, SEXP val)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_seq(st, end), sel_all(), Rf_asReal(val)); }
+SEXP _MatrixExtra_set_colseq_to_zero(SEXP p, SEXP j, SEXP x, SEXP st, SEXP end, SEXP ncols)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_all(), sel_seq(st, end), 0.0); }
+SEXP _MatrixExtra_set_colseq_to_const(SEXP p, SEXP j, SEXP x, SEXP st, SEXP end, SEXP ncols, SEXP val)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_all(), sel_seq(st, end), Rf_asReal(val)); }
+SEXP _MatrixExtra_set_arbitrary_rows_to_zero(SEXP p, SEXP j, SEXP x, SEXP rows)
+{ return assign_scalar(p, j, x, MX_NCOL_UNKNOWN, sel_set(rows), sel_all(), 0.0); }
+SEXP _MatrixExtra_set_arbitrary_rows_to_const(SEXP p, SEXP j, SEXP x, SEXP rows, SEXP ncols, SEXP val)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_set(rows), sel_all(), Rf_asReal(val)); }
+SEXP _MatrixExtra_set_arbitrary_cols_to_zero(SEXP p, SEXP j, SEXP x, SEXP cols, SEXP ncols)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_all(), sel_set(cols), 0.0); }
+SEXP _MatrixExtra_set_arbitrary_cols_to_const(SEXP p, SEXP j, SEXP x, SEXP cols, SEXP ncols, SEXP val)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_all(), sel_set(cols), Rf_asReal(val)); }
+SEXP _MatrixExtra_set_arbitrary_rows_single_col_to_zero(SEXP p, SEXP j, SEXP x, SEXP rows, SEXP col, SEXP ncols)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_set(rows), sel_one(col), 0.0); }
+SEXP _MatrixExtra_set_arbitrary_rows_single_col_to_const(SEXP p, SEXP j, SEXP x, SEXP rows, SEXP col, SEXP val,
+                                                         SEXP ncols)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_set(rows), sel_one(col), Rf_asReal(val)); }
+SEXP _MatrixExtra_set_single_row_arbitrary_cols_to_zero(SEXP p, SEXP j, SEXP x, SEXP row, SEXP cols, SEXP ncols)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_one(row), sel_set(cols), 0.0); }
+SEXP _MatrixExtra_set_single_row_arbitrary_cols_to_const(SEXP p, SEXP j, SEXP x, SEXP row, SEXP cols, SEXP ncols,
+                                                         SEXP val)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_one(row), sel_set(cols), Rf_asReal(val)); }
+SEXP _MatrixExtra_set_arbitrary_rows_arbitrary_cols_to_zero(SEXP p, SEXP j, SEXP x, SEXP rows, SEXP cols, SEXP ncols)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_set(rows), sel_set(cols), 0.0); }
+SEXP _MatrixExtra_set_arbitrary_rows_arbitrary_cols_to_const(SEXP p, SEXP j, SEXP x, SEXP rows, SEXP cols,
+                                                             SEXP ncols, SEXP val)
+{ return assign_scalar(p, j, x, Rf_asInteger(ncols), sel_set(rows), sel_set(cols), Rf_asReal(val)); }
+SEXP _MatrixExtra_set_rowseq_to_smat(SEXP p, SEXP j, SEXP x, SEXP st, SEXP end, SEXP vp, SEXP vj, SEXP vx)
+{ return assign_rows(p, j, x, sel_seq(st, end), vp, vj, vx); }
+SEXP _MatrixExtra_set_arbitrary_rows_to_smat(SEXP p, SEXP j, SEXP x, SEXP rows, SEXP vp, SEXP vj, SEXP vx)
+{ return assign_rows(p, j, x, sel_set(rows), vp, vj, vx); }
+
 #define MX_ENTRY(name, n) {"_MatrixExtra_" #name, (DL_FUNC)&_MatrixExtra_##name, n}
 static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(matmul_dense_csc_numeric, 5), MX_ENTRY(matmul_dense_csc_float32, 5),
@@ -960,6 +1065,16 @@ static const R_CallMethodDef mxgpu_call_entries[] = {
     MX_ENTRY(matmul_colvec_by_scolvecascsr_f32, 4), MX_ENTRY(matmul_colvec_by_scolvecascsr, 4),
     MX_ENTRY(matmul_spcolvec_by_scolvecascsr_numeric, 6), MX_ENTRY(matmul_spcolvec_by_scolvecascsr_integer, 6),
     MX_ENTRY(matmul_spcolvec_by_scolvecascsr_logical, 6), MX_ENTRY(matmul_spcolvec_by_scolvecascsr_binary, 5),
+    MX_ENTRY(set_single_row_to_zero, 4), MX_ENTRY(set_single_col_to_zero, 4), MX_ENTRY(set_single_val_to_zero, 5),
+    MX_ENTRY(set_single_row_to_const, 6), MX_ENTRY(set_single_col_to_const, 6), MX_ENTRY(set_single_val_to_const, 7),
+    MX_ENTRY(set_rowseq_to_zero, 5), MX_ENTRY(set_rowseq_to_const, 7),
+    MX_ENTRY(set_colseq_to_zero, 6), MX_ENTRY(set_colseq_to_const, 7),
+    MX_ENTRY(set_arbitrary_rows_to_zero, 4), MX_ENTRY(set_arbitrary_rows_to_const, 6),
+    MX_ENTRY(set_arbitrary_cols_to_zero, 5), MX_ENTRY(set_arbitrary_cols_to_const, 6),
+    MX_ENTRY(set_arbitrary_rows_single_col_to_zero, 6), MX_ENTRY(set_arbitrary_rows_single_col_to_const, 7),
+    MX_ENTRY(set_single_row_arbitrary_cols_to_zero, 6), MX_ENTRY(set_single_row_arbitrary_cols_to_const, 7),
+    MX_ENTRY(set_arbitrary_rows_arbitrary_cols_to_zero, 6), MX_ENTRY(set_arbitrary_rows_arbitrary_cols_to_const, 7),
+    MX_ENTRY(set_rowseq_to_smat, 8), MX_ENTRY(set_arbitrary_rows_to_smat, 7),
     {"mxgpu_csr_transpose", (DL_FUNC)&mxgpu_csr_transpose, 4},
     {"mxgpu_coo_to_csr", (DL_FUNC)&mxgpu_coo_to_csr, 5},
     {NULL, NULL, 0}

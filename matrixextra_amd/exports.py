@@ -1200,3 +1200,173 @@ def multiply_coo_by_dense_float32(X_, Y_coo_row, Y_coo_col, Y_coo_val):
 def logicaland_coo_by_dense_logical(X_, Y_coo_row, Y_coo_col, Y_coo_val):
     """src/operators.cpp:840-855: R logicals in and out, R's three-valued AND."""
     return _coo_by_dense(_lib.load().mx_logicaland_coo_by_dense_logical, 4, X_, Y_coo_row, Y_coo_col, Y_coo_val)
+
+
+# ----------------------------------------------------------------------------- `[<-` of a dgRMatrix (assign.hip)
+_SEL_ALL, _SEL_SINGLE, _SEL_RANGE, _SEL_ARBITRARY = (_lib.MX_SEL_ALL, _lib.MX_SEL_SINGLE, _lib.MX_SEL_RANGE,
+                                                     _lib.MX_SEL_ARBITRARY)
+_ALL = (_SEL_ALL, 0, 0, None)
+# the zero-route exports of the reference take no ncol, and the zero route needs none
+_NCOL_UNKNOWN = 2**31 - 1
+
+
+def _one(k):
+    return (_SEL_SINGLE, int(k), int(k), None)
+
+
+def _seq(lo, hi):
+    return (_SEL_RANGE, int(lo), int(hi), None)
+
+
+def _arb(idx):
+    return (_SEL_ARBITRARY, 0, 0, _i32(idx))
+
+
+def _assigned(res, info, inputs):
+    """dict(indptr, indices, values) of an assignment: the input objects themselves (MX_ALIAS_ALL), the input indptr
+    and indices with new values (alias 1), or three new vectors, as the reference's export returns them."""
+    if info.alias_structure == _lib.MX_ALIAS_ALL:
+        check(_lib.load().mx_result_discard(res))
+        return dict(indptr=inputs[0], indices=inputs[1], values=inputs[2])
+    return _finish(res, info, alias_from=inputs[:2])
+
+
+def rows_are_sorted(p, j):
+    """Host check: every row's column indices strictly ascend."""
+    p, j = np.asarray(p), np.asarray(j)
+    back = np.flatnonzero(j[1:] <= j[:-1]) + 1          # entries not above their predecessor: row starts only
+    return bool(np.isin(back, p).all())
+
+
+def _assign_scalar(indptr, indices, values, ncols, sel_i, sel_j, value):
+    p, j, v = _i32(indptr), _i32(indices), _f64(values)
+    if j.size != v.size or p.size < 1:
+        raise ValueError("indptr, indices and values do not form a CSR")
+    (ki, ilo, ihi, rows), (kj, jlo, jhi, cols) = sel_i, sel_j
+    return _begin(_lib.load().mx_assign_csr_scalar_begin, ptr(p), p.size - 1, ptr(j), ptr(v), int(ncols),
+                  ki, ilo, ihi, ptr(rows), 0 if rows is None else rows.size,
+                  kj, jlo, jhi, ptr(cols), 0 if cols is None else cols.size, float(value),
+                  finish=_assigned, inputs=(indptr, indices, values))[0]
+
+
+def _assign_rows(indptr, indices, values, sel_i, indptr_other, indices_other, values_other):
+    p, j, v = _i32(indptr), _i32(indices), _f64(values)
+    vp, vj, vv = _i32(indptr_other), _i32(indices_other), _f64(values_other)
+    if j.size != v.size or p.size < 1 or vj.size != vv.size or vp.size < 1:
+        raise ValueError("indptr, indices and values do not form a CSR")
+    ki, ilo, ihi, rows = sel_i
+    return _begin(_lib.load().mx_assign_csr_rows_begin, ptr(p), p.size - 1, ptr(j), ptr(v), ki, ilo, ihi, ptr(rows),
+                  0 if rows is None else rows.size, ptr(vp), vp.size - 1, ptr(vj), ptr(vv),
+                  finish=_assigned, inputs=(indptr, indices, values))[0]
+
+
+def set_single_row_to_zero(indptr, indices, values, row_set):
+    """src/assignment.cpp:384-424."""
+    return _assign_scalar(indptr, indices, values, _NCOL_UNKNOWN, _one(row_set), _ALL, 0.0)
+
+
+def set_single_col_to_zero(indptr, indices, values, col_set):
+    """src/assignment.cpp:426-496."""
+    return _assign_scalar(indptr, indices, values, _NCOL_UNKNOWN, _ALL, _one(col_set), 0.0)
+
+
+def set_single_row_to_const(indptr, indices, values, ncols, row_set, val_set):
+    """src/assignment.cpp:498-559."""
+    return _assign_scalar(indptr, indices, values, ncols, _one(row_set), _ALL, val_set)
+
+
+def set_single_col_to_const(indptr, indices, values, ncols, col_set, val_set):
+    """src/assignment.cpp:561-630."""
+    return _assign_scalar(indptr, indices, values, ncols, _ALL, _one(col_set), val_set)
+
+
+def set_single_val_to_zero(indptr, indices, values, row_set, col_set):
+    """src/assignment.cpp:632-684."""
+    return _assign_scalar(indptr, indices, values, _NCOL_UNKNOWN, _one(row_set), _one(col_set), 0.0)
+
+
+def set_single_val_to_const(indptr, indices, values, ncols, row_set, col_set, val_set):
+    """src/assignment.cpp:686-769."""
+    return _assign_scalar(indptr, indices, values, ncols, _one(row_set), _one(col_set), val_set)
+
+
+def set_rowseq_to_zero(indptr, indices, values, row_set_st, row_set_end):
+    """src/assignment.cpp:1135-1171: always new vectors."""
+    return _assign_scalar(indptr, indices, values, _NCOL_UNKNOWN, _seq(row_set_st, row_set_end), _ALL, 0.0)
+
+
+def set_rowseq_to_const(indptr, indices, values, row_set_st, row_set_end, ncols, val_set):
+    """src/assignment.cpp:1173-1233."""
+    return _assign_scalar(indptr, indices, values, ncols, _seq(row_set_st, row_set_end), _ALL, val_set)
+
+
+def set_colseq_to_zero(indptr, indices, values, col_set_st, col_set_end, ncols):
+    """src/assignment.cpp:1235-1291."""
+    return _assign_scalar(indptr, indices, values, ncols, _ALL, _seq(col_set_st, col_set_end), 0.0)
+
+
+def set_colseq_to_const(indptr, indices, values, col_set_st, col_set_end, ncols, val_set):
+    """src/assignment.cpp:1293-1364: always new vectors."""
+    return _assign_scalar(indptr, indices, values, ncols, _ALL, _seq(col_set_st, col_set_end), val_set)
+
+
+def set_arbitrary_rows_to_zero(indptr, indices, values, rows_set):
+    """src/assignment.cpp:1366-1443."""
+    return _assign_scalar(indptr, indices, values, _NCOL_UNKNOWN, _arb(rows_set), _ALL, 0.0)
+
+
+def set_arbitrary_rows_to_const(indptr, indices, values, rows_set, ncols, val_set):
+    """src/assignment.cpp:1445-1597."""
+    return _assign_scalar(indptr, indices, values, ncols, _arb(rows_set), _ALL, val_set)
+
+
+def set_arbitrary_cols_to_zero(indptr, indices, values, cols_set, ncols):
+    """src/assignment.cpp:1599-1661."""
+    return _assign_scalar(indptr, indices, values, ncols, _ALL, _arb(cols_set), 0.0)
+
+
+def set_arbitrary_cols_to_const(indptr, indices, values, cols_set, ncols, val_set):
+    """src/assignment.cpp:1663-1793."""
+    return _assign_scalar(indptr, indices, values, ncols, _ALL, _arb(cols_set), val_set)
+
+
+def set_arbitrary_rows_single_col_to_zero(indptr, indices, values, rows_set, col_set, ncols):
+    """src/assignment.cpp:1795-1898."""
+    return _assign_scalar(indptr, indices, values, ncols, _arb(rows_set), _one(col_set), 0.0)
+
+
+def set_arbitrary_rows_single_col_to_const(indptr, indices, values, rows_set, col_set, val_set, ncols):
+    """src/assignment.cpp:1900-2060."""
+    return _assign_scalar(indptr, indices, values, ncols, _arb(rows_set), _one(col_set), val_set)
+
+
+def set_single_row_arbitrary_cols_to_zero(indptr, indices, values, row_set, cols_set, ncols):
+    """src/assignment.cpp:2062-2159."""
+    return _assign_scalar(indptr, indices, values, ncols, _one(row_set), _arb(cols_set), 0.0)
+
+
+def set_single_row_arbitrary_cols_to_const(indptr, indices, values, row_set, cols_set, ncols, val_set):
+    """src/assignment.cpp:2161-2251."""
+    return _assign_scalar(indptr, indices, values, ncols, _one(row_set), _arb(cols_set), val_set)
+
+
+def set_arbitrary_rows_arbitrary_cols_to_zero(indptr, indices, values, rows_set, cols_set, ncols):
+    """src/assignment.cpp:2253-2358."""
+    return _assign_scalar(indptr, indices, values, ncols, _arb(rows_set), _arb(cols_set), 0.0)
+
+
+def set_arbitrary_rows_arbitrary_cols_to_const(indptr, indices, values, rows_set, cols_set, ncols, val_set):
+    """src/assignment.cpp:2360-2476."""
+    return _assign_scalar(indptr, indices, values, ncols, _arb(rows_set), _arb(cols_set), val_set)
+
+
+def set_rowseq_to_smat(indptr, indices, values, row_set_st, row_set_end, indptr_other, indices_other, values_other):
+    """src/assignment.cpp:2478-2521."""
+    return _assign_rows(indptr, indices, values, _seq(row_set_st, row_set_end), indptr_other, indices_other,
+                        values_other)
+
+
+def set_arbitrary_rows_to_smat(indptr, indices, values, rows_set, indptr_other, indices_other, values_other):
+    """src/assignment.cpp:2523-2598, in any order of rows_set and without its tail defect (:2554): row rows_set[k]
+    becomes row k of the other matrix."""
+    return _assign_rows(indptr, indices, values, _arb(rows_set), indptr_other, indices_other, values_other)

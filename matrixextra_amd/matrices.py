@@ -193,6 +193,15 @@ class dgRMatrix(RsparseMatrix):
     value_dtype = np.float64
     r_class = "dgRMatrix"
 
+    def __setitem__(self, key, value):                # `[<-`  R/assignment.R:521-553 (0-based here; assign_csr is 1-based)
+        from . import assign, slice as _slice
+        rows, cols = _slice.canonical_key(self, key)
+        res = assign.assign_csr(self, rows, cols, value)
+        if not isinstance(res, RsparseMatrix):
+            stop("This assignment gives a dense matrix, which cannot replace a dgRMatrix in place: "
+                 "use assign_csr(x, i, j, value) and keep what it returns.")
+        self.p, self.j, self.x = res.p, res.j, res.x
+
 
 class lgRMatrix(RsparseMatrix):
     value_dtype = np.int32
