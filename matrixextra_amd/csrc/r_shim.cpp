@@ -8,9 +8,13 @@
 // as.csr.matrix / as.csc.matrix of a TsparseMatrix.  Written against the plain R C API
 // (no Rcpp): INTEGER()/REAL(), Rf_allocMatrix, Rf_error.
 //
-// This file is NOT part of libmxgpu.so and cannot be compiled in the development image (no R headers):
-// it is built on a machine that has R with
+// This file is NOT part of libmxgpu.so: it is built on a machine that has R with
 //     R CMD SHLIB -o mxgpu_r.so r_shim.cpp -L<repo>/matrixextra_amd -lmxgpu -I<repo>/include
+// No R has compiled or run it yet.  What does compile and run it is the project's own build: `make rshim` builds it
+// with -Wall -Wextra -Werror against the stand-in for R's C API under tests/rstub, once linked to libmxgpu.so and once
+// to a generated fake of the C-ABI, and tests/test_rshim_host.py / tests/test_gpu_rshim.py call every routine below
+// through it (registration, handle lifecycle, PROTECT balance under a gctorture-like mode, result types and names,
+// and the reference-run records on the device).
 // See INTEGRATION.md.  Everything numerically meaningful lives behind the C-ABI and is tested through it;
 // what is left here is mechanical marshalling:
 //   * inputs are borrowed (no copies unless the SEXP type differs, as Rcpp's input_parameter<> does);
@@ -38,7 +42,7 @@ struct Protect {          // PROTECT counter that unwinds on scope exit (normal 
     ~Protect() { if (n) UNPROTECT(n); }
 };
 
-inline SEXP as_type(SEXP x, SEXPTYPE t, Protect &p) { return TYPEOF(x) == t ? x : p(Rf_coerceVector(x, t)); }
+inline SEXP as_type(SEXP x, SEXPTYPE t, Protect &p) { return (SEXPTYPE)TYPEOF(x) == t ? x : p(Rf_coerceVector(x, t)); }
 inline void fail() { Rf_error("%s", mx_last_error()); }
 
 // float32@Data is an INTSXP matrix carrying binary32 bit patterns (R/matmul.R:260,276; matmul.cpp:213)
@@ -59,18 +63,24 @@ SEXP named_list3(SEXP indptr, SEXP indices, SEXP values, Protect &p)
     return out;
 }
 
-SEXP finish_list(mx_result *res, const mx_result_info &info, SEXP alias_p, SEXP alias_j, Protect &p)
+// mx_result_finish owns the handle from the moment it is entered and deletes it on every return, failure included:
+// `res` is cleared before the call, so that no cleanup releases it a second time
+SEXP finish_list(mx_result *&res, const mx_result_info &info, SEXP alias_p, SEXP alias_j, Protect &p)
 {
-    const SEXPTYPE vt = info.values_dtype == MX_F64 ? REALSXP : (info.values_dtype == MX_LGL ? LGLSXP : REALSXP);
+    // doubles, logicals, or the integers of an isparseVector; no values at all is an empty double vector
+    const SEXPTYPE vt = info.values_dtype == MX_LGL ? LGLSXP : (info.values_dtype == MX_I32 ? INTSXP : REALSXP);
     const R_xlen_t nv = info.values_dtype == MX_NONE ? 0 : (R_xlen_t)info.values_len;
     SEXP values = p(Rf_allocVector(vt, nv));           // may long-jump on allocation failure:
-    void *vptr = vt == REALSXP ? (void *)REAL(values) : (void *)LOGICAL(values);
+    void *vptr = vt == REALSXP ? (void *)REAL(values)
+               : vt == LGLSXP  ? (void *)LOGICAL(values) : (void *)INTEGER(values);
     SEXP indptr = alias_p, indices = alias_j;
     if (!info.alias_structure) {
         indptr = p(Rf_allocVector(INTSXP, (R_xlen_t)info.indptr_len));
         indices = p(Rf_allocVector(INTSXP, (R_xlen_t)info.nnz));
     }
-    if (mx_result_finish(res, info.alias_structure ? nullptr : INTEGER(indptr),
+    mx_result *handle = res;
+    res = nullptr;
+    if (mx_result_finish(handle, info.alias_structure ? nullptr : INTEGER(indptr),
                          info.alias_structure ? nullptr : INTEGER(indices), nv ? vptr : nullptr))
         fail();
     return named_list3(indptr, indices, values, p);
@@ -82,8 +92,7 @@ void finish_body(void *d)
 {
     FinishArgs *a = static_cast<FinishArgs *>(d);
     Protect p;
-    a->out = finish_list(a->res, a->info, a->alias_p, a->alias_j, p);
-    a->res = nullptr;                      // consumed by mx_result_finish
+    a->out = finish_list(a->res, a->info, a->alias_p, a->alias_j, p);     // consumes a->res
     R_PreserveObject(a->out);              // survives p's UNPROTECT; released by the caller
 }
 void finish_cleanup(void *d)
@@ -526,8 +535,9 @@ static SEXP slice_coo_single(int dtype, SEXP ii, SEXP jj, SEXP xx, SEXP i, SEXP 
     int found = 0;
     double vd = 0;
     int vl = 0;
+    void *value_out = dtype == MX_F64 ? (void *)&vd : dtype == MX_LGL ? (void *)&vl : nullptr;     // a pattern has none
     if (mx_slice_coo_single(INTEGER(ii), INTEGER(jj), xv, dtype, (int64_t)XLENGTH(ii), Rf_asInteger(i),
-                            Rf_asInteger(j), &found, dtype == MX_F64 ? (void *)&vd : (void *)&vl))
+                            Rf_asInteger(j), &found, value_out))
         fail();
     if (dtype == MX_F64) return Rf_ScalarReal(found ? vd : 0.0);
     return Rf_ScalarLogical(found && (dtype == MX_NONE || vl != 0));       // C++ bool: NA reads as TRUE
@@ -677,17 +687,7 @@ static SEXP rz_svec(int dtype, SEXP ii, SEXP xx, SEXP na_rm)
     else if (dtype == MX_LGL) rc = mx_remove_zero_valued_svec_logical(INTEGER(ii), LOGICAL(xx), n, na, &res, &info);
     else rc = mx_remove_zero_valued_svec_integer(INTEGER(ii), INTEGER(xx), n, na, &res, &info);
     if (rc) fail();
-    // finish_list allocates REALSXP for MX_I32 results; an integer svec keeps its INTSXP type
-    if (dtype == MX_I32 && info.alias_structure != MX_ALIAS_ALL) {
-        SEXP ni = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)info.nnz));
-        SEXP nx = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)info.values_len));
-        if (mx_result_finish(res, nullptr, INTEGER(ni), INTEGER(nx))) fail();
-        SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
-        SET_VECTOR_ELT(out, 0, ni);
-        SET_VECTOR_ELT(out, 1, nx);
-        UNPROTECT(3);
-        return named(out, "ii", "xx", nullptr);
-    }
+    // the integer kind reports MX_I32 and finish_list keeps it an INTSXP; every kind goes through the guarded finish
     return named(compacted(res, info, R_NilValue, ii, xx, 2), "ii", "xx", nullptr);
 }
 SEXP _MatrixExtra_remove_zero_valued_svec_numeric(SEXP ii, SEXP xx, SEXP na_rm) { return rz_svec(MX_F64, ii, xx, na_rm); }

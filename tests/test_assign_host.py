@@ -252,17 +252,13 @@ def test_export_helpers_refuse_before_any_device_call():
 
 
 def test_the_r_side_carries_the_same_names():
-    with open(os.path.join(ROOT, "matrixextra_amd", "csrc", "r_shim.cpp")) as f:
-        shim = f.read()
-    with open(os.path.join(ROOT, "matrixextra_amd", "R", "mxgpu_overlay.R")) as f:
-        overlay = f.read()
+    import rshim_registry
     with open(os.path.join(ROOT, "include", "mxgpu.h")) as f:
         header = f.read()
+    with open(os.path.join(ROOT, "matrixextra_amd", "csrc", "r_shim.cpp")) as f:
+        shim = f.read()
     for name in AM.ORDER:
-        arity = 3 + len(AM.ORDER[name])
-        assert re.search(r"MX_ENTRY\(%s, %d\)" % (name, arity), shim), name
-        assert len(re.search(r"SEXP _MatrixExtra_%s\(([^)]*)\)" % name, shim).group(1).split(",")) == arity, name
-        assert '"%s"' % name in overlay, name
+        rshim_registry.assert_shim_and_overlay_carry(name, 3 + len(AM.ORDER[name]))     # registered, exported, rebound
         assert callable(getattr(G, name))
     assert "mx_assign_csr_scalar_begin" in shim and "mx_assign_csr_rows_begin" in shim
     for proto in ("mx_assign_csr_scalar_begin", "mx_assign_csr_rows_begin"):

@@ -73,12 +73,9 @@ def test_more_entries_than_int32_are_refused_before_anything_is_allocated():
 
 
 def test_shim_and_overlay_carry_the_three_routines():
-    pkg = os.path.dirname(_lib.LIB_PATH)
-    shim = open(os.path.join(pkg, "csrc", "r_shim.cpp")).read()
-    overlay = open(os.path.join(pkg, "R", "mxgpu_overlay.R")).read()
+    import rshim_registry
     for name, nargs in (("sort_coo_indices_numeric", 3), ("sort_coo_indices_logical", 3), ("sort_coo_indices_binary", 2)):
-        assert f"MX_ENTRY({name}, {nargs})" in shim and f"SEXP _MatrixExtra_{name}(" in shim
-        assert f'"{name}"' in overlay
+        rshim_registry.assert_shim_and_overlay_carry(name, nargs)
 
 
 def test_exports_check_their_arguments_before_any_device_call():

@@ -71,10 +71,8 @@ def test_entry_points_declared_and_exported():
         assert lib.mxd_dvec_na_special_workspace_bytes(1000) >= 3 * 4 * 1000
         assert lib.mxd_dvec_na_cells_workspace_bytes(1000) >= 2 * 4 * 1000
     assert callable(G.multiply_csr_by_dvec_with_NAs)
-    shim = open(os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc", "r_shim.cpp")).read()
-    assert "MX_ENTRY(multiply_csr_by_dvec_with_NAs, 11)" in shim
-    overlay = open(os.path.join(os.path.dirname(_lib.LIB_PATH), "R", "mxgpu_overlay.R")).read()
-    assert '"multiply_csr_by_dvec_with_NAs"' in overlay
+    import rshim_registry
+    rshim_registry.assert_shim_and_overlay_carry("multiply_csr_by_dvec_with_NAs", 11)
 
 
 def test_option_off_raises_as_before(monkeypatch):
