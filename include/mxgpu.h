@@ -590,6 +590,31 @@ int mxd_csr_replace_rows_fill(int nrows, const int32_t *indptr, const int32_t *i
                               const int32_t *v_indices, const double *v_values, double avg_row_len,
                               const int32_t *new_indptr, int32_t *new_indices, double *new_values, void *stream);
 
+/* X[, c] <- vector and the pattern of X[r, ] <- vector of a CSR with f64 values (assignvec.hip).
+ * A pattern is (ii, xx, n_xx, length): 0-based positions ii[0..n_xx) inside [0, length) and their values; ii == NULL
+ * is the dense pattern 0..length-1 (n_xx == length).  A sparse pattern without entries passes n_xx = 0.
+ *   col_count / col_fill: set_single_col_to_colvec (src/assignment.cpp:839-913) and set_single_col_to_svec
+ *           (:1009-1133) with their per-row insert_col_into_row (:8-117) / remove_col_from_row (:119-180): row r ends
+ *           up holding (col, xx[.]) when the pattern stores r % length (ii ascending), and without col otherwise.
+ *           Rows must be sorted.  count -> scan -> fill as mxd_csr_assign_*; workspace:
+ *           mxd_gather_workspace_bytes(nrows); one host synchronisation.  *changed_out_host = the rows whose structure
+ *           changes (0: new_indices may be NULL in the fill, which then writes values only).  A total above INT32_MAX
+ *           fails with the reference's message (:380-382).
+ *   expand_pattern_row: the recycling loops of set_single_row_to_rowvec (:771-837) and set_single_row_to_svec
+ *           (:915-1007): row_indices[t] = ii[t % n_xx] + length * (t / n_xx) (t when dense), row_values[t] =
+ *           xx[t % n_xx] for t < n_xx * n_repeats, row_indptr = {0, n_xx * n_repeats}: a one-row CSR for
+ *           mxd_csr_replace_rows_*.  row_indptr and row_indices may be NULL (values only). */
+int mxd_csr_assign_col_count(int nrows, int ncols, const int32_t *indptr, const int32_t *indices, int64_t nnz,
+                             int col, const int32_t *ii, int64_t n_xx, int length, double avg_row_len,
+                             int32_t *new_indptr, void *workspace, int64_t *nnz_out_host, int64_t *changed_out_host,
+                             void *stream);
+int mxd_csr_assign_col_fill(int nrows, int ncols, const int32_t *indptr, const int32_t *indices, const double *values,
+                            int col, const int32_t *ii, const double *xx, int64_t n_xx, int length,
+                            double avg_row_len, const int32_t *new_indptr, int32_t *new_indices, double *new_values,
+                            void *stream);
+int mxd_csr_expand_pattern_row(const int32_t *ii, const double *xx, int64_t n_xx, int length, int n_repeats,
+                               int32_t *row_indptr, int32_t *row_indices, double *row_values, void *stream);
+
 /* Stable compaction of sparse entries (compact.hip), the core of remove_sparse_zeros and filterSparse
  * (remove_zero_valued_{csr,coo,svec}_*, src/misc.cpp:553-968; rebuild_indptr_after_filter, :1099-1116).
  * Entry k of n is kept by `rule`, evaluated on values[k] (value_dtype MX_F64, MX_LGL or MX_I32) or on mask[k]:
@@ -922,6 +947,22 @@ int mx_assign_csr_rows_begin(const int32_t *indptr, int nrows, const int32_t *in
                              int i_kind, int i_lo, int i_hi, const int32_t *rows_set, int64_t n_rows_set,
                              const int32_t *v_indptr, int64_t v_nrows, const int32_t *v_indices,
                              const double *v_values, mx_result **res, mx_result_info *info);
+/* X[row, ] <- vector: set_single_row_to_rowvec (src/assignment.cpp:771-837; ii == NULL, length == n_xx) and
+ * set_single_row_to_svec (:915-1007; ii as stored, any order).  The row becomes the pattern recycled ncols / length
+ * times, every other row is copied.  info.alias_structure = 1 when the row's indices already equal the recycled
+ * pattern element for element (only values are made); the fast path of :939-966 is taken on that condition alone, so
+ * its two defects (a read past ii, values written past a shorter row) are not copied.  An ii without entries empties
+ * the row.  A full row that is not sorted gives three new vectors (the reference returns its indptr, :800-808). */
+int mx_assign_csr_row_vec_begin(const int32_t *indptr, int nrows, const int32_t *indices, const double *values,
+                                int ncols, int row, const int32_t *ii, const double *xx, int64_t n_xx, int length,
+                                mx_result **res, mx_result_info *info);
+/* X[, col] <- vector: set_single_col_to_colvec (src/assignment.cpp:839-913; ii == NULL, length == n_xx) and
+ * set_single_col_to_svec (:1009-1133; ii strictly ascending), recycled nrows / length times.  Rows that are not sorted
+ * are sorted in the device copy first.  info.alias_structure = 1 for a dense vector when every row already stores
+ * the column and no row had to be sorted; a sparse vector never aliases, as in the reference. */
+int mx_assign_csr_col_vec_begin(const int32_t *indptr, int nrows, const int32_t *indices, const double *values,
+                                int ncols, int col, const int32_t *ii, const double *xx, int64_t n_xx, int length,
+                                mx_result **res, mx_result_info *info);
 int mx_result_finish(mx_result *res, int32_t *out_indptr, int32_t *out_indices, void *out_values);
 int mx_result_discard(mx_result *res);
 

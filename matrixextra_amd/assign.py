@@ -12,6 +12,11 @@ the reference sends through the `Matrix` package (assign_through_matrix) or thro
 (set_single_row_to_rowvec, set_single_col_to_colvec, set_single_*_to_svec) raises MatrixExtraError naming the route:
 there is no silent fallback.
 
+Under options["mxgpu.assign_vec_route"] (off unless set) the four vector-valued routines run on the
+device instead of refusing: one row with all columns, or all rows with one column, given a dense vector, a
+sparseVector, or a sparse matrix of one row or one column (which becomes the sparseVector it spells).  Everything
+else refuses as without the option.
+
 Rows of `x` that are not sorted: a sorted copy is made first (sort_sparse_indices(copy=True)), so the result differs
 from the reference's only in the order inside rows the assignment does not touch; the reference instead sorts the
 selected rows of the caller's own vectors in place, which is not done here.
@@ -24,7 +29,8 @@ import numpy as np
 
 from . import exports
 from .matrices import (DenseMatrix, MatrixExtraError, NA_INTEGER, NA_REAL, RsparseMatrix, TsparseMatrix,
-                       as_csr_matrix, dgCMatrix, dgRMatrix, float32, sort_sparse_indices, sparseVector, stop)
+                       as_csr_matrix, as_sparse_vector, dgCMatrix, dgRMatrix, dsparseVector, float32, nsparseVector,
+                       options, sort_sparse_indices, sparseVector, stop)
 from .slice import get_ij_properties
 
 _SPARSE_MATRIX = (RsparseMatrix, TsparseMatrix, dgCMatrix)
@@ -36,6 +42,10 @@ def throw_shape_err():
 
 def _not_on_device(route):
     raise MatrixExtraError(f"This assignment takes the reference's route '{route}', which is not on the device.")
+
+
+def _vec_route():
+    return bool(options.get("mxgpu.assign_vec_route", False))
 
 
 def check_shapes_are_assignable_2d(x1, x2, y1, y2):
@@ -104,6 +114,22 @@ def _sorted_operand(x):
     if exports.rows_are_sorted(x.p, x.j):
         return x
     return sort_sparse_indices(x, copy=True)
+
+
+def _numeric_svec(value, route):
+    """The sparseVector with float64 @x (integer and logical NA become NA_real_).  An nsparseVector has no @x for the
+    reference to read (R/assignment.R:320, :340) and is refused."""
+    if isinstance(value, nsparseVector):
+        _not_on_device(f"{route} (nsparseVector value, which has no @x)")
+    return value if isinstance(value, dsparseVector) else as_sparse_vector(value)
+
+
+def _spelled_vector(value):
+    """The sparseVector a sparse matrix of one row or one column spells.  The reference hands the matrix's own index
+    and value slots to set_single_*_to_svec (R/assignment.R:386, :399, :461, :474), with ncol(value) as the length:
+    for a one-column value that length is 1, a defect.  Here the length is the vector's, and a column assignment
+    sorts the vector like any other sparseVector."""
+    return as_sparse_vector(value)
 
 
 def _finish(x, res):
@@ -224,11 +250,16 @@ def _assign_csr_internal(x, i, j, value, P):
         if all_j and i.size == 1:
             if n > ncol or ncol % n != 0:
                 throw_shape_err()
-            _not_on_device("set_single_row_to_rowvec")
+            if not _vec_route():
+                _not_on_device("set_single_row_to_rowvec")
+            return _finish(x, E.set_single_row_to_rowvec(x.p, x.j, x.x, ncol, int(i[0]) - 1, value))
         if all_i and j.size == 1 and not all_j:
             if n > nrow or nrow % n != 0:
                 throw_shape_err()
-            _not_on_device("set_single_col_to_colvec")
+            if not _vec_route():
+                _not_on_device("set_single_col_to_colvec")
+            x = _sorted_operand(x)                               # an insert lands at its ascending place
+            return _finish(x, E.set_single_col_to_colvec(x.p, x.j, x.x, ncol, int(j[0]) - 1, value))
         if not all_i and not all_j and not check_shapes_are_assignable_1d(i.size, j.size, n):
             throw_shape_err()
         _not_on_device("assign_through_matrix (vector value)")
@@ -240,11 +271,20 @@ def _assign_csr_internal(x, i, j, value, P):
         if all_j and not all_i and i.size == 1:
             if len(value) > ncol or ncol % len(value) != 0:
                 throw_shape_err()
-            _not_on_device("set_single_row_to_svec")
+            if not _vec_route():
+                _not_on_device("set_single_row_to_svec")
+            value = _numeric_svec(value, "set_single_row_to_svec")
+            return _finish(x, E.set_single_row_to_svec(x.p, x.j, x.x, ncol, int(i[0]) - 1, value.i - 1, value.x,
+                                                       len(value)))                # ii as stored (:320)
         if all_i and not all_j and j.size == 1:
             if len(value) > nrow or nrow % len(value) != 0:
                 throw_shape_err()
-            _not_on_device("set_single_col_to_svec")
+            if not _vec_route():
+                _not_on_device("set_single_col_to_svec")
+            value = sort_sparse_indices(_numeric_svec(value, "set_single_col_to_svec"), copy=True)     # :335-338
+            x = _sorted_operand(x)
+            return _finish(x, E.set_single_col_to_svec(x.p, x.j, x.x, ncol, int(j[0]) - 1, value.i - 1, value.x,
+                                                       len(value)))
         if all_i and all_j and not check_shapes_are_assignable_1d(nrow, ncol, len(value)):
             throw_shape_err()
         _not_on_device("assign_through_matrix (sparseVector value)")
@@ -263,6 +303,8 @@ def _assign_csr_internal(x, i, j, value, P):
                 throw_shape_err()
             if v_nrow == 1 and v_ncol == 1:                      # :375-378
                 return _assign_csr_internal(x, i, j, as_csr_matrix(value).toarray().reshape(-1), P)
+            if _vec_route() and (v_nrow == 1 or v_ncol == 1):
+                return _assign_csr_internal(x, i, j, _spelled_vector(value), P)
             _not_on_device("set_single_row_to_svec")
         if v_nrow != i.size or v_ncol != ncol:
             if i_seq:                                            # :422-425
@@ -284,5 +326,7 @@ def _assign_csr_internal(x, i, j, value, P):
             throw_shape_err()
         if v_nrow == 1 and v_ncol == 1:
             return _assign_csr_internal(x, i, j, as_csr_matrix(value).toarray().reshape(-1), P)
+        if _vec_route() and (v_nrow == 1 or v_ncol == 1):
+            return _assign_csr_internal(x, i, j, _spelled_vector(value), P)
         _not_on_device("set_single_col_to_svec")
     _not_on_device("assign_through_matrix (sparse matrix value)")

@@ -1,5 +1,5 @@
 // api_assign.hip — export level of `[<-` for a dgRMatrix (host pointers): the set_* routines of the reference's
-// src/assignment.cpp as two entries over the kernels of assign.hip.  Arguments are checked before any device call;
+// src/assignment.cpp as four entries over the kernels of assign.hip and assignvec.hip.  Arguments are checked before any device call;
 // the alias cases (the reference returning its input vectors) are decided from the count pass, before any fill.
 #include "mx_export.h"
 
@@ -195,6 +195,150 @@ static int rows_begin(const int32_t *indptr, int nrows, const int32_t *indices, 
     });
 }
 
+// ---- vector values: one row or one column -------------------------------------------------------
+// Host checks of a pattern (ii, xx, n_xx, length) recycled along an axis of n entries, before any device call.
+static int pattern_check(const char *what, const char *axis, const int32_t *ii, const double *xx, int64_t n_xx,
+                         int length, int n, bool ascending)
+{
+    MX_REQUIRE(length > 0, "%s: the value's length %d is not positive", what, length);
+    MX_REQUIRE(length <= n && n % length == 0, "%s: the value's length %d does not divide the %d %s", what, length, n,
+               axis);
+    MX_REQUIRE(n_xx >= 0 && n_xx <= length, "%s: the value has %lld entries, its length is %d", what,
+               (long long)n_xx, length);
+    MX_REQUIRE(n_xx == 0 || xx, "%s: null values of the vector", what);
+    if (!ii || n_xx == 0) {
+        MX_REQUIRE(n_xx == 0 || n_xx == length, "%s: a dense vector of %lld values, its length is %d", what,
+                   (long long)n_xx, length);
+        return 0;
+    }
+    for (int64_t t = 0; t < n_xx; t++) {
+        MX_REQUIRE(ii[t] >= 0 && ii[t] < length, "%s: vector index %d outside [0, %d)", what, ii[t], length);
+        MX_REQUIRE(!ascending || t == 0 || ii[t] > ii[t - 1], "%s: the vector's indices are not strictly ascending",
+                   what);
+    }
+    return 0;
+}
+
+// The pattern on the device.  A sparse pattern without entries keeps a non-null ii, which is what says "sparse" to
+// the device level.
+struct Pattern {
+    Dev<int32_t> ii;
+    Dev<double> xx;
+    bool dense = false;
+    int upload(const int32_t *h_ii, const double *h_xx, int64_t n_xx)
+    {
+        dense = !h_ii && n_xx > 0;
+        if (!dense && ii.upload(h_ii, n_xx)) return 1;
+        return xx.upload(h_xx, n_xx);
+    }
+    const int32_t *ii_ptr() const { return dense ? nullptr : (const int32_t *)ii; }
+};
+
+static int row_vec_begin(const int32_t *indptr, int nrows, const int32_t *indices, const double *values, int ncols,
+                         int row, const int32_t *ii, const double *xx, int64_t n_xx, int length, mx_result **res_out,
+                         mx_result_info *info)
+{
+    const char *what = "mx_assign_csr_row_vec_begin";
+    MX_REQUIRE(res_out && info, "%s: null output pointer", what);
+    if (csr_args_check(what, indptr, nrows, indices, values)) return 1;
+    MX_REQUIRE(ncols >= 0, "%s: negative number of columns %d", what, ncols);
+    MX_REQUIRE(row >= 0 && row < nrows, "%s: row index %d outside [0, %d)", what, row, nrows);
+    if (pattern_check(what, "columns", ii, xx, n_xx, length, ncols, false)) return 1;
+    *res_out = nullptr;
+    const bool dense = !ii && n_xx > 0;
+    const int n_repeats = ncols / length;
+    const int64_t nnz = indptr[nrows], v_nnz = n_xx * n_repeats;
+    const int s = indptr[row], e = indptr[row + 1];
+    // the caller's own vectors hold the row: does it already spell the recycled pattern, element for element?
+    bool same = (int64_t)e - s == v_nnz && v_nnz > 0;
+    for (int64_t t = 0; same && t < v_nnz; t++)
+        same = indices[s + t] == (dense ? (int32_t)t : ii[t % n_xx] + length * (int32_t)(t / n_xx));
+    const double avg = nrows > 0 ? (double)(nnz + v_nnz) / (double)nrows : 0.0;
+    return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
+        Pattern pat;
+        if (pat.upload(ii, xx, n_xx)) return 1;
+        if (same) {                                              // values only, beside the caller's structure
+            res.alias(1, (int64_t)nrows + 1, nnz);
+            if (res.alloc_values(nnz, sizeof(double))) return 1;
+            if (mx::xfer_h2d(res.values, values, (size_t)nnz * sizeof(double))) return 1;
+            return mxd_csr_expand_pattern_row(pat.ii_ptr(), pat.xx, n_xx, length, n_repeats, nullptr, nullptr,
+                                              (double *)res.values + s, nullptr);
+        }
+        Csr X;
+        Dev<int32_t> vp, vj;
+        Dev<double> vx;
+        DevBuf ws;
+        if (X.upload(indptr, indices, values, nrows, sizeof(double))) return 1;
+        if (vp.alloc(2) || vj.alloc(v_nnz) || vx.alloc(v_nnz)) return 1;
+        if (mxd_csr_expand_pattern_row(pat.ii_ptr(), pat.xx, n_xx, length, n_repeats, vp, vj, vx, nullptr)) return 1;
+        const mx_coo_axis ai = {MX_AXIS_AFFINE, row, row, 0, 0, nullptr, nullptr};
+        if (ws.alloc_bytes(mxd_gather_workspace_bytes(nrows))) return 1;
+        if (res.alloc_indptr((int64_t)nrows + 1)) return 1;
+        int64_t total = 0;
+        if (mxd_csr_replace_rows_count(nrows, X.p, &ai, 1, vp, res.indptr, ws, &total, nullptr)) return 1;
+        if (res.alloc_entries(total, sizeof(double))) return 1;
+        return mxd_csr_replace_rows_fill(nrows, X.p, X.j, X.x, &ai, 1, vp, vj, vx, avg, res.indptr, res.indices,
+                                         res.values, nullptr);
+    });
+}
+
+static int col_vec_begin(const int32_t *indptr, int nrows, const int32_t *indices, const double *values, int ncols,
+                         int col, const int32_t *ii, const double *xx, int64_t n_xx, int length, mx_result **res_out,
+                         mx_result_info *info)
+{
+    const char *what = "mx_assign_csr_col_vec_begin";
+    MX_REQUIRE(res_out && info, "%s: null output pointer", what);
+    if (csr_args_check(what, indptr, nrows, indices, values)) return 1;
+    MX_REQUIRE(ncols >= 0, "%s: negative number of columns %d", what, ncols);
+    MX_REQUIRE(col >= 0 && col < ncols, "%s: column index %d outside [0, %d)", what, col, ncols);
+    if (pattern_check(what, "rows", ii, xx, n_xx, length, nrows, true)) return 1;
+    *res_out = nullptr;
+    const int64_t nnz = indptr[nrows];
+    const double avg = nrows > 0 ? (double)nnz / (double)nrows : 0.0;
+    return begin_result(res_out, info, MX_F64, [&](mx_result &res) {
+        Pattern pat;
+        if (pat.upload(ii, xx, n_xx)) return 1;
+        Csr X;
+        DevBuf ws;
+        if (X.upload(indptr, indices, values, nrows, sizeof(double))) return 1;
+        // an insert wants a sorted row: rows that are not are sorted in the device copy, all of them (the reference
+        // sorts the rows it inserts into, src/assignment.cpp:67-112, and leaves the others as stored)
+        int sorted = 1;
+        if (nnz > 1) {
+            Dev<int32_t> flag;
+            if (flag.alloc(4)) return 1;
+            if (mxd_csr_rows_sorted(nrows, X.p, X.j, flag, &sorted, nullptr)) return 1;
+            if (!sorted) {
+                Dev<int32_t> tj;
+                Dev<double> tx;
+                if (tj.alloc(nnz) || tx.alloc(nnz)) return 1;
+                if (mxd_csr_sort_rows(nrows, nnz, X.p, X.j, X.x, MX_F64, tj, tx, nullptr)) return 1;
+                MX_HIP(hipStreamSynchronize(nullptr));             // tj / tx are freed on leaving this block
+            }
+        }
+        if (ws.alloc_bytes(mxd_gather_workspace_bytes(nrows))) return 1;
+        Dev<int32_t> new_p;                                       // the result's only when the structure changes
+        if (new_p.alloc((int64_t)nrows + 1)) return 1;
+        int64_t total = 0, changed = 0;
+        if (mxd_csr_assign_col_count(nrows, ncols, X.p, X.j, nnz, col, pat.ii_ptr(), n_xx, length, avg, new_p, ws,
+                                     &total, &changed, nullptr)) return 1;
+        // set_single_col_to_colvec's diff == 0 branch (:856-873); set_single_col_to_svec always builds new vectors
+        const bool same_structure = pat.dense && changed == 0 && sorted;
+        if (same_structure) {
+            res.alias(1, (int64_t)nrows + 1, nnz);
+            if (res.alloc_values(nnz, sizeof(double))) return 1;
+        } else {
+            if (res.alloc_indptr((int64_t)nrows + 1)) return 1;
+            if (res.indptr.copy_from(new_p, (int64_t)nrows + 1)) return 1;
+            if (res.alloc_entries(total, sizeof(double))) return 1;
+        }
+        const int32_t *const rp = same_structure ? (const int32_t *)X.p : (const int32_t *)res.indptr;
+        int32_t *const rj = same_structure ? nullptr : (int32_t *)res.indices;
+        return mxd_csr_assign_col_fill(nrows, ncols, X.p, X.j, X.x, col, pat.ii_ptr(), pat.xx, n_xx, length, avg, rp,
+                                       rj, res.values, nullptr);
+    });
+}
+
 // the selector maps live in std::vector: an allocation failure becomes an error, not an exception through the C ABI
 extern "C" {
 
@@ -219,6 +363,28 @@ int mx_assign_csr_rows_begin(const int32_t *indptr, int nrows, const int32_t *in
     try {
         return rows_begin(indptr, nrows, indices, values, i_kind, i_lo, i_hi, rows_set, n_rows_set, v_indptr, v_nrows,
                           v_indices, v_values, res, info);
+    } catch (const std::bad_alloc &) {
+        return set_error("out of host memory");
+    }
+}
+
+int mx_assign_csr_row_vec_begin(const int32_t *indptr, int nrows, const int32_t *indices, const double *values,
+                                int ncols, int row, const int32_t *ii, const double *xx, int64_t n_xx, int length,
+                                mx_result **res, mx_result_info *info)
+{
+    try {
+        return row_vec_begin(indptr, nrows, indices, values, ncols, row, ii, xx, n_xx, length, res, info);
+    } catch (const std::bad_alloc &) {
+        return set_error("out of host memory");
+    }
+}
+
+int mx_assign_csr_col_vec_begin(const int32_t *indptr, int nrows, const int32_t *indices, const double *values,
+                                int ncols, int col, const int32_t *ii, const double *xx, int64_t n_xx, int length,
+                                mx_result **res, mx_result_info *info)
+{
+    try {
+        return col_vec_begin(indptr, nrows, indices, values, ncols, col, ii, xx, n_xx, length, res, info);
     } catch (const std::bad_alloc &) {
         return set_error("out of host memory");
     }

@@ -24,12 +24,9 @@
 //          binary search in the row.  Every slot is written once; a slot outside [new_indptr[r], new_indptr[r+1]),
 //          which only a row that is not sorted can produce, is not written.
 // Row replacement.  A selected row r becomes row k of `value`, k = r's position in the selector; a two-source gather.
-#include "mx_dispatch.h"
-#include "mx_workspace.h"
+#include "mx_assign.h"
 
 namespace mx {
-
-constexpr int AS_BLOCK = 256;
 
 struct AsgAxis {
     int map, lo, hi, rev, nmap;
@@ -89,16 +86,7 @@ void assign_count_kernel(int nrows, const int32_t *__restrict__ indptr, const in
 }
 
 // ---- scalar value: fill ------------------------------------------------------------------------------------------
-// values travel as their 64 bits: a NaN's payload (R's NA_real_) is written as given.  new_indices may be null (the
-// structure stays the caller's and only values are made).
-__device__ __forceinline__ void asg_store(int32_t *__restrict__ new_indices, uint64_t *__restrict__ new_values,
-                                          int lo, int hi, int pos, int c, uint64_t v)
-{
-    if (pos < lo || pos >= hi) return;                 // never outside the row's own slots
-    if (new_indices) new_indices[pos] = c;
-    new_values[pos] = v;
-}
-
+// every store goes through asg_store (mx_assign.h): values as their 64 bits, never outside the row's own slots
 template <int G, bool CONST>
 __global__ __launch_bounds__(AS_BLOCK)
 void assign_fill_kernel(int nrows, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
@@ -211,19 +199,6 @@ static int asg_check_axis(const char *what, const mx_coo_axis *a, int n, const c
         MX_REQUIRE(a->kind == MX_AXIS_AFFINE, "%s: unknown %s axis kind %d", what, name, a->kind);
         MX_REQUIRE(a->lo >= 0 && a->lo <= a->hi && a->hi < n, "%s: %s range [%d, %d] outside [0, %d)", what, name,
                    a->lo, a->hi, n);
-    }
-    return 0;
-}
-
-// scan the counts; a total beyond R's int32 index range fails with the reference's text (check_max_size,
-// src/assignment.cpp:380-382) before the caller allocates anything
-static int asg_finish_count(int nrows, void *workspace, int32_t *new_indptr, int64_t *nnz_out_host, hipStream_t st)
-{
-    *nnz_out_host = 0;
-    if (finish_count(nrows, workspace, new_indptr, nnz_out_host, st)) {
-        if (*nnz_out_host > (int64_t)INT_MAX)
-            return set_error("Error: resulting matrix would be larger than INT_MAX limit.");
-        return 1;
     }
     return 0;
 }

@@ -1370,3 +1370,43 @@ def set_arbitrary_rows_to_smat(indptr, indices, values, rows_set, indptr_other, 
     """src/assignment.cpp:2523-2598, in any order of rows_set and without its tail defect (:2554): row rows_set[k]
     becomes row k of the other matrix."""
     return _assign_rows(indptr, indices, values, _arb(rows_set), indptr_other, indices_other, values_other)
+
+
+def _assign_vec(fn, indptr, indices, values, ncols, at, ii, xx, length):
+    """One row or one column <- a pattern (ii, xx, length); ii None for a dense vector."""
+    p, j, v = _i32(indptr), _i32(indices), _f64(values)
+    if j.size != v.size or p.size < 1:
+        raise ValueError("indptr, indices and values do not form a CSR")
+    xx = _f64(xx)
+    ii = None if ii is None else _i32(ii)
+    if ii is not None and ii.size != xx.size:
+        raise ValueError("the vector's indices and values differ in length")
+    # an empty sparse vector travels as n_xx = 0; a dense one as a null ii
+    return _begin(fn, ptr(p), p.size - 1, ptr(j), ptr(v), int(ncols), int(at), ptr(ii), ptr(xx), xx.size, int(length),
+                  finish=_assigned, inputs=(indptr, indices, values))[0]
+
+
+def set_single_row_to_rowvec(indptr, indices, values, ncols, row_set, vec_set):
+    """src/assignment.cpp:771-837; a full row that is not sorted gives three new vectors."""
+    vec = _f64(vec_set)
+    return _assign_vec(_lib.load().mx_assign_csr_row_vec_begin, indptr, indices, values, ncols, row_set, None, vec,
+                       vec.size)
+
+
+def set_single_col_to_colvec(indptr, indices, values, ncols, col_set, vec_set):
+    """src/assignment.cpp:839-913."""
+    vec = _f64(vec_set)
+    return _assign_vec(_lib.load().mx_assign_csr_col_vec_begin, indptr, indices, values, ncols, col_set, None, vec,
+                       vec.size)
+
+
+def set_single_row_to_svec(indptr, indices, values, ncols, row_set, ii, xx, length):
+    """src/assignment.cpp:915-1007, ii 0-based in any order; without the two defects of its fast path (:939-966)."""
+    return _assign_vec(_lib.load().mx_assign_csr_row_vec_begin, indptr, indices, values, ncols, row_set, _i32(ii), xx,
+                       length)
+
+
+def set_single_col_to_svec(indptr, indices, values, ncols, col_set, ii, xx, length):
+    """src/assignment.cpp:1009-1133, ii 0-based and ascending: always new vectors."""
+    return _assign_vec(_lib.load().mx_assign_csr_col_vec_begin, indptr, indices, values, ncols, col_set, _i32(ii), xx,
+                       length)
