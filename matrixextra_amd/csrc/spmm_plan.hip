@@ -402,13 +402,70 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
     real_t *const my_rows = my_oct + (size_t)g * PLAN_RB * S + lg * VEC;                // this group's bundle
     MX_PROBE(long long pr_t = 0; int pr_kind = 0; unsigned long long pr_sum[3] = {0, 0, 0}; unsigned pr_cnt[3] = {0, 0, 0};)
 
+    // What a wavefront carries from one work item to its next one (item + nwg: octet n_oct), so that the next item
+    // starts without a load it has to wait for behind its predecessor's stores of C:
+    //   * n_row: the next octet's row of step_off (lane p = start of panel p), a vector load issued at the START of
+    //     the current item: it is older than every B-line load of the item and returns with the first of them.
+    //   * n_beg / n_end: the next octet's first step and end, scalars (the address is wave-uniform, so these are
+    //     scalar loads).  A scalar load is waited for at the next barrier, whoever uses it, and the current item needs
+    //     n_beg in front of its stream loop (the last read-ahead goes there).  So they are read one item EARLIER still:
+    //     an item issues the loads for the item after next (f_oct, f_beg, f_end) behind its first barrier, and the
+    //     next item takes them over as its n_beg / n_end.  Only a workgroup's first item waits for bounds.
+    //   * (rc, rv): the next octet's first plan chunk, read by the stream loop's last read-ahead (see there);
+    //     held_step is the step it was read from.  A chunk is a function of its step alone (the plan is read-only
+    //     here), so an item may use the held chunk whenever held_step equals its first step, and loads the chunk itself
+    //     in every other case: the first item, the item behind an empty stream, an item without a predecessor.
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);       // the compiler cannot prove threadIdx.x >> 6 uniform
+    // item = slab * ngens + gen moves on by nwg per item: one 64-bit divide in front of the first item, none between
+    // the epilogue of one item and the first loads of the next
+    const int gen_step = nwg % ngens, slab_step = nwg / ngens;
+    int slab_c = (int)((lo + wg) / ngens), gen_c = (int)((lo + wg) % ngens);
+    int n_oct = -1, n_row = 0, n_beg = 0, n_end = 0;
+    int f_oct = -1, f_beg = 0, f_end = 0;
+    int held_step = -1;
+    int rc[PLAN_CHUNK];
+    double rv[PLAN_CHUNK];
+#pragma unroll
+    for (int k = 0; k < PLAN_CHUNK; k++) { rc[k] = 0; rv[k] = 0.0; }
+
     for (int it = 0; it < niter; it++) {
         const long long item_raw = lo + wg + (long long)it * nwg;
         const bool have = item_raw < hi;
-        const long long item = have ? item_raw : lo;
-        const int slab = (int)(item / ngens), gen = (int)(item % ngens);
-        const int oct = gen * PLAN_WAVES + wave;
+        const int slab = have ? slab_c : 0, gen = have ? gen_c : 0;
+        const int oct = gen * PLAN_WAVES + wave_u;
         const bool oct_ok = have && oct < noct;
+
+        // This item's bounds: carried by the previous item, or (first item, previous item without an octet) read
+        // here and waited for inside the branch, so that the carried path meets no wait at all.
+        int so_row = 0, sbeg = 0, send = 0;
+        if (oct_ok) {
+            if (n_oct != oct) {
+                n_row = step_off[(size_t)oct * npanels + min(lane, npanels)];
+                n_beg = step_off[(size_t)oct * npanels];
+                n_end = step_off[(size_t)oct * npanels + npanels];
+                asm volatile("" : "+v"(n_row));
+            }
+            so_row = n_row; sbeg = n_beg; send = n_end;
+        }
+        // The next item's bounds.  It exists iff item + nwg is inside the XCD group's range and its octet inside the
+        // matrix; otherwise the load goes to octet 0 (always there) and is not used.  n_beg / n_end are what the
+        // previous item read as f_beg / f_end, or (first item) are read here.
+        int ngen = gen_c + gen_step;
+        slab_c += slab_step + (ngen >= ngens ? 1 : 0);
+        ngen -= ngen >= ngens ? ngens : 0;
+        gen_c = ngen;
+        {
+            const int noct_raw = ngen * PLAN_WAVES + wave_u;
+            const bool nvalid = item_raw + nwg < hi && noct_raw < noct;
+            const size_t nrow0 = nvalid ? (size_t)noct_raw * npanels : 0;
+            n_oct = nvalid ? noct_raw : -1;
+            n_row = step_off[nrow0 + min(lane, npanels)];
+            if (nvalid && f_oct != noct_raw) {
+                f_beg = step_off[nrow0];
+                f_end = step_off[nrow0 + npanels];
+            }
+            n_beg = f_beg; n_end = f_end;
+        }
         // slab base is wave-uniform (scalar registers), the per-lane part is a 32-bit byte offset: one VALU op per
         // address.  A slab is K x 128 B < 4 GiB because K < 2^27... checked on the host (K * 128 < 2^32).
         const char *__restrict__ Bbase = reinterpret_cast<const char *>(Bp + (size_t)slab * slab_stride);
@@ -418,6 +475,17 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
         // workgroup-wide synchronisation around a generation, the wavefronts only meet at the panel boundaries.
         for (int i = lane; i < PLAN_OCT_ROWS * S; i += 64) my_oct[i] = 0;
         if (sync_mode > 0) __syncthreads();                          // locality only: start the first panel together
+        // the bounds of the item after next, behind the barrier: nothing waits for them before the first panel meeting
+        {
+            int fgen = ngen + gen_step;
+            fgen -= fgen >= ngens ? ngens : 0;
+            const int foct_raw = fgen * PLAN_WAVES + wave_u;
+            const bool fvalid = item_raw + 2LL * nwg < hi && foct_raw < noct;
+            const size_t frow0 = fvalid ? (size_t)foct_raw * npanels : 0;
+            f_oct = fvalid ? foct_raw : -1;
+            f_beg = step_off[frow0];
+            f_end = step_off[frow0 + npanels];
+        }
 
         // One continuous, software-pipelined stream over the octet's entries of ALL panels (they are contiguous in
         // the plan).  Panel boundaries only matter for locality: when the stream crosses one, the 16 waves of the
@@ -428,18 +496,14 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
         // data and drift by a fraction of a panel.
         {
             if (sync_mode >= 2) xcd_timing_barrier(my_ctr, (unsigned)(it + 1) * (unsigned)nwg);
-            // The octet's whole row of step_off is read here, once: lane p holds the start of panel p (npanels <= 64
-            // lanes), the end of the last panel sits in a second register.  Every panel boundary the stream meets
-            // later is a v_readlane of that register: a load at the meeting would have to be waited for with
-            // vmcnt(0), and vector loads return in order, so that wait would drain the B lines and the plan chunk in
-            // flight.
-            int so_row = 0, so_end = 0;
-            if (oct_ok) {
-                if (lane < npanels) so_row = step_off[(size_t)oct * npanels + lane];
-                so_end = step_off[(size_t)oct * npanels + npanels];
-            }
-            const int sbeg = __builtin_amdgcn_readfirstlane(so_row);   // wave-uniform: keep the loop control scalar
-            const int send = __builtin_amdgcn_readfirstlane(so_end);
+            // The octet's whole row of step_off is in a register (so_row, see the carry above): lane p holds the
+            // start of panel p (npanels <= 64 lanes), the first step and the end of the last panel are scalars.
+            // Every panel boundary the stream meets later is a v_readlane of that register: a load at the meeting
+            // would have to be waited for with vmcnt(0), and vector loads return in order, so that wait would drain
+            // the B lines and the plan chunk in flight.
+            // Where the last read-ahead of this stream goes: the next item's first step, or (no next item) -1.  Taken
+            // here, in front of the loop (n_beg was read an item ago), so that no wait for a scalar load is inside it.
+            const int nfirst = n_oct >= 0 ? n_beg : -1;
             int next_b = npanels > 1 ? __builtin_amdgcn_readlane(so_row, 1) : send;
             int p = 0;
             int cur = 0;
@@ -461,13 +525,17 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
             // Vector loads return in order, so a slot read that misses to HBM (the plan is a pure stream) holds back
             // every younger B-line load behind it; fetching one batch per iteration put that full latency into every
             // iteration (measured: 1.95 us per 8 steps per wave, whatever the locality of B).  Now it is paid once
-            // per 32 steps.  The last read-ahead of an octet runs one chunk past it (the next octet's slots / the
-            // padding behind the last octet): it is fetched and dropped, never used.  Nothing of the NEXT generation
-            // is in flight when this one's stream ends: the turnover (last batch, epilogue, zeroing, step_off row,
-            // first chunk, first batch of B lines, each waited for in turn) measures 11 us per generation and
-            // wavefront, see DESIGN.md 4.1.
-            int rc[PLAN_CHUNK], rn[PLAN_CHUNK];
-            double rv[PLAN_CHUNK], rvn[PLAN_CHUNK];
+            // per 32 steps.  The last read-ahead of an octet has nothing of this octet left to fetch: it reads the
+            // first chunk of the wavefront's NEXT work item instead (a scalar select of the step, the same four loads),
+            // which stays in (rc, rv) across the epilogue, so the next item starts its B-line loads without a plan
+            // read (first touch of an HBM stream) to wait for.  Without a next item it runs one chunk past the octet,
+            // as it always did, and is dropped.  Either way it reads slots [8 t, 8 t + 256) with t <= total steps
+            // (t = this octet's end, or step_off[next octet * P], the sum of the steps in front of that octet):
+            // inside the PLAN_TAIL_SLOTS = 512 slots of padding behind the last octet.
+            // What is still not in flight when a stream ends is the next item's first batch of B lines: the turnover
+            // is last batch, epilogue, zeroing, first batch of B lines, see DESIGN.md 4.1.
+            int rn[PLAN_CHUNK];
+            double rvn[PLAN_CHUNK];
             auto load_chunk = [&](int step, int (&c)[PLAN_CHUNK], double (&v)[PLAN_CHUNK]) {
                 const long long e = (long long)step * 8 + lane;
 #pragma unroll
@@ -501,10 +569,11 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
                 for (int v = 0; v < VEC; v++) asm volatile("" : "+v"(acc[v]));
                 __builtin_amdgcn_sched_barrier(0);
             };
-            if (send > sbeg) {
+            if (send > sbeg && held_step != sbeg) {
                 load_chunk(sbeg, rc, rv);
                 // the first chunk has to be there before anything can start; with it complete at loop entry the
-                // compiler's vmcnt bookkeeping is exact on both edges of the loop
+                // compiler's vmcnt bookkeeping is exact on both edges of the loop.  (A held chunk is complete: it is
+                // older than the B lines the previous stream's last batch waited for.)
 #pragma unroll
                 for (int k = 0; k < PLAN_CHUNK; k++) asm volatile("" : "+v"(rc[k]), "+v"(rv[k]));
             }
@@ -513,7 +582,9 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
             // B-line loads per wavefront are in flight all the time.  The first pass consumes the no-op batch set up
             // above, the last batch is consumed after the loop.
             for (int s = sbeg; s < send; s += U * PLAN_CHUNK) {      // sbeg, send are wave-uniform
-                load_chunk(s + U * PLAN_CHUNK, rn, rvn);
+                const int ahead = s + U * PLAN_CHUNK;
+                const int ra = ahead >= send && nfirst >= 0 ? nfirst : ahead;
+                load_chunk(ra, rn, rvn);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int k = 0; k < PLAN_CHUNK; k++) {
@@ -546,6 +617,7 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
                 }
 #pragma unroll
                 for (int k = 0; k < PLAN_CHUNK; k++) { rc[k] = rn[k]; rv[k] = rvn[k]; }
+                held_step = ra;
             }
             MX_PROBE(if (send > sbeg) { pr_kind = 3; pr_t = wall_clock64(); })
 #pragma unroll
