@@ -558,6 +558,42 @@ int mxd_coo_slice_fill(int nrow, int ncol, const int32_t *rows, const int32_t *c
 size_t mxd_coo_single_workspace_bytes(void);
 int mxd_coo_single(const int32_t *rows, const int32_t *cols, const void *values, int value_dtype, int64_t nnz,
                    int r, int c, void *workspace, int64_t *k_host, void *value_host, void *stream);
+/* NA rows / columns injected into a COO (coona.hip), replacing inject_NAs_inplace_coo_template
+ * (src/slice_coo.cpp:708-946).  rows_na[n_rna] / cols_na[n_cna]: device arrays of 0-based indices, ascending and
+ * distinct (which(is.na(.)) - 1L); a list that is not, or that leaves [0, nrow) / [0, ncol), fails the count.
+ * Output, bit for bit the reference's: the kept triplets in storage order (a triplet is dropped when its row is an
+ * NA row / its column an NA column, and when both lists are given only when both hold), then the NA block, every
+ * value NA_real_ (MX_F64) or NA_LOGICAL (MX_LGL):
+ *   n_rna > n_cna:  (r, 0 .. ncol-1) per r of rows_na, then (rem[k], c), k < nrow - n_rna, per c of cols_na
+ *   otherwise:      (0 .. nrow-1, c) per c of cols_na, then (r, rem[k]), k < ncol - n_cna, per r of rows_na
+ * where rem is what the reference's swap loop (:729-739) leaves of 0 .. n-1 over the major axis.
+ * count: *nnz_out_host = kept + n_rna*ncol + n_cna*(nrow - n_rna) in 64 bits after one read-back; a total above
+ * INT32_MAX fails the call.  fill writes that many entries.  value_dtype MX_F64 or MX_LGL.
+ * Two caller-allocated regions, shared by both passes: workspace, mxd_compact_workspace_bytes(nnz) bytes (the kept
+ * pass is the tiled compaction of compact.hip), and maps, int32[4 + nrow + ncol + max(nrow, ncol)] (the list
+ * flags, the two membership maps and rem). */
+int mxd_coo_inject_na_count(int nrow, int ncol, const int32_t *rows, const int32_t *cols, int64_t nnz,
+                            const int32_t *rows_na, int64_t n_rna, const int32_t *cols_na, int64_t n_cna,
+                            void *workspace, int32_t *maps, int64_t *nnz_out_host, void *stream);
+int mxd_coo_inject_na_fill(int nrow, int ncol, const int32_t *rows, const int32_t *cols, const void *values,
+                           int value_dtype, int64_t nnz, const int32_t *rows_na, int64_t n_rna,
+                           const int32_t *cols_na, int64_t n_cna, const void *workspace, const int32_t *maps,
+                           int32_t *out_rows, int32_t *out_cols, void *out_values, void *stream);
+/* X[i, j] with scalar i, j of a CSR (extract_single_val_csr with is_sorted = false, src/slice.cpp:661-785):
+ * *k_host = the first k of [indptr[r], indptr[r+1]), in storage order, with indices[k] == c, or -1 (an empty row is
+ * no hit); value_host as for mxd_coo_single.  One wavefront, one host read-back.  workspace: 16 bytes. */
+int mxd_csr_single(int nrows, const int32_t *indptr, const int32_t *indices, const void *values, int value_dtype,
+                   int64_t nnz, int r, int c, void *workspace, int64_t *k_host, void *value_host, void *stream);
+/* repeat_indices_n_times (src/slice.cpp:636-659): out[t + n_indices*rep] = indices[t] + ix_length*rep for
+ * rep < desired_length / ix_length, then out[n_indices*full + t] = remainder[t] + ix_length*full; out holds
+ * n_indices * (desired_length / ix_length) + n_remainder entries. */
+int mxd_repeat_indices(const int32_t *indices, int64_t n_indices, const int32_t *remainder, int64_t n_remainder,
+                       int ix_length, int desired_length, int32_t *out, void *stream);
+/* The dense vector of n entries at distinct 0-based positions (drop_slice's as.vector(), R/slice.R:210-236):
+ * out[len] (out_dtype MX_F64, or MX_LGL for int32 R logicals) is zero-filled, then out[pos[k]] = values[k], or 1
+ * when value_dtype is MX_NONE; otherwise value_dtype equals out_dtype.  Positions outside [0, len) are skipped. */
+int mxd_entries_to_dense_vector(const int32_t *pos, const void *values, int value_dtype, int64_t n, void *out,
+                                int out_dtype, int64_t len, void *stream);
 
 /* X[i, j] <- scalar and X[i, ] <- CSR of a CSR with f64 values (assign.hip): count -> scan -> fill
  * with one lane group per row, chosen from avg_row_len as for mxd_csr_colrange_*.  Both selectors are mx_coo_axis
@@ -878,6 +914,27 @@ int mx_slice_coo_arbitrary_begin(const int32_t *ii, const int32_t *jj, const voi
  * the value of the first one in storage order. */
 int mx_slice_coo_single(const int32_t *ii, const int32_t *jj, const void *xx, int value_dtype, int64_t nnz, int i,
                         int j, int *found, void *value_out);
+/* inject_NAs_inplace_coo_{numeric,logical}  src/slice_coo.cpp:902-946 (R/slice.R:177-194), through
+ * mxd_coo_inject_na_count / _fill: value_dtype MX_F64 or MX_LGL; rows_na / cols_na 0-based, ascending, distinct.
+ * The result is a COO held in the mx_result, as for mx_slice_coo_arbitrary_begin.  Both lists empty gives an empty
+ * result (the reference returns an empty list there, and R then leaves the matrix alone). */
+int mx_inject_NAs_inplace_coo_begin(const int32_t *ii, const int32_t *jj, const void *xx, int value_dtype,
+                                    int64_t nnz, const int32_t *rows_na, int64_t n_rows_na, const int32_t *cols_na,
+                                    int64_t n_cols_na, int nrows, int ncols, mx_result **res, mx_result_info *info);
+/* extract_single_val_csr_{numeric,logical,binary}  src/slice.cpp:737-785: row, col 0-based; *found = 1 when the row
+ * stores the column, and value_out (when non-null; f64 for MX_F64, int32 for MX_LGL) receives the value of the first
+ * such entry in storage order. */
+int mx_extract_single_val_csr(const int32_t *indptr, int nrows, const int32_t *indices, const void *values,
+                              int value_dtype, int row, int col, int *found, void *value_out);
+/* repeat_indices_n_times  src/slice.cpp:636-659; out holds n_indices * (desired_length / ix_length) + n_remainder
+ * entries. */
+int mx_repeat_indices_n_times(const int32_t *indices, int64_t n_indices, const int32_t *remainder,
+                              int64_t n_remainder, int ix_length, int desired_length, int32_t *out);
+/* as.vector() of a one-row / one-column slice (drop_slice, R/slice.R:210-236) through mxd_entries_to_dense_vector:
+ * out[len] of out_dtype (MX_F64, or MX_LGL for int32 R logicals); pos are distinct 0-based positions inside
+ * [0, len). */
+int mx_entries_to_dense_vector(const int32_t *pos, const void *values, int value_dtype, int64_t n, void *out,
+                               int out_dtype, int64_t len);
 /* remove_sparse_zeros (R/utils.R:255-346) through mxd_compact_count / _fill.  remove_NAs is the na.rm flag; the
  * keep rule of each export is the reference's loop, quirks included.  When every entry is kept,
  * info.alias_structure = MX_ALIAS_ALL: the reference returns the input vectors themselves (src/misc.cpp:586-590,

@@ -20,32 +20,13 @@
 // fall into rows: a 1 M-entry row is 256 tiles like any other 1 M entries.
 // Loads of a tile are issued together ahead of their first use, in blocks hoisted out of any per-element condition
 // (a wave-uniform condition per element still makes hipcc wait for each load in turn).
+#include "mx_compact_tile.h"
 #include "mx_workspace.h"
 
 namespace mx {
 
-constexpr int CP_BLOCK = 256;
-constexpr int CP_WAVES = CP_BLOCK / MX_WAVE;
-constexpr int CP_ROUNDS = 16;
-constexpr int CP_TILE = CP_BLOCK * CP_ROUNDS;      // 4096 entries per tile
-static_assert(CP_ROUNDS * CP_WAVES == MX_WAVE, "one lane of wave 0 per (round, wave) pair");
-
 template <int VB> struct CpValue { using T = int32_t; };     // 4: R logical / integer; 0: no values
 template <> struct CpValue<8> { using T = double; };
-
-// a[r] = src[base + r * CP_BLOCK + threadIdx.x] for the tile's entries (0 past n)
-template <typename T>
-__device__ __forceinline__ void cp_load(T (&a)[CP_ROUNDS], const T *__restrict__ src, int64_t base, int64_t n)
-{
-    const T *s = src + base + threadIdx.x;
-    if (base + CP_TILE <= n) {
-#pragma unroll
-        for (int r = 0; r < CP_ROUNDS; r++) a[r] = s[r * CP_BLOCK];
-    } else {
-#pragma unroll
-        for (int r = 0; r < CP_ROUNDS; r++) a[r] = base + r * CP_BLOCK + threadIdx.x < n ? s[r * CP_BLOCK] : T{};
-    }
-}
 
 // the keep rule (mx_keep_rule) on a loaded value / mask entry
 template <int VB>
@@ -70,8 +51,6 @@ void compact_count_kernel(int64_t n, const void *__restrict__ values, int rule, 
                           int32_t *__restrict__ tile_counts)
 {
     using T = typename CpValue<VB>::T;
-    __shared__ int s_cnt[CP_WAVES];
-    const int wave = threadIdx.x / MX_WAVE;
     const int64_t base = (int64_t)blockIdx.x * CP_TILE;
     T v[CP_ROUNDS];
     int mk[CP_ROUNDS];
@@ -90,14 +69,7 @@ void compact_count_kernel(int64_t n, const void *__restrict__ values, int rule, 
         const bool in = base + r * CP_BLOCK + threadIdx.x < n;
         cnt += __popcll(__ballot(in && cp_keep<VB>(rule, v[r], mk[r])));
     }
-    if (lane_id() == 0) s_cnt[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-#pragma unroll
-        for (int w = 0; w < CP_WAVES; w++) t += s_cnt[w];
-        tile_counts[blockIdx.x] = t;
-    }
+    cp_store_tile_count(cnt, tile_counts);
 }
 
 // tile_off[tile] = kept entries before the tile (exclusive scan of the counts).  Outputs may be null (not written).
@@ -110,13 +82,10 @@ void compact_fill_kernel(int64_t n, int64_t ntiles, const void *__restrict__ val
                          int32_t *__restrict__ out1, void *__restrict__ out_values, int32_t *__restrict__ out_indptr)
 {
     using T = typename CpValue<VB>::T;
-    __shared__ unsigned long long s_mask[MX_WAVE];        // [round * CP_WAVES + wave]
-    __shared__ int s_off[MX_WAVE];                        // exclusive in-tile offset of that (round, wave)
-    __shared__ int s_total;
-    const int lane = lane_id(), wave = threadIdx.x / MX_WAVE;
+    __shared__ CpTileRanks S;
+    const int lane = lane_id();
     const int64_t base = (int64_t)blockIdx.x * CP_TILE;
     const int64_t len = n - base < CP_TILE ? n - base : CP_TILE;
-    const unsigned long long below = (1ull << lane) - 1;
 
     T v[CP_ROUNDS];
     int mk[CP_ROUNDS], i0[CP_ROUNDS], i1[CP_ROUNDS];
@@ -131,26 +100,13 @@ void compact_fill_kernel(int64_t n, int64_t ntiles, const void *__restrict__ val
         if (rule != MX_KEEP_MASK) mk[r] = 0;
         const bool in = base + r * CP_BLOCK + threadIdx.x < n;
         bal[r] = __ballot(in && cp_keep<VB>(rule, v[r], mk[r]));
-        if (lane == 0) s_mask[r * CP_WAVES + wave] = bal[r];
     }
-    __syncthreads();
-    if (wave == 0) {                                      // scan of the 64 (round, wave) counts in storage order
-        const int c = __popcll(s_mask[lane]);
-        int incl = c;
-#pragma unroll
-        for (int off = 1; off < MX_WAVE; off <<= 1) {
-            const int o = __shfl_up(incl, off, MX_WAVE);
-            if (lane >= off) incl += o;
-        }
-        s_off[lane] = incl - c;
-        if (lane == MX_WAVE - 1) s_total = incl;
-    }
-    __syncthreads();
+    cp_rank_tile(S, bal);
     const int64_t t0 = tile_off[blockIdx.x];
 #pragma unroll
     for (int r = 0; r < CP_ROUNDS; r++) {
         if (!((bal[r] >> lane) & 1)) continue;
-        const int64_t q = t0 + s_off[r * CP_WAVES + wave] + __popcll(bal[r] & below);
+        const int64_t q = t0 + cp_rank_of(S, r, bal[r]);
         if (out0) out0[q] = i0[r];
         if (out1) out1[q] = i1[r];
         if constexpr (VB != 0) {
@@ -183,12 +139,7 @@ void compact_fill_kernel(int64_t n, int64_t ntiles, const void *__restrict__ val
         if (p >= end) break;                              // p is non-decreasing: later rows start later still
         if (p < base) continue;                           // only for a non-monotone p: never index LDS with it
         const int64_t qi = p - base;
-        int rank;
-        if (qi >= len) rank = s_total;
-        else {
-            const int slot = (int)(qi / MX_WAVE);         // = round * CP_WAVES + wave of entry p
-            rank = s_off[slot] + __popcll(s_mask[slot] & ((1ull << (qi % MX_WAVE)) - 1));
-        }
+        const int rank = qi >= len ? S.total : cp_rank_before(S, (int)qi);
         out_indptr[r] = (int32_t)(t0 + rank);
     }
 }

@@ -331,6 +331,54 @@ def coo_slice(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor | None, m: int, 
     return oi[:k], oj[:k], None if ox is None else ox[:k]      # reuses the blocks only on this same stream)
 
 
+def coo_inject_na(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor, m: int, n: int, rows_na: torch.Tensor,
+                  cols_na: torch.Tensor):
+    """NA rows / columns injected into an m x n COO held in HBM through mxd_coo_inject_na_count / _fill (DESIGN.md
+    §4.18), as (i, j, x) of the result: the triplets that stay, in storage order, then the NA block.  x: float64
+    (NA_real_) or int32 R logicals (NA_LOGICAL); rows_na / cols_na: int32 tensors of 0-based indices, ascending and
+    distinct (either may be empty)."""
+    lib = _lib.load()
+    dev = i.device
+    nnz = int(i.numel())
+    if int(j.numel()) != nnz or x is None or int(x.numel()) != nnz:
+        raise ValueError("i, j and x must have the same length")
+    for t in (i, j, rows_na, cols_na):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"i, j, rows_na and cols_na must be contiguous int32 tensors on {dev}")
+    vd = _value_dtype(x)
+    n_rna, n_cna = int(rows_na.numel()), int(cols_na.numel())
+    ws = torch.empty(max(lib.mxd_compact_workspace_bytes(nnz), 16), dtype=torch.uint8, device=dev)
+    maps = torch.empty(4 + int(m) + int(n) + max(int(m), int(n)), dtype=torch.int32, device=dev)
+    nnz_out = C.c_int64(0)
+    check(lib.mxd_coo_inject_na_count(int(m), int(n), _dp(i), _dp(j), nnz, _dp(rows_na), n_rna, _dp(cols_na), n_cna,
+                                      _dp(ws), _dp(maps), C.byref(nnz_out), _stream()))
+    k = int(nnz_out.value)
+    oi = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    oj = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    ox = torch.empty(max(k, 1), dtype=x.dtype, device=dev)
+    if k:
+        check(lib.mxd_coo_inject_na_fill(int(m), int(n), _dp(i), _dp(j), _dp(x.contiguous()), vd, nnz, _dp(rows_na),
+                                         n_rna, _dp(cols_na), n_cna, _dp(ws), _dp(maps), _dp(oi), _dp(oj), _dp(ox), _stream()))
+    return oi[:k], oj[:k], ox[:k]
+
+
+def csr_single(A: DeviceCSR, r: int, c: int):
+    """A[r, c] (0-based) of a device-resident CSR through mxd_csr_single: (found, value) of the first entry of row r,
+    in storage order, at column c; value is None for a pattern matrix or a miss."""
+    lib = _lib.load()
+    if not 0 <= int(r) < A.m:
+        raise ValueError(f"csr_single: row {r} outside [0, {A.m})")
+    vd = _value_dtype(A.values)
+    ws = torch.empty(16, dtype=torch.uint8, device=A.indptr.device)
+    k = C.c_int64(-1)
+    val = C.c_double(0.0) if vd == MX_F64 else C.c_int32(0)
+    check(lib.mxd_csr_single(A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values), vd, A.nnz, int(r), int(c), _dp(ws),
+                             C.byref(k), C.byref(val), _stream()))
+    if k.value < 0:
+        return False, None
+    return True, (None if vd == MX_NONE else val.value)
+
+
 def _csr_compact(A: DeviceCSR, rule: int, mask: torch.Tensor | None) -> DeviceCSR:
     """count (one 8-byte read-back) -> fill through mxd_compact_count / _fill; A itself when a zero rule keeps all."""
     lib = _lib.load()

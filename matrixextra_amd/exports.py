@@ -981,6 +981,95 @@ def slice_coo_single_binary(ii, jj, i, j) -> bool:
     return hit
 
 
+# ----------------------------------------------------------------------------- what finishes `[` (coona.hip): NA
+#                                                       injection, the CSR scalar lookup, recycled selector indices
+def _inject_NAs_inplace_coo(ii, jj, xx, vdt, rows_na, cols_na, nrows, ncols):
+    i, j = _i32(ii), _i32(jj)
+    v = np.ascontiguousarray(xx, dtype=np.float64 if vdt == MX_F64 else np.int32)
+    if i.size != j.size or v.size != i.size:
+        raise ValueError("indices and values have different number of entries")
+    rn, cn = _i32(rows_na).reshape(-1), _i32(cols_na).reshape(-1)
+    if rn.size == 0 and cn.size == 0:
+        return {}                                   # the reference's empty list: nothing to inject
+    out = _begin(_lib.load().mx_inject_NAs_inplace_coo_begin, ptr(i), ptr(j), ptr(v), vdt, i.size, ptr(rn), rn.size,
+                 ptr(cn), cn.size, int(nrows), int(ncols), empty_values_dtype=v.dtype)[0]
+    return dict(ii=out["indptr"], jj=out["indices"], xx=out["values"].astype(v.dtype, copy=False))
+
+
+def inject_NAs_inplace_coo_numeric(ii, jj, xx, rows_na_, cols_na_, nrows, ncols):
+    """src/slice_coo.cpp:902-923: dict(ii, jj, xx) of the triplets that stay (storage order) followed by the NA
+    block of the 0-based, ascending rows_na_ / cols_na_, every value of it NA_real_."""
+    return _inject_NAs_inplace_coo(ii, jj, xx, MX_F64, rows_na_, cols_na_, nrows, ncols)
+
+
+def inject_NAs_inplace_coo_logical(ii, jj, xx, rows_na_, cols_na_, nrows, ncols):
+    """src/slice_coo.cpp:925-946 (R logicals, int32 in and out; the block holds NA_LOGICAL)."""
+    return _inject_NAs_inplace_coo(ii, jj, xx, MX_LGL, rows_na_, cols_na_, nrows, ncols)
+
+
+def _extract_single_val_csr(indptr, indices, values, vdt, row, col):
+    p, j = _i32(indptr), _i32(indices)
+    v, val = None, None
+    if vdt == MX_F64:
+        v, val = _f64(values), C.c_double(0.0)
+    elif vdt == MX_LGL:
+        v, val = np.ascontiguousarray(values, dtype=np.int32), C.c_int32(0)
+    if v is not None and v.size != j.size:
+        raise ValueError("values and indices have different number of entries")
+    found = C.c_int(0)
+    check(_lib.load().mx_extract_single_val_csr(ptr(p), p.size - 1, ptr(j), ptr(v), vdt, int(row), int(col),
+                                                C.byref(found), None if val is None else C.byref(val)))
+    return bool(found.value), (None if val is None else val.value)
+
+
+def extract_single_val_csr_numeric(indptr, indices, values, row, col) -> float:
+    """src/slice.cpp:737-752: the value of the first entry (storage order) of 0-based `row` at column `col`, or 0."""
+    hit, val = _extract_single_val_csr(indptr, indices, values, MX_F64, row, col)
+    return float(val) if hit else 0.0
+
+
+def extract_single_val_csr_logical(indptr, indices, values, row, col) -> int:
+    """src/slice.cpp:754-769: the export returns an int, so NA_LOGICAL comes back as it is stored."""
+    hit, val = _extract_single_val_csr(indptr, indices, values, MX_LGL, row, col)
+    return int(val) if hit else 0
+
+
+def extract_single_val_csr_binary(indptr, indices, row, col) -> float:
+    """src/slice.cpp:771-785: 1 when the row stores the column, else 0."""
+    hit, _ = _extract_single_val_csr(indptr, indices, None, MX_NONE, row, col)
+    return 1.0 if hit else 0.0
+
+
+def repeat_indices_n_times(indices, remainder, ix_length, desired_length):
+    """src/slice.cpp:636-659: `indices` shifted by ix_length per full repeat inside desired_length, then `remainder`
+    shifted past them."""
+    ix, rem = _i32(indices).reshape(-1), _i32(remainder).reshape(-1)
+    if int(ix_length) <= 0:
+        raise ValueError("ix_length must be positive")
+    out = np.empty(ix.size * (int(desired_length) // int(ix_length)) + rem.size, dtype=np.int32)
+    check(_lib.load().mx_repeat_indices_n_times(ptr(ix), ix.size, ptr(rem), rem.size, int(ix_length),
+                                                int(desired_length), ptr(out)))
+    return out
+
+
+def entries_to_dense_vector(pos, values, length, logical=False):
+    """as.vector() of a one-row / one-column slice (drop_slice, R/slice.R:210-236; no export of the reference's, the
+    mirror's way to mxd_entries_to_dense_vector): zeros of `length` with values[k] at the distinct 0-based pos[k] —
+    float64, or int32 R logicals for int32 values and, with logical=True, for no values (TRUE)."""
+    ps = _i32(pos).reshape(-1)
+    if values is None:
+        v, vdt, odt = None, MX_NONE, MX_LGL if logical else MX_F64
+    elif np.asarray(values).dtype == np.float64:
+        v, vdt, odt = _f64(values), MX_F64, MX_F64
+    else:
+        v, vdt, odt = np.ascontiguousarray(values, dtype=np.int32), MX_LGL, MX_LGL
+    if v is not None and v.size != ps.size:
+        raise ValueError("values and positions have different number of entries")
+    out = np.empty(int(length), dtype=np.float64 if odt == MX_F64 else np.int32)
+    check(_lib.load().mx_entries_to_dense_vector(ptr(ps), ptr(v), vdt, ps.size, ptr(out), odt, out.size))
+    return out
+
+
 # ----------------------------------------------------------------------------- remove_sparse_zeros / filterSparse /
 #                                                                               check_sparse_matrix (compact.hip)
 def _compacted(res, info, inputs, vdt):

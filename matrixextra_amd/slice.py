@@ -9,28 +9,92 @@ native routines — row gather, column-range / arbitrary-column slices, reversal
 
 `subset_coo(x, i, j, drop)` is the same for a TsparseMatrix, after R/slice_coo.R: a scalar (i, j) pair goes to
 slice_coo_single_*, everything else to slice_coo_arbitrary_* (the COO slice kernels).
+
+A selector may hold NA (NA_INTEGER, a float nan, None) or be an lsparseVector / nsparseVector mask: get_ij_properties
+replaces the NAs by the first index that is none and both routes end in inject_NAs, which makes the NA rows and
+columns of the result NA throughout.  `drop` to a vector and the CSR scalar lookup are taken under
+options["mxgpu.slice_drop_route"].
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import exports
-from .matrices import (RsparseMatrix, TsparseMatrix, check_valid_matrix, dgRMatrix, dgTMatrix, lgRMatrix,
-                       lgTMatrix, ngRMatrix, ngTMatrix, stop)
+from .matrices import (NA_INTEGER, NA_LOGICAL, NA_REAL, RsparseMatrix, TsparseMatrix, _coo_to_compressed,
+                       as_coo_matrix, as_csr_matrix, as_sparse_vector, check_valid_matrix, dgRMatrix, dgTMatrix,
+                       lgRMatrix, lgTMatrix, lsparseVector, ngRMatrix, ngTMatrix, nsparseVector, options,
+                       sort_sparse_indices, stop)
 
 
-def get_indices_integer(i, max_i, index_names):
-    """R/slice.R:2-53 for integer / logical / character `i`; returns 1-based int32."""
+def _svec_selector(v, max_i):
+    """R/slice.R:4-30: an lsparseVector / nsparseVector mask as 1-based indices, recycled over the axis like base R
+    (repeat_indices_n_times).  An lsparseVector that stores an NA reads as the dense logical it spells (TRUE selects,
+    NA gives an NA index); one without NA selects the positions whose stored value is TRUE."""
+    v = sort_sparse_indices(v, copy=not options.get("MatrixExtra.inplace_sort", False))
+    if v.length > max_i:
+        stop("Dimension of indexing vector is larger than matrix to subset.")
+    if v.length == 0:
+        return np.zeros(0, dtype=np.int32)
+    if isinstance(v, lsparseVector):
+        if np.any(v.x == NA_LOGICAL):                                 # seq(1L, max_i)[as.logical(i)]
+            dense = np.zeros(v.length, dtype=np.int32)
+            dense[v.i.astype(np.int64) - 1] = v.x
+            reps = -(-max_i // max(v.length, 1))
+            dense = np.tile(dense, reps)[:max_i]
+            pos = np.flatnonzero(dense != 0)
+            return np.where(dense[pos] == NA_LOGICAL, NA_INTEGER, (pos + 1).astype(np.int32)).astype(np.int32)
+        v = nsparseVector(v.i[v.x != 0], None, v.length)
+    if v.length == max_i:
+        return v.i.astype(np.int32)
+    remainder = max_i - v.length * (max_i // v.length)                # i[seq(1L, remainder)]@i: the positions inside it
+    return exports.repeat_indices_n_times(v.i, v.i[v.i <= remainder], v.length, max_i)
+
+
+def _as_integer_with_na(i, index_names):
+    """(int64 indices, NA mask) of a selector: NA is NA_INTEGER in an integer array, nan in a float one and None in an
+    object array (assign._has_na's reading); names are looked up, floats truncated as as.integer() does."""
     i = np.asarray(i)
-    if i.dtype.kind in ("U", "S", "O"):
+    if i.dtype.kind == "O":
+        flat = i.reshape(-1).tolist()
+        na = np.array([v is None or (isinstance(v, (float, np.floating)) and np.isnan(v)) for v in flat], dtype=bool)
+        lookup = None
+        if index_names is not None and any(isinstance(v, str) for v in flat):
+            lookup = {nm: k + 1 for k, nm in reversed(list(enumerate(index_names)))}
+        vals = np.zeros(len(flat), dtype=np.int64)
+        for k, v in enumerate(flat):
+            if na[k]:
+                continue
+            if lookup is not None:
+                if v not in lookup:
+                    stop("some of row subset indices are not present in matrix")
+                vals[k] = lookup[v]
+            else:
+                vals[k] = int(v)
+        return vals, na
+    if i.dtype.kind in ("U", "S"):
         if index_names is not None:
             lookup = {nm: k + 1 for k, nm in reversed(list(enumerate(index_names)))}
             try:
-                i = np.array([lookup[s] for s in i.tolist()], dtype=np.int64)
+                i = np.array([lookup[s] for s in i.reshape(-1).tolist()], dtype=np.int64)
             except KeyError:
                 stop("some of row subset indices are not present in matrix")
         else:
             i = i.astype(np.int64)
+        return i.reshape(-1), np.zeros(i.size, dtype=bool)
+    i = i.reshape(-1)
+    if i.dtype.kind == "f":
+        na = np.isnan(i)
+        return np.where(na, 0.0, i).astype(np.int64), na
+    na = i == NA_INTEGER if i.dtype.kind == "i" else np.zeros(i.size, dtype=bool)
+    return np.where(na, 0, i).astype(np.int64), na
+
+
+def get_indices_integer(i, max_i, index_names):
+    """R/slice.R:2-53 for integer / logical / character / sparseVector `i`; returns 1-based int32, NA_INTEGER where
+    the selector holds an NA.  An NA is exempt from the exclusion rule and from the bounds check (:48-51)."""
+    if isinstance(i, (lsparseVector, nsparseVector)):
+        i = _svec_selector(i, max_i)
+    i = np.asarray(i)
     if i.dtype == np.bool_:
         if i.size != max_i:
             if i.size > max_i:
@@ -38,65 +102,191 @@ def get_indices_integer(i, max_i, index_names):
             reps = -(-max_i // max(i.size, 1))
             i = np.tile(i, reps)[:max_i]            # seq(1, max_i)[i] recycles the mask
         i = np.flatnonzero(i) + 1
-    i = i.astype(np.int64, copy=False).reshape(-1)
-    if np.any(i <= 0):
-        if np.any(i > 0):
+    i, na = _as_integer_with_na(i, index_names)
+    good = i[~na]
+    if np.any(good <= 0):
+        if np.any(good > 0):
             stop("can't mix positive and negative subscripts")
+        if na.any():
+            stop("can't mix NAs with negative subscripts")
         keep = np.ones(max_i, dtype=bool)
         drop = -i[i < 0]
         if np.any(drop > max_i):
             drop = drop[drop <= max_i]
         keep[drop - 1] = False
         i = np.flatnonzero(keep) + 1
-    if i.size and np.any(i > max_i):
+        na = np.zeros(i.size, dtype=bool)
+    elif good.size and np.any(good > max_i):
         stop("some of row subset indices are not present in matrix")
-    return i.astype(np.int32)
+    out = i.astype(np.int32)
+    out[na] = NA_INTEGER
+    return out
+
+
+def find_first_non_na(i):
+    """find_first_non_na (src/slice.cpp): the first index that is not NA, or NA_INTEGER.  A host scan: the selector is
+    host data and the scan ends at the first hit."""
+    for v in i:
+        if v != NA_INTEGER:
+            return np.int32(v)
+    return NA_INTEGER
 
 
 class IJProperties:
-    """What get_ij_properties returns (R/slice.R:59-143), without the NA fields: 1-based int32 `i` / `j`, the six
-    classification flags, n_row / n_col, and the selected dimnames (None when the matrix has none)."""
+    """What get_ij_properties returns (R/slice.R:59-143): 1-based int32 `i` / `j` (an NA replaced by the first
+    index that is none; all NA_INTEGER when every one is), the six classification flags, n_row / n_col, the selected
+    dimnames (None when the matrix has none, or when the whole axis is NA), and per axis has_NA, all_NA and NAs — the
+    1-based positions of the NA entries in the selector, or None."""
     __slots__ = ("i", "j", "all_i", "all_j", "i_is_seq", "j_is_seq", "i_is_rev_seq", "j_is_rev_seq", "n_row",
-                 "n_col", "row_names", "col_names")
+                 "n_col", "row_names", "col_names", "i_has_NA", "i_all_NA", "i_NAs", "j_has_NA", "j_all_NA", "j_NAs")
 
     def __init__(self, **kw):
         for k, v in kw.items():
             setattr(self, k, v)
 
 
+def _fill_NAs(idx):
+    """R/slice.R:111-132 for one axis: (indices with the NAs replaced, all_NA, the 1-based NA positions or None)"""
+    first = find_first_non_na(idx)
+    if first == NA_INTEGER:
+        return idx, True, None
+    NAs = (np.flatnonzero(idx == NA_INTEGER) + 1).astype(np.int32)
+    return np.where(idx == NA_INTEGER, first, idx).astype(np.int32), False, NAs
+
+
 def get_ij_properties(x, i, j):
-    """R/slice.R:59-143 for integer / logical / name / negative selectors (`None` = missing).  The asymmetry is the
-    reference's (:79-103): a full-range i sets both all_i and i_is_seq, a full-range j sets all_j and leaves
-    j_is_seq FALSE."""
+    """R/slice.R:59-143 for integer / logical / name / negative / sparseVector selectors (`None` = missing), NA
+    entries included.  The asymmetry is the reference's (:79-103): a full-range i sets both all_i and i_is_seq, a
+    full-range j sets all_j and leaves j_is_seq FALSE.  The flag checks are skipped for an axis with NAs."""
     row_names, col_names = x.Dimnames[0], x.Dimnames[1]
     nrow, ncol = x.Dim
     all_i = all_j = i_is_seq = j_is_seq = i_is_rev_seq = j_is_rev_seq = False
+    i_has_NA = j_has_NA = i_all_NA = j_all_NA = False
+    i_NAs = j_NAs = None
     if j is None:
         all_j = True
         j = np.arange(1, ncol + 1, dtype=np.int32)
     else:
         j = get_indices_integer(j, ncol, col_names)
-        if j.size == ncol and ncol > 0 and j[0] == 1 and j[-1] == ncol:
-            all_j = exports.check_is_seq(j)
-        else:
-            j_is_seq = exports.check_is_seq(j)
+        j_has_NA = bool(np.any(j == NA_INTEGER))
+        if not j_has_NA:
+            if j.size == ncol and ncol > 0 and j[0] == 1 and j[-1] == ncol:
+                all_j = exports.check_is_seq(j)
+            else:
+                j_is_seq = exports.check_is_seq(j)
     if i is None:
         i = np.arange(1, nrow + 1, dtype=np.int32)
         all_i = i_is_seq = True
     else:
         i = get_indices_integer(i, nrow, row_names)
-        i_is_seq = exports.check_is_seq(i)
+        i_has_NA = bool(np.any(i == NA_INTEGER))
+        if not i_has_NA:
+            i_is_seq = exports.check_is_seq(i)
         if i_is_seq and i.size == nrow and nrow > 0 and i[0] == 1 and i[-1] == nrow:
             all_i = True
-    if not all_i and not i_is_seq:
+    if not all_i and not i_is_seq and not i_has_NA:
         i_is_rev_seq = exports.check_is_rev_seq(i)
-    if not all_j and not j_is_seq:
+    if not all_j and not j_is_seq and not j_has_NA:
         j_is_rev_seq = exports.check_is_rev_seq(j)
-    new_rn = None if row_names is None or not len(row_names) else [row_names[k - 1] for k in i]
-    new_cn = None if col_names is None or not len(col_names) else [col_names[k - 1] for k in j]
+    if i_has_NA:
+        i, i_all_NA, i_NAs = _fill_NAs(i)
+    if j_has_NA:
+        j, j_all_NA, j_NAs = _fill_NAs(j)
+    new_rn = None if row_names is None or not len(row_names) or i_all_NA else [row_names[k - 1] for k in i]
+    new_cn = None if col_names is None or not len(col_names) or j_all_NA else [col_names[k - 1] for k in j]
     return IJProperties(i=i, j=j, all_i=all_i, all_j=all_j, i_is_seq=i_is_seq, j_is_seq=j_is_seq,
                         i_is_rev_seq=i_is_rev_seq, j_is_rev_seq=j_is_rev_seq, n_row=int(i.size), n_col=int(j.size),
-                        row_names=new_rn, col_names=new_cn)
+                        row_names=new_rn, col_names=new_cn, i_has_NA=i_has_NA, i_all_NA=i_all_NA, i_NAs=i_NAs,
+                        j_has_NA=j_has_NA, j_all_NA=j_all_NA, j_NAs=j_NAs)
+
+
+# ----------------------------------------------------------------------------- inject_NAs / drop_slice: R/slice.R:145-236
+def _drop_route():
+    """`drop` to vectors and the CSR scalar lookup are taken only under options["mxgpu.slice_drop_route"] (off
+    unless set): with it off every call returns what it returned before they existed."""
+    return bool(options.get("mxgpu.slice_drop_route", False))
+
+
+def _is_logical_kind(x):
+    return isinstance(x, (lgRMatrix, ngRMatrix, lgTMatrix, ngTMatrix))
+
+
+def _names_without(names, NAs):
+    if names is None or NAs is None or not NAs.size:
+        return names
+    names = list(names)
+    for k in NAs:
+        names[k - 1] = None                                            # NA_character_
+    return names
+
+
+def inject_NAs(x, i_NAs, j_NAs):
+    """R/slice.R:145-208: rows i_NAs and columns j_NAs (1-based positions in x) become NA throughout; their dimnames
+    become None.  A CSR takes two scalar assignments of NA_real_ (§4.16) as a dgRMatrix and goes back to logical for
+    lgRMatrix / ngRMatrix input; a COO goes to inject_NAs_inplace_coo_* as a dgTMatrix / lgTMatrix.  The reference
+    leaves the COO result without dimnames (it fills a new object, :183-192); here it keeps them."""
+    ni = 0 if i_NAs is None else int(i_NAs.size)
+    nj = 0 if j_NAs is None else int(j_NAs.size)
+    if not ni and not nj:
+        return x
+    names = [_names_without(x.Dimnames[0], i_NAs), _names_without(x.Dimnames[1], j_NAs)]
+    nrow, ncol = x.Dim
+    logical = _is_logical_kind(x)
+    if isinstance(x, RsparseMatrix):
+        from .assign import _assign_csr_internal                      # assign imports this module
+        y = as_csr_matrix(x)
+        y = dgRMatrix(y.p, y.j, y.x, y.Dim, names)
+        if ni:
+            y = _assign_csr_internal(y, i_NAs, np.arange(1, ncol + 1, dtype=np.int32), NA_REAL, None)
+        if nj:
+            y = _assign_csr_internal(y, np.arange(1, nrow + 1, dtype=np.int32), j_NAs, NA_REAL, None)
+        return as_csr_matrix(y, logical=True) if logical else y
+    y = as_coo_matrix(x, logical=logical)
+    rows_na = np.zeros(0, dtype=np.int32) if not ni else (i_NAs - 1).astype(np.int32)
+    cols_na = np.zeros(0, dtype=np.int32) if not nj else (j_NAs - 1).astype(np.int32)
+    fn = exports.inject_NAs_inplace_coo_logical if logical else exports.inject_NAs_inplace_coo_numeric
+    res = fn(y.i, y.j, y.x, rows_na, cols_na, nrow, ncol)
+    return (lgTMatrix if logical else dgTMatrix)(res["ii"], res["jj"], res["xx"], x.Dim, names)
+
+
+def _as_vector(x):
+    """as.vector() of a one-row or one-column sparse matrix: float64, or R logicals (int32) for the l and n kinds.  A
+    COO goes through the COO -> CSR route first, which merges its repeated triplets."""
+    if isinstance(x, TsparseMatrix):
+        x = _coo_to_compressed(x)
+    nrow, ncol = x.Dim
+    pos = x.j if nrow == 1 else np.repeat(np.arange(nrow, dtype=np.int32), np.diff(x.p))
+    return exports.entries_to_dense_vector(pos, x.x, nrow * ncol, logical=x.x is None)
+
+
+def drop_slice(x, drop, i_NAs=None, j_NAs=None):
+    """R/slice.R:210-236: inject_NAs, then — under the drop route — a one-row or one-column result as a dense vector,
+    or as a sparseVector of its kind under MatrixExtra.drop_sparse when it is not 1 x 1."""
+    x = inject_NAs(x, i_NAs, j_NAs)
+    if drop and _drop_route() and isinstance(x, (RsparseMatrix, TsparseMatrix)):
+        nrow, ncol = x.Dim
+        if nrow == 1 or ncol == 1:
+            if not (nrow == 1 and ncol == 1) and options.get("MatrixExtra.drop_sparse", False):
+                has_x = x.x is not None                                # as(x, "sparseVector") keeps the kind
+                return as_sparse_vector(x, binary=not has_x, logical=has_x and x.x.dtype == np.int32)
+            return _as_vector(x)
+    return x
+
+
+def _scalar_index(v):
+    """as.integer() of a scalar selector, NA_INTEGER for nan / None / NA_INTEGER"""
+    v = np.asarray(v, dtype=object).reshape(-1)[0]
+    if v is None or (isinstance(v, (float, np.floating)) and np.isnan(v)):
+        return int(NA_INTEGER)
+    return int(v)
+
+
+def _na_matrix_entries(n_row, n_col, logical):
+    """row-major cells of an n_row x n_col matrix of NA: (rows, cols, values)"""
+    rows = np.repeat(np.arange(n_row, dtype=np.int32), n_col)
+    cols = np.tile(np.arange(n_col, dtype=np.int32), n_row)
+    vals = np.full(n_row * n_col, NA_LOGICAL, dtype=np.int32) if logical else np.full(n_row * n_col, NA_REAL)
+    return rows, cols, vals
 
 
 def _empty_like(x, n_row, row_names):
@@ -119,8 +309,10 @@ def _call3(kind, fn_numeric, fn_logical, fn_binary, p, j, xv, *rest):
 
 
 def subset_csr(x, i=None, j=None, drop=False):
-    """`x[i, j]` for RsparseMatrix — R/slice.R:293-585 (integer / logical / name / negative indices; NA indices and
-    `drop` to vectors are not mirrored).  Branch selection is the reference's (:439-565):
+    """`x[i, j]` for RsparseMatrix — R/slice.R:293-585 (integer / logical / name / negative / sparseVector indices,
+    NA entries included: an NA row or column of the result is NA throughout, through inject_NAs).  `drop` and the
+    scalar (i, j) lookup (:302-381, extract_single_val_csr_*) are taken under options["mxgpu.slice_drop_route"]
+    only.  Branch selection is the reference's (:439-565):
       contiguous ascending rows, all columns      -> host slicing, as the reference does in pure R (:477-483)
       descending rows, all columns                -> host slicing + reverse_rows_*                    (:484-501)
       other rows, all columns                     -> copy_csr_rows_*            (row-gather kernel)   (:502-515)
@@ -130,7 +322,9 @@ def subset_csr(x, i=None, j=None, drop=False):
       full reversal of both                       -> reverse_rows_* + reverse_columns_inplace_*       (:439-469)"""
     check_valid_matrix(x)
     if i is None and j is None:
-        return x
+        return drop_slice(x, drop)
+    if _drop_route() and i is not None and j is not None and _is_scalar_number(i) and _is_scalar_number(j):
+        return _subset_csr_single(x, i, j, drop)
     P = get_ij_properties(x, i, j)
     i, j = P.i, P.j
     nrow, ncol = x.Dim
@@ -143,11 +337,18 @@ def subset_csr(x, i=None, j=None, drop=False):
         out = _empty_like(x, n_row, new_rn)
         out.Dim = (n_row, n_col)
         out.Dimnames = [new_rn, new_cn]
-        return out
+        return drop_slice(out, drop)
     if all_i and all_j:                                         # R/slice.R:423-425
-        return x
-
+        return drop_slice(x, drop)
     kind = _cls_kind(x)
+    if P.i_all_NA or P.j_all_NA:
+        # R/slice.R:428-437 takes this branch when each axis is all NA or all of it.  An axis that is all NA beside a
+        # partial one is NA throughout just the same; the reference goes on with NA_integer_ indices there.
+        rows, cols, vals = _na_matrix_entries(n_row, n_col, kind != "d")
+        indptr = (np.arange(n_row + 1, dtype=np.int64) * n_col).astype(np.int32)
+        names = [_names_without(new_rn, P.i_NAs), _names_without(new_cn, P.j_NAs)]
+        return drop_slice((dgRMatrix if kind == "d" else lgRMatrix)(indptr, cols, vals, (n_row, n_col), names), drop)
+
     has_x = x.x is not None
     E = exports
 
@@ -163,7 +364,7 @@ def subset_csr(x, i=None, j=None, drop=False):
             res.x = None
         res.Dim = (n_row, n_col)
         res.Dimnames = [new_rn, new_cn]
-        return res
+        return drop_slice(res, drop, P.i_NAs, P.j_NAs)          # R/slice.R:583
 
     if i_is_rev_seq and j_is_rev_seq and n_row == nrow and n_col == ncol:          # R/slice.R:439-469
         t = _call3(kind, E.reverse_rows_numeric, E.reverse_rows_logical, E.reverse_rows_binary, x.p, x.j, x.x)
@@ -270,6 +471,47 @@ def _is_scalar_number(v):
     return a is not None and a.size == 1 and a.dtype.kind in ("i", "u", "f")
 
 
+def _subset_csr_single(x, i, j, drop):
+    """R/slice.R:302-381, under the drop route: `x[i, j]` with two scalar numbers through extract_single_val_csr_*.
+    A scalar (float; TRUE / FALSE / NA_LOGICAL for an lgRMatrix), or with drop=False the 1 x 1 matrix that is empty
+    when the value is 0.  The symmetric / triangular branches (:316-333) have no stand-in class here.  A scalar <= 0
+    is no exclusion on this route: it selects nothing and gives 0, as on the COO route (the reference reads row
+    i - 1 < 0 of the index pointer there)."""
+    i, j = _scalar_index(i), _scalar_index(j)
+    nrow, ncol = x.Dim
+    kind = _cls_kind(x)
+    if i == NA_INTEGER or j == NA_INTEGER:                      # :309-310
+        res = NA_REAL
+    elif i > nrow or j > ncol:
+        stop("Subscript out of bounds.")
+    elif i < 1 or j < 1:
+        res = 0.0
+    elif kind == "d":
+        res = exports.extract_single_val_csr_numeric(x.p, x.j, x.x, i - 1, j - 1)
+    elif kind == "l":                                           # as.logical() of the int the export returns
+        v = exports.extract_single_val_csr_logical(x.p, x.j, x.x, i - 1, j - 1)
+        res = NA_LOGICAL if v == NA_LOGICAL else bool(v)
+    else:
+        res = exports.extract_single_val_csr_binary(x.p, x.j, i - 1, j - 1)
+    if drop:
+        return res                              # names(res) <- colnames(x)[j] (:347-348) is not mirrored
+    is_na = (isinstance(res, float) and np.isnan(res)) or (not isinstance(res, (bool, float)) and res == NA_LOGICAL)
+    rn = x.Dimnames[0][i - 1] if x.Dimnames[0] is not None and len(x.Dimnames[0]) and i >= 1 else None
+    cn = x.Dimnames[1][j - 1] if x.Dimnames[1] is not None and len(x.Dimnames[1]) and j >= 1 else None
+    cls = {"d": dgRMatrix, "l": lgRMatrix, "n": ngRMatrix}[kind]
+    names = [None if rn is None else [rn], None if cn is None else [cn]]
+    if not is_na and res == 0:                                  # :367-369
+        return cls(np.zeros(2, dtype=np.int32), np.zeros(0, dtype=np.int32), None, (1, 1), names)
+    # the reference's `if (res == 0)` stops on an NA (:367); here the one cell holds it
+    if kind == "d":
+        xv = np.array([res], dtype=np.float64)
+    elif kind == "l":
+        xv = np.array([NA_LOGICAL if is_na else 1], dtype=np.int32)
+    else:
+        xv = None
+    return cls(np.array([0, 1], dtype=np.int32), np.zeros(1, dtype=np.int32), xv, (1, 1), names)
+
+
 def _empty_coo(kind, n_row, n_col, row_names, col_names):
     xv = None if kind == "n" else np.zeros(0, dtype=_COO_CLS[kind].value_dtype)
     return _COO_CLS[kind](np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), xv, (n_row, n_col),
@@ -278,8 +520,16 @@ def _empty_coo(kind, n_row, n_col, row_names, col_names):
 
 def _subset_coo_single(x, i, j, drop):
     """R/slice_coo.R:10-84.  The symmetric / triangular branches (:22-42) have no stand-in class here."""
-    i, j = int(np.asarray(i).reshape(-1)[0]), int(np.asarray(j).reshape(-1)[0])   # as.integer(): truncates
+    i, j = _scalar_index(i), _scalar_index(j)                  # as.integer(): truncates
     nrow, ncol = x.Dim
+    if i == NA_INTEGER or j == NA_INTEGER:                      # :17-18
+        if drop:
+            return NA_REAL
+        out = _empty_coo(_coo_kind(x), 1, 1, None, None)        # :75-82: the one cell holds the NA
+        out.i, out.j = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        if out.x is not None:
+            out.x = np.array([NA_REAL]) if isinstance(x, dgTMatrix) else np.array([NA_LOGICAL], dtype=np.int32)
+        return out
     if i > nrow or j > ncol:
         stop("Subscript out of bounds.")
     # (sic) a scalar <= 0 is not an exclusion here: it reaches the native routine as i-1 < 0, finds no triplet and
@@ -308,9 +558,10 @@ def _subset_coo_single(x, i, j, drop):
 
 
 def subset_coo(x, i=None, j=None, drop=True):
-    """`x[i, j]` for TsparseMatrix — R/slice_coo.R:1-232 (integer / logical / name / negative indices).  As in
-    subset_csr, NA indices and `drop` to a vector for non-scalar selections are not mirrored; `drop` only matters
-    for the scalar (i, j) route.  Routes:
+    """`x[i, j]` for TsparseMatrix — R/slice_coo.R:1-232 (integer / logical / name / negative / sparseVector
+    indices, NA entries included, through inject_NAs_inplace_coo_*).  As in subset_csr, `drop` to a vector for
+    non-scalar selections is taken under options["mxgpu.slice_drop_route"] only; without it `drop` only matters for
+    the scalar (i, j) route.  Routes:
       both i and j scalar numbers                 -> slice_coo_single_*, a scalar, or 1 x 1 with drop=False (:10-84)
       empty i or j, or no entries                 -> empty T-matrix of the same kind                      (:108-125)
       all rows and all columns                    -> x itself                                             (:127-129)
@@ -320,20 +571,24 @@ def subset_coo(x, i=None, j=None, drop=True):
       anything else                               -> slice_coo_arbitrary_*                                (:160-196)"""
     check_valid_matrix(x)
     if i is None and j is None:
-        return x
+        return drop_slice(x, drop)
     if i is not None and j is not None and _is_scalar_number(i) and _is_scalar_number(j):
         return _subset_coo_single(x, i, j, drop)
-    return _subset_coo_vectors(x, i, j)
+    return _subset_coo_vectors(x, i, j, drop)
 
 
-def _subset_coo_vectors(x, i, j):
+def _subset_coo_vectors(x, i, j, drop=False):
     """R/slice_coo.R:87-232: everything but the scalar route."""
     P = get_ij_properties(x, i, j)
     kind = _coo_kind(x)
     if P.n_row == 0 or P.n_col == 0 or x.i.size == 0:                  # :108-125
-        return _empty_coo(kind, P.n_row, P.n_col, P.row_names, P.col_names)
+        return drop_slice(_empty_coo(kind, P.n_row, P.n_col, P.row_names, P.col_names), drop)
     if P.all_i and P.all_j:                                             # :127-129
-        return x
+        return drop_slice(x, drop)
+    if P.i_all_NA or P.j_all_NA:                                        # :131-140, and as in subset_csr
+        rows, cols, vals = _na_matrix_entries(P.n_row, P.n_col, kind != "d")
+        names = [_names_without(P.row_names, P.i_NAs), _names_without(P.col_names, P.j_NAs)]
+        return drop_slice((dgTMatrix if kind == "d" else lgTMatrix)(rows, cols, vals, (P.n_row, P.n_col), names), drop)
     nrow, ncol = x.Dim
     flags = (P.all_i, P.all_j, P.i_is_seq, P.j_is_seq, P.i_is_rev_seq, P.j_is_rev_seq, nrow, ncol)
     if kind == "d":
@@ -346,4 +601,4 @@ def _subset_coo_vectors(x, i, j):
     res.i, res.j, res.x = t["ii"], t["jj"], t["xx"] if kind != "n" else None
     res.Dim = (P.n_row, P.n_col)
     res.Dimnames = [P.row_names, P.col_names]
-    return res
+    return drop_slice(res, drop, P.i_NAs, P.j_NAs)                      # :203
