@@ -227,12 +227,31 @@ int mxd_reversed_iota(int n, int32_t *out, void *stream);   /* out[i] = n-1-i: r
 int mxd_csr_cbind(int nX, int nY, const int32_t *Xp, const int32_t *Xj, const void *Xx, const int32_t *Yp,
                   const int32_t *Yj_plus_ncol, const void *Yx, int value_dtype, int64_t nnz_total,
                   int32_t *indptr, int32_t *indices, void *values, void *stream);
+/* the same for device-resident operands whose column ids nobody has shifted: Y's ids + ncolX */
+int mxd_csr_cbind_shift(int nX, int nY, int ncolX, const int32_t *Xp, const int32_t *Xj, const void *Xx,
+                        const int32_t *Yp, const int32_t *Yj, const void *Yx, int value_dtype, int64_t nnz_total,
+                        int32_t *indptr, int32_t *indices, void *values, void *stream);
 /* rbind: append one operand at (row_offset, entry_offset) with the value conversions of concat_csr_batch
  * (src/rbind.cpp:24-173).  in_kind 0 dgR, 1 lgR, 2 ngR, 3/4/5/6 d/i/l/n sparseVector (1-based indices, one row);
  * out_kind 0 dgR, 1 lgR, 2 ngR. */
 int mxd_csr_rbind_append(int in_kind, const int32_t *indptr_in, const int32_t *indices_in, const void *values_in,
                          int nrows_in, int64_t nnz_in, int out_kind, int row_offset, int64_t entry_offset,
                          int32_t *out_indptr, int32_t *out_indices, void *out_values, void *stream);
+/* The whole rbind at once: mxd_csr_rbind_batch, declared with its table record beside mx_rbind_input below.
+ * COO rbind: append one operand's triplets at entry_offset.  in_kind 0 dgT, 1 lgT, 2 ngT (0-based i_in / j_in,
+ * rows moved down by row_offset), 3/4/5/6 d/i/l/n sparseVector (i_in ignored, j_in 1-based: the one row
+ * row_offset); out_kind 0 dgT, 1 lgT, 2 ngT; values converted as mxd_csr_rbind_append converts them. */
+int mxd_coo_rbind_append(int in_kind, const int32_t *i_in, const int32_t *j_in, const void *values_in,
+                         int64_t nnz_in, int out_kind, int row_offset, int64_t entry_offset,
+                         int32_t *out_i, int32_t *out_j, void *out_values, void *stream);
+/* cbind of a CSR and a sparse vector as one column: X (x_kind 0 dgR, 1 lgR, 2 ngR; nX rows, ncolX columns), the
+ * vector as nv SORTED 1-based indices <= length with values of v_kind 3/4/5/6 (d/i/l/n sparseVector).  first = 0:
+ * the entry of row r follows X's row r with column ncolX; first = 1: it comes first with column 0 and X's columns
+ * move up by one.  Outputs: indptr[max(nX, length) + 1], indices / values[Xp[nX] + nv] of out_kind 0 dgR, 1 lgR,
+ * 2 ngR; no scan, no workspace. */
+int mxd_csr_cbind_svec(int nX, int ncolX, const int32_t *Xp, const int32_t *Xj, const void *Xx, int x_kind,
+                       const int32_t *vi, const void *vx, int v_kind, int nv, int length, int first,
+                       int out_kind, int32_t *indptr, int32_t *indices, void *values, void *stream);
 
 /* SURVEY §8f rank 4.
  * CSR x sparse vector (matmul_csr_svec<>, src/matmul.cpp:486-641): y given as sorted 1-based indices + values;
@@ -671,6 +690,15 @@ int mxd_compact_count(int64_t n, const void *values, int value_dtype, int rule, 
 int mxd_compact_fill(int64_t n, const void *values, int value_dtype, int rule, const int32_t *mask,
                      const int32_t *idx0, const int32_t *idx1, int m, const int32_t *indptr, const void *workspace,
                      int32_t *out_idx0, int32_t *out_idx1, void *out_values, int32_t *out_indptr, void *stream);
+/* A dense R vector (dtype MX_F64 numeric, MX_I32 integer, MX_LGL logical; n < INT_MAX cells) as a dsparseVector, by
+ * the same two passes: a cell is kept when it is not zero or is NA / NaN; out_indices_base1 receives the kept
+ * cells' 1-based positions in order, out_values their values as f64 (NA_integer_ / NA -> NA_real_, TRUE -> 1).
+ * workspace: mxd_compact_workspace_bytes(n), the same tiles.  The count reads the total back (one synchronisation);
+ * the fill needs the workspace the count left. */
+int mxd_dense_to_svec_count(int64_t n, const void *dense, int dtype, void *workspace, int64_t *kept_host,
+                            void *stream);
+int mxd_dense_to_svec_fill(int64_t n, const void *dense, int dtype, const void *workspace,
+                           int32_t *out_indices_base1, double *out_values, void *stream);
 /* Index validation of check_sparse_matrix (check_valid_{csr,coo}_matrix, check_valid_svec, src/misc.cpp:970-1097):
  * *flags_host (one read-back) ORs MX_BAD_NEGATIVE / MX_BAD_BOUND / MX_BAD_NA over indices[0..n) against [0, bound),
  * MX_BAD_PTR_NA over indptr[0..n_ptr) and MX_BAD_PTR_ORDER for some r < n_mono with indptr[r] > indptr[r+1]
@@ -865,6 +893,44 @@ typedef struct {
 } mx_rbind_input;
 int mx_concat_csr_batch_begin(const mx_rbind_input *objects, int n_inputs, int out_kind,
                               mx_result **res, mx_result_info *info);
+/* The device-level form of the same concat (declared here, beside mx_rbind_input, whose members it repeats): one
+ * record per operand in DEVICE memory, pointers to device arrays, with the operand's place in the output.
+ * row_offset / entry_offset are the exclusive prefix sums of the operands' rows (a vector counts one) and entries,
+ * in table order; operands without rows or without entries are allowed anywhere.  Two launches whatever n_items is,
+ * no workspace, no synchronisation.  Outputs: out_indptr[nrows_out + 1], out_indices / out_values[nnz_out]
+ * (f64 for out_kind 0, int32 for 1, unused for 2). */
+typedef struct {
+    int kind;                  /* as mx_rbind_input.kind */
+    int nrows;                 /* matrices: rows; vectors: ignored (one row) */
+    const int32_t *indptr;     /* matrices only */
+    const int32_t *indices;
+    const void *values;
+    int64_t nnz;
+    int64_t entry_offset;      /* where the operand's entries start in the output */
+    int row_offset;            /* where its rows start */
+} mx_rbind_item;
+int mxd_csr_rbind_batch(const mx_rbind_item *items_dev, int n_items, int out_kind, int nrows_out, int64_t nnz_out,
+                        int32_t *out_indptr, int32_t *out_indices, void *out_values, void *stream);
+/* rbind2_coo / rbind2_coo_vec  R/rbind.R:405-520 over plain arrays: the operands' triplets one after the other, a
+ * matrix's rows moved down by the rows before it, a sparse vector as one row.  objects as for the CSR batch with
+ * kinds 0 / 1 / 2 = dgT / lgT / ngT, whose `indptr` member holds the ROW ids (nnz of them); out_kind 0 dgT, 1 lgT,
+ * 2 ngT.  row_offsets[n_inputs] gives each operand's first output row; NULL places them one below the other in
+ * table order (rbind2_coo_vec with the vector first stores the matrix's triplets first all the same, :497-498).
+ * The result is a COO held in the mx_result as mx_multiply_csr_by_coo_begin's is: the indptr vector holds
+ * the row ids (info.indptr_len = info.nnz). */
+int mx_rbind_coo_begin(const mx_rbind_input *objects, int n_inputs, const int32_t *row_offsets, int out_kind,
+                       mx_result **res, mx_result_info *info);
+/* cbind2(RsparseMatrix, sparseVector) / cbind2(sparseVector, RsparseMatrix): X (x_kind 0 dgR, 1 lgR, 2 ngR) with
+ * the vector (v_kind 3 / 4 / 5 / 6 d / i / l / n sparseVector, 1-based indices, any order, below `length`) as one
+ * more column, last (first = 0) or first (first = 1).  max(nrows_X, length) rows; out_kind 0 dgR, 1 lgR, 2 ngR. */
+int mx_cbind_csr_svec_begin(const int32_t *X_indptr, int nrows_X, int ncols_X, const int32_t *X_indices,
+                            const void *X_values, int x_kind, const int32_t *v_indices, const void *v_values,
+                            int v_kind, int nv, int length, int first, int out_kind,
+                            mx_result **res, mx_result_info *info);
+/* A dense vector bound to a sparse matrix becomes a dsparseVector first (mxd_dense_to_svec_*): dtype MX_F64 /
+ * MX_I32 / MX_LGL.  The result holds no indptr (info.indptr_len = 0), the 1-based positions as indices and f64
+ * values. */
+int mx_dense_to_svec_begin(const void *dense, int64_t n, int dtype, mx_result **res, mx_result_info *info);
 /* t_deep / as.csc.matrix / as.csr.matrix(dgCMatrix): replaces t_deep_internal (R/trans.R:46-56) and the Matrix
  * coercions that R/conversions.R's as.csr.matrix / as.csc.matrix call, through mxd_csr_transpose.  indptr has
  * nrows + 1 entries starting at 0; value_dtype MX_F64 / MX_LGL / MX_NONE; n_values = length of the values vector

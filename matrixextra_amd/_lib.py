@@ -103,6 +103,7 @@ MX_DV_OPS = {"*": HEADER.constants["MX_DV_MULTIPLY"], "^": HEADER.constants["MX_
 ResultInfo = HEADER.structs["mx_result_info"]
 CooAxis = HEADER.structs["mx_coo_axis"]
 RbindInput = HEADER.structs["mx_rbind_input"]
+RbindItem = HEADER.structs["mx_rbind_item"]
 
 _lib = None
 

@@ -1024,25 +1024,35 @@ int mx_concat_csr_batch_begin(const mx_rbind_input *objs, int n_inputs, int out_
     return begin_result(res_out, info, out_kind == 0 ? MX_F64 : out_kind == 1 ? MX_LGL : MX_NONE, [&](mx_result &res) {
         if (res.alloc_indptr(nrows + 1)) return 1;
         if (res.alloc_entries(nnz, vb)) return 1;
-        if (res.indptr.zero(1)) return 1;
+        // every operand's arrays in ONE device buffer, sent up as one stream (a small batch is packed on the host and
+        // goes up in one copy, a large one is gathered chunk by chunk into the pinned transfer slots), then the table,
+        // two launches, and begin_result's one synchronisation
+        BindStaging in;
+        std::vector<mx_rbind_item> items((size_t)n_inputs);
         int row = 0;
         int64_t pos = 0;
         for (int k = 0; k < n_inputs; k++) {
             const mx_rbind_input &o = objs[k];
             const bool vec = o.kind >= 3;
             const size_t ivb = (o.kind == 0 || o.kind == 3) ? 8 : (o.kind == 2 || o.kind == 6) ? 0 : 4;
-            Dev<int32_t> p, j;                            // p stays null for a vector, x without values
-            DevBuf x;
-            if (!vec && p.upload(o.indptr, (int64_t)o.nrows + 1)) return 1;
-            if (j.upload(o.indices, o.nnz)) return 1;
-            if (ivb && x.upload(o.values, o.nnz, ivb)) return 1;
-            if (mxd_csr_rbind_append(o.kind, p, j, x, vec ? 1 : o.nrows, o.nnz, out_kind, row, pos, res.indptr,
-                                     res.indices, res.values, nullptr)) return 1;
-            MX_HIP(hipStreamSynchronize(nullptr));
-            row += vec ? 1 : o.nrows;
+            MX_REQUIRE(o.nnz >= 0 && (vec || o.nrows >= 0), "mx_concat_csr_batch_begin: negative size in argument %d", k);
+            mx_rbind_item &it = items[(size_t)k];
+            it.kind = o.kind;
+            it.nrows = vec ? 1 : o.nrows;
+            it.nnz = o.nnz;
+            it.row_offset = row;
+            it.entry_offset = pos;
+            in.add(vec ? nullptr : o.indptr, vec ? 0 : ((size_t)o.nrows + 1) * sizeof(int32_t), (const void **)&it.indptr);
+            in.add(o.indices, (size_t)o.nnz * sizeof(int32_t), (const void **)&it.indices);
+            in.add(ivb ? o.values : nullptr, (size_t)o.nnz * ivb, &it.values);
+            row += it.nrows;
             pos += o.nnz;
         }
-        return 0;
+        if (in.upload()) return 1;
+        Dev<mx_rbind_item> table;
+        if (table.upload(items.data(), n_inputs)) return 1;
+        return mxd_csr_rbind_batch(table, n_inputs, out_kind, (int)nrows, nnz, res.indptr, res.indices, res.values,
+                                   nullptr);
     });
 }
 

@@ -170,6 +170,38 @@ void validate_kernel(const int32_t *__restrict__ idx, int64_t n, int bound, cons
     if (lane_id() == 0 && f) atomicOr(flags, f);
 }
 
+// A dense R vector as a dsparseVector: the second pass of the same compaction with the cell's 1-based position as
+// its index and the value widened to f64 (NA_integer_ / NA -> NA_real_; LGL: TRUE -> 1).  The keep rule is
+// MX_KEEP_NONZERO, under which NaN and NA count as non-zero, so the count pass is compact_count_kernel itself.
+template <int VB, bool LGL>
+__global__ __launch_bounds__(CP_BLOCK)
+void dense_to_svec_fill_kernel(int64_t n, const void *__restrict__ dense, const int32_t *__restrict__ tile_off,
+                               int32_t *__restrict__ out_idx, double *__restrict__ out_values)
+{
+    using T = typename CpValue<VB>::T;
+    __shared__ CpTileRanks S;
+    const int lane = lane_id();
+    const int64_t base = (int64_t)blockIdx.x * CP_TILE;
+    T v[CP_ROUNDS];
+    cp_load(v, (const T *)dense, base, n);
+    unsigned long long bal[CP_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < CP_ROUNDS; r++) {
+        const bool in = base + r * CP_BLOCK + threadIdx.x < n;
+        bal[r] = __ballot(in && cp_keep<VB>(MX_KEEP_NONZERO, v[r], 0));
+    }
+    cp_rank_tile(S, bal);
+    const int64_t t0 = tile_off[blockIdx.x];
+#pragma unroll
+    for (int r = 0; r < CP_ROUNDS; r++) {
+        if (!((bal[r] >> lane) & 1)) continue;
+        const int64_t q = t0 + cp_rank_of(S, r, bal[r]);
+        out_idx[q] = (int32_t)(base + r * CP_BLOCK + threadIdx.x + 1);
+        if constexpr (VB == 8) out_values[q] = v[r];
+        else out_values[q] = v[r] == MX_NA_INT ? na_real() : LGL ? (double)(v[r] != 0) : (double)v[r];
+    }
+}
+
 static int64_t compact_ntiles(int64_t n) { return ceil_div(n > 0 ? n : 0, CP_TILE); }
 // per tile: its count, then its offset in the output
 struct CompactLayout : CountOffsetsLayout {
@@ -247,6 +279,39 @@ extern "C" int mxd_compact_fill(int64_t n, const void *values, int value_dtype, 
     else
         hipLaunchKernelGGL(mx::compact_fill_kernel<0>, dim3((unsigned)t), dim3(mx::CP_BLOCK), 0, st, n, t, values, rule,
                            mask, idx0, idx1, m, indptr, off, out_idx0, out_idx1, ov, out_indptr);
+    MX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mxd_dense_to_svec_count(int64_t n, const void *dense, int dtype, void *workspace, int64_t *kept_host,
+                                       void *stream)
+{
+    MX_REQUIRE(dtype == MX_F64 || dtype == MX_I32 || dtype == MX_LGL, "mxd_dense_to_svec_count: unsupported dtype %d",
+               dtype);
+    MX_REQUIRE(n >= 0 && n < INT_MAX, "mxd_dense_to_svec_count: bad size");
+    return mxd_compact_count(n, dense, dtype, MX_KEEP_NONZERO, nullptr, workspace, kept_host, stream);
+}
+
+extern "C" int mxd_dense_to_svec_fill(int64_t n, const void *dense, int dtype, const void *workspace,
+                                      int32_t *out_indices_base1, double *out_values, void *stream)
+{
+    const char *what = "mxd_dense_to_svec_fill";
+    MX_REQUIRE(dtype == MX_F64 || dtype == MX_I32 || dtype == MX_LGL, "%s: unsupported dtype %d", what, dtype);
+    MX_REQUIRE(n >= 0 && n < INT_MAX, "%s: bad size", what);
+    if (n == 0) return 0;
+    MX_REQUIRE(dense && workspace && out_indices_base1 && out_values, "%s: null pointer", what);
+    hipStream_t st = mx::as_stream(stream);
+    const int64_t t = mx::compact_ntiles(n);
+    const int32_t *off = mx::CompactLayout(workspace, n).offsets;
+    if (dtype == MX_F64)
+        hipLaunchKernelGGL((mx::dense_to_svec_fill_kernel<8, false>), dim3((unsigned)t), dim3(mx::CP_BLOCK), 0, st, n,
+                           dense, off, out_indices_base1, out_values);
+    else if (dtype == MX_LGL)
+        hipLaunchKernelGGL((mx::dense_to_svec_fill_kernel<4, true>), dim3((unsigned)t), dim3(mx::CP_BLOCK), 0, st, n,
+                           dense, off, out_indices_base1, out_values);
+    else
+        hipLaunchKernelGGL((mx::dense_to_svec_fill_kernel<4, false>), dim3((unsigned)t), dim3(mx::CP_BLOCK), 0, st, n,
+                           dense, off, out_indices_base1, out_values);
     MX_LAUNCH_CHECK();
     return 0;
 }

@@ -64,6 +64,9 @@ int finish_count(int64_t n, void *workspace, int32_t *indptr, int64_t *nnz_out_h
 // xfer.hip: synchronous host <-> device copies, pipelined through pinned slots + a host copy pool when large
 int xfer_h2d(void *dst_dev, const void *src_host, size_t bytes);
 int xfer_d2h(void *dst_host, const void *src_dev, size_t bytes);
+// many host arrays into one device buffer, part k at dst_dev + at (ascending, disjoint, below total)
+struct XferPart { const void *host; size_t bytes, at; };
+int xfer_h2d_parts(void *dst_dev, size_t total, const XferPart *parts, size_t nparts);
 
 // spmv.hip; v_dtype is an mx_dtype, or SPMV_F32_PATTERN: a float32 vector and a matrix without values (values unread)
 constexpr int SPMV_F32_PATTERN = 100;

@@ -4,8 +4,10 @@
 // units.
 #pragma once
 #include "mx_common.h"
+#include <cstring>
 #include <memory>
 #include <new>
+#include <vector>
 #pragma GCC visibility push(hidden)     // helpers of the unit that includes it: none of this joins the dynamic symbols
 namespace mx {
 
@@ -125,6 +127,33 @@ struct Csr {
         if (j.upload(indices, nnz)) return 1;
         if (value_bytes && x.upload(values, nnz, value_bytes)) return 1;
         return 0;
+    }
+};
+
+// Many host arrays in ONE device buffer (the operands of an rbind).  add() gives an array its 16-byte aligned place
+// and remembers where its device pointer is to be written; upload() allocates, fills those pointers in and sends
+// everything up as one stream (xfer_h2d_parts): no transfer per array and no host copy of the whole.
+class BindStaging {
+    std::vector<XferPart> parts;
+    std::vector<const void **> devs;
+    size_t total = 0;
+    DevBuf buf;
+
+public:
+    // an absent array (host null or no bytes of it) keeps a null device pointer
+    void add(const void *host, size_t bytes, const void **dev)
+    {
+        *dev = nullptr;
+        if (!host || bytes == 0) return;
+        parts.push_back(XferPart{host, bytes, total});
+        devs.push_back(dev);
+        total += (bytes + 15) & ~(size_t)15;
+    }
+    int upload()
+    {
+        if (buf.alloc_bytes(total)) return 1;
+        for (size_t k = 0; k < parts.size(); k++) *devs[k] = (char *)buf.p + parts[k].at;
+        return mx::xfer_h2d_parts(buf.p, total, parts.data(), parts.size());
     }
 };
 

@@ -6,9 +6,13 @@
 // takes a page fault per 4 KiB: 1 GB of C came back at ~10-14 GB/s.  Here large transfers run as a pipeline over
 // three pinned 8 MiB slots: the DMA engine moves slot k+1 while a small pool of host threads copies slot k to /
 // from the caller's buffer (page faults and memcpy spread over the pool).  Synchronous at return, like hipMemcpy.
+#include <algorithm>
 #include <condition_variable>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <mutex>
+#include <new>
 #include <thread>
 #include <vector>
 
@@ -36,9 +40,14 @@ public:
     // dst[0..n) = src[0..n), split over the pool in page-aligned pieces; returns when all pieces are done
     void copy(void *dst, const void *src, size_t n)
     {
-        if (n < ((size_t)1 << 20) || n_ <= 1) { memcpy(dst, src, n); return; }
+        run(n, [dst, src](size_t off, size_t len) { memcpy((char *)dst + off, (const char *)src + off, len); });
+    }
+    // job(off, len) over [0, n) in page-aligned pieces, one per thread; returns when all pieces are done
+    void run(size_t n, const std::function<void(size_t, size_t)> &job)
+    {
+        if (n < ((size_t)1 << 20) || n_ <= 1) { job(0, n); return; }
         std::unique_lock<std::mutex> lk(mu_);
-        dst_ = (char *)dst; src_ = (const char *)src; bytes_ = n;
+        job_ = &job; bytes_ = n;
         piece_ = ((n + n_ - 1) / n_ + 4095) & ~(size_t)4095;
         pending_ = n_;
         gen_++;
@@ -52,7 +61,7 @@ private:
     {
         unsigned long seen = 0;
         for (;;) {
-            char *d; const char *s; size_t off, len;
+            const std::function<void(size_t, size_t)> *job; size_t off, len;
             {
                 std::unique_lock<std::mutex> lk(mu_);
                 cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
@@ -60,9 +69,9 @@ private:
                 seen = gen_;
                 off = piece_ * (size_t)id;
                 len = off < bytes_ ? (bytes_ - off < piece_ ? bytes_ - off : piece_) : 0;
-                d = dst_ + off; s = src_ + off;
+                job = job_;
             }
-            if (len) memcpy(d, s, len);
+            if (len) (*job)(off, len);
             {
                 std::lock_guard<std::mutex> lk(mu_);
                 if (--pending_ == 0) done_.notify_one();
@@ -76,8 +85,7 @@ private:
     bool stop_ = false;
     unsigned long gen_ = 0;
     int pending_ = 0;
-    char *dst_ = nullptr;
-    const char *src_ = nullptr;
+    const std::function<void(size_t, size_t)> *job_ = nullptr;
     size_t bytes_ = 0, piece_ = 0;
 };
 
@@ -176,6 +184,46 @@ int xfer_h2d(void *dst_dev, const void *src_host, size_t bytes)
         if (c >= (size_t)XF_SLOTS) MX_HIP(hipEventSynchronize(e.ev[s]));      // the DMA out of this slot has finished
         e.pool->copy(e.slot[s], (const char *)src_host + c * XF_CHUNK, len);
         MX_HIP(hipMemcpyAsync((char *)dst_dev + c * XF_CHUNK, e.slot[s], len, hipMemcpyHostToDevice, e.st));
+        MX_HIP(hipEventRecord(e.ev[s], e.st));
+    }
+    MX_HIP(hipStreamSynchronize(e.st));
+    return 0;
+}
+
+// Many host arrays into one device buffer: part k goes to dst_dev + parts[k].at; the parts are in ascending, disjoint
+// places below `total` (the bytes between them are padding, whose content is unspecified).  Large totals run through
+// the same pinned slots as xfer_h2d, each chunk gathered from the parts that cross it by the copy pool, so neither a
+// host copy of the whole nor a transfer per part is made; small ones are packed on the host and go up in one copy.
+int xfer_h2d_parts(void *dst_dev, size_t total, const XferPart *parts, size_t nparts)
+{
+    if (total == 0 || nparts == 0) return 0;
+    // dst[0..len) = the bytes [start, start + len) of the packed image
+    auto gather = [&](char *dst, size_t start, size_t len) {
+        const XferPart *k = std::upper_bound(parts, parts + nparts, start,
+                                             [](size_t s, const XferPart &p) { return s < p.at + p.bytes; });
+        for (; k < parts + nparts && k->at < start + len; k++) {
+            const size_t lo = k->at > start ? k->at : start;
+            const size_t hi = k->at + k->bytes < start + len ? k->at + k->bytes : start + len;
+            if (lo < hi) memcpy(dst + (lo - start), (const char *)k->host + (lo - k->at), hi - lo);
+        }
+    };
+    Engine &e = engine();
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (total < XF_MIN || !e.init()) {
+        std::unique_ptr<char[]> packed(new (std::nothrow) char[total]);
+        MX_REQUIRE(packed, "out of host memory");
+        gather(packed.get(), 0, total);
+        MX_HIP(hipMemcpy(dst_dev, packed.get(), total, hipMemcpyHostToDevice));
+        return 0;
+    }
+    const size_t nch = (total + XF_CHUNK - 1) / XF_CHUNK;
+    for (size_t c = 0; c < nch; c++) {
+        const int s = (int)(c % XF_SLOTS);
+        const size_t len = c + 1 < nch ? XF_CHUNK : total - c * XF_CHUNK;
+        if (c >= (size_t)XF_SLOTS) MX_HIP(hipEventSynchronize(e.ev[s]));      // the DMA out of this slot has finished
+        char *slot = (char *)e.slot[s];
+        e.pool->run(len, [&](size_t off, size_t n) { gather(slot + off, c * XF_CHUNK + off, n); });
+        MX_HIP(hipMemcpyAsync((char *)dst_dev + c * XF_CHUNK, slot, len, hipMemcpyHostToDevice, e.st));
         MX_HIP(hipEventRecord(e.ev[s], e.st));
     }
     MX_HIP(hipStreamSynchronize(e.st));

@@ -698,3 +698,112 @@ def rowvec_by_csc(v: torch.Tensor, A: DeviceCSR):
     check(lib.mxd_rowvec_by_csc(A.m, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v.contiguous()), _dp(out),
                                 _stream()))
     return out
+
+
+# ---- rbind / cbind: output sizes come from the operands' shapes, so nothing here waits for the device
+_BIND_OUT = {0: torch.float64, 1: torch.int32, 2: None}
+_SVEC_KIND = {"d": 3, "i": 4, "l": 5, "n": 6}
+
+
+def _matrix_kind(values) -> int:
+    """0 dgR, 1 lgR, 2 ngR by the values tensor"""
+    return {MX_F64: 0, MX_LGL: 1, MX_NONE: 2}[_value_dtype(values)]
+
+
+def _vector_kind(vx, kind) -> int:
+    """3 / 4 / 5 / 6 (d / i / l / n sparseVector): `kind` when given, else by the values tensor (int32: logical)"""
+    if kind is not None:
+        return _SVEC_KIND[kind]
+    return {MX_F64: 3, MX_LGL: 5, MX_NONE: 6}[_value_dtype(vx)]
+
+
+def _bind_out_kind(kinds) -> int:
+    """R/rbind.R:66-75: any numeric operand -> dgR (0), else any logical -> lgR (1), else ngR (2)"""
+    if any(k in (0, 3, 4) for k in kinds):
+        return 0
+    return 1 if any(k in (1, 5) for k in kinds) else 2
+
+
+def csr_rbind(items) -> DeviceCSR:
+    """rbind of device-resident operands through mxd_csr_rbind_batch: two launches whatever len(items) is.  An item
+    is a DeviceCSR (f64, int32 R-logical or no values) or a sparse vector (vi, vx, length) / (vi, vx, length, kind)
+    with vi its int32 1-based indices, vx f64 / int32 / None and kind "d" / "i" / "l" / "n" (default by vx: int32 is
+    logical).  The result has the value type R/rbind.R:66-75 gives and max-over-operands columns."""
+    lib = _lib.load()
+    items = list(items)
+    if not items:
+        raise ValueError("csr_rbind: no operands")
+    table = (_lib.RbindItem * len(items))()
+    row = pos = ncol = 0
+    kinds, dev = [], None
+    for k, it in enumerate(items):
+        if isinstance(it, DeviceCSR):
+            kind, p, j, x, nr, nc = _matrix_kind(it.values), it.indptr, it.indices, it.values, it.m, it.K
+        else:
+            vi, vx, length = it[:3]
+            kind, p, j, x, nr, nc = _vector_kind(vx, it[3] if len(it) > 3 else None), None, vi, vx, 1, int(length)
+            if kind == 6:
+                x = None
+        if j.dtype != torch.int32 or not j.is_contiguous() or (x is not None and int(x.numel()) != int(j.numel())):
+            raise ValueError(f"csr_rbind: operand {k}: indices must be contiguous int32, values as many as indices")
+        dev = j.device if dev is None else dev
+        n = int(j.numel())
+        table[k] = _lib.RbindItem(kind, nr, None if p is None else p.data_ptr(), j.data_ptr(),
+                                  None if x is None else x.data_ptr(), n, pos, row)
+        kinds.append(kind)
+        row, pos, ncol = row + nr, pos + n, max(ncol, nc)
+    if row >= 2**31 - 1 or pos > 2**31 - 1:
+        raise ValueError("csr_rbind: the result exceeds R's int32 index range")
+    out_kind = _bind_out_kind(kinds)
+    host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8)
+    dtable = host.to(dev)
+    out_p = torch.empty(row + 1, dtype=torch.int32, device=dev)
+    out_j = torch.empty(pos, dtype=torch.int32, device=dev)
+    out_x = None if out_kind == 2 else torch.empty(pos, dtype=_BIND_OUT[out_kind], device=dev)
+    check(lib.mxd_csr_rbind_batch(_dp(dtable), len(items), out_kind, row, pos, _dp(out_p), _dp(out_j), _dp(out_x),
+                                  _stream()))
+    return DeviceCSR(out_p, out_j, out_x, row, ncol, pos)
+
+
+def csr_cbind(A: DeviceCSR, B: DeviceCSR) -> DeviceCSR:
+    """cbind of two device-resident CSR operands of one value type (both f64, both int32 R-logical or both without
+    values) through mxd_csr_cbind_shift: row r is A's row r, then B's with its columns moved up by A.K; the shorter
+    operand contributes nothing past its end."""
+    lib = _lib.load()
+    vd = _value_dtype(A.values)
+    if _value_dtype(B.values) != vd:
+        raise ValueError("csr_cbind: the operands must hold the same kind of values (convert one first)")
+    if A.K + B.K > 2**31 - 1 or A.nnz + B.nnz > 2**31 - 1:
+        raise ValueError("csr_cbind: the result exceeds R's int32 index range")
+    dev = A.indptr.device
+    m, nnz = max(A.m, B.m), A.nnz + B.nnz
+    out_p = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    out_j = torch.empty(nnz, dtype=torch.int32, device=dev)
+    out_x = None if A.values is None else torch.empty(nnz, dtype=A.values.dtype, device=dev)
+    check(lib.mxd_csr_cbind_shift(A.m, B.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(B.indptr),
+                                  _dp(B.indices), _dp(B.values), vd, nnz, _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
+    return DeviceCSR(out_p, out_j, out_x, m, A.K + B.K, nnz)
+
+
+def csr_cbind_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, length: int, first: bool = False,
+                   kind: str | None = None) -> DeviceCSR:
+    """A with a sparse vector (vi: SORTED int32 1-based indices <= length, vx f64 / int32 / None, `kind` as in
+    csr_rbind) as one more column, behind A's columns or (first=True) in front of them, through mxd_csr_cbind_svec.
+    max(A.m, length) rows; the value type follows R/cbind.R:82-99."""
+    lib = _lib.load()
+    if vi.dtype != torch.int32 or not vi.is_contiguous() or (vx is not None and int(vx.numel()) != int(vi.numel())):
+        raise ValueError("csr_cbind_svec: vi must be contiguous int32, vx as long as vi")
+    xk, vk = _matrix_kind(A.values), _vector_kind(vx, kind)
+    nv, length = int(vi.numel()), int(length)
+    if nv > length or A.K + 1 > 2**31 - 1 or A.nnz + nv > 2**31 - 1:
+        raise ValueError("csr_cbind_svec: more entries than cells, or a result beyond R's int32 index range")
+    out_kind = 2 if (xk == 2 and vk == 6) else 1 if (xk in (1, 2) and vk in (5, 6)) else 0
+    dev = A.indptr.device
+    m, nnz = max(A.m, length), A.nnz + nv
+    out_p = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    out_j = torch.empty(nnz, dtype=torch.int32, device=dev)
+    out_x = None if out_kind == 2 else torch.empty(nnz, dtype=_BIND_OUT[out_kind], device=dev)
+    check(lib.mxd_csr_cbind_svec(A.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), xk, _dp(vi),
+                                 _dp(None if vk == 6 else vx), vk, nv, length, int(bool(first)), out_kind, _dp(out_p),
+                                 _dp(out_j), _dp(out_x), _stream()))
+    return DeviceCSR(out_p, out_j, out_x, m, A.K + 1, nnz)

@@ -615,6 +615,58 @@ def concat_csr_batch(objects, out_kind):
     return out
 
 
+def rbind_coo(objects, out_kind, row_offsets=None):
+    """rbind2_coo / rbind2_coo_vec (R/rbind.R:405-520) over plain arrays: objects = list of
+    (kind, i|None, j, values|None, nrows) with kind 0 dgT, 1 lgT, 2 ngT (0-based i, j), 3/4/5/6 d/i/l/n sparseVector
+    (i None, j = its 1-based indices, one row); out_kind 0 dgT, 1 lgT, 2 ngT; row_offsets = each operand's first
+    output row (default: one below the other, in the order given).  Returns dict(ii, jj, xx), xx None for
+    out_kind 2: the COO shape slice_coo_arbitrary_* return."""
+    lib = _lib.load()
+    keep, arr = [], (_RbindInput * max(len(objects), 1))()
+    for k, (kind, i, j, x, nr) in enumerate(objects):
+        jj = _i32(j)
+        ii = None if i is None else _i32(i)
+        if ii is not None and ii.size != jj.size:
+            raise ValueError("row and column indices have different length")
+        xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64 if kind in (0, 3) else np.int32)
+        if xx is not None and xx.size != jj.size:
+            raise ValueError("indices and values have different number of entries")
+        keep += [jj, ii, xx]
+        arr[k] = _RbindInput(kind, None if ii is None else ii.ctypes.data, jj.ctypes.data,
+                             None if xx is None else xx.ctypes.data, int(nr), jj.size)
+    offs = None if row_offsets is None else _i32(row_offsets)
+    if offs is not None and offs.size != len(objects):
+        raise ValueError("one row offset per operand")
+    out = _begin(lib.mx_rbind_coo_begin, arr, len(objects), ptr(offs), out_kind)[0]
+    return dict(ii=out["indptr"], jj=out["indices"], xx=None if out_kind == 2 else out["values"])
+
+
+def cbind_csr_svec(X_csr_indptr, X_csr_indices, X_csr_values, ncols_X, x_kind, v_indices_base1, v_values, v_kind,
+                   length, first, out_kind):
+    """cbind2(RsparseMatrix, sparseVector) (first=False) / cbind2(sparseVector, RsparseMatrix) (first=True): X of
+    x_kind 0 dgR, 1 lgR, 2 ngR with the vector (v_kind 3/4/5/6 d/i/l/n sparseVector, 1-based indices in any order)
+    as one more column.  Returns dict(indptr, indices, values), values None for out_kind 2."""
+    p, j, vi = _i32(X_csr_indptr), _i32(X_csr_indices), _i32(v_indices_base1)
+    xv = None if x_kind == 2 else np.ascontiguousarray(X_csr_values, dtype=np.float64 if x_kind == 0 else np.int32)
+    vv = None if v_kind == 6 else np.ascontiguousarray(v_values, dtype=np.float64 if v_kind == 3 else np.int32)
+    if (xv is not None and xv.size != j.size) or (vv is not None and vv.size != vi.size):
+        raise ValueError("indices and values have different number of entries")
+    out = _begin(_lib.load().mx_cbind_csr_svec_begin, ptr(p), p.size - 1, int(ncols_X), ptr(j), ptr(xv), x_kind,
+                 ptr(vi), ptr(vv), v_kind, vi.size, int(length), int(bool(first)), out_kind)[0]
+    if out_kind == 2:
+        out["values"] = None
+    return out
+
+
+def dense_to_svec(dense, dtype):
+    """A dense numeric (MX_F64) / integer (MX_I32) / logical (MX_LGL) vector as the (1-based positions, f64 values) of
+    a dsparseVector: cells that are zero are dropped, NA / NaN cells stay (NA_integer_ / NA -> NA_real_, TRUE -> 1).
+    Returns dict(ii, xx)."""
+    a = np.ascontiguousarray(dense, dtype=np.float64 if dtype == MX_F64 else np.int32).reshape(-1)
+    out = _begin(_lib.load().mx_dense_to_svec_begin, ptr(a), a.size, dtype)[0]
+    return dict(ii=out["indices"], xx=out["values"])
+
+
 def check_is_seq(indices) -> bool:
     """src/slice.cpp:25-35."""
     a = _i32(indices)
