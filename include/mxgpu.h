@@ -103,7 +103,8 @@ int mxd_spmm_csr_dense(int m, int n,
  *                          the plan is rebuilt on every call here — hold a plan yourself to amortise it
  *   algo MX_SPMM_AUTO    : PLANNED when B is larger than an XCD's L2, the operands qualify and there is enough
  *                          work to fill the chip, else ROWWAVE
- * npanels <= 0 / wg_per_cu <= 0 pick defaults. */
+ * npanels <= 0 / wg_per_cu <= 0 pick defaults.  ROWWAVE and SLAB enqueue and return; PLANNED, and AUTO when it picks
+ * PLANNED, synchronises once with the stream's work up to the plan's sizing pass, as mxd_spmm_plan_create does. */
 typedef enum { MX_SPMM_AUTO = 0, MX_SPMM_ROWWAVE = 1, MX_SPMM_SLAB = 2, MX_SPMM_PLANNED = 3 } mx_spmm_algo;
 int mxd_spmm_csr_dense_ex(int m, int n, int K,
                           const int32_t *indptr, const int32_t *indices, const double *values,
@@ -120,7 +121,11 @@ int mxd_spmm_csr_dense_ex(int m, int n, int K,
  * 2 = 1 + one timing barrier per generation among the workgroups of an XCD group; -1 = default (1).
  * Needs 16-B aligned rows of B (and of C when C is row-major).  wg_per_cu 1 / 2 / 4 = that many workgroups of
  * 16 / 8 / 4 wavefronts per CU (1024 / 512 / 256 rows per generation); any other value picks the default (1).
- * mxd_spmm_csr_dense_ex runs its plans with the defaults (wg_per_cu and sync_mode). */
+ * mxd_spmm_csr_dense_ex runs its plans with the defaults (wg_per_cu and sync_mode).
+ * Streams: a plan's arrays are written on the stream given to mxd_spmm_plan_create, and the call returns once the sizes
+ * are back, possibly before the fill has run: the plan is bound to the stream order of its creation.  Run it on that
+ * stream, or on another one only after the creating stream has been synchronised.  mxd_spmm_plan_run itself enqueues
+ * and returns; it packs B into scratch of the calling thread (see mxd_release_workspaces). */
 typedef struct mx_spmm_plan mx_spmm_plan;
 int mxd_spmm_plan_create(int m, int K, const int32_t *indptr, const int32_t *indices, const double *values,
                          int npanels, void *stream, mx_spmm_plan **plan);
@@ -132,7 +137,14 @@ int mxd_spmm_plan_copy_to_host(const mx_spmm_plan *plan, int32_t *step_off, int3
 int mxd_spmm_plan_run(const mx_spmm_plan *plan, int n, const void *B, size_t ldb, void *C, size_t ldc,
                       int dense_dtype, int colmajor_out, int wg_per_cu, int sync_mode, void *stream);
 
-/* AUTO's plan and the slab-major copy of B live in grow-only per-thread device buffers between calls; this frees them */
+/* AUTO's plan and the slab-major copy of B live in grow-only per-thread device buffers between calls; this frees them.
+ * That scratch (the packed copy of B, the timing barrier's counters, AUTO's plan buffers, the ring of timing events)
+ * is per host thread and per device, not per stream: every stream of one thread shares it.  So the SpMM calls of one
+ * thread (mxd_spmm_csr_dense_ex, mxd_spmm_plan_run) must be ordered on one stream, or separated by a synchronisation;
+ * two of them in flight on two streams of one thread would share the packed B and the plan.  Growth alone is safe:
+ * every buffer grows through hipFree + hipMalloc, and hipFree waits for the whole device, so no kernel still reads a
+ * buffer that is freed (a call that grows scratch is therefore not asynchronous; one of the same sizes before it is).
+ * Different host threads never share scratch. */
 int mxd_release_workspaces(void);
 
 /* HIP-event timing of the dominant kernel of every SpMM launch of this thread (events recorded on the launch stream
@@ -180,7 +192,8 @@ int mxd_values_elemwise(int op, int64_t nnz, const void *values1, const void *va
                         void *out_values, void *stream);
 
 /* Row gather  out = A[rows_take, :]  (copy_csr_rows_template, src/slice.cpp:225-274)
- * pass 1: new_indptr[r+1] + total;  pass 2: copy.  value_dtype MX_F64 / MX_LGL / MX_NONE. */
+ * pass 1: new_indptr[r+1] + total, *nnz_out_host written after an internal stream sync;  pass 2: copy.
+ * value_dtype MX_F64 / MX_LGL / MX_NONE. */
 size_t mxd_gather_workspace_bytes(int r);
 int mxd_csr_gather_count(int r, const int32_t *indptr, const int32_t *rows_take,
                          int32_t *new_indptr, void *workspace,
@@ -190,7 +203,8 @@ int mxd_csr_gather_fill(int r, const int32_t *indptr, const int32_t *indices, co
                         int32_t *new_indices, void *new_values, int value_dtype,
                         int64_t nnz_out /* lanes-per-row hint, -1 = unknown */, void *stream);
 
-/* Column-filtering slices.  Same count -> scan -> fill shape as the row gather; workspace of
+/* Column-filtering slices.  Same count -> scan -> fill shape as the row gather (each count
+ * synchronises the stream once, for *nnz_out_host; the fills and mxd_colmap_build do not); workspace of
  * mxd_gather_workspace_bytes(r).  avg_row_len (mean entries per source row) only steers the lanes-per-row choice.
  *   colrange: keep min_col <= col <= max_col, re-based to min_col, input order kept; values come out as f64
  *             whatever the input kind (copy_csr_rows_col_seq_template, src/slice.cpp:326-383)
@@ -233,7 +247,7 @@ int mxd_csr_cbind_shift(int nX, int nY, int ncolX, const int32_t *Xp, const int3
                         int32_t *indptr, int32_t *indices, void *values, void *stream);
 /* rbind: append one operand at (row_offset, entry_offset) with the value conversions of concat_csr_batch
  * (src/rbind.cpp:24-173).  in_kind 0 dgR, 1 lgR, 2 ngR, 3/4/5/6 d/i/l/n sparseVector (1-based indices, one row);
- * out_kind 0 dgR, 1 lgR, 2 ngR. */
+ * out_kind 0 dgR, 1 lgR, 2 ngR.  No synchronisation, for a vector as for a matrix. */
 int mxd_csr_rbind_append(int in_kind, const int32_t *indptr_in, const int32_t *indices_in, const void *values_in,
                          int nrows_in, int64_t nnz_in, int out_kind, int row_offset, int64_t entry_offset,
                          int32_t *out_indptr, int32_t *out_indices, void *out_values, void *stream);
@@ -390,7 +404,8 @@ int mxd_rowvec_by_csc(int ncols, int64_t nnz, const int32_t *indptr, const int32
 /* sort_sparse_indices of a sparse vector (sort_vector_indices_*, src/misc.cpp:460-527): ii[n] (non-negative) and
  * its values xx[n] (MX_F64, MX_I32 / MX_LGL, or MX_NONE with xx NULL) sorted by ii in place, stably, by the LSD
  * radix passes of the transpose.  One reduction first: *was_sorted_host = 1 and nothing is
- * written when ii is already non-decreasing.  workspace: mxd_sort_vector_indices_workspace_bytes(n). */
+ * written when ii is already non-decreasing.  One synchronise (after the reduction).
+ * workspace: mxd_sort_vector_indices_workspace_bytes(n). */
 size_t mxd_sort_vector_indices_workspace_bytes(int64_t n);
 int mxd_sort_vector_indices(int32_t *ii, void *xx, int64_t n, int value_dtype, void *workspace,
                             int *was_sorted_host, void *stream);
@@ -480,7 +495,7 @@ int mxd_exclusive_scan_i32(const int32_t *counts, int64_t n, int32_t *out,
 
 /* Next-row components: per-row sortedness check and
  * per-row index sort (check_is_sorted / sort_sparse_indices_known_ncol,
- * src/misc.cpp:118-128, :261-298). */
+ * src/misc.cpp:118-128, :261-298).  *flag_host is written after an internal stream sync. */
 int mxd_csr_rows_sorted(int m, const int32_t *indptr, const int32_t *indices,
                         int32_t *workspace4, int *flag_host, void *stream);
 /* sorts every row by column id (stable), in place; tmp_indices / tmp_values are

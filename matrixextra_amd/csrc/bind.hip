@@ -47,6 +47,12 @@ void indptr_offset_kernel(const int32_t *__restrict__ src, int n, int offset, in
     if (i < n) dst[i] = offset + src[i];
 }
 
+// the one indptr entry behind a sparse vector's row: written on the stream, so that the append needs no host copy
+__global__ void indptr_end_kernel(int32_t *__restrict__ dst, int32_t end)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) *dst = end;
+}
+
 // value conversion of concat_csr_batch (rbind.cpp:72-166), one entry.  IN: 0 f64, 1 R logical, 2 none, 4 R integer;
 // OUT: 0 f64, 1 R logical, 2 none.  `vec` says the input is a sparse vector (an lsparseVector's TRUE becomes 1.0, an
 // lgRMatrix's value is widened as it is).  This is the one statement of the table: every concat kernel calls it.
@@ -296,9 +302,9 @@ extern "C" int mxd_csr_rbind_append(int in_kind, const int32_t *indptr_in, const
     const bool vec = in_kind >= 3;
     if (row_offset == 0) MX_HIP(hipMemsetAsync(out_indptr, 0, sizeof(int32_t), st));
     if (vec) {
-        const int32_t end = (int32_t)(entry_offset + nnz_in);
-        MX_HIP(hipMemcpyAsync(out_indptr + row_offset + 1, &end, sizeof(int32_t), hipMemcpyHostToDevice, st));
-        MX_HIP(hipStreamSynchronize(st));          // `end` is a stack temporary
+        hipLaunchKernelGGL(mx::indptr_end_kernel, dim3(1), dim3(1), 0, st, out_indptr + row_offset + 1,
+                           (int32_t)(entry_offset + nnz_in));
+        MX_LAUNCH_CHECK();
     } else if (nrows_in > 0) {
         hipLaunchKernelGGL(mx::indptr_offset_kernel, dim3((unsigned)mx::ceil_div(nrows_in, 256)), dim3(256), 0, st,
                            indptr_in + 1, nrows_in, (int)entry_offset, out_indptr + row_offset + 1);
