@@ -16,6 +16,7 @@ from typing import NamedTuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmxgpu.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu.h")
+REDUCE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_reduce.h")
 
 
 class MxError(RuntimeError):
@@ -85,17 +86,21 @@ def parse_header(text: str) -> Header:
     return Header(functions, constants, structs)
 
 
-def _read_header() -> Header:
+def _read_header(path: str = HEADER_PATH) -> Header:
     try:
-        with open(HEADER_PATH) as f:
+        with open(path) as f:
             return parse_header(f.read())
     except OSError as e:
-        raise MxError(f"{HEADER_PATH} not readable ({e}): the ctypes signatures, constants and structs of "
+        raise MxError(f"{path} not readable ({e}): the ctypes signatures, constants and structs of "
                       "libmxgpu.so are bound from it") from e
 
 
 HEADER = _read_header()
 globals().update(HEADER.constants)        # MX_F64 ... MX_NONE, MX_OP_*, MX_KEEP_*, MX_ALIAS_ALL, MXGPU_ABI_VERSION, ...
+# the reduction family has a header and a table of its own (include/mxgpu_reduce.h), bound on the same library;
+# HEADER and declared_symbols() stay what include/mxgpu.h declares
+REDUCE_HEADER = _read_header(REDUCE_HEADER_PATH)
+globals().update(REDUCE_HEADER.constants)  # MX_RED_SUM, MX_RED_ABS_SUM, MX_RED_SQ_SUM, MX_RED_ABS_MAX
 # mx_dvec_op, by R's operator
 MX_DV_OPS = {"*": HEADER.constants["MX_DV_MULTIPLY"], "^": HEADER.constants["MX_DV_POWERTO"],
              "/": HEADER.constants["MX_DV_DIVIDE"], "%%": HEADER.constants["MX_DV_DIVREST"],
@@ -126,12 +131,13 @@ def load() -> C.CDLL:
     except Exception:  # pragma: no cover - torch is optional for the plain C-ABI
         pass
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [name for name in HEADER.functions if not hasattr(lib, name)]
-    if missing:
-        raise MxError(f"libmxgpu.so lacks symbols declared in include/mxgpu.h: {missing}")
-    for name, (restype, argtypes) in HEADER.functions.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    for header, path in ((HEADER, "include/mxgpu.h"), (REDUCE_HEADER, "include/mxgpu_reduce.h")):
+        missing = [name for name in header.functions if not hasattr(lib, name)]
+        if missing:
+            raise MxError(f"libmxgpu.so lacks symbols declared in {path}: {missing}")
+        for name, (restype, argtypes) in header.functions.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     if lib.mx_abi_version() != HEADER.constants["MXGPU_ABI_VERSION"]:
         raise MxError("libmxgpu.so ABI version mismatch")
     _lib = lib

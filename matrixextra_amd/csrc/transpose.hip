@@ -34,7 +34,10 @@
 // rows from the caller instead of an indptr search (TP_SRC_ROWS).  The sort of a sparse vector
 // (mxd_sort_vector_indices, after it) runs them once, on one key.  The sort of COO triplets (mxd_coo_sort, last)
 // runs them on both keys, the second run taking up the first run's permutation, and gathers the values once.
+// The column order of a CSR pattern (mxd_csr_column_order, after the transpose) is the transpose's passes and its
+// indptr step without the gather: the permutation itself is the result.
 #include "mx_dispatch.h"
+#include "mx_reduce.h"
 #include "mx_workspace.h"
 
 namespace mx {
@@ -523,6 +526,36 @@ static int csr_transpose(int m, int n, const int32_t *indptr, const int32_t *ind
     return 0;
 }
 
+// ---- column order of a CSR pattern: the transpose's sort, its permutation handed out -------------------------
+// perm_out[q] = row-major position of the q-th entry in column-major order (stable: rows ascend inside a column),
+// colptr_out = the column pointer.  The reductions over columns (reduce.hip) read the values through it, for every
+// matrix that shares the pattern.
+static int csr_column_order(int m, int n, const int32_t *indptr, const int32_t *indices, int64_t nnz,
+                            int32_t *perm_out, int32_t *colptr_out, void *workspace, hipStream_t st)
+{
+    MX_REQUIRE(m >= 0 && n >= 0 && nnz >= 0 && nnz <= INT_MAX, "mxd_csr_column_order: bad size");
+    MX_REQUIRE(m > 0 || nnz == 0, "mxd_csr_column_order: entries without rows");
+    MX_REQUIRE(colptr_out && (nnz == 0 || (indptr && indices && perm_out && workspace)),
+               "mxd_csr_column_order: null pointer");
+    if (nnz == 0) {
+        MX_HIP(hipMemsetAsync(colptr_out, 0, sizeof(int32_t) * ((size_t)n + 1), st));
+        return 0;
+    }
+    TpLayout L(workspace, nnz);
+    MX_HIP(hipMemsetAsync(L.flags, 0, 2 * sizeof(int32_t), st));
+    int fin = 0;
+    if (tp_sort_passes(TP_SRC_INDPTR, indices, nullptr, indptr, m, n, nnz, L, L.flags, &fin, st)) return 1;
+    MX_HIP(hipMemcpyAsync(perm_out, L.perm[fin], sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(tp_indptr_kernel, dim3(grid_for((int64_t)n + 1, 256, TP_GRID_CAP)), dim3(256), 0, st,
+                       L.keys[fin], nnz, (int64_t)n, colptr_out);
+    MX_LAUNCH_CHECK();
+    int32_t bad = 0;
+    MX_HIP(hipMemcpyAsync(&bad, L.flags, sizeof(bad), hipMemcpyDeviceToHost, st));
+    MX_HIP(hipStreamSynchronize(st));
+    MX_REQUIRE(!bad, "mxd_csr_column_order: column index outside [0, %d)", n);
+    return 0;
+}
+
 // ---- COO -> CSR: the transpose's passes run twice -----------------------------------------------------------
 // Stage 1 stably sorts the triplets by column, carrying the row id and the entry index: pass 0 reads the rows
 // from the caller (TP_SRC_ROWS) instead of searching an indptr.  The result is a CSC whose columns list their
@@ -816,6 +849,12 @@ extern "C" int mxd_csr_to_coo(int m, int64_t nnz, const int32_t *indptr, int32_t
 }
 
 extern "C" size_t mxd_csr_transpose_workspace_bytes(int64_t nnz) { return mx::TpLayout(nullptr, nnz).bytes; }
+
+extern "C" int mxd_csr_column_order(int m, int n, const int32_t *indptr, const int32_t *indices, int64_t nnz,
+                                    int32_t *perm_out, int32_t *colptr_out, void *workspace, void *stream)
+{
+    return mx::csr_column_order(m, n, indptr, indices, nnz, perm_out, colptr_out, workspace, mx::as_stream(stream));
+}
 
 extern "C" int mxd_csr_transpose(int m, int n, const int32_t *indptr, const int32_t *indices, const void *values,
                                  int value_dtype, int64_t nnz, int32_t *out_indptr, int32_t *out_indices,

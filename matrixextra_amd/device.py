@@ -37,6 +37,8 @@ class DeviceCSR:
     _sorted: bool | None = None
     _plan: object = None
     _plan_panels: int = -1
+    _order: object = None
+    _order_builds: int = 0
 
     def plan(self, npanels: int = 0, rebuild: bool = False):
         """Device-resident SpMM plan (mxd_spmm_plan_create); cached per DeviceCSR, buffers re-used on rebuild."""
@@ -71,6 +73,22 @@ class DeviceCSR:
                                           _stream()))
             self._sorted = bool(flag.value)
         return self._sorted
+
+    def column_order(self):
+        """(perm, colptr) of the pattern through mxd_csr_column_order: perm[q] is the row-major
+        position of the q-th entry in column-major order, colptr the column pointer.  Cached beside the plan: it
+        depends on indptr and indices only, so it also serves any DeviceCSR that shares them (col_reduce's `order`)."""
+        if self._order is None:
+            lib = _lib.load()
+            dev = self.indptr.device
+            ws = torch.empty(max(lib.mxd_csr_transpose_workspace_bytes(self.nnz), 16), dtype=torch.uint8, device=dev)
+            perm = torch.empty(max(self.nnz, 1), dtype=torch.int32, device=dev)
+            colptr = torch.empty(self.K + 1, dtype=torch.int32, device=dev)
+            check(lib.mxd_csr_column_order(self.m, self.K, _dp(self.indptr), _dp(self.indices), self.nnz, _dp(perm),
+                                           _dp(colptr), _dp(ws), _stream()))
+            self._order = (perm[:self.nnz], colptr)
+            self._order_builds += 1
+        return self._order
 
     @classmethod
     def from_host(cls, indptr, indices, values, K, device="cuda"):
@@ -807,3 +825,78 @@ def csr_cbind_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, leng
                                  _dp(None if vk == 6 else vx), vk, nv, length, int(bool(first)), out_kind, _dp(out_p),
                                  _dp(out_j), _dp(out_x), _stream()))
     return DeviceCSR(out_p, out_j, out_x, m, A.K + 1, nnz)
+
+
+# ---- reductions: one segmented reduction over entries, by rows or through the column order
+REDUCE_OPS = {"sum": _lib.MX_RED_SUM, "abs_sum": _lib.MX_RED_ABS_SUM, "sq_sum": _lib.MX_RED_SQ_SUM,
+              "abs_max": _lib.MX_RED_ABS_MAX}
+
+
+def segment_reduce(values, op, segptr: torch.Tensor, nnz: int, perm=None, na_rm: bool = False, value_dtype=None):
+    """out[s] = op over q in [segptr[s], segptr[s + 1]) of f(values[perm[q]]) through mxd_segment_reduce, as
+    (float64 out, int32 skipped or None).  values: float64, int32 R logicals, or None (every entry is 1); op: a key of
+    REDUCE_OPS; segptr: int32, nseg + 1 offsets.  No synchronisation."""
+    lib = _lib.load()
+    if op not in REDUCE_OPS:
+        raise ValueError(f"op must be one of {sorted(REDUCE_OPS)}, got {op!r}")
+    dev = segptr.device
+    nseg = int(segptr.numel()) - 1
+    vd = _value_dtype(values) if value_dtype is None else value_dtype
+    out = torch.empty(max(nseg, 0), dtype=torch.float64, device=dev)
+    skipped = torch.empty(max(nseg, 0), dtype=torch.int32, device=dev) if na_rm else None
+    ws = torch.empty(max(4 * lib.mxd_compact_workspace_bytes(int(nnz)), 16), dtype=torch.uint8, device=dev)
+    check(lib.mxd_segment_reduce(REDUCE_OPS[op], _dp(values), vd, _dp(perm), int(nnz), _dp(segptr), nseg,
+                                 int(bool(na_rm)), _dp(out), _dp(skipped), _dp(ws), _stream()))
+    return out, skipped
+
+
+def row_reduce(A: DeviceCSR, op: str = "sum", na_rm: bool = False):
+    """op over every row of a device-resident CSR (rowSums with "sum"): float64[A.m], or (result, skipped int32[A.m])
+    with na_rm, which leaves NaN / NA entries out and counts them per row."""
+    out, skipped = segment_reduce(A.values, op, A.indptr, A.nnz, None, na_rm)
+    return (out, skipped) if na_rm else out
+
+
+def col_reduce(A: DeviceCSR, op: str = "sum", na_rm: bool = False, order=None):
+    """op over every column of a device-resident CSR (colSums with "sum"): float64[A.K], or (result, skipped) with
+    na_rm.  order: the (perm, colptr) of DeviceCSR.column_order(), A's own (built once and cached) when None; pass the
+    order of another DeviceCSR with the same indptr and indices (the values-only X * v shares them with X) and the
+    sort is paid once per fit, not once per gradient."""
+    perm, colptr = A.column_order() if order is None else order
+    if int(colptr.numel()) != A.K + 1 or int(perm.numel()) != A.nnz:
+        raise ValueError("col_reduce: the order belongs to another pattern")
+    out, skipped = segment_reduce(A.values, op, colptr, A.nnz, perm, na_rm)
+    return (out, skipped) if na_rm else out
+
+
+def norm(A: DeviceCSR, type: str = "O") -> float:
+    """norm(A, type) for type "O" (largest column sum of |x|), "I" (largest row sum), "F" (Frobenius) or "M" (largest
+    |x|): the margin sums, then the same reduction over them as one "abs_max" segment.  Synchronises (a float)."""
+    if type not in ("O", "I", "F", "M"):
+        raise ValueError(f"norm: type must be one of 'O', 'I', 'F', 'M', got {type!r}")
+    if A.m == 0 or A.K == 0 or A.nnz == 0:
+        return 0.0
+    dev = A.indptr.device
+
+    def whole(values, op, n, vd=None):
+        segptr = torch.tensor([0, n], dtype=torch.int32, device=dev)
+        return float(segment_reduce(values, op, segptr, n, value_dtype=vd)[0].item())
+
+    if type == "F":
+        return float(np.sqrt(whole(A.values, "sq_sum", A.nnz, _value_dtype(A.values))))
+    if type == "M":
+        return whole(A.values, "abs_max", A.nnz, _value_dtype(A.values))
+    sums = row_reduce(A, "abs_sum") if type == "I" else col_reduce(A, "abs_sum")
+    return whole(sums, "abs_max", int(sums.numel()), MX_F64)
+
+
+def diag(A: DeviceCSR):
+    """diag(A) through mxd_csr_diag: the first stored (k, k) of every row k < min(A.m, A.K), 0 where there is none;
+    float64 for numeric values, int32 R logicals for logical values (NA kept) and for a pattern (0 / 1)."""
+    lib = _lib.load()
+    vd = _value_dtype(A.values)
+    d = min(A.m, A.K)
+    out = torch.empty(d, dtype=torch.float64 if vd == MX_F64 else torch.int32, device=A.indptr.device)
+    check(lib.mxd_csr_diag(A.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), vd, A.nnz, int(A.rows_sorted()),
+                           _dp(out), _stream()))
+    return out

@@ -1551,3 +1551,50 @@ def set_single_col_to_svec(indptr, indices, values, ncols, col_set, ii, xx, leng
     """src/assignment.cpp:1009-1133, ii 0-based and ascending: always new vectors."""
     return _assign_vec(_lib.load().mx_assign_csr_col_vec_begin, indptr, indices, values, ncols, col_set, _i32(ii), xx,
                        length)
+
+
+# ----------------------------------------------------------------------------- reductions (include/mxgpu_reduce.h)
+def _csr_values(values, value_dtype):
+    """(values array or None, mx_dtype) of a CSR operand's @x: float64, int32 R logicals, or None for a pattern."""
+    if values is None:
+        return None, MX_NONE
+    if value_dtype is None:
+        value_dtype = MX_LGL if np.asarray(values).dtype == np.int32 else MX_F64
+    return (_i32(values) if value_dtype == MX_LGL else _f64(values)), value_dtype
+
+
+def _csr_operand(indptr, indices, values, value_dtype):
+    p, j = _i32(indptr), _i32(indices)
+    x, vd = _csr_values(values, value_dtype)
+    if p.size < 1 or int(p[-1]) != j.size or (x is not None and x.size != j.size):
+        raise ValueError("indptr, indices and values do not form a CSR")
+    return p, j, x, vd
+
+
+def csr_margin_reduce(indptr, indices, values, ncols, axis, op=_lib.MX_RED_SUM, na_rm=False, mean=False,
+                      value_dtype=None):
+    """mx_csr_margin_reduce: `op` (an mx_reduce_op) over the rows (axis 0) or the columns (axis 1) of a CSR with
+    `ncols` columns, as float64[nrow or ncol]; mean=True divides by the other dimension, less the NAs na_rm skipped."""
+    p, j, x, vd = _csr_operand(indptr, indices, values, value_dtype)
+    nrow, ncol = p.size - 1, int(ncols)
+    out = np.empty(nrow if int(axis) == 0 else ncol, dtype=np.float64)
+    check(_lib.load().mx_csr_margin_reduce(nrow, ncol, ptr(p), ptr(j), ptr(x), vd, int(axis), int(op), int(bool(na_rm)),
+                                           int(bool(mean)), ptr(out)))
+    return out
+
+
+def csr_norm(indptr, indices, values, ncols, type, value_dtype=None):
+    """mx_csr_norm: type one of "O", "I", "F", "M" (norm_csr, R/csr_linalg.R:13-31), as a float."""
+    p, j, x, vd = _csr_operand(indptr, indices, values, value_dtype)
+    out = np.zeros(1, dtype=np.float64)
+    check(_lib.load().mx_csr_norm(p.size - 1, int(ncols), ptr(p), ptr(j), ptr(x), vd, ord(type), ptr(out)))
+    return float(out[0])
+
+
+def csr_diag(indptr, indices, values, ncols, value_dtype=None):
+    """mx_csr_diag: the first stored (k, k) of every row k < min(nrow, ncol), 0 where there is none; float64 for
+    numeric values, int32 R logicals for logical values (NA kept) and for a pattern (0 / 1)."""
+    p, j, x, vd = _csr_operand(indptr, indices, values, value_dtype)
+    out = np.empty(min(p.size - 1, int(ncols)), dtype=np.float64 if vd == MX_F64 else np.int32)
+    check(_lib.load().mx_csr_diag(p.size - 1, int(ncols), ptr(p), ptr(j), ptr(x), vd, ptr(out)))
+    return out
