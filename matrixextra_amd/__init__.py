@@ -5,6 +5,7 @@ Layers (SURVEY.md §1 / DESIGN.md):
   exports.py                     twins of R/RcppExports.R wrappers (ctypes -> C-ABI)
   matrices.py                    dgRMatrix / lgRMatrix / ngRMatrix / dgCMatrix / d/l/ngTMatrix / d/i/l/nsparseVector / float32
                                  stand-ins
+  structured.py                  dsR / lsR / nsR / dtR / ltR / ntR / dsC / dtC stand-ins and their device expansion
   matmul.py operators.py slice.py assign.py cleanup.py bind.py reduce.py   mirrors of the R glue (checks, messages, dimnames, classes)
   device.py                      device-resident CSR + mxd_* launches on torch tensors (bench, multi-GPU)
   distributed.py                 row-block sharding + RCCL all-gather of C
@@ -27,6 +28,8 @@ from .slice import subset_coo, subset_csr  # noqa: F401
 from .assign import assign_csr  # noqa: F401
 from .cleanup import check_sparse_matrix, filterSparse, remove_sparse_zeros  # noqa: F401
 from .bind import cbind, cbind2, rbind, rbind2, rbind_csr  # noqa: F401
+from .structured import (StructuredMatrix, dsCMatrix, dsRMatrix, dtCMatrix, dtRMatrix, lsRMatrix, ltRMatrix,  # noqa: F401
+                         nsRMatrix, ntRMatrix)
 from .reduce import colMeans, colSums, diag, norm, rowMeans, rowSums  # noqa: F401
 
 __version__ = "0.1.0"

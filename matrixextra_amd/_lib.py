@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmxgpu.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu.h")
 REDUCE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_reduce.h")
+SYM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_sym.h")
 
 
 class MxError(RuntimeError):
@@ -101,6 +102,9 @@ globals().update(HEADER.constants)        # MX_F64 ... MX_NONE, MX_OP_*, MX_KEEP
 # HEADER and declared_symbols() stay what include/mxgpu.h declares
 REDUCE_HEADER = _read_header(REDUCE_HEADER_PATH)
 globals().update(REDUCE_HEADER.constants)  # MX_RED_SUM, MX_RED_ABS_SUM, MX_RED_SQ_SUM, MX_RED_ABS_MAX
+# so has the structured-matrix family (include/mxgpu_sym.h): symmetric / unit-triangular expansion, triangle check
+SYM_HEADER = _read_header(SYM_HEADER_PATH)
+globals().update(SYM_HEADER.constants)     # MX_UPLO_UPPER, MX_UPLO_LOWER
 # mx_dvec_op, by R's operator
 MX_DV_OPS = {"*": HEADER.constants["MX_DV_MULTIPLY"], "^": HEADER.constants["MX_DV_POWERTO"],
              "/": HEADER.constants["MX_DV_DIVIDE"], "%%": HEADER.constants["MX_DV_DIVREST"],
@@ -131,7 +135,8 @@ def load() -> C.CDLL:
     except Exception:  # pragma: no cover - torch is optional for the plain C-ABI
         pass
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for header, path in ((HEADER, "include/mxgpu.h"), (REDUCE_HEADER, "include/mxgpu_reduce.h")):
+    for header, path in ((HEADER, "include/mxgpu.h"), (REDUCE_HEADER, "include/mxgpu_reduce.h"),
+                         (SYM_HEADER, "include/mxgpu_sym.h")):
         missing = [name for name in header.functions if not hasattr(lib, name)]
         if missing:
             raise MxError(f"libmxgpu.so lacks symbols declared in {path}: {missing}")

@@ -24,6 +24,7 @@ from .matrices import (NA_LOGICAL, MatrixExtraError, RsparseMatrix, TsparseMatri
                        check_valid_matrix, dgCMatrix, dgRMatrix, dgTMatrix, dimnames_of, dsparseVector, isparseVector,
                        lgRMatrix, lgTMatrix, lsparseVector, ngRMatrix, ngTMatrix, nsparseVector, sparseVector, stop,
                        t_shallow)
+from .structured import StructuredMatrix, as_general
 
 _INT_MAX = 2147483647                     # .Machine$integer.max
 _BINARY = (ngRMatrix, ngTMatrix, nsparseVector)                        # "nsparseMatrix", "nsparseVector"
@@ -65,11 +66,17 @@ def _dense_as_svec(x, length=None, what="bind"):
 
 
 def _is_binary(x):
-    return isinstance(x, _BINARY)
+    return isinstance(x, _BINARY) or (isinstance(x, StructuredMatrix) and x.value_dtype is None)
 
 
 def _is_logical(x):
-    return isinstance(x, _LOGICAL)
+    return isinstance(x, _LOGICAL) or (isinstance(x, StructuredMatrix) and x.value_dtype == np.int32)
+
+
+def _expanded(x):
+    """a symmetric / triangular operand as the general class of its kind and layout (R/rbind.R:297-306,
+    R/cbind.R:83-85: as.csr.matrix with the kind kept); anything else as it is"""
+    return as_general(x) if isinstance(x, StructuredMatrix) else x
 
 
 def _kind2(x, y):
@@ -199,6 +206,8 @@ def rbind_csr(*args):
                 lx = np.where(np.isnan(v.x), NA_LOGICAL, (v.x != 0).astype(np.int32)).astype(np.int32)
                 return lsparseVector(v.i, lx, v.length)
             return v
+        # a triangular with diag = "N" passes through unexpanded (:31-34): its slots are the general CSR already,
+        # and _cast_csr_same relabels them without a copy; every other structured class is expanded
         return _cast_csr_same(x)
 
     args = [cast_if_not_csr(x) for x in args]
@@ -303,6 +312,7 @@ def _no_method(what, x, y):
 
 def rbind2(x, y):
     """The rbind2 methods of R/rbind.R:322-401, :466, :524-542 by the classes of x and y."""
+    x, y = _expanded(x), _expanded(y)
     xd, yd = _is_dense_vector(x), _is_dense_vector(y)
     if xd or yd:
         if xd and yd:
@@ -410,6 +420,7 @@ def _cbind_csr_svec(X, v, first, kind=None):
 
 def cbind2(x, y):
     """The cbind2 methods of R/cbind.R:20-54, :137, :150-195 by the classes of x and y."""
+    x, y = _expanded(x), _expanded(y)
     xd, yd = _is_dense_vector(x), _is_dense_vector(y)
     if xd or yd:
         if xd and yd:

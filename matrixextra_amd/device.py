@@ -900,3 +900,73 @@ def diag(A: DeviceCSR):
     check(lib.mxd_csr_diag(A.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), vd, A.nnz, int(A.rows_sorted()),
                            _dp(out), _stream()))
     return out
+
+
+# ---- symmetric / unit-triangular operands (include/mxgpu_sym.h) ----------------------------------
+def _uplo(uplo: str) -> int:
+    if uplo not in ("U", "L"):
+        raise ValueError("uplo must be 'U' or 'L'")
+    return _lib.MX_UPLO_UPPER if uplo == "U" else _lib.MX_UPLO_LOWER
+
+
+def csr_triangle_check(A: DeviceCSR, uplo: str, strict: bool = False) -> int:
+    """How many entries of the square A lie outside the triangle `uplo` (strict: or on the diagonal)."""
+    lib = _lib.load()
+    ws = torch.empty(16, dtype=torch.uint8, device=A.indptr.device)
+    outside = C.c_int64(0)
+    check(lib.mxd_csr_triangle_check(A.m, _dp(A.indptr), _dp(A.indices), A.nnz, _uplo(uplo), int(bool(strict)), _dp(ws),
+                                     C.byref(outside), _stream()))
+    return int(outside.value)
+
+
+def csr_symmetric_count(A: DeviceCSR, uplo: str):
+    """The count pass of the symmetric expansion: (out_indptr, workspace, nnz_out); the workspace holds the column
+    order and the row ids that csr_symmetric_fill reads."""
+    lib = _lib.load()
+    dev = A.indptr.device
+    ws = torch.empty(max(lib.mxd_csr_sym_workspace_bytes(A.m, A.nnz), 16), dtype=torch.uint8, device=dev)
+    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
+    nnz_out = C.c_int64(0)
+    check(lib.mxd_csr_symmetric_to_general_count(A.m, _dp(A.indptr), _dp(A.indices), A.nnz, _uplo(uplo), _dp(out_p),
+                                                 _dp(ws), C.byref(nnz_out), _stream()))
+    return out_p, ws, int(nnz_out.value)
+
+
+def csr_symmetric_fill(A: DeviceCSR, uplo: str, out_p: torch.Tensor, ws: torch.Tensor, nnz_out: int,
+                       out_j: torch.Tensor | None = None, out_x: torch.Tensor | None = None) -> DeviceCSR:
+    """The fill pass: the general CSR, written into out_j / out_x when they are given."""
+    lib = _lib.load()
+    dev = A.indptr.device
+    if out_j is None:
+        out_j = torch.empty(max(nnz_out, 1), dtype=torch.int32, device=dev)
+    if out_x is None and A.values is not None:
+        out_x = torch.empty(max(nnz_out, 1), dtype=A.values.dtype, device=dev)
+    check(lib.mxd_csr_symmetric_to_general_fill(A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values), _value_dtype(A.values),
+                                                A.nnz, _uplo(uplo), _dp(out_p), nnz_out, _dp(out_j), _dp(out_x), _dp(ws),
+                                                _stream()))
+    return DeviceCSR(out_p, out_j[:nnz_out], None if A.values is None else out_x[:nnz_out], A.m, A.K, nnz_out)
+
+
+def csr_symmetric_to_general(A: DeviceCSR, uplo: str) -> DeviceCSR:
+    """The general CSR of a symmetric A that stores the triangle `uplo`: count, scan, fill (mxgpu_sym.h)."""
+    if A.m != A.K:
+        raise ValueError("a symmetric matrix is square")
+    out_p, ws, nnz_out = csr_symmetric_count(A, uplo)
+    return csr_symmetric_fill(A, uplo, out_p, ws, nnz_out)
+
+
+def csr_unit_triangular_to_general(A: DeviceCSR, uplo: str, out=None) -> DeviceCSR:
+    """The general CSR of a strictly triangular A with an implied unit diagonal: one launch, no synchronisation.
+    `out`: (indptr, indices, values) tensors to write into."""
+    lib = _lib.load()
+    dev = A.indptr.device
+    if A.m != A.K:
+        raise ValueError("a triangular matrix is square")
+    n_out = A.nnz + A.m
+    if out is None:
+        out = (torch.empty(A.m + 1, dtype=torch.int32, device=dev), torch.empty(max(n_out, 1), dtype=torch.int32, device=dev),
+               None if A.values is None else torch.empty(max(n_out, 1), dtype=A.values.dtype, device=dev))
+    out_p, out_j, out_x = out
+    check(lib.mxd_csr_unit_triangular_to_general(A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values), _value_dtype(A.values),
+                                                 A.nnz, _uplo(uplo), _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
+    return DeviceCSR(out_p, out_j[:n_out], None if out_x is None else out_x[:n_out], A.m, A.K, n_out)

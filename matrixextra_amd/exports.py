@@ -1598,3 +1598,46 @@ def csr_diag(indptr, indices, values, ncols, value_dtype=None):
     out = np.empty(min(p.size - 1, int(ncols)), dtype=np.float64 if vd == MX_F64 else np.int32)
     check(_lib.load().mx_csr_diag(p.size - 1, int(ncols), ptr(p), ptr(j), ptr(x), vd, ptr(out)))
     return out
+
+
+# ----------------------------------------------------------------------------- structured operands (include/mxgpu_sym.h)
+_UPLO = {"U": _lib.MX_UPLO_UPPER, "L": _lib.MX_UPLO_LOWER}
+
+
+def _uplo(uplo):
+    if uplo not in _UPLO:
+        raise ValueError("Matrix has invalid 'uplo' field.")
+    return _UPLO[uplo]
+
+
+def _structured_begin(fn, indptr, indices, values, uplo, value_dtype):
+    p, j, x, vd = _csr_operand(indptr, indices, values, value_dtype)
+    out = _begin(fn, ptr(p), p.size - 1, ptr(j), ptr(x), vd, 0 if x is None else x.size, _uplo(uplo),
+                 empty_values_dtype=np.float64 if x is None else x.dtype)[0]
+    out["values"] = None if x is None else out["values"].astype(x.dtype, copy=False)
+    return out
+
+
+def csr_symmetric_to_general(indptr, indices, values, uplo, value_dtype=None):
+    """mx_csr_symmetric_to_general_begin: the general CSR of an n x n symmetric CSR that stores the triangle `uplo`
+    ("U" / "L"), Matrix's as(x, "generalMatrix") behind as.csr.matrix of a dsR / lsR / nsR (R/conversions.R:180-295);
+    a dsC's (p, i, x) with uplo flipped gives its general CSC arrays.  Row r of the result is the mirrored entries and
+    the stored row (U: mirrored first, L: stored first); values are copied bit for bit.  values None -> a pattern."""
+    return _structured_begin(_lib.load().mx_csr_symmetric_to_general_begin, indptr, indices, values, uplo, value_dtype)
+
+
+def csr_unit_triangular_to_general(indptr, indices, values, uplo, value_dtype=None):
+    """mx_csr_unit_triangular_to_general_begin: the general CSR of a triangular CSR with diag = "U": every row gains
+    (r, r) = 1.0 / TRUE / pattern, in front of the stored row (U) or behind it (L).  An entry on the diagonal or in
+    the other triangle is an error."""
+    return _structured_begin(_lib.load().mx_csr_unit_triangular_to_general_begin, indptr, indices, values, uplo,
+                             value_dtype)
+
+
+def csr_triangle_check(indptr, indices, uplo, strict=False):
+    """mx_csr_triangle_check: how many entries of the square CSR lie outside the triangle `uplo` (strict: or on the
+    diagonal)."""
+    p, j = _i32(indptr), _i32(indices)
+    out = C.c_int64(0)
+    check(_lib.load().mx_csr_triangle_check(ptr(p), p.size - 1, ptr(j), _uplo(uplo), int(bool(strict)), C.byref(out)))
+    return int(out.value)

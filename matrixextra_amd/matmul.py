@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import exports
-from .matrices import (NA_INTEGER, NA_REAL, DenseMatrix, RsparseMatrix, as_csr_matrix, as_sparse_vector,
+from .matrices import (NA_INTEGER, NA_REAL, DenseMatrix, RsparseMatrix, as_csc_matrix, as_csr_matrix, as_sparse_vector,
                        check_valid_matrix, dgCMatrix, dgRMatrix, dimnames_of, dsparseVector, float32, isparseVector,
                        lsparseVector, nsparseVector, options, sort_sparse_indices, sparseVector, stop)
 
@@ -336,8 +336,18 @@ class RLogical(np.ndarray):
 
 
 # ---- dispatch (setMethod("%*%"/"tcrossprod"/"crossprod", ...)) ----------------------------------------
+def _general(o):
+    """A symmetric or triangular operand as the general class of its layout, as R/matmul.R reaches it through
+    as.csr.matrix / as.csc.matrix; anything else as it is."""
+    from .structured import StructuredMatrix
+    if not isinstance(o, StructuredMatrix):
+        return o
+    return as_csr_matrix(o) if o.layout == "R" else as_csc_matrix(o)
+
+
 def matmul(x, y):
     """`%*%` for the signatures the hot path registers (R/matmul.R:200,281,469,512,755-767)."""
+    x, y = _general(x), _general(y)
     if isinstance(x, RsparseMatrix):
         outer = _outer_route()
         if isinstance(y, float32):
@@ -363,6 +373,7 @@ def matmul(x, y):
 
 def tcrossprod(x, y):
     """tcrossprod for (Rsparse, matrix|float32) and (matrix|float32, Rsparse) — R/matmul.R:307,385,461,538."""
+    x, y = _general(x), _general(y)
     if isinstance(x, RsparseMatrix):
         return tcrossprod_csr_f32(x, y) if isinstance(y, float32) else tcrossprod_csr_dense(x, y)
     if isinstance(y, RsparseMatrix):
@@ -375,6 +386,7 @@ def tcrossprod(x, y):
 def crossprod(x, y):
     """crossprod(matrix, CsparseMatrix) — R/matmul.R:393; (float32 vector, CsparseMatrix) — :434, under
     options["mxgpu.outer_route"]."""
+    x, y = _general(x), _general(y)
     if isinstance(y, dgCMatrix) and isinstance(x, float32) and x.is_vector and _outer_route():
         return crossprod_f32_csc(x, y)
     if isinstance(y, dgCMatrix) and not isinstance(x, float32):

@@ -119,6 +119,8 @@ class RsparseMatrix:
 
     def __mul__(self, other):                         # R/operators.R:147 (CSR), :1217-1260 (vector)
         from . import operators
+        if _is_structured(other):                     # a symmetric / triangular operand converts itself and comes back
+            return NotImplemented
         if isinstance(other, TsparseMatrix):          # R/operators.R:81-135, :169-180
             return operators.multiply_csr_by_coo(self, other, logical=False)
         if isinstance(other, sparseVector):           # :1634
@@ -135,6 +137,8 @@ class RsparseMatrix:
 
     def __and__(self, other):                         # R/operators.R:183 (CSR), :1163-1169 (vector)
         from . import operators
+        if _is_structured(other):
+            return NotImplemented
         if isinstance(other, TsparseMatrix):          # :194-206
             return operators.multiply_csr_by_coo(self, other, logical=True)
         if not isinstance(other, RsparseMatrix):
@@ -304,7 +308,7 @@ class TsparseMatrix:
             return operators.multiply_csr_by_coo(other, self, logical=False)
         if isinstance(other, dgCMatrix):              # :189-192
             return t_shallow(operators.multiply_csr_by_coo(t_shallow(other), t_shallow(self), logical=False))
-        if isinstance(other, TsparseMatrix):
+        if isinstance(other, TsparseMatrix) or _is_structured(other):
             return NotImplemented
         if _coo_dense_route(other):                   # :495-515
             return operators.multiply_coo_by_dense(self, other)
@@ -322,7 +326,7 @@ class TsparseMatrix:
             return operators.multiply_csr_by_coo(other, self, logical=True)
         if isinstance(other, dgCMatrix):
             return t_shallow(operators.multiply_csr_by_coo(t_shallow(other), t_shallow(self), logical=True))
-        if isinstance(other, TsparseMatrix):
+        if isinstance(other, TsparseMatrix) or _is_structured(other):
             return NotImplemented
         if _coo_dense_route(other):                   # :544-552
             return operators.logicaland_coo_by_dense(self, other)
@@ -624,7 +628,11 @@ def as_csr_matrix(x, logical=False, binary=False):
     dgRMatrix passes through; lgRMatrix/ngRMatrix are expanded to numeric (or kept/converted
     to logical when `logical=TRUE`); a dgCMatrix goes through the device transpose, a d/l/n TsparseMatrix through
     the device COO sort (repeated triplets merged before the value type changes); scipy matrices and dense
-    arrays are converted."""
+    arrays are converted.  A symmetric or triangular operand (structured.py) is expanded on the device in its own kind
+    first, as as(x, "generalMatrix") does, and then follows the same rules."""
+    if _is_structured(x):
+        from . import structured
+        return structured.as_csr(x, logical=logical, binary=binary)
     if isinstance(x, dgCMatrix):
         check_valid_matrix(x)
         x = _csc_to_csr(x, binary=binary)
@@ -654,6 +662,12 @@ def as_csr_matrix(x, logical=False, binary=False):
         out.Dimnames = list(dimnames_of(x))
         return out
     return from_scipy(x, logical=logical, binary=binary)
+
+
+def _is_structured(x):
+    """a symmetric or triangular operand (structured.py, which imports this module)"""
+    from .structured import StructuredMatrix
+    return isinstance(x, StructuredMatrix)
 
 
 def _csc_to_csr(x, binary=False):
@@ -690,6 +704,9 @@ def as_coo_matrix(x, binary=False, logical=False):
     from . import exports
     if binary and logical:
         stop("Can pass only one of 'binary' or 'logical'.")
+    if _is_structured(x):                             # expanded in its own kind first, then the rules below
+        from . import structured
+        return structured.as_coo(x, binary=binary, logical=logical)
     if ((type(x) is dgTMatrix and not binary and not logical) or (type(x) is ngTMatrix and binary)
             or (type(x) is lgTMatrix and logical)):
         return x
@@ -733,6 +750,9 @@ def as_csc_matrix(x):
     from . import exports
     if isinstance(x, dgCMatrix):
         return x
+    if _is_structured(x):
+        from . import structured
+        return structured.as_csc(x)
     if isinstance(x, TsparseMatrix):
         check_valid_matrix(x)
         T = as_csr_matrix(_coo_to_compressed(x, csc=True))            # CSR of x^T in f64 = the CSC of x
@@ -750,6 +770,9 @@ def t_shallow(x):
     """t_shallow (R/trans.R:1-30, :128-150): relabels CSR as the CSC of the transpose (and back) without copying:
     the result shares x's `p` and index arrays; Dim and Dimnames are swapped.  Only dgRMatrix <-> dgCMatrix exist
     here.  A TsparseMatrix stays one, with its `i` and `j` arrays swapped."""
+    if _is_structured(x):                             # R <-> C with uplo flipped (R/trans.R:1-44)
+        from . import structured
+        return structured.t_shallow(x)
     Dim = (x.Dim[1], x.Dim[0])
     Dimnames = list(reversed(dimnames_of(x)))
     if isinstance(x, TsparseMatrix):                  # t_coo_to_coo (R/trans.R:74-76): i and j swap roles
@@ -774,6 +797,9 @@ def t_deep(x):
     """t_deep (R/trans.R:46-56, :153-162): a real transpose on the device that keeps the class: the CSR (or CSC)
     arrays of x^T, rows in ascending order, Dim and Dimnames swapped."""
     from . import exports
+    if _is_structured(x):                             # the stored triangle transposed, uplo flipped
+        from . import structured
+        return structured.t_deep(x)
     if not isinstance(x, (RsparseMatrix, dgCMatrix)):
         stop(f"t_deep: unsupported class {type(x).__name__}.")
     check_valid_matrix(x)
@@ -900,6 +926,9 @@ def check_valid_matrix(X):
         stop("Row names of matrix do not match with number of rows.")
     if dn[1] is not None and len(dn[1]) and len(dn[1]) != ncols:
         stop("Column names of matrix do not match with number of columns.")
+    if _is_structured(X):                             # :367-373, then the compressed-layout checks
+        from . import structured
+        return structured.check_valid_structured(X)
     if isinstance(X, TsparseMatrix):
         if X.i.size != X.j.size:
             stop("Matrix is invalid (row and column indices have different length).")

@@ -20,6 +20,7 @@ import numpy as np
 from . import _lib, exports
 from .matrices import (MatrixExtraError, RsparseMatrix, TsparseMatrix, as_csr_matrix, check_valid_matrix, dgCMatrix,
                        dimnames_of, lgRMatrix, stop)
+from .structured import StructuredMatrix
 
 NORM_TYPES = ("O", "o", "1", "I", "i", "F", "f", "M", "m", "2")
 _NORM_KIND = {"O": "O", "o": "O", "1": "O", "I": "I", "i": "I", "F": "F", "f": "F", "M": "M", "m": "M"}
@@ -39,8 +40,8 @@ class NamedVector(np.ndarray):
 
 def _operand(x):
     """(p, idx, values, value_dtype, nrow, ncol of the CSR that the slots form, transposed?, Dimnames of x)"""
-    if isinstance(x, TsparseMatrix):
-        x = as_csr_matrix(x)                    # validates, sorts and merges repeated triplets on the device
+    if isinstance(x, (TsparseMatrix, StructuredMatrix)):
+        x = as_csr_matrix(x)                    # validates; sorts and merges repeated triplets, or expands, on the device
     if isinstance(x, dgCMatrix):
         check_valid_matrix(x)
         return x.p, x.i, x.x, _lib.MX_F64, x.Dim[1], x.Dim[0], True, dimnames_of(x)

@@ -19,11 +19,12 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import exports
+from . import exports, structured
 from .matrices import (NA_INTEGER, NA_LOGICAL, NA_REAL, RsparseMatrix, TsparseMatrix, _coo_to_compressed,
                        as_coo_matrix, as_csr_matrix, as_sparse_vector, check_valid_matrix, dgRMatrix, dgTMatrix,
                        lgRMatrix, lgTMatrix, lsparseVector, ngRMatrix, ngTMatrix, nsparseVector, options,
                        sort_sparse_indices, stop)
+from .structured import StructuredMatrix
 
 
 def _svec_selector(v, max_i):
@@ -321,6 +322,12 @@ def subset_csr(x, i=None, j=None, drop=False):
       anything else                               -> copy_csr_arbitrary_*                             (:547-565)
       full reversal of both                       -> reverse_rows_* + reverse_columns_inplace_*       (:439-469)"""
     check_valid_matrix(x)
+    if isinstance(x, StructuredMatrix):
+        if x.layout != "R":
+            stop("subset_csr takes the row-compressed classes; convert a CsparseMatrix with as_csr_matrix first.")
+        if _drop_route() and i is not None and j is not None and _is_scalar_number(i) and _is_scalar_number(j):
+            return _subset_csr_single(x, i, j, drop)                # :316-333 come before the lookup
+        return subset_csr(structured.as_general(x), i, j, drop)    # :473-474
     if i is None and j is None:
         return drop_slice(x, drop)
     if _drop_route() and i is not None and j is not None and _is_scalar_number(i) and _is_scalar_number(j):
@@ -474,11 +481,21 @@ def _is_scalar_number(v):
 def _subset_csr_single(x, i, j, drop):
     """R/slice.R:302-381, under the drop route: `x[i, j]` with two scalar numbers through extract_single_val_csr_*.
     A scalar (float; TRUE / FALSE / NA_LOGICAL for an lgRMatrix), or with drop=False the 1 x 1 matrix that is empty
-    when the value is 0.  The symmetric / triangular branches (:316-333) have no stand-in class here.  A scalar <= 0
+    when the value is 0.  A symmetric / triangular operand takes the branches of :316-333 first (0 outside a
+    triangular's triangle, 1 on a unit diagonal, (i, j) swapped into a symmetric's stored triangle).  A scalar <= 0
     is no exclusion on this route: it selects nothing and gives 0, as on the COO route (the reference reads row
     i - 1 < 0 of the index pointer there)."""
     i, j = _scalar_index(i), _scalar_index(j)
     nrow, ncol = x.Dim
+    known = None
+    if isinstance(x, StructuredMatrix):
+        if i != NA_INTEGER and j != NA_INTEGER and 1 <= i <= nrow and 1 <= j <= ncol:
+            route = structured.scalar_route(x, i, j)
+            if route[0] == "value":
+                known = route[1]
+            else:
+                i, j = route[1], route[2]
+        x = structured.stored_as_general(x)
     kind = _cls_kind(x)
     if i == NA_INTEGER or j == NA_INTEGER:                      # :309-310
         res = NA_REAL
@@ -486,6 +503,8 @@ def _subset_csr_single(x, i, j, drop):
         stop("Subscript out of bounds.")
     elif i < 1 or j < 1:
         res = 0.0
+    elif known is not None:                                     # :316-322: `res <- 0` / `res <- 1.`, numbers in every kind
+        res = known
     elif kind == "d":
         res = exports.extract_single_val_csr_numeric(x.p, x.j, x.x, i - 1, j - 1)
     elif kind == "l":                                           # as.logical() of the int the export returns
@@ -519,7 +538,8 @@ def _empty_coo(kind, n_row, n_col, row_names, col_names):
 
 
 def _subset_coo_single(x, i, j, drop):
-    """R/slice_coo.R:10-84.  The symmetric / triangular branches (:22-42) have no stand-in class here."""
+    """R/slice_coo.R:10-84.  The symmetric / triangular branches (:22-42) concern symmetric / triangular triplet
+    classes, which have no stand-in here; a compressed one reaches subset_coo expanded."""
     i, j = _scalar_index(i), _scalar_index(j)                  # as.integer(): truncates
     nrow, ncol = x.Dim
     if i == NA_INTEGER or j == NA_INTEGER:                      # :17-18
@@ -568,8 +588,11 @@ def subset_coo(x, i=None, j=None, drop=True):
       full reversal of both                       -> slice_coo_arbitrary_* with the rev-seq flags; the reference
                                                      flips (nrow-1) - i, (ncol-1) - j in R (:142-154), which the
                                                      kernel's affine reversed axes reproduce bit for bit
-      anything else                               -> slice_coo_arbitrary_*                                (:160-196)"""
+      anything else                               -> slice_coo_arbitrary_*                                (:160-196)
+    A symmetric / triangular compressed operand is expanded to the TsparseMatrix of its kind first."""
     check_valid_matrix(x)
+    if isinstance(x, StructuredMatrix):
+        x = as_coo_matrix(x, binary=x.value_dtype is None, logical=x.value_dtype == np.int32)
     if i is None and j is None:
         return drop_slice(x, drop)
     if i is not None and j is not None and _is_scalar_number(i) and _is_scalar_number(j):
