@@ -66,12 +66,9 @@ class DeviceCSR:
     def rows_sorted(self) -> bool:
         """check_is_sorted per row on the device (src/misc.cpp:118-128); cached."""
         if self._sorted is None:
-            lib = _lib.load()
-            ws = torch.empty(4, dtype=torch.int32, device=self.indptr.device)
-            flag = C.c_int(0)
-            check(lib.mxd_csr_rows_sorted(self.m, _dp(self.indptr), _dp(self.indices), _dp(ws), C.byref(flag),
-                                          _stream()))
-            self._sorted = bool(flag.value)
+            ws = _int32(self.indptr.device, 4)
+            flag, = _call("mxd_csr_rows_sorted", self.m, _dp(self.indptr), _dp(self.indices), _dp(ws), cells=(C.c_int,))
+            self._sorted = bool(flag)
         return self._sorted
 
     def column_order(self):
@@ -79,13 +76,12 @@ class DeviceCSR:
         position of the q-th entry in column-major order, colptr the column pointer.  Cached beside the plan: it
         depends on indptr and indices only, so it also serves any DeviceCSR that shares them (col_reduce's `order`)."""
         if self._order is None:
-            lib = _lib.load()
             dev = self.indptr.device
-            ws = torch.empty(max(lib.mxd_csr_transpose_workspace_bytes(self.nnz), 16), dtype=torch.uint8, device=dev)
-            perm = torch.empty(max(self.nnz, 1), dtype=torch.int32, device=dev)
-            colptr = torch.empty(self.K + 1, dtype=torch.int32, device=dev)
-            check(lib.mxd_csr_column_order(self.m, self.K, _dp(self.indptr), _dp(self.indices), self.nnz, _dp(perm),
-                                           _dp(colptr), _dp(ws), _stream()))
+            ws = _workspace(dev, "mxd_csr_transpose_workspace_bytes", self.nnz)
+            perm, = _entries(dev, self.nnz, torch.int32)
+            colptr = _int32(dev, self.K + 1)
+            _call("mxd_csr_column_order", self.m, self.K, _dp(self.indptr), _dp(self.indices), self.nnz, _dp(perm),
+                  _dp(colptr), _dp(ws))
             self._order = (perm[:self.nnz], colptr)
             self._order_builds += 1
         return self._order
@@ -171,69 +167,9 @@ def spmv(A: DeviceCSR, v: torch.Tensor, v_dtype=None, out=None):
     return out
 
 
-def csr_elemwise(op, A: DeviceCSR, B: DeviceCSR):
-    """CSR (+) CSR on device-resident operands: count -> scan -> (one host round trip for nnz) -> fill."""
-    lib = _lib.load()
-    assert A.m == B.m
-    dev = A.indptr.device
-    ws = torch.empty(lib.mxd_merge_workspace_bytes(A.m), dtype=torch.uint8, device=dev)
-    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
-    nnz_out = C.c_int64(0)
-    check(lib.mxd_csr_merge_count(op, A.m, _dp(A.indptr), _dp(A.indices), A.nnz, _dp(B.indptr), _dp(B.indices), B.nnz,
-                                  _dp(out_p), _dp(ws), C.byref(nnz_out), _stream()))
-    logical = op in (_lib.MX_OP_OR, _lib.MX_OP_XOR, _lib.MX_OP_AND)
-    out_j = torch.empty(nnz_out.value, dtype=torch.int32, device=dev)
-    out_x = torch.empty(nnz_out.value, dtype=torch.int32 if logical else torch.float64, device=dev)
-    check(lib.mxd_csr_merge_fill(op, A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values), A.nnz, _dp(B.indptr),
-                                 _dp(B.indices), _dp(B.values), B.nnz, _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
-    return DeviceCSR(out_p, out_j, out_x, A.m, A.K, int(nnz_out.value))
-
-
-def csr_gather_rows(A: DeviceCSR, rows: torch.Tensor):
-    """A[rows, :] on device (copy_csr_rows).  rows int32, 0-based."""
-    lib = _lib.load()
-    dev = A.indptr.device
-    r = int(rows.numel())
-    ws = torch.empty(lib.mxd_gather_workspace_bytes(r), dtype=torch.uint8, device=dev)
-    new_p = torch.empty(r + 1, dtype=torch.int32, device=dev)
-    nnz_out = C.c_int64(0)
-    check(lib.mxd_csr_gather_count(r, _dp(A.indptr), _dp(rows), _dp(new_p), _dp(ws), C.byref(nnz_out), _stream()))
-    new_j = torch.empty(nnz_out.value, dtype=torch.int32, device=dev)
-    if A.values is None:
-        vd, new_x = MX_NONE, None
-    else:
-        vd = MX_F64 if A.values.dtype == torch.float64 else MX_LGL
-        new_x = torch.empty(nnz_out.value, dtype=A.values.dtype, device=dev)
-    check(lib.mxd_csr_gather_fill(r, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(rows), _dp(new_p), _dp(new_j),
-                                  _dp(new_x), vd, nnz_out.value, _stream()))
-    return DeviceCSR(new_p, new_j, new_x, r, A.K, int(nnz_out.value))
-
-
-def csr_transpose(A: DeviceCSR) -> DeviceCSR:
-    """CSR of A^T (equivalently: CSR <-> CSC) on device-resident operands through mxd_csr_transpose: rows of the
-    result in ascending source-row order, values copied bit for bit, repeated (row, col) pairs merged."""
-    lib = _lib.load()
-    dev = A.indptr.device
-    if A.values is None:
-        vd = MX_NONE
-    elif A.values.dtype == torch.float64:
-        vd = MX_F64
-    elif A.values.dtype == torch.int32:
-        vd = MX_LGL
-    else:
-        raise ValueError(f"values must be float64 or int32 (R logical), got {A.values.dtype}")
-    ws = torch.empty(max(lib.mxd_csr_transpose_workspace_bytes(A.nnz), 16), dtype=torch.uint8, device=dev)
-    out_p = torch.empty(A.K + 1, dtype=torch.int32, device=dev)
-    out_j = torch.empty(max(A.nnz, 1), dtype=torch.int32, device=dev)
-    out_x = None if A.values is None else torch.empty(max(A.nnz, 1), dtype=A.values.dtype, device=dev)
-    nnz_out = C.c_int64(0)
-    check(lib.mxd_csr_transpose(A.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), vd, A.nnz, _dp(out_p),
-                                _dp(out_j), _dp(out_x), _dp(ws), C.byref(nnz_out), _stream()))
-    nnz = int(nnz_out.value)
-    return DeviceCSR(out_p, out_j[:nnz], None if out_x is None else out_x[:nnz], A.K, A.m, nnz)
-
-
+# ---- what the wrappers below are made of: kinds, buffers, the call, operand checks, the second pass --
 def _value_dtype(values) -> int:
+    """The mx_dtype of a values tensor; the only place that maps one."""
     if values is None:
         return MX_NONE
     if values.dtype == torch.float64:
@@ -243,34 +179,177 @@ def _value_dtype(values) -> int:
     raise ValueError(f"values must be float64 or int32 (R logical), got {values.dtype}")
 
 
+def _dtype(values):
+    return None if values is None else values.dtype
+
+
+def _float_dtype(t) -> int:
+    """MX_F64 / MX_F32 of a dense float operand"""
+    return MX_F64 if t.dtype == torch.float64 else MX_F32
+
+
+# dense_kind of the products with a dense operand (mxgpu.h): 0 double, 1 float32, 2 R integer, 3 R logical
+_DENSE_DOUBLE, _DENSE_FLOAT32, _DENSE_INTEGER, _DENSE_LOGICAL = range(4)
+# mx_rbind_input.kind (mxgpu.h): 0 dgR, 1 lgR, 2 ngR, 3 dsparseVector, 4 isparseVector, 5 lsparseVector, 6 nsparseVector
+_DGR, _LGR, _NGR, _DSVEC, _ISVEC, _LSVEC, _NSVEC = range(7)
+
+
+def _dense_kind(what: str, X: torch.Tensor, logical: bool):
+    """(X as the kernels read it, its dense_kind): bool becomes int32 R logicals, int32 is R integer, or R logical
+    with `logical`."""
+    if X.dtype == torch.bool:
+        return X.to(torch.int32), _DENSE_LOGICAL
+    if X.dtype == torch.int32:
+        return X, _DENSE_LOGICAL if logical else _DENSE_INTEGER
+    if X.dtype == torch.float64:
+        return X, _DENSE_DOUBLE
+    if X.dtype == torch.float32:
+        return X, _DENSE_FLOAT32
+    raise ValueError(f"{what}: unsupported dense dtype {X.dtype}")
+
+
+def _scratch(dev, nbytes):
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+
+def _workspace(dev, size_fn: str, *args):
+    """The workspace of one kernel family: as many bytes as its mxd_*_workspace_bytes(*args) asks for."""
+    return _scratch(dev, getattr(_lib.load(), size_fn)(*args))
+
+
+def _int32(dev, n):
+    return torch.empty(n, dtype=torch.int32, device=dev)
+
+
+def _entries(dev, k, *dtypes, floor=1):
+    """One buffer of k elements per dtype, None (no values) giving None.  A buffer is never shorter than `floor`:
+    most kernels are handed a valid pointer for an empty result too; floor=0 allocates exactly k."""
+    return [None if dt is None else torch.empty(max(k, floor), dtype=dt, device=dev) for dt in dtypes]
+
+
+_COUNT = (C.c_int64,)       # the host cell of a count pass
+
+
+def _call(fn: str, *args, cells=()):
+    """check(lib.<fn>(*args, one host out-cell per ctypes type in `cells`, the stream)): in every mxd_* prototype the
+    *_host parameters stand directly in front of the stream.  Returns the cells' values as plain Python numbers."""
+    cells = [t() for t in cells]
+    check(getattr(_lib.load(), fn)(*args, *map(C.byref, cells), _stream()))
+    return [c.value for c in cells]
+
+
+def _fill_pass(dev, k, dtypes, fill, floor=1, always=False):
+    """The second half of a count -> fill family, given the count k that the first pass read back: one entry buffer
+    per dtype (_entries), `fill(*buffers)`, the buffers cut to k entries.  An empty result launches no fill, unless
+    `always`: csr_elemwise, csr_gather_rows, _csr_compact and csc_by_dense launch theirs (every fill accepts an empty
+    result; skipping it only saves a launch).  The count pass is a plain _call in front, so what else it reads back,
+    and any decision between the passes, stays a local variable of the wrapper."""
+    buffers = _entries(dev, k, *dtypes, floor=floor)
+    if k or always:
+        fill(*buffers)
+    if k >= floor:              # the buffers are k long already
+        return buffers
+    return [b if b is None else b[:k] for b in buffers]
+
+
+def _coo_triplets(i, j, x, need_x=False, int32=True) -> int:
+    """nnz of the COO triplets (i, j, x), checked: equal lengths (x may be None unless need_x) and, with int32,
+    contiguous int32 i and j."""
+    nnz = int(i.numel())
+    if int(j.numel()) != nnz or (x is None and need_x) or (x is not None and int(x.numel()) != nnz):
+        raise ValueError("i, j and x must have the same length")
+    if int32 and (i.dtype != torch.int32 or j.dtype != torch.int32 or not (i.is_contiguous() and j.is_contiguous())):
+        raise ValueError("i and j must be contiguous int32 tensors")
+    return nnz
+
+
+def _svec(what: str, dev, vi, vx, vx_dtypes=(torch.float64,), pattern=True):
+    """The sparse vector (vi, vx) of a product, checked and contiguous: vi 1-d int32 on dev; vx of one of vx_dtypes,
+    of vi's shape and on dev, or, where the product takes an nsparseVector (`pattern`), None."""
+    if vi.dtype != torch.int32 or vi.dim() != 1 or vi.device != dev:
+        raise ValueError(f"{what}: vi must be a 1-d int32 tensor on {dev}")
+    if not (pattern and vx is None) and (vx.dtype not in vx_dtypes or vx.shape != vi.shape or vx.device != dev):
+        names = " or ".join(str(dt).replace("torch.", "") for dt in vx_dtypes)
+        raise ValueError(f"{what}: vx must be {names}, of vi's shape and on its device")
+    return vi.contiguous(), None if vx is None else vx.contiguous()
+
+
+def _bind_indices(message: str, j, x):
+    """An operand of a bind is read in place: contiguous int32 indices, and values, where there are any, as many."""
+    if j.dtype != torch.int32 or not j.is_contiguous() or (x is not None and int(x.numel()) != int(j.numel())):
+        raise ValueError(message)
+
+
+def _f64_values(what: str, A: DeviceCSR):
+    if A.values is None or A.values.dtype != torch.float64:
+        raise ValueError(f"{what}: X needs float64 values")
+
+
+def csr_elemwise(op, A: DeviceCSR, B: DeviceCSR):
+    """CSR (+) CSR on device-resident operands: count -> scan -> (one host round trip for nnz) -> fill."""
+    assert A.m == B.m
+    dev = A.indptr.device
+    ws = _workspace(dev, "mxd_merge_workspace_bytes", A.m)
+    out_p = _int32(dev, A.m + 1)
+    k, = _call("mxd_csr_merge_count", op, A.m, _dp(A.indptr), _dp(A.indices), A.nnz, _dp(B.indptr), _dp(B.indices),
+               B.nnz, _dp(out_p), _dp(ws), cells=_COUNT)
+    logical = op in (_lib.MX_OP_OR, _lib.MX_OP_XOR, _lib.MX_OP_AND)
+    out_j, out_x = _fill_pass(
+        dev, k, (torch.int32, torch.int32 if logical else torch.float64),
+        lambda oj, ox: _call("mxd_csr_merge_fill", op, A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values), A.nnz,
+                             _dp(B.indptr), _dp(B.indices), _dp(B.values), B.nnz, _dp(out_p), _dp(oj), _dp(ox)),
+        floor=0, always=True)
+    return DeviceCSR(out_p, out_j, out_x, A.m, A.K, k)
+
+
+def csr_gather_rows(A: DeviceCSR, rows: torch.Tensor):
+    """A[rows, :] on device (copy_csr_rows).  rows int32, 0-based."""
+    dev = A.indptr.device
+    vd = _value_dtype(A.values)
+    r = int(rows.numel())
+    ws = _workspace(dev, "mxd_gather_workspace_bytes", r)
+    new_p = _int32(dev, r + 1)
+    k, = _call("mxd_csr_gather_count", r, _dp(A.indptr), _dp(rows), _dp(new_p), _dp(ws), cells=_COUNT)
+    new_j, new_x = _fill_pass(
+        dev, k, (torch.int32, _dtype(A.values)),
+        lambda nj, nx: _call("mxd_csr_gather_fill", r, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(rows),
+                             _dp(new_p), _dp(nj), _dp(nx), vd, k),
+        floor=0, always=True)
+    return DeviceCSR(new_p, new_j, new_x, r, A.K, k)
+
+
+def csr_transpose(A: DeviceCSR) -> DeviceCSR:
+    """CSR of A^T (equivalently: CSR <-> CSC) on device-resident operands through mxd_csr_transpose: rows of the
+    result in ascending source-row order, values copied bit for bit, repeated (row, col) pairs merged."""
+    dev = A.indptr.device
+    vd = _value_dtype(A.values)
+    ws = _workspace(dev, "mxd_csr_transpose_workspace_bytes", A.nnz)
+    out_p = _int32(dev, A.K + 1)
+    out_j, out_x = _entries(dev, A.nnz, torch.int32, _dtype(A.values))
+    nnz, = _call("mxd_csr_transpose", A.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), vd, A.nnz, _dp(out_p),
+                 _dp(out_j), _dp(out_x), _dp(ws), cells=_COUNT)
+    return DeviceCSR(out_p, out_j[:nnz], None if out_x is None else out_x[:nnz], A.K, A.m, nnz)
+
+
 def coo_to_csr(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor | None, m: int, n: int) -> DeviceCSR:
     """Canonical CSR of an m x n COO held in HBM (int32 0-based triplets, any order) through mxd_coo_to_csr:
     columns ascending and unique per row, repeated (i, j) merged by Matrix's triplet rules.  coo_to_csr(j, i, x,
     n, m) gives the CSC arrays."""
-    lib = _lib.load()
     dev = i.device
-    nnz = int(i.numel())
-    if int(j.numel()) != nnz or (x is not None and int(x.numel()) != nnz):
-        raise ValueError("i, j and x must have the same length")
-    if i.dtype != torch.int32 or j.dtype != torch.int32 or not (i.is_contiguous() and j.is_contiguous()):
-        raise ValueError("i and j must be contiguous int32 tensors")
+    nnz = _coo_triplets(i, j, x)
     vd = _value_dtype(x)
-    ws = torch.empty(max(lib.mxd_coo_to_csr_workspace_bytes(nnz, int(n)), 16), dtype=torch.uint8, device=dev)
-    out_p = torch.empty(int(m) + 1, dtype=torch.int32, device=dev)
-    out_j = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
-    out_x = None if x is None else torch.empty(max(nnz, 1), dtype=x.dtype, device=dev)
-    nnz_out = C.c_int64(0)
-    check(lib.mxd_coo_to_csr(int(m), int(n), _dp(i), _dp(j), _dp(x), vd, nnz, _dp(out_p), _dp(out_j), _dp(out_x),
-                             _dp(ws), C.byref(nnz_out), _stream()))
-    k = int(nnz_out.value)
+    ws = _workspace(dev, "mxd_coo_to_csr_workspace_bytes", nnz, int(n))
+    out_p = _int32(dev, int(m) + 1)
+    out_j, out_x = _entries(dev, nnz, torch.int32, _dtype(x))
+    k, = _call("mxd_coo_to_csr", int(m), int(n), _dp(i), _dp(j), _dp(x), vd, nnz, _dp(out_p), _dp(out_j), _dp(out_x),
+               _dp(ws), cells=_COUNT)
     return DeviceCSR(out_p, out_j[:k], None if out_x is None else out_x[:k], int(m), int(n), k)
 
 
 def csr_to_coo(A: DeviceCSR):
     """(i, j, x) of a device CSR in storage order through mxd_csr_to_coo: i is new, j and x are A's own tensors."""
-    lib = _lib.load()
-    rows = torch.empty(max(A.nnz, 1), dtype=torch.int32, device=A.indptr.device)
-    check(lib.mxd_csr_to_coo(A.m, A.nnz, _dp(A.indptr), _dp(rows), _stream()))
+    rows, = _entries(A.indptr.device, A.nnz, torch.int32)
+    _call("mxd_csr_to_coo", A.m, A.nnz, _dp(A.indptr), _dp(rows))
     return rows[:A.nnz], A.indices, A.values
 
 
@@ -278,20 +357,14 @@ def coo_sort(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor | None, byrow: bo
     """Sorts COO triplets held in HBM (int32 0-based, non-negative) in place through mxd_coo_sort: by (i, j), or by
     (j, i) with byrow=False; x (f64, int32 R logicals, or None) follows.  Entries of one cell keep their input order.
     Returns whether the triplets were already sorted, in which case nothing was written."""
-    lib = _lib.load()
-    nnz = int(i.numel())
-    if int(j.numel()) != nnz or (x is not None and int(x.numel()) != nnz):
-        raise ValueError("i, j and x must have the same length")
-    if i.dtype != torch.int32 or j.dtype != torch.int32 or not (i.is_contiguous() and j.is_contiguous()):
-        raise ValueError("i and j must be contiguous int32 tensors")
+    nnz = _coo_triplets(i, j, x)
     if x is not None and not x.is_contiguous():
         raise ValueError("x must be a contiguous tensor")
     vd = _value_dtype(x)
-    ws = torch.empty(max(lib.mxd_coo_sort_workspace_bytes(nnz), 16), dtype=torch.uint8, device=i.device)
+    ws = _workspace(i.device, "mxd_coo_sort_workspace_bytes", nnz)
     first, second = (i, j) if byrow else (j, i)
-    was_sorted = C.c_int(1)
-    check(lib.mxd_coo_sort(_dp(first), _dp(second), _dp(x), nnz, vd, _dp(ws), C.byref(was_sorted), _stream()))
-    return bool(was_sorted.value)
+    was_sorted, = _call("mxd_coo_sort", _dp(first), _dp(second), _dp(x), nnz, vd, _dp(ws), cells=(C.c_int,))
+    return bool(was_sorted)
 
 
 CooAxis = _lib.CooAxis      # mx_coo_axis, as include/mxgpu.h declares it
@@ -303,14 +376,13 @@ def _coo_axis(take_base1: torch.Tensor | None, kind: str, n: int, lo: int = 0, h
         return CooAxis(0, 0, n - 1, 0, 0, None, None), ()
     if kind in ("seq", "rev"):
         return CooAxis(0, int(lo), int(hi), int(kind == "rev"), 0, None, None), ()
-    lib = _lib.load()
     dev = take_base1.device
     nt = int(take_base1.numel())
     nmap = int(take_base1.max().item()) + 1 if nt else 1
-    start = torch.empty(nmap + 1, dtype=torch.int32, device=dev)
-    pos = torch.empty(max(nt, 1), dtype=torch.int32, device=dev)
-    ws = torch.empty(max(lib.mxd_colmap_workspace_bytes(nmap), 16), dtype=torch.uint8, device=dev)
-    check(lib.mxd_colmap_build(_dp(take_base1), nt, nmap, _dp(start), _dp(pos), _dp(ws), _stream()))
+    start = _int32(dev, nmap + 1)
+    pos, = _entries(dev, nt, torch.int32)
+    ws = _workspace(dev, "mxd_colmap_workspace_bytes", nmap)
+    _call("mxd_colmap_build", _dp(take_base1), nt, nmap, _dp(start), _dp(pos), _dp(ws))
     return CooAxis(1, 0, 0, 0, nmap, start.data_ptr(), pos.data_ptr()), (start, pos, ws)
 
 
@@ -318,11 +390,8 @@ def coo_slice(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor | None, m: int, 
     """X[rows, cols] of an m x n COO held in HBM through mxd_coo_slice_count / _fill, as (i, j, x) of the result.
     Each selector is ("all",), ("seq", lo, hi) / ("rev", lo, hi) with 0-based bounds (positions r - lo / hi - r),
     or ("map", take_base1) with a 1-based int32 tensor (any order, repeats allowed)."""
-    lib = _lib.load()
     dev = i.device
-    nnz = int(i.numel())
-    if int(j.numel()) != nnz or (x is not None and int(x.numel()) != nnz):
-        raise ValueError("i, j and x must have the same length")
+    nnz = _coo_triplets(i, j, x, int32=False)
     vd = _value_dtype(x)
 
     def axis(sel, size):
@@ -334,19 +403,15 @@ def coo_slice(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor | None, m: int, 
 
     ai, keep_i = axis(rows, m)
     aj, keep_j = axis(cols, n)
-    ws = torch.empty(max(lib.mxd_coo_slice_workspace_bytes(nnz), 16), dtype=torch.uint8, device=dev)
-    nnz_out = C.c_int64(0)
-    check(lib.mxd_coo_slice_count(int(m), int(n), _dp(i), _dp(j), nnz, C.byref(ai), C.byref(aj), _dp(ws),
-                                  C.byref(nnz_out), _stream()))
-    k = int(nnz_out.value)
-    oi = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-    oj = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-    ox = None if x is None else torch.empty(max(k, 1), dtype=x.dtype, device=dev)
-    if k:
-        check(lib.mxd_coo_slice_fill(int(m), int(n), _dp(i), _dp(j), _dp(x), vd, nnz, C.byref(ai), C.byref(aj), _dp(ws),
-                                     _dp(oi), _dp(oj), _dp(ox), _stream()))
+    ws = _workspace(dev, "mxd_coo_slice_workspace_bytes", nnz)
+    k, = _call("mxd_coo_slice_count", int(m), int(n), _dp(i), _dp(j), nnz, C.byref(ai), C.byref(aj), _dp(ws),
+               cells=_COUNT)
+    out = _fill_pass(
+        dev, k, (torch.int32, torch.int32, _dtype(x)),
+        lambda oi, oj, ox: _call("mxd_coo_slice_fill", int(m), int(n), _dp(i), _dp(j), _dp(x), vd, nnz, C.byref(ai),
+                                 C.byref(aj), _dp(ws), _dp(oi), _dp(oj), _dp(ox)))
     del keep_i, keep_j          # the maps stay alive until both launches are enqueued (torch's caching allocator
-    return oi[:k], oj[:k], None if ox is None else ox[:k]      # reuses the blocks only on this same stream)
+    return tuple(out)           # reuses the blocks only on this same stream)
 
 
 def coo_inject_na(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor, m: int, n: int, rows_na: torch.Tensor,
@@ -355,65 +420,53 @@ def coo_inject_na(i: torch.Tensor, j: torch.Tensor, x: torch.Tensor, m: int, n: 
     §4.18), as (i, j, x) of the result: the triplets that stay, in storage order, then the NA block.  x: float64
     (NA_real_) or int32 R logicals (NA_LOGICAL); rows_na / cols_na: int32 tensors of 0-based indices, ascending and
     distinct (either may be empty)."""
-    lib = _lib.load()
     dev = i.device
-    nnz = int(i.numel())
-    if int(j.numel()) != nnz or x is None or int(x.numel()) != nnz:
-        raise ValueError("i, j and x must have the same length")
+    nnz = _coo_triplets(i, j, x, need_x=True, int32=False)
     for t in (i, j, rows_na, cols_na):
         if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
             raise ValueError(f"i, j, rows_na and cols_na must be contiguous int32 tensors on {dev}")
     vd = _value_dtype(x)
     n_rna, n_cna = int(rows_na.numel()), int(cols_na.numel())
-    ws = torch.empty(max(lib.mxd_compact_workspace_bytes(nnz), 16), dtype=torch.uint8, device=dev)
-    maps = torch.empty(4 + int(m) + int(n) + max(int(m), int(n)), dtype=torch.int32, device=dev)
-    nnz_out = C.c_int64(0)
-    check(lib.mxd_coo_inject_na_count(int(m), int(n), _dp(i), _dp(j), nnz, _dp(rows_na), n_rna, _dp(cols_na), n_cna,
-                                      _dp(ws), _dp(maps), C.byref(nnz_out), _stream()))
-    k = int(nnz_out.value)
-    oi = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-    oj = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-    ox = torch.empty(max(k, 1), dtype=x.dtype, device=dev)
-    if k:
-        check(lib.mxd_coo_inject_na_fill(int(m), int(n), _dp(i), _dp(j), _dp(x.contiguous()), vd, nnz, _dp(rows_na),
-                                         n_rna, _dp(cols_na), n_cna, _dp(ws), _dp(maps), _dp(oi), _dp(oj), _dp(ox), _stream()))
-    return oi[:k], oj[:k], ox[:k]
+    ws = _workspace(dev, "mxd_compact_workspace_bytes", nnz)
+    maps = _int32(dev, 4 + int(m) + int(n) + max(int(m), int(n)))
+    k, = _call("mxd_coo_inject_na_count", int(m), int(n), _dp(i), _dp(j), nnz, _dp(rows_na), n_rna, _dp(cols_na),
+               n_cna, _dp(ws), _dp(maps), cells=_COUNT)
+    return tuple(_fill_pass(
+        dev, k, (torch.int32, torch.int32, x.dtype),
+        lambda oi, oj, ox: _call("mxd_coo_inject_na_fill", int(m), int(n), _dp(i), _dp(j), _dp(x.contiguous()), vd,
+                                 nnz, _dp(rows_na), n_rna, _dp(cols_na), n_cna, _dp(ws), _dp(maps), _dp(oi), _dp(oj),
+                                 _dp(ox))))
 
 
 def csr_single(A: DeviceCSR, r: int, c: int):
     """A[r, c] (0-based) of a device-resident CSR through mxd_csr_single: (found, value) of the first entry of row r,
     in storage order, at column c; value is None for a pattern matrix or a miss."""
-    lib = _lib.load()
     if not 0 <= int(r) < A.m:
         raise ValueError(f"csr_single: row {r} outside [0, {A.m})")
     vd = _value_dtype(A.values)
-    ws = torch.empty(16, dtype=torch.uint8, device=A.indptr.device)
-    k = C.c_int64(-1)
-    val = C.c_double(0.0) if vd == MX_F64 else C.c_int32(0)
-    check(lib.mxd_csr_single(A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values), vd, A.nnz, int(r), int(c), _dp(ws),
-                             C.byref(k), C.byref(val), _stream()))
-    if k.value < 0:
+    ws = _scratch(A.indptr.device, 16)
+    k, val = _call("mxd_csr_single", A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values), vd, A.nnz, int(r), int(c),
+                   _dp(ws), cells=(C.c_int64, C.c_double if vd == MX_F64 else C.c_int32))
+    if k < 0:
         return False, None
-    return True, (None if vd == MX_NONE else val.value)
+    return True, (None if vd == MX_NONE else val)
 
 
 def _csr_compact(A: DeviceCSR, rule: int, mask: torch.Tensor | None) -> DeviceCSR:
     """count (one 8-byte read-back) -> fill through mxd_compact_count / _fill; A itself when a zero rule keeps all."""
-    lib = _lib.load()
     dev = A.indptr.device
     vd = _value_dtype(A.values)
-    ws = torch.empty(max(lib.mxd_compact_workspace_bytes(A.nnz), 16), dtype=torch.uint8, device=dev)
-    kept = C.c_int64(0)
-    check(lib.mxd_compact_count(A.nnz, _dp(A.values), vd, rule, _dp(mask), _dp(ws), C.byref(kept), _stream()))
-    k = int(kept.value)
+    ws = _workspace(dev, "mxd_compact_workspace_bytes", A.nnz)
+    k, = _call("mxd_compact_count", A.nnz, _dp(A.values), vd, rule, _dp(mask), _dp(ws), cells=_COUNT)
     if k == A.nnz and rule != _lib.MX_KEEP_MASK:
         return A
-    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
-    out_j = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-    out_x = torch.empty(max(k, 1), dtype=A.values.dtype, device=dev)
-    check(lib.mxd_compact_fill(A.nnz, _dp(A.values), vd, rule, _dp(mask), _dp(A.indices), None, A.m, _dp(A.indptr),
-                               _dp(ws), _dp(out_j), None, _dp(out_x), _dp(out_p), _stream()))
-    return DeviceCSR(out_p, out_j[:k], out_x[:k], A.m, A.K, k)
+    out_p = _int32(dev, A.m + 1)
+    out_j, out_x = _fill_pass(
+        dev, k, (torch.int32, A.values.dtype),
+        lambda oj, ox: _call("mxd_compact_fill", A.nnz, _dp(A.values), vd, rule, _dp(mask), _dp(A.indices), None, A.m,
+                             _dp(A.indptr), _dp(ws), _dp(oj), None, _dp(ox), _dp(out_p)),
+        always=True)
+    return DeviceCSR(out_p, out_j, out_x, A.m, A.K, k)
 
 
 def csr_remove_zeros(A: DeviceCSR, na_rm: bool = False) -> DeviceCSR:
@@ -436,41 +489,33 @@ def csc_by_dense(A: DeviceCSR, D: torch.Tensor, keep_na: bool = True, logical: b
     keep_na=True: every NA cell of D outside X's pattern becomes an NA_real_ entry and a repeated row is kept once
     (rows must be sorted inside each column); the result is new tensors.  keep_na=False: values only; the result is
     A.indptr itself, a copy of A.indices and the new values."""
-    lib = _lib.load()
     dev = A.indptr.device
-    if A.values is None or A.values.dtype != torch.float64:
-        raise ValueError("csc_by_dense: X needs float64 values")
+    _f64_values("csc_by_dense", A)
     if D.dim() != 2 or tuple(D.shape) != (A.K, A.m):
         raise ValueError(f"csc_by_dense: D must be {A.K} x {A.m}")
-    if D.dtype == torch.bool:
-        D, kind = D.to(torch.int32), 3
-    elif D.dtype == torch.int32:
-        kind = 3 if logical else 2
-    elif D.dtype in (torch.float64, torch.float32):
-        kind = 0 if D.dtype == torch.float64 else 1
-    else:
-        raise ValueError(f"csc_by_dense: unsupported dense dtype {D.dtype}")
+    D, kind = _dense_kind("csc_by_dense", D, logical)
     Dc = D.t().contiguous()                         # row-major D^T = column-major D
-    out_x = torch.empty(max(A.nnz, 1), dtype=torch.float64, device=dev)
+    out_x, = _entries(dev, A.nnz, torch.float64)
+
+    def values_only():
+        _call("mxd_csc_by_dense_elemwise", A.m, A.K, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(Dc), kind,
+              _dp(out_x))
+        return out_x[:A.nnz]
+
     if not keep_na:
-        check(lib.mxd_csc_by_dense_elemwise(A.m, A.K, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(Dc),
-                                            kind, _dp(out_x), _stream()))
-        return A.indptr, A.indices.clone(), out_x[:A.nnz]
-    ws = torch.empty(max(lib.mxd_csc_dense_na_workspace_bytes(A.K, A.m), 16), dtype=torch.uint8, device=dev)
-    total, outside = C.c_int64(0), C.c_int64(0)
-    check(lib.mxd_csc_dense_na_count(A.K, A.m, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(Dc), kind, _dp(ws),
-                                     C.byref(total), C.byref(outside), _stream()))
-    k = int(total.value)
-    if outside.value == 0 and k == A.nnz:           # the structure does not change: values only, new p and i
-        check(lib.mxd_csc_by_dense_elemwise(A.m, A.K, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(Dc),
-                                            kind, _dp(out_x), _stream()))
-        return A.indptr.clone(), A.indices.clone(), out_x[:k]
-    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
-    out_i = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-    out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
-    check(lib.mxd_csc_dense_na_fill(A.K, A.m, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(Dc), kind,
-                                    _dp(ws), _dp(out_p), _dp(out_i), _dp(out_x), _stream()))
-    return out_p, out_i[:k], out_x[:k]
+        return A.indptr, A.indices.clone(), values_only()
+    ws = _workspace(dev, "mxd_csc_dense_na_workspace_bytes", A.K, A.m)
+    k, outside = _call("mxd_csc_dense_na_count", A.K, A.m, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(Dc), kind, _dp(ws),
+                       cells=_COUNT * 2)
+    if outside == 0 and k == A.nnz:                 # the structure does not change: values only, new p and i
+        return A.indptr.clone(), A.indices.clone(), values_only()
+    out_p = _int32(dev, A.m + 1)
+    out_i, out_x = _fill_pass(
+        dev, k, (torch.int32, torch.float64),
+        lambda oi, ox: _call("mxd_csc_dense_na_fill", A.K, A.m, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values),
+                             _dp(Dc), kind, _dp(ws), _dp(out_p), _dp(oi), _dp(ox)),
+        always=True)
+    return out_p, out_i, out_x
 
 
 def csr_by_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, length: int, keep_na: bool = True):
@@ -479,32 +524,21 @@ def csr_by_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, length:
     an nsparseVector; length must divide A.m.  Rows whose position v does not store drop out, the others are scaled.
     keep_na=True also keeps the NaN / Inf entries of dropped rows (as NaN) and fills every column of a row whose
     vector value is NaN / Inf."""
-    lib = _lib.load()
     dev = A.indptr.device
-    if A.values is None or A.values.dtype != torch.float64:
-        raise ValueError("csr_by_svec: X needs float64 values")
-    if vi.dtype != torch.int32 or vi.dim() != 1 or vi.device != dev:
-        raise ValueError(f"csr_by_svec: vi must be a 1-d int32 tensor on {dev}")
-    if vx is not None and (vx.dtype != torch.float64 or vx.shape != vi.shape or vx.device != dev):
-        raise ValueError("csr_by_svec: vx must be float64, of vi's shape and on its device")
-    length, nv = int(length), int(vi.numel())
+    _f64_values("csr_by_svec", A)
+    vi, vx = _svec("csr_by_svec", dev, vi, vx)
+    length, nv, keep = int(length), int(vi.numel()), int(bool(keep_na))
     if A.m and (length <= 0 or length > A.m or A.m % length or nv > length):
         raise ValueError("csr_by_svec: the vector's length must divide the number of rows")
-    vi = vi.contiguous()
-    vx = None if vx is None else vx.contiguous()
-    ws = torch.empty(max(lib.mxd_csr_by_svec_workspace_bytes(A.m), 16), dtype=torch.uint8, device=dev)
-    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
-    total, x_na = C.c_int64(0), C.c_int64(0)
-    check(lib.mxd_csr_by_svec_count(A.m, A.K, A.nnz, _dp(A.indptr), _dp(A.values), _dp(vi), nv, _dp(vx), length,
-                                    int(bool(keep_na)), _dp(ws), _dp(out_p), C.byref(total), C.byref(x_na), _stream()))
-    k = int(total.value)
-    out_j = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-    out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
-    if k:
-        check(lib.mxd_csr_by_svec_fill(A.m, A.K, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(vi), nv,
-                                       _dp(vx), length, int(bool(keep_na)), _dp(ws), _dp(out_p), _dp(out_j), _dp(out_x),
-                                       _stream()))
-    return out_p, out_j[:k], out_x[:k]
+    ws = _workspace(dev, "mxd_csr_by_svec_workspace_bytes", A.m)
+    out_p = _int32(dev, A.m + 1)
+    k, _ = _call("mxd_csr_by_svec_count", A.m, A.K, A.nnz, _dp(A.indptr), _dp(A.values), _dp(vi), nv, _dp(vx), length,
+                 keep, _dp(ws), _dp(out_p), cells=_COUNT * 2)
+    out_j, out_x = _fill_pass(
+        dev, k, (torch.int32, torch.float64),
+        lambda oj, ox: _call("mxd_csr_by_svec_fill", A.m, A.K, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values),
+                             _dp(vi), nv, _dp(vx), length, keep, _dp(ws), _dp(out_p), _dp(oj), _dp(ox)))
+    return out_p, out_j, out_x
 
 
 def dense_by_svec(X: torch.Tensor, vi: torch.Tensor, vx: torch.Tensor, length: int, keep_na: bool = True,
@@ -515,25 +549,14 @@ def dense_by_svec(X: torch.Tensor, vi: torch.Tensor, vx: torch.Tensor, length: i
     does not divide the number of rows, gives a float64 tensor of X's shape (column-major storage, the vector
     recycled over the cells); a length that divides the number of rows gives the CSR (p, j, x) of full rows.
     keep_na=True keeps the NA / NaN / Inf cells that the vector does not cover, as NA / NaN."""
-    lib = _lib.load()
     dev = X.device
     if X.dim() != 2:
         raise ValueError("dense_by_svec: X must be a matrix")
-    if X.dtype == torch.bool:
-        X, kind = X.to(torch.int32), 3
-    elif X.dtype == torch.int32:
-        kind = 3 if logical else 2
-    elif X.dtype in (torch.float64, torch.float32):
-        kind = 0 if X.dtype == torch.float64 else 1
-    else:
-        raise ValueError(f"dense_by_svec: unsupported dense dtype {X.dtype}")
-    if vi.dtype != torch.int32 or vi.dim() != 1 or vi.device != dev:
-        raise ValueError(f"dense_by_svec: vi must be a 1-d int32 tensor on {dev}")
-    if vx.dtype != torch.float64 or vx.shape != vi.shape or vx.device != dev:
-        raise ValueError("dense_by_svec: vx must be float64, of vi's shape and on its device")
+    X, kind = _dense_kind("dense_by_svec", X, logical)
+    vi, vx = _svec("dense_by_svec", dev, vi, vx, pattern=False)
     nrows, ncols = int(X.shape[0]), int(X.shape[1])
-    length, nv = int(length), int(vi.numel())
-    route = lib.mx_dense_by_svec_route(nrows, ncols, length)
+    length, nv, keep = int(length), int(vi.numel()), int(bool(keep_na))
+    route = _lib.load().mx_dense_by_svec_route(nrows, ncols, length)
     if route < 0:
         check(1)
     if nv > length:
@@ -541,25 +564,21 @@ def dense_by_svec(X: torch.Tensor, vi: torch.Tensor, vx: torch.Tensor, length: i
     if nv and (int(vi.min()) < 1 or int(vi.max()) > length):
         raise ValueError(f"dense_by_svec: positions must lie inside 1..{length}")
     Xc = X.t().contiguous()                         # row-major X^T = column-major X
-    vi, vx, keep = vi.contiguous(), vx.contiguous(), int(bool(keep_na))
     if route in (_lib.MX_DSV_ROUTE_A, _lib.MX_DSV_ROUTE_D):
-        ws = torch.empty(max(lib.mxd_dense_by_svec_workspace_bytes(0, length), 16), dtype=torch.uint8, device=dev)
+        ws = _workspace(dev, "mxd_dense_by_svec_workspace_bytes", 0, length)
         out = torch.empty((ncols, nrows), dtype=torch.float64, device=dev)
-        check(lib.mxd_dense_by_svec_dense(nrows, ncols, _dp(Xc), kind, _dp(vi), nv, _dp(vx), length, keep, _dp(ws),
-                                          _dp(out), _stream()))
+        _call("mxd_dense_by_svec_dense", nrows, ncols, _dp(Xc), kind, _dp(vi), nv, _dp(vx), length, keep, _dp(ws),
+              _dp(out))
         return out.t()
-    ws = torch.empty(max(lib.mxd_dense_by_svec_workspace_bytes(nrows, length), 16), dtype=torch.uint8, device=dev)
-    out_p = torch.empty(nrows + 1, dtype=torch.int32, device=dev)
-    total = C.c_int64(0)
-    check(lib.mxd_dense_by_svec_count(nrows, ncols, _dp(Xc), kind, _dp(vi), nv, length, keep, _dp(ws), _dp(out_p),
-                                      C.byref(total), _stream()))
-    k = int(total.value)
-    out_j = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-    out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
-    if k:
-        check(lib.mxd_dense_by_svec_fill(nrows, ncols, _dp(Xc), kind, _dp(vx), length, keep, _dp(ws), _dp(out_p),
-                                         _dp(out_j), _dp(out_x), _stream()))
-    return out_p, out_j[:k], out_x[:k]
+    ws = _workspace(dev, "mxd_dense_by_svec_workspace_bytes", nrows, length)
+    out_p = _int32(dev, nrows + 1)
+    k, = _call("mxd_dense_by_svec_count", nrows, ncols, _dp(Xc), kind, _dp(vi), nv, length, keep, _dp(ws), _dp(out_p),
+               cells=_COUNT)
+    out_j, out_x = _fill_pass(
+        dev, k, (torch.int32, torch.float64),
+        lambda oj, ox: _call("mxd_dense_by_svec_fill", nrows, ncols, _dp(Xc), kind, _dp(vx), length, keep, _dp(ws),
+                             _dp(out_p), _dp(oj), _dp(ox)))
+    return out_p, out_j, out_x
 
 
 def csr_by_dvec_keep_na(A: DeviceCSR, v: torch.Tensor, op: str = "*"):
@@ -567,12 +586,10 @@ def csr_by_dvec_keep_na(A: DeviceCSR, v: torch.Tensor, op: str = "*"):
     recycled over the matrix, keeping the cells that R makes NA / NaN / 1 / Inf outside X's pattern,
     as (p, j, x) tensors.  A length that divides A.m rules whole rows; any other length up to A.m * A.K goes over the
     flat cells, and when that adds no entry the result's p and j are A's own tensors."""
-    lib = _lib.load()
     dev = A.indptr.device
     if op not in _lib.MX_DV_OPS:
         raise ValueError(f"csr_by_dvec_keep_na: unknown operation {op!r}")
-    if A.values is None or A.values.dtype != torch.float64:
-        raise ValueError("csr_by_dvec_keep_na: X needs float64 values")
+    _f64_values("csr_by_dvec_keep_na", A)
     if v.dtype != torch.float64 or v.dim() != 1 or v.device != dev:
         raise ValueError(f"csr_by_dvec_keep_na: v must be a 1-d float64 tensor on {dev}")
     v = v.contiguous()
@@ -580,49 +597,37 @@ def csr_by_dvec_keep_na(A: DeviceCSR, v: torch.Tensor, op: str = "*"):
     m, K, nnz = A.m, A.K, A.nnz
     if L < 1 or (A.m % L and L > A.m * A.K):
         raise ValueError("csr_by_dvec_keep_na: v needs between 1 and nrow * ncol entries")
-
-    def buf(nbytes):
-        return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-
-    def entries(k):
-        return (torch.empty(max(k, 1), dtype=torch.int32, device=dev),
-                torch.empty(max(k, 1), dtype=torch.float64, device=dev))
-
-    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
+    out_p = _int32(dev, m + 1)
     if L <= A.m and A.m % L == 0:                                       # row-ruled
-        ws = buf(lib.mxd_csr_by_dvec_na_rows_workspace_bytes(m))
-        total = C.c_int64(0)
-        check(lib.mxd_csr_by_dvec_na_rows_count(m, K, nnz, _dp(A.indptr), _dp(v), L, code, _dp(ws), _dp(out_p),
-                                                C.byref(total), _stream()))
-        k = int(total.value)
-        out_j, out_x = entries(k)
-        if k:
-            check(lib.mxd_csr_by_dvec_na_rows_fill(m, K, nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v), L,
-                                                   code, _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
-        return out_p, out_j[:k], out_x[:k]
-    sws = buf(lib.mxd_dvec_na_special_workspace_bytes(L))
-    nsp, cand, new = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    check(lib.mxd_dvec_na_special(m, K, _dp(v), L, code, _dp(sws), C.byref(nsp), C.byref(cand), _stream()))
-    if cand.value:
-        cws = buf(lib.mxd_dvec_na_cells_workspace_bytes(cand.value))
-        check(lib.mxd_dvec_na_cells_count(m, K, nnz, _dp(A.indptr), _dp(A.indices), L, _dp(sws), nsp.value, cand.value,
-                                          _dp(cws), C.byref(new), _stream()))
-    n_new = int(new.value)
-    _, ax = entries(A.nnz)
-    check(lib.mxd_csr_by_dvec(m, K, nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v), L, code, 1, _dp(ax),
-                              _stream()))
+        ws = _workspace(dev, "mxd_csr_by_dvec_na_rows_workspace_bytes", m)
+        k, = _call("mxd_csr_by_dvec_na_rows_count", m, K, nnz, _dp(A.indptr), _dp(v), L, code, _dp(ws), _dp(out_p),
+                   cells=_COUNT)
+        out_j, out_x = _fill_pass(
+            dev, k, (torch.int32, torch.float64),
+            lambda oj, ox: _call("mxd_csr_by_dvec_na_rows_fill", m, K, nnz, _dp(A.indptr), _dp(A.indices),
+                                 _dp(A.values), _dp(v), L, code, _dp(out_p), _dp(oj), _dp(ox)))
+        return out_p, out_j, out_x
+    sws = _workspace(dev, "mxd_dvec_na_special_workspace_bytes", L)
+    nsp, cand = _call("mxd_dvec_na_special", m, K, _dp(v), L, code, _dp(sws), cells=_COUNT * 2)
+    n_new = 0
+    if cand:
+        cws = _workspace(dev, "mxd_dvec_na_cells_workspace_bytes", cand)
+        n_new, = _call("mxd_dvec_na_cells_count", m, K, nnz, _dp(A.indptr), _dp(A.indices), L, _dp(sws), nsp, cand,
+                       _dp(cws), cells=_COUNT)
+    _, ax = _entries(dev, nnz, torch.int32, torch.float64)      # the int32 half is never used; the trace fixture pins it
+    _call("mxd_csr_by_dvec", m, K, nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v), L, code, 1, _dp(ax))
     if n_new == 0:
-        return A.indptr, A.indices, ax[:A.nnz]
-    ni, nx = entries(n_new)
-    nj = torch.empty_like(ni)
-    check(lib.mxd_dvec_na_cells_fill(m, K, _dp(v), L, code, _dp(sws), nsp.value, cand.value, _dp(cws), _dp(ni), _dp(nj),
-                                     _dp(nx), _stream()))
-    B = coo_to_csr(ni[:n_new], nj[:n_new], nx[:n_new], A.m, A.K)
-    k = A.nnz + n_new
-    out_j, out_x = entries(k)
-    check(lib.mxd_csr_join_disjoint(m, _dp(A.indptr), _dp(A.indices), _dp(ax), nnz, _dp(B.indptr), _dp(B.indices),
-                                    _dp(B.values), n_new, _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
-    return out_p, out_j[:k], out_x[:k]
+        return A.indptr, A.indices, ax[:nnz]
+    ni, nx, nj = _fill_pass(
+        dev, n_new, (torch.int32, torch.float64, torch.int32),
+        lambda i, x, j: _call("mxd_dvec_na_cells_fill", m, K, _dp(v), L, code, _dp(sws), nsp, cand, _dp(cws), _dp(i),
+                              _dp(j), _dp(x)))
+    B = coo_to_csr(ni, nj, nx, m, K)
+    out_j, out_x = _fill_pass(
+        dev, nnz + n_new, (torch.int32, torch.float64),
+        lambda oj, ox: _call("mxd_csr_join_disjoint", m, _dp(A.indptr), _dp(A.indices), _dp(ax), nnz, _dp(B.indptr),
+                             _dp(B.indices), _dp(B.values), n_new, _dp(out_p), _dp(oj), _dp(ox)))
+    return out_p, out_j, out_x
 
 
 def csr_filter(A: DeviceCSR, mask: torch.Tensor) -> DeviceCSR:
@@ -640,33 +645,27 @@ def csr_filter(A: DeviceCSR, mask: torch.Tensor) -> DeviceCSR:
 def _one_column(A: DeviceCSR, what: str):
     if A.K != 1:
         raise ValueError(f"{what}: X must have one column")
-    if A.values is None or A.values.dtype != torch.float64:
-        raise ValueError(f"{what}: X needs float64 values")
+    _f64_values(what, A)
 
 
 def csr_outer_dense(A: DeviceCSR, v: torch.Tensor):
     """X %*% v for a device-resident one-column CSR X (f64 values) and a dense f64 or f32 vector, as
     the (p, j, x) tensors of a CSR with A.m rows and v.numel() columns: every non-empty row of X times v, through the
     row's first stored value.  An f32 v gives the float product, widened."""
-    lib = _lib.load()
     dev = A.indptr.device
     _one_column(A, "csr_outer_dense")
     if v.dtype not in (torch.float64, torch.float32) or v.dim() != 1 or v.device != dev:
         raise ValueError(f"csr_outer_dense: v must be a 1-d float64 or float32 tensor on {dev}")
     v = v.contiguous()
     dim = int(v.numel())
-    ws = torch.empty(max(lib.mxd_csr_outer_dense_workspace_bytes(A.m), 16), dtype=torch.uint8, device=dev)
-    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
-    total = C.c_int64(0)
-    check(lib.mxd_csr_outer_dense_count(A.m, dim, _dp(A.indptr), _dp(ws), _dp(out_p), C.byref(total), _stream()))
-    k = int(total.value)
-    out_j = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-    out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
-    if k:
-        check(lib.mxd_csr_outer_dense_fill(A.m, dim, A.nnz, _dp(A.indptr), _dp(A.values), _dp(v),
-                                           MX_F64 if v.dtype == torch.float64 else MX_F32, _dp(out_p), _dp(out_j),
-                                           _dp(out_x), _stream()))
-    return out_p, out_j[:k], out_x[:k]
+    ws = _workspace(dev, "mxd_csr_outer_dense_workspace_bytes", A.m)
+    out_p = _int32(dev, A.m + 1)
+    k, = _call("mxd_csr_outer_dense_count", A.m, dim, _dp(A.indptr), _dp(ws), _dp(out_p), cells=_COUNT)
+    out_j, out_x = _fill_pass(
+        dev, k, (torch.int32, torch.float64),
+        lambda oj, ox: _call("mxd_csr_outer_dense_fill", A.m, dim, A.nnz, _dp(A.indptr), _dp(A.values), _dp(v),
+                             _float_dtype(v), _dp(out_p), _dp(oj), _dp(ox)))
+    return out_p, out_j, out_x
 
 
 def csr_outer_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, length: int, v_dtype=None):
@@ -674,72 +673,63 @@ def csr_outer_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, leng
     of a CSC with A.m rows and `length` columns: column vi[k] - 1 holds every non-empty row of X, ascending, times
     vx[k].  vi: sorted, unique 1-based int32 positions; vx: f64 values, int32 values (v_dtype MX_I32, the default, or
     MX_LGL; NA gives NA_real_), or None for an nsparseVector."""
-    lib = _lib.load()
     dev = A.indptr.device
     _one_column(A, "csr_outer_svec")
-    if vi.dtype != torch.int32 or vi.dim() != 1 or vi.device != dev:
-        raise ValueError(f"csr_outer_svec: vi must be a 1-d int32 tensor on {dev}")
-    if vx is not None and (vx.dtype not in (torch.float64, torch.int32) or vx.shape != vi.shape or vx.device != dev):
-        raise ValueError("csr_outer_svec: vx must be float64 or int32, of vi's shape and on its device")
+    vi, vx = _svec("csr_outer_svec", dev, vi, vx, (torch.float64, torch.int32))
     if v_dtype is None:
-        v_dtype = MX_NONE if vx is None else MX_F64 if vx.dtype == torch.float64 else _lib.MX_I32
+        v_dtype = _value_dtype(vx)
+        if v_dtype == MX_LGL:           # an int32 vector is R integer unless the caller says logical
+            v_dtype = _lib.MX_I32
     length, nv = int(length), int(vi.numel())
     if length < 0 or nv > length:
         raise ValueError("csr_outer_svec: more stored positions than the vector's length")
-    vi = vi.contiguous()
-    vx = None if vx is None else vx.contiguous()
-    ws = torch.empty(max(lib.mxd_csr_outer_svec_workspace_bytes(A.m, length), 16), dtype=torch.uint8, device=dev)
-    out_p = torch.empty(length + 1, dtype=torch.int32, device=dev)
-    nonempty, total = C.c_int64(0), C.c_int64(0)
-    check(lib.mxd_csr_outer_svec_count(A.m, A.nnz, _dp(A.indptr), _dp(A.values), _dp(vi), nv, length, _dp(ws),
-                                       _dp(out_p), C.byref(nonempty), C.byref(total), _stream()))
-    k = int(total.value)
-    out_i = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-    out_x = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
-    if k:
-        check(lib.mxd_csr_outer_svec_fill(A.m, _dp(vi), nv, _dp(vx), v_dtype, length, nonempty.value, _dp(ws),
-                                          _dp(out_p), _dp(out_i), _dp(out_x), _stream()))
-    return out_p, out_i[:k], out_x[:k]
+    ws = _workspace(dev, "mxd_csr_outer_svec_workspace_bytes", A.m, length)
+    out_p = _int32(dev, length + 1)
+    nonempty, k = _call("mxd_csr_outer_svec_count", A.m, A.nnz, _dp(A.indptr), _dp(A.values), _dp(vi), nv, length,
+                        _dp(ws), _dp(out_p), cells=_COUNT * 2)
+    out_i, out_x = _fill_pass(
+        dev, k, (torch.int32, torch.float64),
+        lambda oi, ox: _call("mxd_csr_outer_svec_fill", A.m, _dp(vi), nv, _dp(vx), v_dtype, length, nonempty, _dp(ws),
+                             _dp(out_p), _dp(oi), _dp(ox)))
+    return out_p, out_i, out_x
 
 
 def rowvec_by_csc(v: torch.Tensor, A: DeviceCSR):
     """v %*% Y for a float32 row vector and a device-resident CSC Y held as DeviceCSR(p, i, x): A.m compressed columns
     over A.K rows, f64 values or None.  Returns float32[A.m]: per column the sum of x * v[i], each
     product in double, accumulated in float.  The row ids must lie below v.numel()."""
-    lib = _lib.load()
     dev = A.indptr.device
     if v.dtype != torch.float32 or v.dim() != 1 or v.device != dev or int(v.numel()) != A.K:
         raise ValueError(f"rowvec_by_csc: v must be a 1-d float32 tensor of Y's {A.K} rows on {dev}")
     if A.values is not None and A.values.dtype != torch.float64:
         raise ValueError("rowvec_by_csc: Y needs float64 values or none")
     out = torch.empty(A.m, dtype=torch.float32, device=dev)
-    check(lib.mxd_rowvec_by_csc(A.m, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v.contiguous()), _dp(out),
-                                _stream()))
+    _call("mxd_rowvec_by_csc", A.m, A.nnz, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(v.contiguous()), _dp(out))
     return out
 
 
 # ---- rbind / cbind (DESIGN.md §4.19): output sizes come from the operands' shapes, so nothing here waits for the device
-_BIND_OUT = {0: torch.float64, 1: torch.int32, 2: None}
-_SVEC_KIND = {"d": 3, "i": 4, "l": 5, "n": 6}
+_BIND_OUT = {_DGR: torch.float64, _LGR: torch.int32, _NGR: None}
+_SVEC_KIND = {"d": _DSVEC, "i": _ISVEC, "l": _LSVEC, "n": _NSVEC}
 
 
 def _matrix_kind(values) -> int:
-    """0 dgR, 1 lgR, 2 ngR by the values tensor"""
-    return {MX_F64: 0, MX_LGL: 1, MX_NONE: 2}[_value_dtype(values)]
+    """dgR, lgR or ngR by the values tensor"""
+    return {MX_F64: _DGR, MX_LGL: _LGR, MX_NONE: _NGR}[_value_dtype(values)]
 
 
 def _vector_kind(vx, kind) -> int:
-    """3 / 4 / 5 / 6 (d / i / l / n sparseVector): `kind` when given, else by the values tensor (int32: logical)"""
+    """d / i / l / n sparseVector: `kind` when given, else by the values tensor (int32: logical)"""
     if kind is not None:
         return _SVEC_KIND[kind]
-    return {MX_F64: 3, MX_LGL: 5, MX_NONE: 6}[_value_dtype(vx)]
+    return {MX_F64: _DSVEC, MX_LGL: _LSVEC, MX_NONE: _NSVEC}[_value_dtype(vx)]
 
 
 def _bind_out_kind(kinds) -> int:
-    """R/rbind.R:66-75: any numeric operand -> dgR (0), else any logical -> lgR (1), else ngR (2)"""
-    if any(k in (0, 3, 4) for k in kinds):
-        return 0
-    return 1 if any(k in (1, 5) for k in kinds) else 2
+    """R/rbind.R:66-75: any numeric operand -> dgR, else any logical -> lgR, else ngR"""
+    if any(k in (_DGR, _DSVEC, _ISVEC) for k in kinds):
+        return _DGR
+    return _LGR if any(k in (_LGR, _LSVEC) for k in kinds) else _NGR
 
 
 def csr_rbind(items) -> DeviceCSR:
@@ -747,7 +737,6 @@ def csr_rbind(items) -> DeviceCSR:
     is a DeviceCSR (f64, int32 R-logical or no values) or a sparse vector (vi, vx, length) / (vi, vx, length, kind)
     with vi its int32 1-based indices, vx f64 / int32 / None and kind "d" / "i" / "l" / "n" (default by vx: int32 is
     logical).  The result has the value type R/rbind.R:66-75 gives and max-over-operands columns."""
-    lib = _lib.load()
     items = list(items)
     if not items:
         raise ValueError("csr_rbind: no operands")
@@ -760,10 +749,9 @@ def csr_rbind(items) -> DeviceCSR:
         else:
             vi, vx, length = it[:3]
             kind, p, j, x, nr, nc = _vector_kind(vx, it[3] if len(it) > 3 else None), None, vi, vx, 1, int(length)
-            if kind == 6:
+            if kind == _NSVEC:
                 x = None
-        if j.dtype != torch.int32 or not j.is_contiguous() or (x is not None and int(x.numel()) != int(j.numel())):
-            raise ValueError(f"csr_rbind: operand {k}: indices must be contiguous int32, values as many as indices")
+        _bind_indices(f"csr_rbind: operand {k}: indices must be contiguous int32, values as many as indices", j, x)
         dev = j.device if dev is None else dev
         n = int(j.numel())
         table[k] = _lib.RbindItem(kind, nr, None if p is None else p.data_ptr(), j.data_ptr(),
@@ -775,11 +763,9 @@ def csr_rbind(items) -> DeviceCSR:
     out_kind = _bind_out_kind(kinds)
     host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8)
     dtable = host.to(dev)
-    out_p = torch.empty(row + 1, dtype=torch.int32, device=dev)
-    out_j = torch.empty(pos, dtype=torch.int32, device=dev)
-    out_x = None if out_kind == 2 else torch.empty(pos, dtype=_BIND_OUT[out_kind], device=dev)
-    check(lib.mxd_csr_rbind_batch(_dp(dtable), len(items), out_kind, row, pos, _dp(out_p), _dp(out_j), _dp(out_x),
-                                  _stream()))
+    out_p = _int32(dev, row + 1)
+    out_j, out_x = _entries(dev, pos, torch.int32, _BIND_OUT[out_kind], floor=0)
+    _call("mxd_csr_rbind_batch", _dp(dtable), len(items), out_kind, row, pos, _dp(out_p), _dp(out_j), _dp(out_x))
     return DeviceCSR(out_p, out_j, out_x, row, ncol, pos)
 
 
@@ -787,7 +773,6 @@ def csr_cbind(A: DeviceCSR, B: DeviceCSR) -> DeviceCSR:
     """cbind of two device-resident CSR operands of one value type (both f64, both int32 R-logical or both without
     values) through mxd_csr_cbind_shift: row r is A's row r, then B's with its columns moved up by A.K; the shorter
     operand contributes nothing past its end."""
-    lib = _lib.load()
     vd = _value_dtype(A.values)
     if _value_dtype(B.values) != vd:
         raise ValueError("csr_cbind: the operands must hold the same kind of values (convert one first)")
@@ -795,11 +780,10 @@ def csr_cbind(A: DeviceCSR, B: DeviceCSR) -> DeviceCSR:
         raise ValueError("csr_cbind: the result exceeds R's int32 index range")
     dev = A.indptr.device
     m, nnz = max(A.m, B.m), A.nnz + B.nnz
-    out_p = torch.empty(m + 1, dtype=torch.int32, device=dev)
-    out_j = torch.empty(nnz, dtype=torch.int32, device=dev)
-    out_x = None if A.values is None else torch.empty(nnz, dtype=A.values.dtype, device=dev)
-    check(lib.mxd_csr_cbind_shift(A.m, B.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(B.indptr),
-                                  _dp(B.indices), _dp(B.values), vd, nnz, _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
+    out_p = _int32(dev, m + 1)
+    out_j, out_x = _entries(dev, nnz, torch.int32, _dtype(A.values), floor=0)
+    _call("mxd_csr_cbind_shift", A.m, B.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), _dp(B.indptr),
+          _dp(B.indices), _dp(B.values), vd, nnz, _dp(out_p), _dp(out_j), _dp(out_x))
     return DeviceCSR(out_p, out_j, out_x, m, A.K + B.K, nnz)
 
 
@@ -808,22 +792,20 @@ def csr_cbind_svec(A: DeviceCSR, vi: torch.Tensor, vx: torch.Tensor | None, leng
     """A with a sparse vector (vi: SORTED int32 1-based indices <= length, vx f64 / int32 / None, `kind` as in
     csr_rbind) as one more column, behind A's columns or (first=True) in front of them, through mxd_csr_cbind_svec.
     max(A.m, length) rows; the value type follows R/cbind.R:82-99."""
-    lib = _lib.load()
-    if vi.dtype != torch.int32 or not vi.is_contiguous() or (vx is not None and int(vx.numel()) != int(vi.numel())):
-        raise ValueError("csr_cbind_svec: vi must be contiguous int32, vx as long as vi")
+    _bind_indices("csr_cbind_svec: vi must be contiguous int32, vx as long as vi", vi, vx)
     xk, vk = _matrix_kind(A.values), _vector_kind(vx, kind)
     nv, length = int(vi.numel()), int(length)
     if nv > length or A.K + 1 > 2**31 - 1 or A.nnz + nv > 2**31 - 1:
         raise ValueError("csr_cbind_svec: more entries than cells, or a result beyond R's int32 index range")
-    out_kind = 2 if (xk == 2 and vk == 6) else 1 if (xk in (1, 2) and vk in (5, 6)) else 0
+    # R/cbind.R:82-99: pattern only from two patterns, logical when neither side is numeric
+    out_kind = _NGR if (xk, vk) == (_NGR, _NSVEC) else _LGR if (xk in (_LGR, _NGR) and vk in (_LSVEC, _NSVEC)) else _DGR
     dev = A.indptr.device
     m, nnz = max(A.m, length), A.nnz + nv
-    out_p = torch.empty(m + 1, dtype=torch.int32, device=dev)
-    out_j = torch.empty(nnz, dtype=torch.int32, device=dev)
-    out_x = None if out_kind == 2 else torch.empty(nnz, dtype=_BIND_OUT[out_kind], device=dev)
-    check(lib.mxd_csr_cbind_svec(A.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), xk, _dp(vi),
-                                 _dp(None if vk == 6 else vx), vk, nv, length, int(bool(first)), out_kind, _dp(out_p),
-                                 _dp(out_j), _dp(out_x), _stream()))
+    out_p = _int32(dev, m + 1)
+    out_j, out_x = _entries(dev, nnz, torch.int32, _BIND_OUT[out_kind], floor=0)
+    _call("mxd_csr_cbind_svec", A.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), xk, _dp(vi),
+          _dp(None if vk == _NSVEC else vx), vk, nv, length, int(bool(first)), out_kind, _dp(out_p), _dp(out_j),
+          _dp(out_x))
     return DeviceCSR(out_p, out_j, out_x, m, A.K + 1, nnz)
 
 
@@ -836,17 +818,15 @@ def segment_reduce(values, op, segptr: torch.Tensor, nnz: int, perm=None, na_rm:
     """out[s] = op over q in [segptr[s], segptr[s + 1]) of f(values[perm[q]]) through mxd_segment_reduce, as
     (float64 out, int32 skipped or None).  values: float64, int32 R logicals, or None (every entry is 1); op: a key of
     REDUCE_OPS; segptr: int32, nseg + 1 offsets.  No synchronisation."""
-    lib = _lib.load()
     if op not in REDUCE_OPS:
         raise ValueError(f"op must be one of {sorted(REDUCE_OPS)}, got {op!r}")
     dev = segptr.device
     nseg = int(segptr.numel()) - 1
     vd = _value_dtype(values) if value_dtype is None else value_dtype
-    out = torch.empty(max(nseg, 0), dtype=torch.float64, device=dev)
-    skipped = torch.empty(max(nseg, 0), dtype=torch.int32, device=dev) if na_rm else None
-    ws = torch.empty(max(4 * lib.mxd_compact_workspace_bytes(int(nnz)), 16), dtype=torch.uint8, device=dev)
-    check(lib.mxd_segment_reduce(REDUCE_OPS[op], _dp(values), vd, _dp(perm), int(nnz), _dp(segptr), nseg,
-                                 int(bool(na_rm)), _dp(out), _dp(skipped), _dp(ws), _stream()))
+    out, skipped = _entries(dev, nseg, torch.float64, torch.int32 if na_rm else None, floor=0)
+    ws = _scratch(dev, 4 * _lib.load().mxd_compact_workspace_bytes(int(nnz)))
+    _call("mxd_segment_reduce", REDUCE_OPS[op], _dp(values), vd, _dp(perm), int(nnz), _dp(segptr), nseg,
+          int(bool(na_rm)), _dp(out), _dp(skipped), _dp(ws))
     return out, skipped
 
 
@@ -878,27 +858,25 @@ def norm(A: DeviceCSR, type: str = "O") -> float:
         return 0.0
     dev = A.indptr.device
 
-    def whole(values, op, n, vd=None):
+    def whole(values, op, n):
         segptr = torch.tensor([0, n], dtype=torch.int32, device=dev)
-        return float(segment_reduce(values, op, segptr, n, value_dtype=vd)[0].item())
+        return float(segment_reduce(values, op, segptr, n)[0].item())
 
     if type == "F":
-        return float(np.sqrt(whole(A.values, "sq_sum", A.nnz, _value_dtype(A.values))))
+        return float(np.sqrt(whole(A.values, "sq_sum", A.nnz)))
     if type == "M":
-        return whole(A.values, "abs_max", A.nnz, _value_dtype(A.values))
+        return whole(A.values, "abs_max", A.nnz)
     sums = row_reduce(A, "abs_sum") if type == "I" else col_reduce(A, "abs_sum")
-    return whole(sums, "abs_max", int(sums.numel()), MX_F64)
+    return whole(sums, "abs_max", int(sums.numel()))
 
 
 def diag(A: DeviceCSR):
     """diag(A) through mxd_csr_diag: the first stored (k, k) of every row k < min(A.m, A.K), 0 where there is none;
     float64 for numeric values, int32 R logicals for logical values (NA kept) and for a pattern (0 / 1)."""
-    lib = _lib.load()
     vd = _value_dtype(A.values)
-    d = min(A.m, A.K)
-    out = torch.empty(d, dtype=torch.float64 if vd == MX_F64 else torch.int32, device=A.indptr.device)
-    check(lib.mxd_csr_diag(A.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), vd, A.nnz, int(A.rows_sorted()),
-                           _dp(out), _stream()))
+    out, = _entries(A.indptr.device, min(A.m, A.K), torch.float64 if vd == MX_F64 else torch.int32, floor=0)
+    _call("mxd_csr_diag", A.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), vd, A.nnz, int(A.rows_sorted()),
+          _dp(out))
     return out
 
 
@@ -911,39 +889,33 @@ def _uplo(uplo: str) -> int:
 
 def csr_triangle_check(A: DeviceCSR, uplo: str, strict: bool = False) -> int:
     """How many entries of the square A lie outside the triangle `uplo` (strict: or on the diagonal)."""
-    lib = _lib.load()
-    ws = torch.empty(16, dtype=torch.uint8, device=A.indptr.device)
-    outside = C.c_int64(0)
-    check(lib.mxd_csr_triangle_check(A.m, _dp(A.indptr), _dp(A.indices), A.nnz, _uplo(uplo), int(bool(strict)), _dp(ws),
-                                     C.byref(outside), _stream()))
-    return int(outside.value)
+    ws = _scratch(A.indptr.device, 16)
+    outside, = _call("mxd_csr_triangle_check", A.m, _dp(A.indptr), _dp(A.indices), A.nnz, _uplo(uplo),
+                     int(bool(strict)), _dp(ws), cells=_COUNT)
+    return outside
 
 
 def csr_symmetric_count(A: DeviceCSR, uplo: str):
     """The count pass of the symmetric expansion: (out_indptr, workspace, nnz_out); the workspace holds the column
     order and the row ids that csr_symmetric_fill reads."""
-    lib = _lib.load()
     dev = A.indptr.device
-    ws = torch.empty(max(lib.mxd_csr_sym_workspace_bytes(A.m, A.nnz), 16), dtype=torch.uint8, device=dev)
-    out_p = torch.empty(A.m + 1, dtype=torch.int32, device=dev)
-    nnz_out = C.c_int64(0)
-    check(lib.mxd_csr_symmetric_to_general_count(A.m, _dp(A.indptr), _dp(A.indices), A.nnz, _uplo(uplo), _dp(out_p),
-                                                 _dp(ws), C.byref(nnz_out), _stream()))
-    return out_p, ws, int(nnz_out.value)
+    ws = _workspace(dev, "mxd_csr_sym_workspace_bytes", A.m, A.nnz)
+    out_p = _int32(dev, A.m + 1)
+    nnz_out, = _call("mxd_csr_symmetric_to_general_count", A.m, _dp(A.indptr), _dp(A.indices), A.nnz, _uplo(uplo),
+                     _dp(out_p), _dp(ws), cells=_COUNT)
+    return out_p, ws, nnz_out
 
 
 def csr_symmetric_fill(A: DeviceCSR, uplo: str, out_p: torch.Tensor, ws: torch.Tensor, nnz_out: int,
                        out_j: torch.Tensor | None = None, out_x: torch.Tensor | None = None) -> DeviceCSR:
     """The fill pass: the general CSR, written into out_j / out_x when they are given."""
-    lib = _lib.load()
     dev = A.indptr.device
     if out_j is None:
-        out_j = torch.empty(max(nnz_out, 1), dtype=torch.int32, device=dev)
-    if out_x is None and A.values is not None:
-        out_x = torch.empty(max(nnz_out, 1), dtype=A.values.dtype, device=dev)
-    check(lib.mxd_csr_symmetric_to_general_fill(A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values), _value_dtype(A.values),
-                                                A.nnz, _uplo(uplo), _dp(out_p), nnz_out, _dp(out_j), _dp(out_x), _dp(ws),
-                                                _stream()))
+        out_j, = _entries(dev, nnz_out, torch.int32)
+    if out_x is None:
+        out_x, = _entries(dev, nnz_out, _dtype(A.values))
+    _call("mxd_csr_symmetric_to_general_fill", A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values), _value_dtype(A.values),
+          A.nnz, _uplo(uplo), _dp(out_p), nnz_out, _dp(out_j), _dp(out_x), _dp(ws))
     return DeviceCSR(out_p, out_j[:nnz_out], None if A.values is None else out_x[:nnz_out], A.m, A.K, nnz_out)
 
 
@@ -958,15 +930,13 @@ def csr_symmetric_to_general(A: DeviceCSR, uplo: str) -> DeviceCSR:
 def csr_unit_triangular_to_general(A: DeviceCSR, uplo: str, out=None) -> DeviceCSR:
     """The general CSR of a strictly triangular A with an implied unit diagonal: one launch, no synchronisation.
     `out`: (indptr, indices, values) tensors to write into."""
-    lib = _lib.load()
     dev = A.indptr.device
     if A.m != A.K:
         raise ValueError("a triangular matrix is square")
     n_out = A.nnz + A.m
     if out is None:
-        out = (torch.empty(A.m + 1, dtype=torch.int32, device=dev), torch.empty(max(n_out, 1), dtype=torch.int32, device=dev),
-               None if A.values is None else torch.empty(max(n_out, 1), dtype=A.values.dtype, device=dev))
+        out = (_int32(dev, A.m + 1), *_entries(dev, n_out, torch.int32, _dtype(A.values)))
     out_p, out_j, out_x = out
-    check(lib.mxd_csr_unit_triangular_to_general(A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values), _value_dtype(A.values),
-                                                 A.nnz, _uplo(uplo), _dp(out_p), _dp(out_j), _dp(out_x), _stream()))
+    _call("mxd_csr_unit_triangular_to_general", A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values),
+          _value_dtype(A.values), A.nnz, _uplo(uplo), _dp(out_p), _dp(out_j), _dp(out_x))
     return DeviceCSR(out_p, out_j[:n_out], None if out_x is None else out_x[:n_out], A.m, A.K, n_out)
