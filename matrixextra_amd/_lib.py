@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libmxgpu.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu.h")
 REDUCE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_reduce.h")
 SYM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_sym.h")
+TPROD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_tprod.h")
 
 
 class MxError(RuntimeError):
@@ -105,6 +106,8 @@ globals().update(REDUCE_HEADER.constants)  # MX_RED_SUM, MX_RED_ABS_SUM, MX_RED_
 # so has the structured-matrix family (include/mxgpu_sym.h): symmetric / unit-triangular expansion, triangle check
 SYM_HEADER = _read_header(SYM_HEADER_PATH)
 globals().update(SYM_HEADER.constants)     # MX_UPLO_UPPER, MX_UPLO_LOWER
+# and the transposed products (include/mxgpu_tprod.h): the segmented dot, the transpose by a column order, X^T v, X^T B
+TPROD_HEADER = _read_header(TPROD_HEADER_PATH)
 # mx_dvec_op, by R's operator
 MX_DV_OPS = {"*": HEADER.constants["MX_DV_MULTIPLY"], "^": HEADER.constants["MX_DV_POWERTO"],
              "/": HEADER.constants["MX_DV_DIVIDE"], "%%": HEADER.constants["MX_DV_DIVREST"],
@@ -136,7 +139,7 @@ def load() -> C.CDLL:
         pass
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for header, path in ((HEADER, "include/mxgpu.h"), (REDUCE_HEADER, "include/mxgpu_reduce.h"),
-                         (SYM_HEADER, "include/mxgpu_sym.h")):
+                         (SYM_HEADER, "include/mxgpu_sym.h"), (TPROD_HEADER, "include/mxgpu_tprod.h")):
         missing = [name for name in header.functions if not hasattr(lib, name)]
         if missing:
             raise MxError(f"libmxgpu.so lacks symbols declared in {path}: {missing}")

@@ -24,70 +24,13 @@
 // atomic on a value anywhere: the grouping of every sum is fixed by the positions alone and repeated calls give the
 // same bits.  NaN: sums propagate it by themselves; the maximum is written as (b > a || b != b) ? b : a, which keeps
 // a NaN once it has one (fmax would drop it).
+// The tile's device helpers, its workspace layout and the fill / combine launches are declared in mx_reduce.h: the
+// segmented dot product of tprod.hip is the same scheme around a tile kernel of its own.
 #include "mx_dispatch.h"
 #include "mx_reduce.h"
 #include "mx_workspace.h"
 
 namespace mx {
-
-constexpr int RD_BLOCK = 256;
-constexpr int RD_ITEMS = 16;
-constexpr int RD_TILE = RD_BLOCK * RD_ITEMS;        // 4096 entries per tile, the tile of mxd_compact_workspace_bytes
-constexpr int RD_CHUNKS = RD_TILE / RD_ITEMS;       // one chunk partial per thread
-constexpr int RD_SPAN_CAP = 1024;                   // segments of a tile whose segptr is staged in LDS
-static_assert(RD_CHUNKS == RD_BLOCK, "one chunk per thread");
-
-// staged entry i lives at i + i / 16: a lane that walks its own chunk (stride 17 doubles between lanes) meets no
-// bank conflict with ds_read_b64, and the lane-strided staging writes stay consecutive
-__device__ __forceinline__ int rd_slot(int i) { return i + (i >> 4); }
-
-template <int OP> __device__ __forceinline__ double rd_map(double v)
-{
-    if constexpr (OP == MX_RED_SUM) return v;
-    else if constexpr (OP == MX_RED_SQ_SUM) return v * v;
-    else return fabs(v);
-}
-
-template <int OP> __device__ __forceinline__ double rd_join(double a, double b)
-{
-    if constexpr (OP == MX_RED_ABS_MAX) return (b > a || b != b) ? b : a;
-    else return a + b;
-}
-
-// last s in [0, nseg) with segptr[s] <= q (0 when there is none)
-__device__ __forceinline__ int rd_seg_of(const int32_t *__restrict__ segptr, int nseg, int64_t q)
-{
-    int lo = 0, count = nseg;                       // first s with segptr[s] > q
-    while (count > 0) {
-        const int step = count >> 1;
-        if ((int64_t)segptr[lo + step] <= q) { lo += step + 1; count -= step + 1; }
-        else count = step;
-    }
-    return lo > 0 ? lo - 1 : 0;
-}
-
-// the part of segment [a, b) that holds entries: clipped into [0, nnz]
-__device__ __forceinline__ void rd_clip(int64_t &a, int64_t &b, int64_t nnz)
-{
-    a = a < 0 ? 0 : a;
-    b = b > nnz ? nnz : b;
-}
-
-// OP over the staged entries [lo, hi) of the tile, left to right, through the chunk partials where a chunk is whole
-template <int OP>
-__device__ __forceinline__ double rd_range(const double *val, const double *csum, int lo, int hi)
-{
-    double acc = 0.0;
-    const int c0 = (lo + RD_ITEMS - 1) / RD_ITEMS, c1 = hi / RD_ITEMS;
-    if (c0 < c1) {
-        for (int i = lo; i < c0 * RD_ITEMS; i++) acc = rd_join<OP>(acc, val[rd_slot(i)]);
-        for (int c = c0; c < c1; c++) acc = rd_join<OP>(acc, csum[c]);
-        for (int i = c1 * RD_ITEMS; i < hi; i++) acc = rd_join<OP>(acc, val[rd_slot(i)]);
-    } else {
-        for (int i = lo; i < hi; i++) acc = rd_join<OP>(acc, val[rd_slot(i)]);
-    }
-    return acc;
-}
 
 // the skipped entries among the staged [lo, hi)
 __device__ __forceinline__ int rd_count(const uint8_t *isna, const int32_t *ccnt, int lo, int hi)
@@ -284,19 +227,24 @@ void rd_diag_kernel(int d, const int32_t *__restrict__ indptr, const int32_t *__
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------
-static int64_t rd_ntiles(int64_t nnz) { return ceil_div(nnz > 0 ? nnz : 0, RD_TILE); }
+int reduce_fill_empty(const int32_t *segptr, int nseg, int64_t nnz, double *out, int32_t *skipped, hipStream_t st)
+{
+    hipLaunchKernelGGL(rd_fill_kernel<false>, dim3(grid_for(nseg, 256, RD_GRID_CAP)), dim3(256), 0, st, segptr, nseg, nnz,
+                       0, out, skipped);
+    MX_LAUNCH_CHECK();
+    return 0;
+}
 
-// per tile: the partial of the segment it starts inside, of the one it ends inside, and their skipped counts
-struct ReduceLayout {
-    WsCursor c;
-    int64_t t;
-    double *head = c.take<double>(8 * (size_t)t), *tail = c.take<double>(8 * (size_t)t);
-    int32_t *head_cnt = c.take<int32_t>(4 * (size_t)t), *tail_cnt = c.take<int32_t>(4 * (size_t)t);
-    size_t bytes = c.bytes();
-    ReduceLayout(const void *ws, int64_t nnz) : c(ws), t(rd_ntiles(nnz)) {}
-};
-
-constexpr int64_t RD_GRID_CAP = 2048;
+int reduce_combine(int64_t nnz, const int32_t *segptr, int nseg, int is_max, const double *head, const double *tail,
+                   const int32_t *head_cnt, const int32_t *tail_cnt, double *out, int32_t *skipped, hipStream_t st)
+{
+    const int64_t ntiles = rd_ntiles(nnz);
+    if (ntiles <= 1) return 0;
+    hipLaunchKernelGGL(rd_combine_kernel, dim3((unsigned)ceil_div(ntiles, 256)), dim3(256), 0, st, nnz, ntiles, segptr,
+                       nseg, is_max, head, tail, head_cnt, tail_cnt, out, skipped);
+    MX_LAUNCH_CHECK();
+    return 0;
+}
 
 static int segment_reduce(int op, const void *values, int value_dtype, const int32_t *perm, int64_t nnz,
                           const int32_t *segptr, int nseg, int na_rm, double *out, int32_t *skipped, void *workspace,
@@ -312,13 +260,14 @@ static int segment_reduce(int op, const void *values, int value_dtype, const int
     MX_REQUIRE(pattern || nnz == 0 || (values && workspace), "mxd_segment_reduce: null pointer");
     const ReduceLayout L(workspace, nnz);
     MX_REQUIRE(L.bytes <= 4 * mxd_compact_workspace_bytes(nnz), "mxd_segment_reduce: the tile carries outgrew the workspace");
-    const dim3 gs(grid_for(nseg, 256, RD_GRID_CAP));
-    if (pattern)
-        hipLaunchKernelGGL(rd_fill_kernel<true>, gs, dim3(256), 0, st, segptr, nseg, nnz, (int)is_max, out, skipped);
-    else
-        hipLaunchKernelGGL(rd_fill_kernel<false>, gs, dim3(256), 0, st, segptr, nseg, nnz, (int)is_max, out, skipped);
-    MX_LAUNCH_CHECK();
-    if (pattern || nnz == 0) return 0;
+    if (pattern) {
+        hipLaunchKernelGGL(rd_fill_kernel<true>, dim3(grid_for(nseg, 256, RD_GRID_CAP)), dim3(256), 0, st, segptr, nseg,
+                           nnz, (int)is_max, out, skipped);
+        MX_LAUNCH_CHECK();
+        return 0;
+    }
+    if (reduce_fill_empty(segptr, nseg, nnz, out, skipped, st)) return 1;
+    if (nnz == 0) return 0;
     const int64_t ntiles = rd_ntiles(nnz);
     const int rc = dispatch_int(int_list<MX_RED_SUM, MX_RED_ABS_SUM, MX_RED_SQ_SUM, MX_RED_ABS_MAX>{},
                                 "mxd_segment_reduce", "operation", op, [&](auto o) {
@@ -336,12 +285,7 @@ static int segment_reduce(int op, const void *values, int value_dtype, const int
         return 0;
     });
     if (rc) return rc;
-    if (ntiles > 1) {
-        hipLaunchKernelGGL(rd_combine_kernel, dim3((unsigned)ceil_div(ntiles, 256)), dim3(256), 0, st, nnz, ntiles, segptr,
-                           nseg, (int)is_max, L.head, L.tail, L.head_cnt, L.tail_cnt, out, skipped);
-        MX_LAUNCH_CHECK();
-    }
-    return 0;
+    return reduce_combine(nnz, segptr, nseg, (int)is_max, L.head, L.tail, L.head_cnt, L.tail_cnt, out, skipped, st);
 }
 
 int reduce_mean_divide(double *out, const int32_t *skipped, int64_t n, double cells, hipStream_t st)

@@ -39,6 +39,7 @@ class DeviceCSR:
     _plan_panels: int = -1
     _order: object = None
     _order_builds: int = 0
+    _rows: object = None
 
     def plan(self, npanels: int = 0, rebuild: bool = False):
         """Device-resident SpMM plan (mxd_spmm_plan_create); cached per DeviceCSR, buffers re-used on rebuild."""
@@ -85,6 +86,32 @@ class DeviceCSR:
             self._order = (perm[:self.nnz], colptr)
             self._order_builds += 1
         return self._order
+
+    def entry_rows(self, order=None):
+        """The row of every entry in column order (mxd_csr_transpose_by_order without values): with
+        the colptr of the order the pattern of X^T.  Cached beside the order, which it goes through: column_order(),
+        or `order`, the (perm, colptr) of a DeviceCSR that shares indptr and indices."""
+        if self._rows is None:
+            perm, _ = _order_of("entry_rows", self, order)
+            rows, = _entries(self.indptr.device, self.nnz, torch.int32)
+            _call("mxd_csr_transpose_by_order", self.m, self.nnz, _dp(self.indptr), None, MX_NONE, _dp(perm), _dp(rows),
+                  None)
+            self._rows = rows[:self.nnz]
+        return self._rows
+
+    def transposed(self, order=None):
+        """X^T (K x m) as a DeviceCSR: indptr is the cached colptr, indices the cached entry rows, and the values are
+        gathered through the order now (None stays None), so a matrix whose values changed pays one gather and no
+        sort.  Its rows are sorted: the order is stable.  order: as col_reduce takes it."""
+        perm, colptr = _order_of("transposed", self, order)
+        rows = self.entry_rows(order)
+        values = None
+        if self.values is not None:
+            values, = _entries(self.indptr.device, self.nnz, self.values.dtype)
+            _call("mxd_csr_transpose_by_order", self.m, self.nnz, _dp(self.indptr), _dp(self.values),
+                  _value_dtype(self.values), _dp(perm), None, _dp(values))
+            values = values[:self.nnz]
+        return DeviceCSR(colptr, rows, values, self.K, self.m, self.nnz, _sorted=True)
 
     @classmethod
     def from_host(cls, indptr, indices, values, K, device="cuda"):
@@ -278,6 +305,14 @@ def _bind_indices(message: str, j, x):
     """An operand of a bind is read in place: contiguous int32 indices, and values, where there are any, as many."""
     if j.dtype != torch.int32 or not j.is_contiguous() or (x is not None and int(x.numel()) != int(j.numel())):
         raise ValueError(message)
+
+
+def _order_of(what: str, A: DeviceCSR, order):
+    """(perm, colptr) for A: its own cached column order, or the caller's, checked against A's sizes"""
+    perm, colptr = A.column_order() if order is None else order
+    if int(colptr.numel()) != A.K + 1 or int(perm.numel()) != A.nnz:
+        raise ValueError(f"{what}: the order belongs to another pattern")
+    return perm, colptr
 
 
 def _f64_values(what: str, A: DeviceCSR):
@@ -842,11 +877,48 @@ def col_reduce(A: DeviceCSR, op: str = "sum", na_rm: bool = False, order=None):
     na_rm.  order: the (perm, colptr) of DeviceCSR.column_order(), A's own (built once and cached) when None; pass the
     order of another DeviceCSR with the same indptr and indices (the values-only X * v shares them with X) and the
     sort is paid once per fit, not once per gradient."""
-    perm, colptr = A.column_order() if order is None else order
-    if int(colptr.numel()) != A.K + 1 or int(perm.numel()) != A.nnz:
-        raise ValueError("col_reduce: the order belongs to another pattern")
+    perm, colptr = _order_of("col_reduce", A, order)
     out, skipped = segment_reduce(A.values, op, colptr, A.nnz, perm, na_rm)
     return (out, skipped) if na_rm else out
+
+
+# ---- transposed products (include/mxgpu_tprod.h, DESIGN.md §4.22): X^T v fused on the tile scheme, X^T B through SpMM
+def segment_dot(values, key: torch.Tensor, w: torch.Tensor, segptr: torch.Tensor, nnz: int, perm=None, out=None):
+    """out[s] = sum over q in [segptr[s], segptr[s + 1]) of values[perm[q]] * w[key[q]] through mxd_segment_dot, float64.
+    values: float64, or None (every entry is 1); key: int32[nnz] in segment order; w: float64.  Each product is rounded
+    by itself and the sums are grouped as segment_reduce(..., "sum") groups them.  No synchronisation."""
+    dev = segptr.device
+    nseg = int(segptr.numel()) - 1
+    if values is not None and values.dtype != torch.float64:
+        raise ValueError(f"segment_dot: values must be float64 or None, got {values.dtype}")
+    if w.dtype != torch.float64 or w.dim() != 1 or not w.is_contiguous() or w.device != dev:
+        raise ValueError(f"segment_dot: w must be a contiguous 1-d float64 tensor on {dev}")
+    if out is None:
+        out, = _entries(dev, nseg, torch.float64, floor=0)
+    elif tuple(out.shape) != (nseg,) or out.dtype != torch.float64 or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"segment_dot: out must be a contiguous float64 tensor of {nseg} elements on {dev}")
+    ws = _scratch(dev, 4 * _lib.load().mxd_compact_workspace_bytes(int(nnz)))
+    _call("mxd_segment_dot", _dp(values), _value_dtype(values), _dp(perm), _dp(key), _dp(w), int(w.numel()), int(nnz),
+          _dp(segptr), nseg, _dp(out), _dp(ws))
+    return out
+
+
+def spmv_t(A: DeviceCSR, v: torch.Tensor, out=None, order=None):
+    """y = A^T @ v (crossprod(X, v)) for a float64 v of A.m elements: float64[A.K], through the column order (A's own
+    cached one, or `order` as col_reduce takes it) and mxd_segment_dot.  Bit for bit the column sums of the written-out
+    A * v[rows].  A's values are float64 or None (a pattern).  No synchronisation once the order is cached."""
+    if v.dim() != 1 or int(v.numel()) != A.m:
+        raise ValueError(f"spmv_t: v must have {A.m} elements, got {tuple(v.shape)}")
+    perm, colptr = _order_of("spmv_t", A, order)
+    rows = A.entry_rows(order)
+    return segment_dot(A.values, rows, v, colptr, A.nnz, perm, out=out)
+
+
+def spmm_t(A: DeviceCSR, B: torch.Tensor, out: torch.Tensor | None = None, colmajor: bool = False, order=None,
+           **spmm_kwargs):
+    """C = A^T @ B (crossprod(X, B)) with B (A.m x n) row-major: spmm(A.transposed(order), B, ...), the same kernels
+    on the CSR of A^T, which costs one gather of the values once the order is cached."""
+    return spmm(A.transposed(order), B, out=out, colmajor=colmajor, **spmm_kwargs)
 
 
 def norm(A: DeviceCSR, type: str = "O") -> float:

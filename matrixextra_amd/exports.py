@@ -1600,6 +1600,39 @@ def csr_diag(indptr, indices, values, ncols, value_dtype=None):
     return out
 
 
+# ----------------------------------------------------------------------------- transposed products (include/mxgpu_tprod.h)
+def csr_tmatvec(indptr, indices, values, ncols, v):
+    """mx_csr_tmatvec: X^T v for a CSR X with `ncols` columns (values float64, or None for a pattern) and a float64 v of
+    nrow elements, as float64[ncols]."""
+    p, j, x, vd = _csr_operand(indptr, indices, values, None if values is None else MX_F64)
+    v = _f64(v).reshape(-1)
+    nrow, ncol = p.size - 1, int(ncols)
+    if v.size != nrow:
+        raise ValueError("csr_tmatvec: v must have one element per row of X")
+    out = np.empty(ncol, dtype=np.float64)
+    check(_lib.load().mx_csr_tmatvec(nrow, ncol, ptr(p), ptr(j), ptr(x), vd, ptr(v), ptr(out)))
+    return out
+
+
+def csr_tmatmul_dense(indptr, indices, values, ncols, B_rowmajor, colmajor_out=True):
+    """mx_csr_tmatmul_dense: X^T B for a CSR X with `ncols` columns and float64 values, B a C-contiguous nrow x n
+    float64 / float32 array: an ncols x n array of B's type, column-major (Fortran order) with colmajor_out, else
+    row-major."""
+    p, j, x, _ = _csr_operand(indptr, indices, values, MX_F64)
+    B = np.asarray(B_rowmajor)
+    if B.ndim != 2 or B.dtype not in (np.float64, np.float32):
+        raise ValueError("csr_tmatmul_dense: B must be a 2-d float64 / float32 array")
+    B = np.ascontiguousarray(B)
+    nrow, ncol, n = p.size - 1, int(ncols), B.shape[1]
+    if B.shape[0] != nrow:
+        raise ValueError("csr_tmatmul_dense: B must have one row per row of X")
+    out = np.empty((ncol, n), dtype=B.dtype, order="F" if colmajor_out else "C")
+    check(_lib.load().mx_csr_tmatmul_dense(nrow, ncol, ptr(p), ptr(j), ptr(x), ptr(B), n, n,
+                                           MX_F64 if B.dtype == np.float64 else _lib.MX_F32, ptr(out),
+                                           ncol if colmajor_out else n, int(bool(colmajor_out))))
+    return out
+
+
 # ----------------------------------------------------------------------------- structured operands (include/mxgpu_sym.h)
 _UPLO = {"U": _lib.MX_UPLO_UPPER, "L": _lib.MX_UPLO_LOWER}
 

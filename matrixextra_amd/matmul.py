@@ -327,6 +327,107 @@ def crossprod_f32_csc(x, y):
     return _rowvec_by_sparse(x, y.p, y.i, y.x)
 
 
+# ---- transposed products on the column order (include/mxgpu_tprod.h) -------------------------------
+# The reference leaves these signatures to Matrix; here they run on X's CSR arrays through the cached column order.
+# A dgCMatrix is read as the CSR of its transpose, so `CsparseMatrix %*% dense` is the transposed product on its arrays.
+def _dense_array(o):
+    """The dense operand of a transposed product as an array (a base-R vector or matrix), or None for anything else: a
+    float32, a sparse matrix or vector."""
+    from .structured import StructuredMatrix
+    if isinstance(o, (float32, RsparseMatrix, dgCMatrix, sparseVector, StructuredMatrix)) or hasattr(o, "Dim"):
+        return None
+    a = np.asarray(o)
+    return a if a.ndim in (1, 2) and a.dtype.kind in "fiub" else None
+
+
+def _as_double(y):
+    """mode(y) <- "double": an integer or logical operand becomes double, NA becoming NA_real_"""
+    y = np.asarray(y)
+    if y.dtype == np.float64:
+        return y
+    if y.dtype == np.int32:
+        return np.where(y == NA_INTEGER, NA_REAL, y.astype(np.float64))
+    return y.astype(np.float64)
+
+
+def _tmatvec(p, idx, x, ncols, v):
+    """t(S) %*% v for the CSR arrays (p, idx, x) of S with `ncols` columns"""
+    v = _as_double(v)
+    if v.ndim != 1 or v.size != p.size - 1:
+        stop("Matrix-vector dimensions do not match.")
+    return exports.csr_tmatvec(p, idx, x, ncols, v)
+
+
+def crossprod_csr_dense(x, y):
+    """crossprod(RsparseMatrix, matrix): t(X) %*% Y, a K x n matrix."""
+    check_dimensions_match(x, y, crossprod=True)
+    y_names = dimnames_of(y)
+    x = as_csr_matrix(x)
+    check_valid_matrix(x)
+    yd = _as_double(y)
+    res = exports.csr_tmatmul_dense(x.p, x.j, x.x, x.Dim[1], np.ascontiguousarray(yd), True)
+    return set_dimnames(res, x, DenseMatrix(yd, y_names), crossprod=True)
+
+
+def crossprod_csr_vec(x, y):
+    """crossprod(RsparseMatrix, numeric / integer / logical vector): t(X) %*% v, a K x 1 matrix."""
+    x = as_csr_matrix(x)
+    check_valid_matrix(x)
+    res = _tmatvec(x.p, x.j, x.x, x.Dim[1], y)
+    return DenseMatrix(res.reshape(-1, 1), [dimnames_of(x)[1], None])
+
+
+def gemv_vec_csr(x, y):
+    """vector %*% RsparseMatrix: the vector as a row, a 1 x K matrix."""
+    y = as_csr_matrix(y)
+    check_valid_matrix(y)
+    res = _tmatvec(y.p, y.j, y.x, y.Dim[1], x)
+    return DenseMatrix(res.reshape(1, -1), [None, dimnames_of(y)[1]])
+
+
+def gemm_dense_csr(x, y):
+    """matrix %*% RsparseMatrix = t(t(Y) %*% t(X)): X's column-major buffer is the row-major t(X), so nothing is
+    transposed on the host, and the row-major result is the column-major product."""
+    check_dimensions_match(x, y, matmult=True)
+    x_names = dimnames_of(x)
+    xd = np.asfortranarray(_as_double(x))
+    y = as_csr_matrix(y)
+    check_valid_matrix(y)
+    res = exports.csr_tmatmul_dense(y.p, y.j, y.x, y.Dim[1], xd.T, False)
+    return set_dimnames(res.T, DenseMatrix(xd, x_names), y, matmult=True)
+
+
+def gemm_csc_dense(x, y):
+    """CsparseMatrix %*% matrix: the CSC arrays are the CSR of t(X), so this is the transposed product on them."""
+    check_dimensions_match(x, y, matmult=True)
+    y_names = dimnames_of(y)
+    x = as_csc_matrix(x)
+    check_valid_matrix(x)
+    yd = _as_double(y)
+    res = exports.csr_tmatmul_dense(x.p, x.i, x.x, x.Dim[0], np.ascontiguousarray(yd), True)
+    return set_dimnames(res, x, DenseMatrix(yd, y_names), matmult=True)
+
+
+def gemv_csc_vec(x, y):
+    """CsparseMatrix %*% numeric / integer / logical vector, an nrow x 1 matrix."""
+    x = as_csc_matrix(x)
+    check_valid_matrix(x)
+    res = _tmatvec(x.p, x.i, x.x, x.Dim[0], y)
+    return DenseMatrix(res.reshape(-1, 1), [dimnames_of(x)[0], None])
+
+
+def tcrossprod_dense_csc(x, y):
+    """tcrossprod(matrix, CsparseMatrix): Y %*% t(X) = t(X %*% t(Y)), with X read through its CSC arrays and Y's
+    column-major buffer as the row-major t(Y)."""
+    check_dimensions_match(x, y, tcrossprod=True)
+    x_names = dimnames_of(x)
+    xd = np.asfortranarray(_as_double(x))
+    y = as_csc_matrix(y)
+    check_valid_matrix(y)
+    res = exports.csr_tmatmul_dense(y.p, y.i, y.x, y.Dim[0], xd.T, False)
+    return set_dimnames(res.T, DenseMatrix(xd, x_names), y, tcrossprod=True)
+
+
 class RLogical(np.ndarray):
     """An int32 vector tagged as an R logical ({0,1,NA_LOGICAL}) so `%*%` picks the logical kernel."""
     r_logical = True
@@ -346,7 +447,8 @@ def _general(o):
 
 
 def matmul(x, y):
-    """`%*%` for the signatures the hot path registers (R/matmul.R:200,281,469,512,755-767)."""
+    """`%*%` for the signatures the hot path registers (R/matmul.R:200,281,469,512,755-767), and vector | matrix %*%
+    RsparseMatrix and CsparseMatrix %*% vector | matrix on the transposed product."""
     x, y = _general(x), _general(y)
     if isinstance(x, RsparseMatrix):
         outer = _outer_route()
@@ -368,11 +470,16 @@ def matmul(x, y):
         if isinstance(x, float32) and x.is_vector and _outer_route():
             return _gemm_f32vec_csc(x, y)
         return gemm_f32_csc(x, y) if isinstance(x, float32) else gemm_dense_csc(x, y)
+    if isinstance(y, RsparseMatrix) and _dense_array(x) is not None:       # vector | matrix %*% RsparseMatrix
+        return gemv_vec_csr(x, y) if _dense_array(x).ndim == 1 else gemm_dense_csr(x, y)
+    if isinstance(x, dgCMatrix) and _dense_array(y) is not None:           # CsparseMatrix %*% vector | matrix
+        return gemv_csc_vec(x, y) if _dense_array(y).ndim == 1 else gemm_csc_dense(x, y)
     stop("Unsupported operand types for %*% in the MI355X hot path.")
 
 
 def tcrossprod(x, y):
-    """tcrossprod for (Rsparse, matrix|float32) and (matrix|float32, Rsparse) — R/matmul.R:307,385,461,538."""
+    """tcrossprod for (Rsparse, matrix|float32) and (matrix|float32, Rsparse) — R/matmul.R:307,385,461,538; and
+    (matrix, CsparseMatrix) on the transposed product."""
     x, y = _general(x), _general(y)
     if isinstance(x, RsparseMatrix):
         return tcrossprod_csr_f32(x, y) if isinstance(y, float32) else tcrossprod_csr_dense(x, y)
@@ -380,15 +487,19 @@ def tcrossprod(x, y):
         if isinstance(x, float32) and x.is_vector and _outer_route():
             return _tcrossprod_f32vec_csr(x, y)
         return tcrossprod_f32_csr(x, y) if isinstance(x, float32) else tcrossprod_dense_csr(x, y)
+    if isinstance(y, dgCMatrix) and _dense_array(x) is not None and _dense_array(x).ndim == 2:
+        return tcrossprod_dense_csc(x, y)
     stop("Unsupported operand types for tcrossprod in the MI355X hot path.")
 
 
 def crossprod(x, y):
     """crossprod(matrix, CsparseMatrix) — R/matmul.R:393; (float32 vector, CsparseMatrix) — :434, under
-    options["mxgpu.outer_route"]."""
+    options["mxgpu.outer_route"]; (RsparseMatrix, vector | matrix) on the transposed product."""
     x, y = _general(x), _general(y)
     if isinstance(y, dgCMatrix) and isinstance(x, float32) and x.is_vector and _outer_route():
         return crossprod_f32_csc(x, y)
     if isinstance(y, dgCMatrix) and not isinstance(x, float32):
         return crossprod_dense_csc(x, y)
+    if isinstance(x, RsparseMatrix) and _dense_array(y) is not None:       # crossprod(RsparseMatrix, vector | matrix)
+        return crossprod_csr_vec(x, y) if _dense_array(y).ndim == 1 else crossprod_csr_dense(x, y)
     stop("Unsupported operand types for crossprod in the MI355X hot path.")

@@ -422,6 +422,10 @@ class dgCMatrix:
     def colnames(self):
         return self.Dimnames[1]
 
+    def __matmul__(self, other):                      # CsparseMatrix %*% matrix / vector: the transposed product
+        from . import matmul
+        return matmul.matmul(self, other)
+
     def __rmatmul__(self, other):                     # matrix %*% CsparseMatrix, R/matmul.R:200
         from . import matmul
         return matmul.matmul(other, self)
