@@ -19,6 +19,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu.h")
 REDUCE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_reduce.h")
 SYM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_sym.h")
 TPROD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_tprod.h")
+SPGEMM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_spgemm.h")
 
 
 class MxError(RuntimeError):
@@ -108,6 +109,8 @@ SYM_HEADER = _read_header(SYM_HEADER_PATH)
 globals().update(SYM_HEADER.constants)     # MX_UPLO_UPPER, MX_UPLO_LOWER
 # and the transposed products (include/mxgpu_tprod.h): the segmented dot, the transpose by a column order, X^T v, X^T B
 TPROD_HEADER = _read_header(TPROD_HEADER_PATH)
+# and the sparse x sparse product (include/mxgpu_spgemm.h): limits, count and fill at device level, one export
+SPGEMM_HEADER = _read_header(SPGEMM_HEADER_PATH)
 # mx_dvec_op, by R's operator
 MX_DV_OPS = {"*": HEADER.constants["MX_DV_MULTIPLY"], "^": HEADER.constants["MX_DV_POWERTO"],
              "/": HEADER.constants["MX_DV_DIVIDE"], "%%": HEADER.constants["MX_DV_DIVREST"],
@@ -139,7 +142,8 @@ def load() -> C.CDLL:
         pass
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for header, path in ((HEADER, "include/mxgpu.h"), (REDUCE_HEADER, "include/mxgpu_reduce.h"),
-                         (SYM_HEADER, "include/mxgpu_sym.h"), (TPROD_HEADER, "include/mxgpu_tprod.h")):
+                         (SYM_HEADER, "include/mxgpu_sym.h"), (TPROD_HEADER, "include/mxgpu_tprod.h"),
+                         (SPGEMM_HEADER, "include/mxgpu_spgemm.h")):
         missing = [name for name in header.functions if not hasattr(lib, name)]
         if missing:
             raise MxError(f"libmxgpu.so lacks symbols declared in {path}: {missing}")

@@ -921,6 +921,27 @@ def spmm_t(A: DeviceCSR, B: torch.Tensor, out: torch.Tensor | None = None, colma
     return spmm(A.transposed(order), B, out=out, colmajor=colmajor, **spmm_kwargs)
 
 
+# ---- sparse x sparse (include/mxgpu_spgemm.h): Gustavson by rows, count -> scan -> fill
+def spgemm(A: DeviceCSR, B: DeviceCSR) -> DeviceCSR:
+    """C = A @ B for two device-resident CSR operands through mxd_csr_spgemm_count / _fill: float64 values (int32 R
+    logicals are read as 0 / 1 / NA_real_, a pattern as ones), rows sorted, nothing dropped.  A's rows may be unsorted
+    and repeat a column; B's rows must not repeat one.  One host round trip (the entry count).  crossprod(X, Y) on
+    resident operands is spgemm(X.transposed(), Y), which goes through X's cached column order."""
+    if A.K != B.m:
+        raise ValueError(f"spgemm: A has {A.K} columns, B has {B.m} rows")
+    dev = A.indptr.device
+    ws = _workspace(dev, "mxd_csr_spgemm_workspace_bytes", A.m, B.K)
+    out_p = _int32(dev, A.m + 1)
+    _, k = _call("mxd_csr_spgemm_count", A.m, A.K, B.K, _dp(A.indptr), _dp(A.indices), A.nnz, _dp(B.indptr),
+                 _dp(B.indices), B.nnz, _dp(out_p), _dp(ws), cells=_COUNT * 2)
+    out_j, out_x = _fill_pass(
+        dev, k, (torch.int32, torch.float64),
+        lambda oj, ox: _call("mxd_csr_spgemm_fill", A.m, A.K, B.K, _dp(A.indptr), _dp(A.indices), _dp(A.values),
+                             _value_dtype(A.values), _dp(B.indptr), _dp(B.indices), _dp(B.values),
+                             _value_dtype(B.values), _dp(out_p), _dp(oj), _dp(ox), _dp(ws)))
+    return DeviceCSR(out_p, out_j, out_x, A.m, B.K, k, _sorted=True)
+
+
 def norm(A: DeviceCSR, type: str = "O") -> float:
     """norm(A, type) for type "O" (largest column sum of |x|), "I" (largest row sum), "F" (Frobenius) or "M" (largest
     |x|): the margin sums, then the same reduction over them as one "abs_max" segment.  Synchronises (a float)."""

@@ -1633,6 +1633,21 @@ def csr_tmatmul_dense(indptr, indices, values, ncols, B_rowmajor, colmajor_out=T
     return out
 
 
+# ----------------------------------------------------------------------------- sparse x sparse (include/mxgpu_spgemm.h)
+def csr_spgemm(p1, j1, x1, dims1, trans_a, p2, j2, x2, dims2, trans_b):
+    """mx_csr_spgemm_begin: op(A) op(B) for the CSR arrays of A (dims1 = (nrow, ncol); values float64, int32 R logicals
+    or None for a pattern) and of B, op(X) = t(X) where trans_a / trans_b is set, as dict(indptr, indices, values) of
+    the CSR of the product: float64 values, rows sorted, nothing dropped.  One upload and one download; a transpose is
+    made on the device."""
+    pa, ja, xa, va = _csr_operand(p1, j1, x1, None)
+    pb, jb, xb, vb = _csr_operand(p2, j2, x2, None)
+    (m, K), (K2, n) = (int(d) for d in dims1), (int(d) for d in dims2)
+    if pa.size != m + 1 or pb.size != K2 + 1:
+        raise ValueError("csr_spgemm: indptr and dims disagree")
+    return _begin(_lib.load().mx_csr_spgemm_begin, ptr(pa), m, K, ptr(ja), ptr(xa), va, int(bool(trans_a)), ptr(pb), K2, n,
+                  ptr(jb), ptr(xb), vb, int(bool(trans_b)))[0]
+
+
 # ----------------------------------------------------------------------------- structured operands (include/mxgpu_sym.h)
 _UPLO = {"U": _lib.MX_UPLO_UPPER, "L": _lib.MX_UPLO_LOWER}
 

@@ -11,7 +11,7 @@ import numpy as np
 from . import exports
 from .matrices import (NA_INTEGER, NA_REAL, DenseMatrix, RsparseMatrix, as_csc_matrix, as_csr_matrix, as_sparse_vector,
                        check_valid_matrix, dgCMatrix, dgRMatrix, dimnames_of, dsparseVector, float32, isparseVector,
-                       lsparseVector, nsparseVector, options, sort_sparse_indices, sparseVector, stop)
+                       lgRMatrix, lsparseVector, ngRMatrix, nsparseVector, options, sort_sparse_indices, sparseVector, stop)
 
 
 def _nthreads():
@@ -40,15 +40,19 @@ def check_dimensions_match(x, y, matmult=False, crossprod=False, tcrossprod=Fals
         stop("Matrix dimensions do not match.")
 
 
-def set_dimnames(res, x, y, matmult=False, crossprod=False, tcrossprod=False):
-    """R/matmul.R:148-167."""
+def _product_dimnames(x, y, matmult=False, crossprod=False):
+    """row names of op(x), column names of op(y) — R/matmul.R:148-167"""
     dx, dy = dimnames_of(x), dimnames_of(y)
     if matmult:
-        rnames, cnames = dx[0], dy[1]
-    elif crossprod:
-        rnames, cnames = dx[1], dy[1]
-    else:
-        rnames, cnames = dx[0], dy[0]
+        return dx[0], dy[1]
+    if crossprod:
+        return dx[1], dy[1]
+    return dx[0], dy[0]
+
+
+def set_dimnames(res, x, y, matmult=False, crossprod=False, tcrossprod=False):
+    """R/matmul.R:148-167."""
+    rnames, cnames = _product_dimnames(x, y, matmult, crossprod)
     if isinstance(res, float32):
         res.Dimnames = [rnames, cnames]
         return res
@@ -428,6 +432,66 @@ def tcrossprod_dense_csc(x, y):
     return set_dimnames(res.T, DenseMatrix(xd, x_names), y, tcrossprod=True)
 
 
+# ---- sparse x sparse products (include/mxgpu_spgemm.h) ----------------------------------------------
+# The reference leaves these signatures to Matrix as well.  They are taken only under options["mxgpu.spgemm_route"];
+# without it every call below stops as it always did.
+def _spgemm_route():
+    return bool(options.get("mxgpu.spgemm_route", False))
+
+
+def _is_sparse_matrix(o):
+    return isinstance(o, (RsparseMatrix, dgCMatrix))
+
+
+def spgemm_flags(signature, layout_x, layout_y):
+    """(trans_a, trans_b, swap) of the one export call behind `signature` ("matmult", "crossprod", "tcrossprod") for
+    operands held as "R" (CSR arrays) or "C" (CSC arrays, which are the CSR of the transpose: a flag, not a
+    conversion).  The flags are relative to the arrays as they are.  Two CSC operands give a dgCMatrix: its arrays are
+    the CSR of the transposed product t(op(y)) t(op(x)), so the operands swap and both flags flip; C1 %*% C2 is then
+    the plain product of C2's arrays by C1's, with no transpose at all."""
+    ta = (signature == "crossprod") != (layout_x == "C")
+    tb = (signature == "tcrossprod") != (layout_y == "C")
+    if layout_x == "C" and layout_y == "C":
+        return (not tb, not ta, True)
+    return (ta, tb, False)
+
+
+def _raw_csr(o):
+    """(indptr, indices, values, dims of the CSR that the arrays spell, layout)"""
+    if isinstance(o, dgCMatrix):
+        return o.p, o.i, o.x, (o.Dim[1], o.Dim[0]), "C"
+    return o.p, o.j, o.x, o.Dim, "R"
+
+
+def _with_sorted_rows(p, idx, x, dims):
+    """the right-hand arrays with every row sorted: as they are when they are sorted, else sorted copies through
+    sort_sparse_indices"""
+    if exports.check_indices_are_sorted(p, idx):
+        return p, idx, x, dims
+    cls = ngRMatrix if x is None else lgRMatrix if x.dtype == np.int32 else dgRMatrix
+    S = sort_sparse_indices(cls(p, idx, x, dims), copy=True)
+    return S.p, S.j, S.x, dims
+
+
+def spgemm_sparse(x, y, signature):
+    """op(x) %*% op(y) for two sparse matrices (RsparseMatrix of any kind, dgCMatrix) on the device: a dgRMatrix, or a
+    dgCMatrix when both operands are dgCMatrix.  l and n operands count as numeric (NA -> NA_real_, a pattern entry is
+    1), which is Matrix's rule under %*%; nothing is dropped from the result."""
+    check_dimensions_match(x, y, **{signature: True})
+    check_valid_matrix(x)
+    check_valid_matrix(y)
+    *a, lx = _raw_csr(x)
+    *b, ly = _raw_csr(y)
+    trans_a, trans_b, swap = spgemm_flags(signature, lx, ly)
+    if swap:
+        a, b = b, a
+    b = _with_sorted_rows(*b)
+    res = exports.csr_spgemm(*a, trans_a, *b, trans_b)
+    Dim = (x.Dim[1] if signature == "crossprod" else x.Dim[0], y.Dim[0] if signature == "tcrossprod" else y.Dim[1])
+    names = list(_product_dimnames(x, y, signature == "matmult", signature == "crossprod"))
+    return (dgCMatrix if swap else dgRMatrix)(res["indptr"], res["indices"], res["values"], Dim, names)
+
+
 class RLogical(np.ndarray):
     """An int32 vector tagged as an R logical ({0,1,NA_LOGICAL}) so `%*%` picks the logical kernel."""
     r_logical = True
@@ -450,6 +514,8 @@ def matmul(x, y):
     """`%*%` for the signatures the hot path registers (R/matmul.R:200,281,469,512,755-767), and vector | matrix %*%
     RsparseMatrix and CsparseMatrix %*% vector | matrix on the transposed product."""
     x, y = _general(x), _general(y)
+    if _spgemm_route() and _is_sparse_matrix(x) and _is_sparse_matrix(y):
+        return spgemm_sparse(x, y, "matmult")
     if isinstance(x, RsparseMatrix):
         outer = _outer_route()
         if isinstance(y, float32):
@@ -477,10 +543,24 @@ def matmul(x, y):
     stop("Unsupported operand types for %*% in the MI355X hot path.")
 
 
-def tcrossprod(x, y):
+def _one_argument(x, what):
+    """crossprod(x) / tcrossprod(x) under options["mxgpu.spgemm_route"]: x as its general class, expanded once and
+    taken for both sides; the usual stop without the option, and for anything but a sparse matrix"""
+    x = _general(x) if _spgemm_route() else x
+    if not (_spgemm_route() and _is_sparse_matrix(x)):
+        stop("Unsupported operand types for %s in the MI355X hot path." % what)
+    return x
+
+
+def tcrossprod(x, y=None):
     """tcrossprod for (Rsparse, matrix|float32) and (matrix|float32, Rsparse) — R/matmul.R:307,385,461,538; and
-    (matrix, CsparseMatrix) on the transposed product."""
+    (matrix, CsparseMatrix) on the transposed product.  Two sparse matrices, and tcrossprod(x) of one, under
+    options["mxgpu.spgemm_route"]."""
+    if y is None:
+        x = y = _one_argument(x, "tcrossprod")
     x, y = _general(x), _general(y)
+    if _spgemm_route() and _is_sparse_matrix(x) and _is_sparse_matrix(y):
+        return spgemm_sparse(x, y, "tcrossprod")
     if isinstance(x, RsparseMatrix):
         return tcrossprod_csr_f32(x, y) if isinstance(y, float32) else tcrossprod_csr_dense(x, y)
     if isinstance(y, RsparseMatrix):
@@ -492,10 +572,15 @@ def tcrossprod(x, y):
     stop("Unsupported operand types for tcrossprod in the MI355X hot path.")
 
 
-def crossprod(x, y):
+def crossprod(x, y=None):
     """crossprod(matrix, CsparseMatrix) — R/matmul.R:393; (float32 vector, CsparseMatrix) — :434, under
-    options["mxgpu.outer_route"]; (RsparseMatrix, vector | matrix) on the transposed product."""
+    options["mxgpu.outer_route"]; (RsparseMatrix, vector | matrix) on the transposed product.  Two sparse matrices, and
+    crossprod(x) of one (the general matrix, not Matrix's dsCMatrix), under options["mxgpu.spgemm_route"]."""
+    if y is None:
+        x = y = _one_argument(x, "crossprod")
     x, y = _general(x), _general(y)
+    if _spgemm_route() and _is_sparse_matrix(x) and _is_sparse_matrix(y):
+        return spgemm_sparse(x, y, "crossprod")
     if isinstance(y, dgCMatrix) and isinstance(x, float32) and x.is_vector and _outer_route():
         return crossprod_f32_csc(x, y)
     if isinstance(y, dgCMatrix) and not isinstance(x, float32):
