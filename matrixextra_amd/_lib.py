@@ -20,6 +20,7 @@ REDUCE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_redu
 SYM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_sym.h")
 TPROD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_tprod.h")
 SPGEMM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_spgemm.h")
+GRAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_gram.h")
 
 
 class MxError(RuntimeError):
@@ -111,6 +112,8 @@ globals().update(SYM_HEADER.constants)     # MX_UPLO_UPPER, MX_UPLO_LOWER
 TPROD_HEADER = _read_header(TPROD_HEADER_PATH)
 # and the sparse x sparse product (include/mxgpu_spgemm.h): limits, count and fill at device level, one export
 SPGEMM_HEADER = _read_header(SPGEMM_HEADER_PATH)
+# and its one-triangle form with the Gram products on it (include/mxgpu_gram.h): count and fill behind a mask, one export
+GRAM_HEADER = _read_header(GRAM_HEADER_PATH)
 # mx_dvec_op, by R's operator
 MX_DV_OPS = {"*": HEADER.constants["MX_DV_MULTIPLY"], "^": HEADER.constants["MX_DV_POWERTO"],
              "/": HEADER.constants["MX_DV_DIVIDE"], "%%": HEADER.constants["MX_DV_DIVREST"],
@@ -143,7 +146,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for header, path in ((HEADER, "include/mxgpu.h"), (REDUCE_HEADER, "include/mxgpu_reduce.h"),
                          (SYM_HEADER, "include/mxgpu_sym.h"), (TPROD_HEADER, "include/mxgpu_tprod.h"),
-                         (SPGEMM_HEADER, "include/mxgpu_spgemm.h")):
+                         (SPGEMM_HEADER, "include/mxgpu_spgemm.h"), (GRAM_HEADER, "include/mxgpu_gram.h")):
         missing = [name for name in header.functions if not hasattr(lib, name)]
         if missing:
             raise MxError(f"libmxgpu.so lacks symbols declared in {path}: {missing}")

@@ -22,9 +22,15 @@
 //            bitmap with popcount prefixes, which also clears it for the workgroup's next row.
 // The count pass runs the same kernels on keys and bitmaps only.  Every product is rounded on its own (__dmul_rn under
 // a contract-off pragma, as tprod.hip does) and added in a statement of its own.  No atomic touches a value.
+//
+// One triangle (include/mxgpu_gram.h): every kernel takes a compile-time mask TRI.  SG_TRI_NONE is the
+// product above, instruction for instruction.  Under SG_TRI_UPPER / SG_TRI_LOWER a product for cell (i, j) is kept when
+// j >= i / j <= i, the bound is ub_i = min(f_i, w_i) with w_i the columns the mask leaves row i, and, when the caller
+// promises ascending rows of B (b_sorted), each row of B is trimmed to the window by a binary search where it is staged:
+// a step with nothing in the window is skipped, and f_i counts the trimmed lengths.
 #include "mx_dispatch.h"
 #include "mx_workspace.h"
-#include "../../include/mxgpu_spgemm.h"
+#include "../../include/mxgpu_gram.h"
 
 #include <initializer_list>
 
@@ -122,12 +128,47 @@ __device__ __forceinline__ void sg_insert(int32_t *keys, double *vals, int slots
     }
 }
 
+// ---- the triangle mask (include/mxgpu_gram.h): a compile-time choice, SG_TRI_NONE is the whole product
+enum { SG_TRI_NONE, SG_TRI_UPPER, SG_TRI_LOWER };
+
+// whether the mask keeps a product for cell (row, j); it stands in front of every insert and every bitmap atomicOr,
+// because the tables are sized from the window and sg_insert gives up silently when a table is full
+template <int TRI>
+__device__ __forceinline__ bool sg_keep(int row, int j)
+{
+    return TRI == SG_TRI_NONE || (TRI == SG_TRI_UPPER ? j >= row : j <= row);
+}
+
+// how many of the n columns the mask leaves row `row`
+template <int TRI>
+__device__ __forceinline__ long long sg_window(long long row, int n)
+{
+    if (TRI == SG_TRI_UPPER) return row < n ? n - row : 0;
+    if (TRI == SG_TRI_LOWER) return row + 1 < n ? row + 1 : n;
+    return n;
+}
+
+// an ascending row of B, [bs, bs + bl), trimmed to the window of `row`: upper from the first column >= row, lower up to
+// the last column <= row.  On a row that is not ascending the search still ends inside [0, bl].
+template <int TRI>
+__device__ __forceinline__ void sg_trim(const int32_t *__restrict__ Bj, int row, long long &bs, int &bl)
+{
+    if (TRI == SG_TRI_UPPER) {
+        const int at = lower_bound_dev(Bj + bs, bl, row);
+        bs += at;
+        bl -= at;
+    } else if (TRI == SG_TRI_LOWER) {
+        bl = lower_bound_dev(Bj + bs, bl, row + 1);                     // row < m <= INT_MAX
+    }
+}
+
 // ---- bounds and bins: eight lanes a row ----------------------------------------------------------------------------
+template <int TRI>
 __global__ __launch_bounds__(SG_BLOCK)
 void sg_bounds_kernel(int m, int K, int n, const int32_t *__restrict__ Ap, const int32_t *__restrict__ Aj, int64_t nnzA,
-                      const int32_t *__restrict__ Bp, int64_t nnzB, int32_t *__restrict__ ub,
-                      int32_t *__restrict__ counts, int32_t *__restrict__ lists, size_t list_stride,
-                      SgHeader *__restrict__ head)
+                      const int32_t *__restrict__ Bp, const int32_t *__restrict__ Bj, int64_t nnzB, int b_sorted,
+                      int32_t *__restrict__ ub, int32_t *__restrict__ counts, int32_t *__restrict__ lists,
+                      size_t list_stride, SgHeader *__restrict__ head)
 {
     const int l8 = threadIdx.x & 7, lane = lane_id();
     const long long row = (long long)blockIdx.x * (SG_BLOCK / 8) + threadIdx.x / 8;
@@ -138,7 +179,13 @@ void sg_bounds_kernel(int m, int K, int n, const int32_t *__restrict__ Ap, const
         for (int64_t q = l8; q < ra.len; q += 8) {
             const int k = Aj[ra.start + q];
             if ((unsigned)k < (unsigned)K) {
-                f += row_bounds(Bp[k], Bp[k + 1], nnzB).len;
+                const RowBounds rb = row_bounds(Bp[k], Bp[k + 1], nnzB);
+                if (TRI != SG_TRI_NONE && b_sorted) {                   // the trimmed length: what the steps will read
+                    long long bs = rb.start;
+                    int bl = (int)rb.len;
+                    sg_trim<TRI>(Bj, (int)row, bs, bl);
+                    f += bl;
+                } else f += rb.len;
                 used++;
             }
         }
@@ -148,7 +195,8 @@ void sg_bounds_kernel(int m, int K, int n, const int32_t *__restrict__ Ap, const
     const bool owner = valid && l8 == 0;
     int bin = -1;
     if (owner) {
-        const long long u = f < n ? f : n;
+        const long long w = sg_window<TRI>(row, n);
+        const long long u = f < w ? f : w;
         ub[row] = (int32_t)u;
         if (u == 0) counts[row] = 0;
         else if (u <= SG_GROUP_UB) {
@@ -174,11 +222,11 @@ void sg_bounds_kernel(int m, int K, int n, const int32_t *__restrict__ Ap, const
 }
 
 // ---- a lane group a row ----------------------------------------------------------------------------------------------
-template <int G, bool FILL>
+template <int G, bool FILL, int TRI>
 __global__ __launch_bounds__(SG_BLOCK)
 void sg_group_kernel(int K, int n, const int32_t *__restrict__ Ap, const int32_t *__restrict__ Aj,
                      const void *__restrict__ Ax, int a_dtype, const int32_t *__restrict__ Bp,
-                     const int32_t *__restrict__ Bj, const void *__restrict__ Bx, int b_dtype,
+                     const int32_t *__restrict__ Bj, const void *__restrict__ Bx, int b_dtype, int b_sorted,
                      const SgHeader *__restrict__ head, int bin, const int32_t *__restrict__ list,
                      int32_t *__restrict__ counts, const int32_t *__restrict__ out_indptr,
                      int32_t *__restrict__ out_indices, double *__restrict__ out_values)
@@ -209,6 +257,7 @@ void sg_group_kernel(int K, int n, const int32_t *__restrict__ Ap, const int32_t
                     const RowBounds rb = row_bounds(Bp[k], Bp[k + 1], nnzB);
                     bs = rb.start;
                     bl = (int)rb.len;
+                    if (TRI != SG_TRI_NONE && b_sorted) sg_trim<TRI>(Bj, row, bs, bl);
                     if (FILL) a = sg_value(Ax, a_dtype, q);
                 }
             }
@@ -220,7 +269,7 @@ void sg_group_kernel(int K, int n, const int32_t *__restrict__ Ap, const int32_t
                 if (blen == 0) continue;
                 for (int u = lg; u < blen; u += G) {
                     const int j = Bj[bstart + u];
-                    if ((unsigned)j >= (unsigned)n) continue;
+                    if ((unsigned)j >= (unsigned)n || !sg_keep<TRI>(row, j)) continue;
                     sg_insert<FILL>(keys, vals, SG_GROUP_SLOTS, j, FILL ? sg_product(at, sg_value(Bx, b_dtype, bstart + u)) : 0.0);
                 }
                 sg_wave_sync();
@@ -253,9 +302,10 @@ struct SgStage {
     double a[SG_BLOCK];
 };
 
-template <bool FILL>
-__device__ __forceinline__ void sg_stage(SgStage &st, const RowBounds ra, int64_t q0, int K, const int32_t *Aj,
-                                         const void *Ax, int a_dtype, const int32_t *Bp, int64_t nnzB)
+template <bool FILL, int TRI>
+__device__ __forceinline__ void sg_stage(SgStage &st, int row, const RowBounds ra, int64_t q0, int K, const int32_t *Aj,
+                                         const void *Ax, int a_dtype, const int32_t *Bp, const int32_t *Bj, int64_t nnzB,
+                                         int b_sorted)
 {
     const int tid = threadIdx.x;
     int bl = 0;
@@ -268,6 +318,7 @@ __device__ __forceinline__ void sg_stage(SgStage &st, const RowBounds ra, int64_
             const RowBounds rb = row_bounds(Bp[k], Bp[k + 1], nnzB);
             bs = rb.start;
             bl = (int)rb.len;
+            if (TRI != SG_TRI_NONE && b_sorted) sg_trim<TRI>(Bj, row, bs, bl);
             if (FILL) a = sg_value(Ax, a_dtype, q);
         }
     }
@@ -302,11 +353,11 @@ __device__ __forceinline__ int sg_block_scan(int v, int *total)
 }
 
 // ---- a workgroup a row, one table in LDS -----------------------------------------------------------------------------
-template <bool FILL>
+template <bool FILL, int TRI>
 __global__ __launch_bounds__(SG_BLOCK)
 void sg_block_kernel(int K, int n, const int32_t *__restrict__ Ap, const int32_t *__restrict__ Aj,
                      const void *__restrict__ Ax, int a_dtype, const int32_t *__restrict__ Bp,
-                     const int32_t *__restrict__ Bj, const void *__restrict__ Bx, int b_dtype,
+                     const int32_t *__restrict__ Bj, const void *__restrict__ Bx, int b_dtype, int b_sorted,
                      const SgHeader *__restrict__ head, const int32_t *__restrict__ list,
                      const int32_t *__restrict__ ub, int32_t *__restrict__ counts,
                      const int32_t *__restrict__ out_indptr, int32_t *__restrict__ out_indices,
@@ -329,7 +380,7 @@ void sg_block_kernel(int K, int n, const int32_t *__restrict__ Ap, const int32_t
         const RowBounds ra = row_bounds(Ap[row], Ap[row + 1], nnzA);
         for (int64_t q0 = 0; q0 < ra.len; q0 += SG_BLOCK) {
             __syncthreads();                                            // the stage is free, the table is clear
-            sg_stage<FILL>(st, ra, q0, K, Aj, Ax, a_dtype, Bp, nnzB);
+            sg_stage<FILL, TRI>(st, row, ra, q0, K, Aj, Ax, a_dtype, Bp, Bj, nnzB, b_sorted);
             __syncthreads();
             const int cnt = ra.len - q0 < SG_BLOCK ? (int)(ra.len - q0) : SG_BLOCK;
             for (int t = 0; t < cnt; t++) {
@@ -339,7 +390,7 @@ void sg_block_kernel(int K, int n, const int32_t *__restrict__ Ap, const int32_t
                 const double at = FILL ? st.a[t] : 1.0;
                 for (int u = tid; u < blen; u += SG_BLOCK) {
                     const int j = Bj[bstart + u];
-                    if ((unsigned)j >= (unsigned)n) continue;
+                    if ((unsigned)j >= (unsigned)n || !sg_keep<TRI>(row, j)) continue;
                     sg_insert<FILL>(keys, vals, slots, j, FILL ? sg_product(at, sg_value(Bx, b_dtype, bstart + u)) : 0.0);
                 }
                 __syncthreads();
@@ -378,11 +429,11 @@ void sg_block_kernel(int K, int n, const int32_t *__restrict__ Ap, const int32_t
 }
 
 // ---- a workgroup a row, a dense accumulator in the workspace --------------------------------------------------------
-template <bool FILL>
+template <bool FILL, int TRI>
 __global__ __launch_bounds__(SG_BLOCK)
 void sg_dense_kernel(int K, int n, const int32_t *__restrict__ Ap, const int32_t *__restrict__ Aj,
                      const void *__restrict__ Ax, int a_dtype, const int32_t *__restrict__ Bp,
-                     const int32_t *__restrict__ Bj, const void *__restrict__ Bx, int b_dtype,
+                     const int32_t *__restrict__ Bj, const void *__restrict__ Bx, int b_dtype, int b_sorted,
                      const SgHeader *__restrict__ head, const int32_t *__restrict__ list, char *dense,
                      size_t dense_bytes, int32_t *__restrict__ counts, const int32_t *__restrict__ out_indptr,
                      int32_t *__restrict__ out_indices, double *__restrict__ out_values)
@@ -403,7 +454,7 @@ void sg_dense_kernel(int K, int n, const int32_t *__restrict__ Ap, const int32_t
         const RowBounds ra = row_bounds(Ap[row], Ap[row + 1], nnzA);
         for (int64_t q0 = 0; q0 < ra.len; q0 += SG_BLOCK) {
             __syncthreads();
-            sg_stage<FILL>(st, ra, q0, K, Aj, Ax, a_dtype, Bp, nnzB);
+            sg_stage<FILL, TRI>(st, row, ra, q0, K, Aj, Ax, a_dtype, Bp, Bj, nnzB, b_sorted);
             __syncthreads();
             const int cnt = ra.len - q0 < SG_BLOCK ? (int)(ra.len - q0) : SG_BLOCK;
             for (int t = 0; t < cnt; t++) {
@@ -413,7 +464,7 @@ void sg_dense_kernel(int K, int n, const int32_t *__restrict__ Ap, const int32_t
                 const double at = FILL ? st.a[t] : 1.0;
                 for (int u = tid; u < blen; u += SG_BLOCK) {
                     const int j = Bj[bstart + u];
-                    if ((unsigned)j >= (unsigned)n) continue;
+                    if ((unsigned)j >= (unsigned)n || !sg_keep<TRI>(row, j)) continue;
                     const unsigned bit = 1u << (j & 31);
                     const unsigned old = atomicOr(&bits[j >> 5], bit);
                     if (FILL) {
@@ -427,11 +478,15 @@ void sg_dense_kernel(int K, int n, const int32_t *__restrict__ Ap, const int32_t
         }
         __syncthreads();
         const int o = FILL ? out_indptr[row] : 0, room = FILL ? out_indptr[row + 1] - o : 0;
+        // no bit outside the row's window is ever set: the walk covers the words of the window alone
+        int w_first = 0, w_end = words;
+        if (TRI == SG_TRI_UPPER) w_first = (row >> 5) < words ? row >> 5 : words;
+        if (TRI == SG_TRI_LOWER) w_end = (row >> 5) + 1 < words ? (row >> 5) + 1 : words;
         int done = 0;
-        for (int w0 = 0; w0 < words; w0 += SG_BLOCK) {
+        for (int w0 = w_first; w0 < w_end; w0 += SG_BLOCK) {
             const int w = w0 + tid;
             unsigned word = 0u;
-            if (w < words) word = atomicExch(&bits[w], 0u);
+            if (w < w_end) word = atomicExch(&bits[w], 0u);
             int total;
             int at = done + sg_block_scan(__popc(word), &total);
             if (FILL)
@@ -459,31 +514,39 @@ struct SgOperands {
     int b_dtype;
 };
 
-template <bool FILL>
-static int sg_launch_bins(const char *what, const SgOperands &o, const SpgemmLayout &L, const int32_t *out_indptr,
-                          int32_t *out_indices, double *out_values, hipStream_t st)
+using spgemm_masks = int_list<SG_TRI_NONE, SG_TRI_UPPER, SG_TRI_LOWER>;
+
+// what the two passes of a masked product share beside the operands: the mask and the caller's promise about B
+struct SgMask {
+    int tri = SG_TRI_NONE;
+    int b_sorted = 0;
+};
+
+template <bool FILL, int TRI>
+static int sg_launch_bins(const char *what, const SgOperands &o, int b_sorted, const SpgemmLayout &L,
+                          const int32_t *out_indptr, int32_t *out_indices, double *out_values, hipStream_t st)
 {
     for (int G : {8, 16, 32}) {
         const int bin = G == 8 ? SG_BIN_G8 : G == 16 ? SG_BIN_G16 : SG_BIN_G32;
         const int64_t per_block = SG_BLOCK / G;
         const int64_t rows = o.m < SG_MAX_BLOCKS * per_block ? o.m : SG_MAX_BLOCKS * per_block;
         const int rc = launch_rows(spgemm_groups{}, what, G, rows, SG_BLOCK, [&](auto g, dim3 grid, dim3 block) {
-            hipLaunchKernelGGL((sg_group_kernel<g(), FILL>), grid, block, 0, st, o.K, o.n, o.Ap, o.Aj, o.Ax, o.a_dtype, o.Bp,
-                               o.Bj, o.Bx, o.b_dtype, L.head, bin, L.list(bin), L.counts, out_indptr, out_indices,
-                               out_values);
+            hipLaunchKernelGGL((sg_group_kernel<g(), FILL, TRI>), grid, block, 0, st, o.K, o.n, o.Ap, o.Aj, o.Ax, o.a_dtype,
+                               o.Bp, o.Bj, o.Bx, o.b_dtype, b_sorted, L.head, bin, L.list(bin), L.counts, out_indptr,
+                               out_indices, out_values);
         });
         if (rc) return rc;
     }
     if (o.n > SG_GROUP_UB) {                                            // ub_i <= n: the bin is empty otherwise
-        hipLaunchKernelGGL(sg_block_kernel<FILL>, dim3(grid_for(o.m, 1, SG_MAX_BLOCKS)), dim3(SG_BLOCK), 0, st, o.K, o.n,
-                           o.Ap, o.Aj, o.Ax, o.a_dtype, o.Bp, o.Bj, o.Bx, o.b_dtype, L.head, L.list(SG_BIN_BLOCK), L.ub,
-                           L.counts, out_indptr, out_indices, out_values);
+        hipLaunchKernelGGL((sg_block_kernel<FILL, TRI>), dim3(grid_for(o.m, 1, SG_MAX_BLOCKS)), dim3(SG_BLOCK), 0, st, o.K,
+                           o.n, o.Ap, o.Aj, o.Ax, o.a_dtype, o.Bp, o.Bj, o.Bx, o.b_dtype, b_sorted, L.head,
+                           L.list(SG_BIN_BLOCK), L.ub, L.counts, out_indptr, out_indices, out_values);
         MX_LAUNCH_CHECK();
     }
     if (o.n > SG_LDS_UB) {
-        hipLaunchKernelGGL(sg_dense_kernel<FILL>, dim3((unsigned)L.groups), dim3(SG_BLOCK), 0, st, o.K, o.n, o.Ap, o.Aj,
-                           o.Ax, o.a_dtype, o.Bp, o.Bj, o.Bx, o.b_dtype, L.head, L.list(SG_BIN_DENSE), L.dense,
-                           sg_dense_bytes(o.n), L.counts, out_indptr, out_indices, out_values);
+        hipLaunchKernelGGL((sg_dense_kernel<FILL, TRI>), dim3((unsigned)L.groups), dim3(SG_BLOCK), 0, st, o.K, o.n, o.Ap,
+                           o.Aj, o.Ax, o.a_dtype, o.Bp, o.Bj, o.Bx, o.b_dtype, b_sorted, L.head, L.list(SG_BIN_DENSE),
+                           L.dense, sg_dense_bytes(o.n), L.counts, out_indptr, out_indices, out_values);
         MX_LAUNCH_CHECK();
     }
     return 0;
@@ -495,11 +558,20 @@ static int sg_check_sizes(const char *what, int m, int K, int n)
     return 0;
 }
 
-static int spgemm_count(int m, int K, int n, const int32_t *Ap, const int32_t *Aj, int64_t nnzA, const int32_t *Bp,
-                        const int32_t *Bj, int64_t nnzB, int32_t *out_indptr, void *workspace, int64_t *products_host,
-                        int64_t *nnz_out_host, hipStream_t st)
+// the mask of a one-triangle entry point: uplo must be an mx_uplo
+static int sg_mask_of(const char *what, int uplo, int b_sorted, SgMask *mask)
 {
-    const char *what = "mxd_csr_spgemm_count";
+    MX_REQUIRE(uplo == MX_UPLO_UPPER || uplo == MX_UPLO_LOWER, "%s: uplo must be MX_UPLO_UPPER or MX_UPLO_LOWER, got %d",
+               what, uplo);
+    mask->tri = uplo == MX_UPLO_UPPER ? SG_TRI_UPPER : SG_TRI_LOWER;
+    mask->b_sorted = b_sorted != 0;
+    return 0;
+}
+
+static int spgemm_count(const char *what, SgMask mask, int m, int K, int n, const int32_t *Ap, const int32_t *Aj,
+                        int64_t nnzA, const int32_t *Bp, const int32_t *Bj, int64_t nnzB, int32_t *out_indptr,
+                        void *workspace, int64_t *products_host, int64_t *nnz_out_host, hipStream_t st)
+{
     if (sg_check_sizes(what, m, K, n)) return 1;
     MX_REQUIRE(nnzA >= 0 && nnzA <= INT_MAX && nnzB >= 0 && nnzB <= INT_MAX, "%s: bad size", what);
     MX_REQUIRE(out_indptr && workspace, "%s: null pointer", what);
@@ -507,11 +579,14 @@ static int spgemm_count(int m, int K, int n, const int32_t *Ap, const int32_t *A
     const SpgemmLayout L(workspace, m, n);
     MX_HIP(hipMemsetAsync(L.head, 0, sizeof(SgHeader), st));
     if (m > 0) {
-        hipLaunchKernelGGL(sg_bounds_kernel, dim3(grid_for(m, SG_BLOCK / 8)), dim3(SG_BLOCK), 0, st, m, K, n, Ap, Aj, nnzA,
-                           Bp, nnzB, L.ub, L.counts, L.lists, padded_i32_bytes(m), L.head);
-        MX_LAUNCH_CHECK();
         const SgOperands o{m, K, n, Ap, Aj, nullptr, MX_NONE, Bp, Bj, nullptr, MX_NONE};
-        if (sg_launch_bins<false>(what, o, L, nullptr, nullptr, nullptr, st)) return 1;
+        const int rc = dispatch_int(spgemm_masks{}, what, "triangle", mask.tri, [&](auto tri) {
+            hipLaunchKernelGGL(sg_bounds_kernel<tri()>, dim3(grid_for(m, SG_BLOCK / 8)), dim3(SG_BLOCK), 0, st, m, K, n, Ap,
+                               Aj, nnzA, Bp, Bj, nnzB, mask.b_sorted, L.ub, L.counts, L.lists, padded_i32_bytes(m), L.head);
+            MX_LAUNCH_CHECK();
+            return sg_launch_bins<false, tri()>(what, o, mask.b_sorted, L, nullptr, nullptr, nullptr, st);
+        });
+        if (rc) return rc;
     }
     if (exclusive_scan_i32(L.counts, m, out_indptr, (int64_t *)&L.head->nnz_out, L.scan_ws(), st)) return 1;
     if (!products_host && !nnz_out_host) return 0;
@@ -525,11 +600,10 @@ static int spgemm_count(int m, int K, int n, const int32_t *Ap, const int32_t *A
     return 0;
 }
 
-static int spgemm_fill(int m, int K, int n, const int32_t *Ap, const int32_t *Aj, const void *Ax, int a_dtype,
-                       const int32_t *Bp, const int32_t *Bj, const void *Bx, int b_dtype, const int32_t *out_indptr,
-                       int32_t *out_indices, double *out_values, void *workspace, hipStream_t st)
+static int spgemm_fill(const char *what, SgMask mask, int m, int K, int n, const int32_t *Ap, const int32_t *Aj,
+                       const void *Ax, int a_dtype, const int32_t *Bp, const int32_t *Bj, const void *Bx, int b_dtype,
+                       const int32_t *out_indptr, int32_t *out_indices, double *out_values, void *workspace, hipStream_t st)
 {
-    const char *what = "mxd_csr_spgemm_fill";
     if (sg_check_sizes(what, m, K, n)) return 1;
     for (int dt : {a_dtype, b_dtype})
         MX_REQUIRE(dt == MX_F64 || dt == MX_LGL || dt == MX_NONE, "%s: unsupported value dtype %d", what, dt);
@@ -537,7 +611,9 @@ static int spgemm_fill(int m, int K, int n, const int32_t *Ap, const int32_t *Aj
     MX_REQUIRE(Ap && (K == 0 || Bp) && out_indptr && out_indices && out_values && workspace, "%s: null pointer", what);
     const SpgemmLayout L(workspace, m, n);
     const SgOperands o{m, K, n, Ap, Aj, Ax, a_dtype, Bp, Bj, Bx, b_dtype};
-    return sg_launch_bins<true>(what, o, L, out_indptr, out_indices, out_values, st);
+    return dispatch_int(spgemm_masks{}, what, "triangle", mask.tri, [&](auto tri) {
+        return sg_launch_bins<true, tri()>(what, o, mask.b_sorted, L, out_indptr, out_indices, out_values, st);
+    });
 }
 
 }  // namespace mx
@@ -557,8 +633,8 @@ extern "C" int mxd_csr_spgemm_count(int m, int K, int n, const int32_t *Ap, cons
                                     const int32_t *Bp, const int32_t *Bj, int64_t nnzB, int32_t *out_indptr,
                                     void *workspace, int64_t *products_host, int64_t *nnz_out_host, void *stream)
 {
-    return mx::spgemm_count(m, K, n, Ap, Aj, nnzA, Bp, Bj, nnzB, out_indptr, workspace, products_host, nnz_out_host,
-                            mx::as_stream(stream));
+    return mx::spgemm_count("mxd_csr_spgemm_count", mx::SgMask{}, m, K, n, Ap, Aj, nnzA, Bp, Bj, nnzB, out_indptr, workspace,
+                            products_host, nnz_out_host, mx::as_stream(stream));
 }
 
 extern "C" int mxd_csr_spgemm_fill(int m, int K, int n, const int32_t *Ap, const int32_t *Aj, const void *Ax, int a_dtype,
@@ -566,6 +642,32 @@ extern "C" int mxd_csr_spgemm_fill(int m, int K, int n, const int32_t *Ap, const
                                    const int32_t *out_indptr, int32_t *out_indices, double *out_values, void *workspace,
                                    void *stream)
 {
-    return mx::spgemm_fill(m, K, n, Ap, Aj, Ax, a_dtype, Bp, Bj, Bx, b_dtype, out_indptr, out_indices, out_values,
-                           workspace, mx::as_stream(stream));
+    return mx::spgemm_fill("mxd_csr_spgemm_fill", mx::SgMask{}, m, K, n, Ap, Aj, Ax, a_dtype, Bp, Bj, Bx, b_dtype,
+                           out_indptr, out_indices, out_values, workspace, mx::as_stream(stream));
+}
+
+// ---- one triangle (include/mxgpu_gram.h): the same two passes behind a mask; uplo and the sizes are checked before
+// anything is launched
+extern "C" int mxd_csr_spgemm_tri_count(int m, int K, int n, const int32_t *Ap, const int32_t *Aj, int64_t nnzA,
+                                        const int32_t *Bp, const int32_t *Bj, int64_t nnzB, int uplo, int b_sorted,
+                                        int32_t *out_indptr, void *workspace, int64_t *products_host,
+                                        int64_t *nnz_out_host, void *stream)
+{
+    const char *what = "mxd_csr_spgemm_tri_count";
+    mx::SgMask mask;
+    if (mx::sg_mask_of(what, uplo, b_sorted, &mask)) return 1;
+    return mx::spgemm_count(what, mask, m, K, n, Ap, Aj, nnzA, Bp, Bj, nnzB, out_indptr, workspace, products_host,
+                            nnz_out_host, mx::as_stream(stream));
+}
+
+extern "C" int mxd_csr_spgemm_tri_fill(int m, int K, int n, const int32_t *Ap, const int32_t *Aj, const void *Ax,
+                                       int a_dtype, const int32_t *Bp, const int32_t *Bj, const void *Bx, int b_dtype,
+                                       int uplo, int b_sorted, const int32_t *out_indptr, int32_t *out_indices,
+                                       double *out_values, void *workspace, void *stream)
+{
+    const char *what = "mxd_csr_spgemm_tri_fill";
+    mx::SgMask mask;
+    if (mx::sg_mask_of(what, uplo, b_sorted, &mask)) return 1;
+    return mx::spgemm_fill(what, mask, m, K, n, Ap, Aj, Ax, a_dtype, Bp, Bj, Bx, b_dtype, out_indptr, out_indices,
+                           out_values, workspace, mx::as_stream(stream));
 }

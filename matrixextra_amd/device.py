@@ -922,24 +922,37 @@ def spmm_t(A: DeviceCSR, B: torch.Tensor, out: torch.Tensor | None = None, colma
 
 
 # ---- sparse x sparse (include/mxgpu_spgemm.h): Gustavson by rows, count -> scan -> fill
-def spgemm(A: DeviceCSR, B: DeviceCSR) -> DeviceCSR:
+def spgemm(A: DeviceCSR, B: DeviceCSR, uplo: str | None = None) -> DeviceCSR:
     """C = A @ B for two device-resident CSR operands through mxd_csr_spgemm_count / _fill: float64 values (int32 R
     logicals are read as 0 / 1 / NA_real_, a pattern as ones), rows sorted, nothing dropped.  A's rows may be unsorted
     and repeat a column; B's rows must not repeat one.  One host round trip (the entry count).  crossprod(X, Y) on
-    resident operands is spgemm(X.transposed(), Y), which goes through X's cached column order."""
+    resident operands is spgemm(X.transposed(), Y), which goes through X's cached column order.
+    uplo "U" / "L": that triangle of the product alone, through mxd_csr_spgemm_tri_count / _fill (include/mxgpu_gram.h,
+    DESIGN.md §4.24) with b_sorted = B.rows_sorted(); None makes exactly the calls above."""
     if A.K != B.m:
         raise ValueError(f"spgemm: A has {A.K} columns, B has {B.m} rows")
     dev = A.indptr.device
+    # the mask's arguments stand behind the operands in both passes: none at all for the whole product
+    tri, mask = ("_tri", (_uplo(uplo), int(B.rows_sorted()))) if uplo is not None else ("", ())
     ws = _workspace(dev, "mxd_csr_spgemm_workspace_bytes", A.m, B.K)
     out_p = _int32(dev, A.m + 1)
-    _, k = _call("mxd_csr_spgemm_count", A.m, A.K, B.K, _dp(A.indptr), _dp(A.indices), A.nnz, _dp(B.indptr),
-                 _dp(B.indices), B.nnz, _dp(out_p), _dp(ws), cells=_COUNT * 2)
+    _, k = _call(f"mxd_csr_spgemm{tri}_count", A.m, A.K, B.K, _dp(A.indptr), _dp(A.indices), A.nnz, _dp(B.indptr),
+                 _dp(B.indices), B.nnz, *mask, _dp(out_p), _dp(ws), cells=_COUNT * 2)
     out_j, out_x = _fill_pass(
         dev, k, (torch.int32, torch.float64),
-        lambda oj, ox: _call("mxd_csr_spgemm_fill", A.m, A.K, B.K, _dp(A.indptr), _dp(A.indices), _dp(A.values),
+        lambda oj, ox: _call(f"mxd_csr_spgemm{tri}_fill", A.m, A.K, B.K, _dp(A.indptr), _dp(A.indices), _dp(A.values),
                              _value_dtype(A.values), _dp(B.indptr), _dp(B.indices), _dp(B.values),
-                             _value_dtype(B.values), _dp(out_p), _dp(oj), _dp(ox), _dp(ws)))
+                             _value_dtype(B.values), *mask, _dp(out_p), _dp(oj), _dp(ox), _dp(ws)))
     return DeviceCSR(out_p, out_j, out_x, A.m, B.K, k, _sorted=True)
+
+
+def gram(A: DeviceCSR, trans: bool = True, uplo: str = "U", order=None) -> DeviceCSR:
+    """The triangle `uplo` of the Gram product of a resident A: A^T A (A.K x A.K) with trans, A A^T (A.m x A.m) without,
+    as a CSR that stores that triangle alone (what a dsRMatrix with this uplo holds).  It is spgemm(A.transposed(order),
+    A, uplo) or spgemm(A, A.transposed(order), uplo): the transpose comes from the cached column order (or `order`, as
+    col_reduce takes it), so a second call sorts nothing.  A must not repeat a cell inside a row."""
+    At = A.transposed(order)
+    return spgemm(At, A, uplo) if trans else spgemm(A, At, uplo)
 
 
 def norm(A: DeviceCSR, type: str = "O") -> float:

@@ -1689,3 +1689,17 @@ def csr_triangle_check(indptr, indices, uplo, strict=False):
     out = C.c_int64(0)
     check(_lib.load().mx_csr_triangle_check(ptr(p), p.size - 1, ptr(j), _uplo(uplo), int(bool(strict)), C.byref(out)))
     return int(out.value)
+
+
+# ----------------------------------------------------------------------------- one-triangle Gram product (mxgpu_gram.h)
+def csr_gram(indptr, indices, values, dims, trans, uplo):
+    """mx_csr_gram_begin: the triangle `uplo` ("U" / "L") of X X^T (trans false) or X^T X (trans true) for the CSR
+    arrays of X (dims = (nrow, ncol); values float64, int32 R logicals or None for a pattern), as dict(indptr, indices,
+    values) of a CSR that stores that triangle alone: float64 values, rows sorted, nothing dropped.  One upload and one
+    download; the transpose is made on the device.  With sorted rows of X the other triangle of the full product holds
+    the same bits."""
+    p, j, x, vd = _csr_operand(indptr, indices, values, None)
+    nrow, ncol = (int(d) for d in dims)
+    if p.size != nrow + 1:
+        raise ValueError("csr_gram: indptr and dims disagree")
+    return _begin(_lib.load().mx_csr_gram_begin, ptr(p), nrow, ncol, ptr(j), ptr(x), vd, int(bool(trans)), _uplo(uplo))[0]

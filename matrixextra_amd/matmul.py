@@ -492,6 +492,39 @@ def spgemm_sparse(x, y, signature):
     return (dgCMatrix if swap else dgRMatrix)(res["indptr"], res["indices"], res["values"], Dim, names)
 
 
+# ---- the one-triangle Gram product (include/mxgpu_gram.h) -------------------------------------------
+# Matrix answers crossprod(x) / tcrossprod(x) of a sparse x with a symmetric matrix.  Under options["mxgpu.spgemm_route"]
+# together with options["mxgpu.gram_symmetric"] the one-argument forms do so too; without the second option they return
+# the general matrix as before.
+def _gram_symmetric():
+    return _spgemm_route() and bool(options.get("mxgpu.gram_symmetric", False))
+
+
+def gram_flags(signature, layout):
+    """(trans, uplo, cls) of the one export call behind `signature` ("crossprod" / "tcrossprod") of an operand held as
+    "R" (CSR arrays) or "C" (CSC arrays, the CSR of the transpose).  trans and uplo are relative to the arrays as they
+    are: t(X) X of a CSC is Y t(Y) of its arrays Y, and the rows of the lower mask, read as columns, are the upper
+    triangle.  The result always has uplo "U": a dsRMatrix for "R" (spgemm_sparse's class rule: the arrays' layout
+    decides; what Matrix gives for a dgRMatrix cannot be pinned without R), a dsCMatrix for "C"."""
+    from .structured import dsCMatrix, dsRMatrix
+    trans = (signature == "crossprod") != (layout == "C")
+    return (trans, "U", dsRMatrix) if layout == "R" else (trans, "L", dsCMatrix)
+
+
+def gram_sparse(x, signature):
+    """crossprod(x) / tcrossprod(x) of a sparse matrix (RsparseMatrix of any kind, dgCMatrix) as a symmetric matrix that
+    stores its upper triangle, computed as that triangle alone.  Unsorted rows are sorted in a copy first, for both
+    forms: the right-hand side needs it, and the stored triangle equals the other one of the full product bit for bit
+    only on sorted rows."""
+    check_valid_matrix(x)
+    *a, layout = _raw_csr(x)
+    trans, uplo, cls = gram_flags(signature, layout)
+    res = exports.csr_gram(*_with_sorted_rows(*a), trans, uplo)
+    n = x.Dim[1] if signature == "crossprod" else x.Dim[0]
+    names = list(_product_dimnames(x, x, False, signature == "crossprod"))
+    return cls(res["indptr"], res["indices"], res["values"], (n, n), names, uplo="U")
+
+
 class RLogical(np.ndarray):
     """An int32 vector tagged as an R logical ({0,1,NA_LOGICAL}) so `%*%` picks the logical kernel."""
     r_logical = True
@@ -555,9 +588,11 @@ def _one_argument(x, what):
 def tcrossprod(x, y=None):
     """tcrossprod for (Rsparse, matrix|float32) and (matrix|float32, Rsparse) — R/matmul.R:307,385,461,538; and
     (matrix, CsparseMatrix) on the transposed product.  Two sparse matrices, and tcrossprod(x) of one, under
-    options["mxgpu.spgemm_route"]."""
+    options["mxgpu.spgemm_route"]; with options["mxgpu.gram_symmetric"] as well, tcrossprod(x) is a symmetric matrix."""
     if y is None:
         x = y = _one_argument(x, "tcrossprod")
+        if _gram_symmetric():
+            return gram_sparse(x, "tcrossprod")
     x, y = _general(x), _general(y)
     if _spgemm_route() and _is_sparse_matrix(x) and _is_sparse_matrix(y):
         return spgemm_sparse(x, y, "tcrossprod")
@@ -575,9 +610,12 @@ def tcrossprod(x, y=None):
 def crossprod(x, y=None):
     """crossprod(matrix, CsparseMatrix) — R/matmul.R:393; (float32 vector, CsparseMatrix) — :434, under
     options["mxgpu.outer_route"]; (RsparseMatrix, vector | matrix) on the transposed product.  Two sparse matrices, and
-    crossprod(x) of one (the general matrix, not Matrix's dsCMatrix), under options["mxgpu.spgemm_route"]."""
+    crossprod(x) of one, under options["mxgpu.spgemm_route"]: the general matrix, or with options["mxgpu.gram_symmetric"]
+    as well the symmetric one Matrix gives (gram_sparse)."""
     if y is None:
         x = y = _one_argument(x, "crossprod")
+        if _gram_symmetric():
+            return gram_sparse(x, "crossprod")
     x, y = _general(x), _general(y)
     if _spgemm_route() and _is_sparse_matrix(x) and _is_sparse_matrix(y):
         return spgemm_sparse(x, y, "crossprod")
