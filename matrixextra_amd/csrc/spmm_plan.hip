@@ -427,6 +427,17 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
     double rv[PLAN_CHUNK];
 #pragma unroll
     for (int k = 0; k < PLAN_CHUNK; k++) { rc[k] = 0; rv[k] = 0.0; }
+    //   * warm hand-over (WARM builds: column-major): the 8 B lines of the next item's first batch,
+    //     requested from the held chunk in FRONT of the 16 (f32: 32) stores of C.  On gfx9 the stores count in vmcnt
+    //     and retire in order with the loads, so a B line requested behind them waits for their acknowledgements;
+    //     requested in front of them it waits for nothing but itself.  `warm` says that held_b is the item's batch 0,
+    //     in flight; such an item enters its stream through a copy of the chunk body of its own (see there).  Only the
+    //     lines are held (32 registers): the batch's (column, value) pairs are broadcast again from the held chunk
+    //     when they are consumed.  The row-major instantiations have no register to hold anything across the epilogue
+    //     (128 VGPRs as they are) and keep the cold start.
+    constexpr bool WARM = COLMAJOR;
+    real_t held_b[U][VEC];
+    bool warm = false;
 
     for (int it = 0; it < niter; it++) {
         const long long item_raw = lo + wg + (long long)it * nwg;
@@ -532,8 +543,9 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
             // as it always did, and is dropped.  Either way it reads slots [8 t, 8 t + 256) with t <= total steps
             // (t = this octet's end, or step_off[next octet * P], the sum of the steps in front of that octet):
             // inside the PLAN_TAIL_SLOTS = 512 slots of padding behind the last octet.
-            // What is still not in flight when a stream ends is the next item's first batch of B lines: the turnover
-            // is last batch, epilogue, zeroing, first batch of B lines, see DESIGN.md 4.1.
+            // The next item's first batch of B lines is requested in front of the epilogue's stores where the hand-over
+            // is warm (see `warm` above); in a cold one the turnover is last batch, epilogue, zeroing, first batch of
+            // B lines, see DESIGN.md 4.1.
             int rn[PLAN_CHUNK];
             double rvn[PLAN_CHUNK];
             auto load_chunk = [&](int step, int (&c)[PLAN_CHUNK], double (&v)[PLAN_CHUNK]) {
@@ -541,15 +553,21 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
 #pragma unroll
                 for (int k = 0; k < PLAN_CHUNK; k++) { c[k] = pcol[e + 64 * k]; v[k] = pval[e + 64 * k]; }
             };
+            // the batch in flight: this block's own, or (WARM builds) the one that lives across the epilogue
             int pc[U];
             double pv[U];
-            real_t b[U][VEC];
+            real_t own_b[U][VEC];
+            real_t (&b)[U][VEC] = *(WARM ? &held_b : &own_b);
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 pc[u] = 0;
                 pv[u] = 0.0;
+            }
+            if (!(WARM && warm)) {                                  // the no-op batch of a cold start
 #pragma unroll
-                for (int v = 0; v < VEC; v++) b[u][v] = 0;
+                for (int u = 0; u < U; u++)
+#pragma unroll
+                    for (int v = 0; v < VEC; v++) b[u][v] = 0;
             }
             // consume step u of the batch in (pc, pv, b): row switch -> fold the finished row into LDS, then FMA
             auto consume = [&](int u) {
@@ -569,7 +587,7 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
                 for (int v = 0; v < VEC; v++) asm volatile("" : "+v"(acc[v]));
                 __builtin_amdgcn_sched_barrier(0);
             };
-            if (send > sbeg && held_step != sbeg) {
+            if (!(WARM && warm) && send > sbeg && held_step != sbeg) {
                 load_chunk(sbeg, rc, rv);
                 // the first chunk has to be there before anything can start; with it complete at loop entry the
                 // compiler's vmcnt bookkeeping is exact on both edges of the loop.  (A held chunk is complete: it is
@@ -581,44 +599,68 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
             // the line of the same step of batch t+1 is requested into the registers the FMA just released, so 8
             // B-line loads per wavefront are in flight all the time.  The first pass consumes the no-op batch set up
             // above, the last batch is consumed after the loop.
-            for (int s = sbeg; s < send; s += U * PLAN_CHUNK) {      // sbeg, send are wave-uniform
-                const int ahead = s + U * PLAN_CHUNK;
-                const int ra = ahead >= send && nfirst >= 0 ? nfirst : ahead;
-                load_chunk(ra, rn, rvn);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int k = 0; k < PLAN_CHUNK; k++) {
-#define MX_PLAN_STEP(UU)                                                                                              \
+            // One chunk of the stream: the read-ahead, then batches K0 .. PLAN_CHUNK - 1 of the chunk in (rc, rv); K0 = 0
+            // everywhere but in the warm entry below.  A macro, not a lambda: each use has to be a copy of the code with
+            // wait counts of its own, and as a lambda the body came out with other registers in every instantiation.
+            // MX_PLAN_STEP: consume step UU of the batch in flight, request the same step of batch k of the chunk.
+            // In the first batch of the warm entry (K0 = 1, k = 1) the step consumed is one of batch 0 of the held chunk,
+            // of which only the B line was kept: its (column, value) pair is broadcast here.
+            // The probe (MX_PROBE) closes an interval behind step 0, except behind the no-op batch of a cold start.
+#define MX_PLAN_STEP(UU, K0)                                                                                          \
+                    if (K0 != 0 && k == K0) plan_bcast<UU>(rc[0], rv[0], pc[UU], pv[UU]);                             \
                     consume(UU);                                                                                      \
                     plan_bcast<UU>(rc[k], rv[k], pc[UU], pv[UU]);                                                     \
                     vload<real_t, VEC>(b[UU], reinterpret_cast<const real_t *>(Bbase + b_offset(pc[UU])));            \
                     __builtin_amdgcn_sched_barrier(0);
-                    MX_PLAN_STEP(0)
-                    MX_PROBE(if (pr_kind && !(pr_kind == 3 && s == sbeg && k == 0)) {   // that first batch is the no-op one
-                        const unsigned long long dt = (unsigned long long)(wall_clock64() - pr_t);
-                        _Pragma("unroll") for (int j = 0; j < 3; j++)
-                            if (pr_kind == j + 1) { pr_sum[j] += dt; pr_cnt[j]++; }
-                        pr_kind = 0;
-                    })
-                    MX_PLAN_STEP(1) MX_PLAN_STEP(2) MX_PLAN_STEP(3)
-                    MX_PLAN_STEP(4) MX_PLAN_STEP(5) MX_PLAN_STEP(6) MX_PLAN_STEP(7)
-#undef MX_PLAN_STEP
-                    MX_PROBE(bool pr_met = false;)
-                    if (sync_mode > 0) {
-                        const int sn = s + U * k;                   // steps consumed so far
-                        while (p < npanels - 1 && sn >= next_b) {   // the stream moved into the next panel
-                            p++;
-                            __syncthreads();
-                            MX_PROBE(pr_met = true; if (pr_kind != 3) pr_t = wall_clock64();)
-                            next_b = p < npanels - 1 ? __builtin_amdgcn_readlane(so_row, p + 1) : send;
-                        }
-                    }
-                    MX_PROBE(if (pr_kind != 3) { pr_kind = pr_met ? 2 : 1; if (!pr_met) pr_t = wall_clock64(); })
-                }
-#pragma unroll
-                for (int k = 0; k < PLAN_CHUNK; k++) { rc[k] = rn[k]; rv[k] = rvn[k]; }
-                held_step = ra;
+#define MX_PLAN_CHUNK(K0)                                                                                             \
+            {                                                                                                         \
+                const int ahead = s + U * PLAN_CHUNK;                                                                 \
+                const int ra = ahead >= send && nfirst >= 0 ? nfirst : ahead;                                         \
+                load_chunk(ra, rn, rvn);                                                                              \
+                __builtin_amdgcn_sched_barrier(0);                                                                    \
+                _Pragma("unroll")                                                                                     \
+                for (int k = K0; k < PLAN_CHUNK; k++) {                                                               \
+                    MX_PLAN_STEP(0, K0)                                                                               \
+                    MX_PROBE(if (pr_kind && !(pr_kind == 3 && s == sbeg && k == 0)) {                                 \
+                        const unsigned long long dt = (unsigned long long)(wall_clock64() - pr_t);                    \
+                        _Pragma("unroll") for (int j = 0; j < 3; j++)                                                 \
+                            if (pr_kind == j + 1) { pr_sum[j] += dt; pr_cnt[j]++; }                                   \
+                        pr_kind = 0;                                                                                  \
+                    })                                                                                                \
+                    MX_PLAN_STEP(1, K0) MX_PLAN_STEP(2, K0) MX_PLAN_STEP(3, K0)                                       \
+                    MX_PLAN_STEP(4, K0) MX_PLAN_STEP(5, K0) MX_PLAN_STEP(6, K0) MX_PLAN_STEP(7, K0)                   \
+                    MX_PROBE(bool pr_met = false;)                                                                    \
+                    if (sync_mode > 0) {                                                                              \
+                        const int sn = s + U * k;                   /* steps consumed so far */                       \
+                        while (p < npanels - 1 && sn >= next_b) {   /* the stream moved into the next panel */        \
+                            p++;                                                                                      \
+                            __syncthreads();                                                                          \
+                            MX_PROBE(pr_met = true; if (pr_kind != 3) pr_t = wall_clock64();)                         \
+                            next_b = p < npanels - 1 ? __builtin_amdgcn_readlane(so_row, p + 1) : send;               \
+                        }                                                                                             \
+                    }                                                                                                 \
+                    MX_PROBE(if (pr_kind != 3) { pr_kind = pr_met ? 2 : 1; if (!pr_met) pr_t = wall_clock64(); })     \
+                }                                                                                                     \
+                _Pragma("unroll")                                                                                     \
+                for (int k = 0; k < PLAN_CHUNK; k++) { rc[k] = rn[k]; rv[k] = rvn[k]; }                               \
+                held_step = ra;                                                                                       \
             }
+            int s = sbeg;                                            // sbeg, send are wave-uniform
+            if constexpr (WARM) {
+                if (warm) {
+                    // Warm entry: the B lines of this stream's batch 0 were requested in front of the previous
+                    // item's stores of C, so there is no no-op batch to consume: the first chunk starts at
+                    // k = 1, which consumes batch 0 while it requests batch 1.  This copy of the chunk body is reached
+                    // from the warm hand-over only, so its wait counts are those of that one path (the first consume
+                    // waits for its own B line, not for the stores behind it); a boundary that k = 0 would have met
+                    // is caught up by the meeting loop of k = 1.
+                    MX_PLAN_CHUNK(1)
+                    s += U * PLAN_CHUNK;
+                }
+            }
+            for (; s < send; s += U * PLAN_CHUNK) MX_PLAN_CHUNK(0)
+#undef MX_PLAN_CHUNK
+#undef MX_PLAN_STEP
             MX_PROBE(if (send > sbeg) { pr_kind = 3; pr_t = wall_clock64(); })
 #pragma unroll
             for (int u = 0; u < U; u++) consume(u);
@@ -628,7 +670,42 @@ void spmm_plan_kernel(int m, int n, int npanels, const int32_t *__restrict__ ste
         }
 
         // each wavefront writes the 64 x W tile of C it accumulated (streaming stores: C is not read again)
-        if (oct_ok) {
+        // Warm hand-over: a full tile (so that the stores are straight-line code whose count the compiler knows
+        // exactly), a next item with a stream, and its first chunk held.  All of it is wave-uniform.
+        bool cold_tile = oct_ok;
+        if constexpr (WARM) {
+            warm = oct_ok && gen * PLAN_WG_ROWS + wave_u * PLAN_OCT_ROWS + PLAN_OCT_ROWS <= m && n - slab * W >= W &&
+                   n_oct >= 0 && n_end > n_beg && held_step == n_beg;
+            if (warm) {
+                // slab_c has moved on: it is the next item's slab, which may be another one than this item's
+                const char *__restrict__ Bnext = reinterpret_cast<const char *>(Bp + (size_t)slab_c * slab_stride);
+#define MX_PLAN_WARM(UU)                                                                                              \
+                vload<real_t, VEC>(held_b[UU], reinterpret_cast<const real_t *>(                                      \
+                    Bnext + ((unsigned)group8_dpp_bcast<UU>(rc[0]) * (unsigned)(W * sizeof(real_t))) + lane_off));
+                MX_PLAN_WARM(0) MX_PLAN_WARM(1) MX_PLAN_WARM(2) MX_PLAN_WARM(3)
+                MX_PLAN_WARM(4) MX_PLAN_WARM(5) MX_PLAN_WARM(6) MX_PLAN_WARM(7)
+#undef MX_PLAN_WARM
+                __builtin_amdgcn_sched_barrier(0);
+                // lane = row, one column per store, eight columns read from LDS at a time; the element offset moves on
+                // in a vector register pair (W scalar offsets would not fit the scalar file)
+                const real_t *src = my_oct + (size_t)lane * S;
+                size_t off = (size_t)(slab * W) * ldc + (size_t)(gen * PLAN_WG_ROWS + wave * PLAN_OCT_ROWS + lane);
+#pragma unroll
+                for (int c0 = 0; c0 < W; c0 += 8) {
+                    real_t t[8];
+#pragma unroll
+                    for (int c = 0; c < 8; c++) t[c] = src[c0 + c];
+#pragma unroll
+                    for (int c = 0; c < 8; c++) {
+                        __builtin_nontemporal_store(t[c], C + off);
+                        off += ldc;
+                        asm volatile("" : "+v"(off));
+                    }
+                }
+                cold_tile = false;
+            }
+        }
+        if (cold_tile) {
             const int row_base = gen * PLAN_WG_ROWS + wave * PLAN_OCT_ROWS;
             const int ncols = min(W, n - slab * W);
             if constexpr (!COLMAJOR) {
