@@ -16,7 +16,7 @@ from . import _lib  # noqa: F401
 from .matrices import (DenseMatrix, MatrixExtraError, NA_INTEGER, NA_LOGICAL, NA_REAL, RsparseMatrix,  # noqa: F401
                        as_csr_matrix, check_valid_matrix, dgCMatrix, dgRMatrix, float32, from_scipy,
                        lgRMatrix, ngRMatrix, options, sort_sparse_indices)
-from .matrices import as_csc_matrix, t_deep, t_shallow  # noqa: F401
+from .matrices import as_csc_matrix, as_matrix, t_deep, t_shallow  # noqa: F401
 from .matrices import TsparseMatrix, as_coo_matrix, dgTMatrix, lgTMatrix, ngTMatrix  # noqa: F401
 from .matrices import (as_sparse_vector, dsparseVector, isparseVector, lsparseVector, nsparseVector,  # noqa: F401
                        sparseVector)

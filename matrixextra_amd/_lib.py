@@ -21,6 +21,7 @@ SYM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_sym.h")
 TPROD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_tprod.h")
 SPGEMM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_spgemm.h")
 GRAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_gram.h")
+DENSE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mxgpu_dense.h")
 
 
 class MxError(RuntimeError):
@@ -114,6 +115,8 @@ TPROD_HEADER = _read_header(TPROD_HEADER_PATH)
 SPGEMM_HEADER = _read_header(SPGEMM_HEADER_PATH)
 # and its one-triangle form with the Gram products on it (include/mxgpu_gram.h): count and fill behind a mask, one export
 GRAM_HEADER = _read_header(GRAM_HEADER_PATH)
+# and the dense <-> compressed conversions (include/mxgpu_dense.h): count, fill and the scatter at device level, two exports
+DENSE_HEADER = _read_header(DENSE_HEADER_PATH)
 # mx_dvec_op, by R's operator
 MX_DV_OPS = {"*": HEADER.constants["MX_DV_MULTIPLY"], "^": HEADER.constants["MX_DV_POWERTO"],
              "/": HEADER.constants["MX_DV_DIVIDE"], "%%": HEADER.constants["MX_DV_DIVREST"],
@@ -146,7 +149,8 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for header, path in ((HEADER, "include/mxgpu.h"), (REDUCE_HEADER, "include/mxgpu_reduce.h"),
                          (SYM_HEADER, "include/mxgpu_sym.h"), (TPROD_HEADER, "include/mxgpu_tprod.h"),
-                         (SPGEMM_HEADER, "include/mxgpu_spgemm.h"), (GRAM_HEADER, "include/mxgpu_gram.h")):
+                         (SPGEMM_HEADER, "include/mxgpu_spgemm.h"), (GRAM_HEADER, "include/mxgpu_gram.h"),
+                         (DENSE_HEADER, "include/mxgpu_dense.h")):
         missing = [name for name in header.functions if not hasattr(lib, name)]
         if missing:
             raise MxError(f"libmxgpu.so lacks symbols declared in {path}: {missing}")

@@ -1046,3 +1046,83 @@ def csr_unit_triangular_to_general(A: DeviceCSR, uplo: str, out=None) -> DeviceC
     _call("mxd_csr_unit_triangular_to_general", A.m, _dp(A.indptr), _dp(A.indices), _dp(A.values),
           _value_dtype(A.values), A.nnz, _uplo(uplo), _dp(out_p), _dp(out_j), _dp(out_x))
     return DeviceCSR(out_p, out_j[:n_out], None if out_x is None else out_x[:n_out], A.m, A.K, n_out)
+
+
+# ---- dense <-> compressed (include/mxgpu_dense.h) ---------------------------------------------------
+def _colmajor_view(what: str, D: torch.Tensor):
+    """(rows, cols, ld, transposed) under which the kernels read the 2-d tensor D as a column-major matrix without a
+    copy: D itself when its rows are contiguous (stride (1, ld)), else its transpose when its columns are (a row-major
+    D, stride (ld, 1)): the CSR arrays of a matrix are the CSC arrays of its transpose.  None when neither holds."""
+    if D.dim() != 2:
+        raise ValueError(f"{what}: the dense operand must be 2-d, got {D.dim()}-d")
+    m, n = (int(s) for s in D.shape)
+    for rows, cols, unit, ld, transposed in ((m, n, D.stride(0), D.stride(1), False),
+                                             (n, m, D.stride(1), D.stride(0), True)):
+        if (rows <= 1 or unit == 1) and (cols <= 1 or ld >= max(rows, 1)):
+            return rows, cols, (int(ld) if cols > 1 else max(rows, 1)), transposed
+    return None
+
+
+def dense_to_csr(D: torch.Tensor, by_col: bool = False, out_kind: int = MX_F64, logical: bool = False,
+                 col_splits: int = 0) -> DeviceCSR:
+    """The CSR arrays (by_col: the CSC arrays, as the DeviceCSR of D^T) of a dense m x n tensor through
+    mxd_dense_to_csr_count / _fill: the cells that are not zero, NaN and NA kept, -0.0 dropped, rows sorted.  D is
+    float64, float32, int32 (R integers, or R logicals with `logical`) or bool, column- or row-major with any leading
+    dimension (read in place); anything else is copied once.  out_kind: MX_F64 (values as f64, NA -> NA_real_), MX_LGL
+    (int32 R logicals, NaN -> NA) or MX_NONE (a pattern)."""
+    if out_kind not in (MX_F64, MX_LGL, MX_NONE):
+        raise ValueError("dense_to_csr: out_kind must be MX_F64, MX_LGL or MX_NONE")
+    if D.dim() != 2:
+        raise ValueError(f"dense_to_csr: the dense operand must be 2-d, got {D.dim()}-d")
+    m, n = (int(s) for s in D.shape)
+    X, kind = _dense_kind("dense_to_csr", D, logical)
+    view = _colmajor_view("dense_to_csr", X)
+    if view is None:
+        X = X.t().contiguous().t()
+        view = _colmajor_view("dense_to_csr", X)
+    rows, cols, ld, transposed = view
+    col = int(bool(by_col) != transposed)
+    dev = X.device
+    nseg, nother = (n, m) if by_col else (m, n)
+    ws = _workspace(dev, "mxd_dense_to_csr_workspace_bytes", rows, cols, col, int(col_splits))
+    out_p = _int32(dev, nseg + 1)
+    k, = _call("mxd_dense_to_csr_count", rows, cols, _dp(X), ld, kind, col, int(col_splits), _dp(out_p), _dp(ws),
+               cells=_COUNT)
+    vdt = {MX_F64: torch.float64, MX_LGL: torch.int32, MX_NONE: None}[out_kind]
+    out_j, out_x = _fill_pass(
+        dev, k, (torch.int32, vdt),
+        lambda oj, ox: _call("mxd_dense_to_csr_fill", rows, cols, _dp(X), ld, kind, col, int(col_splits), _dp(out_p),
+                             _dp(ws), _dp(oj), _dp(ox), out_kind))
+    return DeviceCSR(out_p, out_j, out_x, nseg, nother, k, _sorted=True)
+
+
+def csr_to_dense(A: DeviceCSR, by_col: bool = False, out: torch.Tensor | None = None, logical: bool = False,
+                 flag: torch.Tensor | None = None, col_splits: int = 0) -> torch.Tensor:
+    """A as a dense tensor through mxd_csr_to_dense: A.m x A.K for CSR arrays, A.K x A.m with by_col (A then holds the
+    CSC arrays: A.m columns, indices below A.K).  float64 (NA -> NA_real_, a pattern entry -> 1.0), or int32 R logicals
+    with `logical`.  `out`: a tensor of that shape and dtype, column- or row-major with any leading dimension, of which
+    only the cells of the matrix are written; by default a new column-major one.  Every row of A must be strictly
+    ascending and in range: the kernel sets the int32 device cell `flag` otherwise.  With a caller's `flag` (zeroed by
+    the caller) nothing is read back and the call does not synchronise; without one the flag is read and a flagged
+    operand raises ValueError."""
+    vd = _value_dtype(A.values)
+    dt = torch.int32 if logical else torch.float64
+    dev = A.indptr.device
+    shape = (A.K, A.m) if by_col else (A.m, A.K)
+    if out is None:
+        out = torch.empty(shape[::-1], dtype=dt, device=dev).t()
+    elif tuple(out.shape) != shape or out.dtype != dt or out.device != dev:
+        raise ValueError(f"csr_to_dense: out must be a {shape} {dt} tensor on {dev}, got {tuple(out.shape)} {out.dtype} "
+                         f"on {out.device}")
+    view = _colmajor_view("csr_to_dense", out)
+    if view is None:
+        raise ValueError(f"csr_to_dense: out must have contiguous rows or contiguous columns, got strides {out.stride()}")
+    _, _, ld, transposed = view
+    own = flag is None
+    if own:
+        flag = _int32(dev, 1).zero_()
+    _call("mxd_csr_to_dense", A.m, A.K, _dp(A.indptr), _dp(A.indices), _dp(A.values), vd, int(bool(by_col) != transposed),
+          int(col_splits), _dp(out), ld, MX_LGL if logical else MX_F64, _dp(flag))
+    if own and int(flag.item()):
+        raise ValueError("csr_to_dense: the indices of a row are not strictly ascending or not in range")
+    return out

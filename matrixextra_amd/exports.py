@@ -1703,3 +1703,44 @@ def csr_gram(indptr, indices, values, dims, trans, uplo):
     if p.size != nrow + 1:
         raise ValueError("csr_gram: indptr and dims disagree")
     return _begin(_lib.load().mx_csr_gram_begin, ptr(p), nrow, ncol, ptr(j), ptr(x), vd, int(bool(trans)), _uplo(uplo))[0]
+
+
+# ----------------------------------------------------------------------------- dense <-> compressed (mxgpu_dense.h)
+_DENSE_KINDS = {np.dtype(np.float64): MX_F64, np.dtype(np.float32): _lib.MX_F32, np.dtype(np.int32): _lib.MX_I32}
+
+
+def dense_to_csr(dense, by_col=False, out_dtype=MX_F64):
+    """mx_dense_to_csr_begin: the CSR arrays (by_col: the CSC arrays) of a dense 2-d array as dict(indptr, indices,
+    values): the cells that are not zero, NaN and NA kept, -0.0 dropped, rows sorted.  float64 and float32 arrays are
+    numeric, int32 arrays R integers, bool arrays R logicals.  out_dtype MX_F64: float64 values (NA_integer_ ->
+    NA_real_); MX_LGL: int32 R logicals (NaN -> NA, any other kept cell TRUE); MX_NONE: `values` is None."""
+    M = np.asarray(dense)
+    if M.ndim != 2:
+        raise ValueError("dense operand must be a 2-d matrix")
+    if out_dtype not in (MX_F64, MX_LGL, MX_NONE):
+        raise ValueError("dense_to_csr: out_dtype must be MX_F64, MX_LGL or MX_NONE")
+    if M.dtype == np.bool_:
+        M, kind = np.asfortranarray(M, dtype=np.int32), MX_LGL
+    elif M.dtype in _DENSE_KINDS:
+        M, kind = np.asfortranarray(M), _DENSE_KINDS[M.dtype]
+    else:
+        raise TypeError(f"dense operand must be float64, float32, int32 or bool, got {M.dtype}")
+    out = _begin(_lib.load().mx_dense_to_csr_begin, ptr(M), M.shape[0], M.shape[1], kind, int(bool(by_col)),
+                 int(out_dtype), empty_values_dtype=np.int32 if out_dtype == MX_LGL else np.float64)[0]
+    if out_dtype == MX_NONE:
+        out["values"] = None
+    return out
+
+
+def csr_to_dense(indptr, indices, values, nother, by_col=False, logical=False):
+    """mx_csr_to_dense: the CSR arrays of an nrow x `nother` matrix (by_col: the CSC arrays of an `nother` x ncol one;
+    values float64, int32 R logicals or None for a pattern) as a dense column-major array: float64 (NA -> NA_real_, a
+    pattern entry -> 1.0), or int32 R logicals with `logical`.  Unsorted rows and repeated cells are normalised on the
+    device first (repeated cells merged as coo_to_csr merges them); an index out of bounds is an error."""
+    p, j, x, vd = _csr_operand(indptr, indices, values, None)
+    nseg, nother = p.size - 1, int(nother)
+    shape = (nother, nseg) if by_col else (nseg, nother)
+    out = np.empty(shape, dtype=np.int32 if logical else np.float64, order="F")
+    check(_lib.load().mx_csr_to_dense(ptr(p), nseg, nother, ptr(j), ptr(x), vd, int(bool(by_col)), ptr(out),
+                                      MX_LGL if logical else MX_F64))
+    return out

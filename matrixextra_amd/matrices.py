@@ -81,6 +81,8 @@ class RsparseMatrix:
 
     def toarray(self):
         """as.matrix(): dense float64 (NA_LOGICAL -> nan for logical matrices)."""
+        if _dense_route_on():
+            return np.asarray(as_matrix(self))
         out = np.zeros(self.Dim, dtype=np.float64)
         for r in range(self.Dim[0]):
             s, e = self.p[r], self.p[r + 1]
@@ -259,6 +261,8 @@ class TsparseMatrix:
     def toarray(self):
         """as.matrix(): dense float64 with repeated triplets combined as Matrix does (numeric: summed; logical:
         R's `|`, NA -> nan; pattern: 1)."""
+        if _dense_route_on():
+            return np.asarray(as_matrix(self))
         out = np.zeros(self.Dim, dtype=np.float64)
         if self.x is None:
             out[self.i, self.j] = 1.0
@@ -614,6 +618,52 @@ def dimnames_of(x):
     return getattr(x, "Dimnames", [None, None]) or [None, None]
 
 
+def _dense_route_on():
+    """options["mxgpu.dense_route"] (off unless set): the dense <-> sparse conversions run on the device
+    (include/mxgpu_dense.h) and no longer through scipy and the Python loops of toarray()."""
+    return bool(options.get("mxgpu.dense_route", False))
+
+
+def _dense_route(x):
+    """Whether as_csr_matrix / as_csc_matrix / as_coo_matrix of `x` take the device route: only under the option, and
+    only for a dense matrix (ndarray, DenseMatrix) or a float32 matrix."""
+    return _dense_route_on() and ((isinstance(x, float32) and not x.is_vector)
+                                  or (isinstance(x, np.ndarray) and x.ndim == 2))
+
+
+def _dense_to_compressed(x, by_col=False, logical=False, binary=False):
+    """dict(indptr, indices, values) of the dense matrix `x` through exports.dense_to_csr: float64 / float32 arrays are
+    numeric, int32 arrays R integers (NA_integer_ -> NA_real_), bool arrays logicals; with `logical` a NaN / NA cell
+    becomes NA, with `binary` there are no values."""
+    from . import _lib, exports
+    data = x.Data if isinstance(x, float32) else np.asarray(x)
+    if data.dtype not in (np.float64, np.float32, np.int32, np.bool_):
+        data = data.astype(np.float64)
+    kind = _lib.MX_NONE if binary else _lib.MX_LGL if logical else _lib.MX_F64
+    return exports.dense_to_csr(data, by_col, kind)
+
+
+def as_matrix(x, logical=False):
+    """as.matrix() on the device (exports.csr_to_dense): a DenseMatrix with x's Dimnames, float64 (NA -> NA_real_, a
+    pattern entry -> 1.0), or int32 R logicals with `logical`.  A TsparseMatrix goes through the device COO sort first
+    (repeated triplets merged), a symmetric or triangular operand is expanded on the device first."""
+    from . import exports
+    if _is_structured(x):
+        from . import structured
+        x = structured.as_general(x)
+    names = list(dimnames_of(x))
+    if isinstance(x, TsparseMatrix):
+        check_valid_matrix(x)
+        x = _coo_to_compressed(x)
+    if isinstance(x, RsparseMatrix):
+        out = exports.csr_to_dense(x.p, x.j, x.x, x.Dim[1], False, logical)
+    elif isinstance(x, dgCMatrix):
+        out = exports.csr_to_dense(x.p, x.i, x.x, x.Dim[0], True, logical)
+    else:
+        stop(f"as_matrix: unsupported class {type(x).__name__}.")
+    return DenseMatrix(out, names)
+
+
 def from_scipy(A, logical=False, binary=False):
     """as.csr.matrix() for a scipy sparse matrix (canonical general CSR; sums duplicates like R's coercion)."""
     import scipy.sparse as sp
@@ -660,6 +710,10 @@ def as_csr_matrix(x, logical=False, binary=False):
             return dgRMatrix(x.p, x.j, np.ones(x.j.size), x.Dim, x.Dimnames)
         xv = np.where(x.x == NA_LOGICAL, NA_REAL, x.x.astype(np.float64))
         return dgRMatrix(x.p, x.j, xv, x.Dim, x.Dimnames)
+    if _dense_route(x):
+        res = _dense_to_compressed(x, logical=logical, binary=binary)
+        cls = ngRMatrix if binary else lgRMatrix if logical else dgRMatrix
+        return cls(res["indptr"], res["indices"], res["values"], x.shape, list(dimnames_of(x)))
     if isinstance(x, np.ndarray):
         import scipy.sparse as sp
         out = from_scipy(sp.csr_matrix(x), logical=logical, binary=binary)
@@ -761,6 +815,9 @@ def as_csc_matrix(x):
         check_valid_matrix(x)
         T = as_csr_matrix(_coo_to_compressed(x, csc=True))            # CSR of x^T in f64 = the CSC of x
         return dgCMatrix(T.p, T.j, T.x, x.Dim, list(dimnames_of(x)))
+    if _dense_route(x):
+        res = _dense_to_compressed(x, by_col=True)
+        return dgCMatrix(res["indptr"], res["indices"], res["values"], x.shape, list(dimnames_of(x)))
     x = as_csr_matrix(x)
     check_valid_matrix(x)
     res = exports.csr_transpose(x.p, x.j, x.x, x.Dim[1])
